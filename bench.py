@@ -17,7 +17,11 @@ processes, before anything touches a GPU).  The global stream list (N x the per-
 (losslessh264_amd/shard.py), every rank compresses its share, the per-stream result records are gathered over RCCL and checked
 once on rank 0.  Weak scaling; no data-path collective.
 
-Prints ONE JSON line (the contract in the task description).
+Prints ONE JSON line: `value` (MB/s), `ms_per_step` and the configuration.  A plain run sets up, warms up, times `--steps` steps
+and prints it; `--full` adds everything that takes runs or checks of its own: the steps with one batch in flight, per-stage times,
+the kernel's time alone and the coder's roofline figure, parity of every coded stream with the reference's files and the round trip,
+the host stages, the CPU baselines, the gathered result records of N > 1 and the longest stream of `--mixed` alone.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -166,6 +170,42 @@ def reference_cli_baseline(stream, stream_bytes, procs):
         return None
 
 
+def _sample(rng, sizes, budget, most=16):
+    """a seeded sample of up to `most` of the items (indices into sizes), taken in a random order while their sizes fit the budget"""
+    out, used = [], 0
+    for i in rng.permutation(len(sizes)):
+        if len(out) == most:
+            break
+        if used + sizes[i] <= budget:
+            out.append(int(i)); used += sizes[i]
+    return sorted(out)
+
+
+def dump_outputs(path, sess, coder, order, n_local):
+    """what a caller of the timed path receives, as .npy (float32 / float64, under 64 MB in all): the coded length of every tag of every
+    stream in full, the coded bytes of a seeded sample of streams and the reconstructed pictures (Y, U, V, macroblock-aligned) of a
+    seeded sample of (stream, picture) pairs.  Only the device buffers are read."""
+    import numpy as np
+    from losslessh264_amd import _lib as L
+    from losslessh264_amd.coder import TAG_OF_SLOT
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20260)
+    lens = coder.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)[:, :len(TAG_OF_SLOT)].astype(np.int64)
+    streams = _sample(rng, lens.sum(axis=1), 6 << 20)
+    coded = [b"".join(tg[t] for t in TAG_OF_SLOT if t in tg) for tg in (coder.tags(c) for c in streams)]
+    pairs = [(c, i) for c in range(n_local) for i in range(len(order[c % len(order)]))]
+    px = [order[c % len(order)][i].mb_w * order[c % len(order)][i].mb_h * 384 for c, i in pairs]
+    pics = [pairs[k] for k in _sample(rng, px, 8 << 20)]
+    planes = [p.ravel() for c, i in pics for p in sess.picture(c, i)]
+    arrays = {"tag_lengths": lens.astype(np.float64),
+              "tag_bytes_streams": np.array(streams, dtype=np.float64),
+              "tag_bytes": np.frombuffer(b"".join(coded), dtype=np.uint8).astype(np.float32),
+              "pictures_index": np.array(pics, dtype=np.float64).reshape(-1, 2),
+              "pictures_yuv": (np.concatenate(planes) if planes else np.zeros(0, np.uint8)).astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -180,6 +220,8 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="every batch on its own: no second batch's context indexing beside the coder")
     ap.add_argument("--mixed", action="store_true", help="configs[1] as a heterogeneous batch: the eleven Baseline streams SURVEY 8(d) lists, interleaved "
                                                          "(46 of each = 506 streams per GPU), the longest first within every group of eleven")
+    ap.add_argument("--full", action="store_true", help="also the figures and checks that take runs of their own (see the module's docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (rank 0's streams)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)                                   # does not return
@@ -370,14 +412,16 @@ def main():
 
     step(timed=True)            # untimed priming pass on one stream: the coder's work memory is allocated here, not beside the first kernel
     torch.cuda.synchronize(dev)
-    # a few steps with every batch on its own (two streams, no second batch in flight): reported beside the pipelined figure
-    step()
-    torch.cuda.synchronize(dev)
-    t_u = time.perf_counter()
-    for _ in range(3):
+    unpipelined_ms = None
+    if args.full:
+        # a few steps with every batch on its own (two streams, no second batch in flight): reported beside the pipelined figure
         step()
-    torch.cuda.synchronize(dev)
-    unpipelined_ms = (time.perf_counter() - t_u) / 3 * 1e3
+        torch.cuda.synchronize(dev)
+        t_u = time.perf_counter()
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize(dev)
+        unpipelined_ms = (time.perf_counter() - t_u) / 3 * 1e3
     if pipeline:
         state["pipelined"] = True
         ctxs[0].run()
@@ -402,16 +446,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    # the buffers the last timed step coded into (two sets alternate when two batches are in flight)
+    last = coders[(state["k"] - 1) & 1] if state["pipelined"] else coder
+    ln = last.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)
+    assert not ln[:, L.N_TAG_SLOTS].any(), "device coder status %s" % sorted(set(ln[:, L.N_TAG_SLOTS].tolist()))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess, last, order, n_local)
+
     state["pipelined"] = False
-    torch.cuda.synchronize(dev)
-    # per-stage device time, hipEvents on the launch stream (torch's current stream is the stream the C ABI launches on), a few extra steps
-    n_ev = max(2, min(args.steps, 5))
-    for _ in range(n_ev):
-        step(timed=True)
+    if args.full:
         torch.cuda.synchronize(dev)
-        k_ms["recon"] += ev[0].elapsed_time(ev[1]); k_ms["ctx"] += ev[1].elapsed_time(ev[2]); k_ms["coder"] += ev[2].elapsed_time(ev[3])
-    for k in k_ms:
-        k_ms[k] /= n_ev
+        # per-stage device time, hipEvents on the launch stream (torch's current stream is the stream the C ABI launches on), a few extra steps
+        n_ev = max(2, min(args.steps, 5))
+        for _ in range(n_ev):
+            step(timed=True)
+            torch.cuda.synchronize(dev)
+            k_ms["recon"] += ev[0].elapsed_time(ev[1]); k_ms["ctx"] += ev[1].elapsed_time(ev[2]); k_ms["coder"] += ev[2].elapsed_time(ev[3])
+        for k in k_ms:
+            k_ms[k] /= n_ev
     types = np.concatenate([f.mbs["mb_type"] for fr in order for f in fr])
     n_intra = int(np.count_nonzero(types & 0x207))
     n_inter = int(np.count_nonzero(types & 0x1F8))
@@ -441,161 +493,150 @@ def main():
     except (OSError, KeyError, ValueError):
         pass
 
-    # the coder's own memory-bound figure: what its stages have to move (symbols read twice, 8-byte decision words and 2-byte list
-    # entries written once and read once, the bytes written)
-    dw, le = L.C.c_ulonglong(), L.C.c_ulonglong()
-    L.check(L.lib().lh264_code_last_totals(L.C.byref(dw), L.C.byref(le)))
-    n_ctx_syms = int(ctx.d_nsyms.view(torch.int16).to(torch.int64).sum().item())
-    n_syn_syms = sum(len(f.syn_syms) for fr in order for f in fr) * rep
-    lens = coder.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)
-    assert not lens[:, L.N_TAG_SLOTS].any(), "device coder status %s" % sorted(set(lens[:, L.N_TAG_SLOTS].tolist()))
-    coded_local = lens[:, :35].astype(np.int64).sum(axis=1)
-    coder_bytes = 2 * 8 * (n_ctx_syms + n_syn_syms) + 2 * 8 * dw.value + 2 * 2 * le.value + int(coded_local.sum())
+    if args.full:
+        # the coder's own memory-bound figure: what its stages have to move (symbols read twice, 8-byte decision words and 2-byte list
+        # entries written once and read once, the bytes written)
+        dw, le = L.C.c_ulonglong(), L.C.c_ulonglong()
+        L.check(L.lib().lh264_code_last_totals(L.C.byref(dw), L.C.byref(le)))
+        n_ctx_syms = int(ctx.d_nsyms.view(torch.int16).to(torch.int64).sum().item())
+        n_syn_syms = sum(len(f.syn_syms) for fr in order for f in fr) * rep
+        lens = coder.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)
+        assert not lens[:, L.N_TAG_SLOTS].any(), "device coder status %s" % sorted(set(lens[:, L.N_TAG_SLOTS].tolist()))
+        coded_local = lens[:, :35].astype(np.int64).sum(axis=1)
+        coder_bytes = 2 * 8 * (n_ctx_syms + n_syn_syms) + 2 * 8 * dw.value + 2 * 2 * le.value + int(coded_local.sum())
 
-    # ---- parity outside the timed region ---------------------------------------------------------------------------------------------------
-    # every stream's compressed size must be what the reference wrote (fixture: the files of its console application), the last
-    # picture of the first and last replica must have the reference decoder's plane CRCs where the fixture has them
-    # (a stream used whole: the files of the reference's console application, tests/golden/cli_*.npz; the first pictures of a longer
-    # stream: what the reference wrote after exactly those pictures, tests/golden/bench_cut.json - length and SHA-1 of every tag)
-    import hashlib
-    cuts = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_cut.json")))
-    sweep = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_sweep.json")))
-    ref_tagged, ref_tags = [], []
-    for k, name in enumerate(cfg["streams"]):
-        p = os.path.join(ROOT, "tests", "golden", "cli_" + name + ".npz")
-        cut = cuts.get("%s:%d" % (name, len(distinct[k])))
-        if os.path.exists(p) and whole[k]:
-            z = np.load(p)
-            ref_tags.append({int(f[4:]): (len(z[f]), hashlib.sha1(z[f].tobytes()).hexdigest()) for f in z.files if f.startswith("tag_")})
-        elif whole[k] and name in sweep and sweep[name].get("compress_rc") == 0:
-            # (the sweep of the unmodified reference over every shipped stream, tests/golden/ref_sweep.json: size and SHA-1 of every file)
-            ref_tags.append({int(t): (v[0], v[1]) for t, v in sweep[name]["files"].items() if t.isdigit()})
-        elif cut is not None and cut["pictures"] == len(distinct[k]):
-            ref_tags.append({int(t): (v[0], v[1]) for t, v in cut["tags"].items()})
+        # ---- parity outside the timed region ---------------------------------------------------------------------------------------------------
+        # every stream's compressed size must be what the reference wrote (fixture: the files of its console application), the last
+        # picture of the first and last replica must have the reference decoder's plane CRCs where the fixture has them
+        # (a stream used whole: the files of the reference's console application, tests/golden/cli_*.npz; the first pictures of a longer
+        # stream: what the reference wrote after exactly those pictures, tests/golden/bench_cut.json - length and SHA-1 of every tag)
+        import hashlib
+        cuts = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_cut.json")))
+        sweep = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_sweep.json")))
+        ref_tagged, ref_tags = [], []
+        for k, name in enumerate(cfg["streams"]):
+            p = os.path.join(ROOT, "tests", "golden", "cli_" + name + ".npz")
+            cut = cuts.get("%s:%d" % (name, len(distinct[k])))
+            if os.path.exists(p) and whole[k]:
+                z = np.load(p)
+                ref_tags.append({int(f[4:]): (len(z[f]), hashlib.sha1(z[f].tobytes()).hexdigest()) for f in z.files if f.startswith("tag_")})
+            elif whole[k] and name in sweep and sweep[name].get("compress_rc") == 0:
+                # (the sweep of the unmodified reference over every shipped stream, tests/golden/ref_sweep.json: size and SHA-1 of every file)
+                ref_tags.append({int(t): (v[0], v[1]) for t, v in sweep[name]["files"].items() if t.isdigit()})
+            elif cut is not None and cut["pictures"] == len(distinct[k]):
+                ref_tags.append({int(t): (v[0], v[1]) for t, v in cut["tags"].items()})
+            else:
+                ref_tags.append(None)
+            ref_tagged.append(None if ref_tags[-1] is None else sum(v[0] for v in ref_tags[-1].values()))
+        # every batch that was coded in the timed steps: both sets of buffers when two batches are in flight
+        checked = {"batches": 0, "streams_sizes": 0, "streams_sha1": 0}
+        from losslessh264_amd.coder import TAG_OF_SLOT
+        for cd in coders:
+            ln = cd.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)
+            assert not ln[:, L.N_TAG_SLOTS].any(), "device coder status %s" % sorted(set(ln[:, L.N_TAG_SLOTS].tolist()))
+            checked["batches"] += 1
+            for c in range(n_local):
+                want = ref_tags[(my_kinds[0] + c) % len(distinct)]
+                if want is None:
+                    continue
+                got = {TAG_OF_SLOT[sl]: int(ln[c, sl]) for sl in range(35) if ln[c, sl]}
+                assert got == {t: v[0] for t, v in want.items() if v[0]}, "stream %d: tag sizes %s, the reference wrote %s" % (c, got, {t: v[0] for t, v in want.items()})
+                checked["streams_sizes"] += 1
+            for k in range(len(distinct)):                  # the bytes of the first and the last replica of every distinct stream
+                if ref_tags[k] is None:
+                    continue
+                reps = [i for i in range(n_local) if (my_kinds[0] + i) % len(distinct) == k]
+                for c in sorted({reps[0], reps[-1]}) if reps else []:
+                    tg = cd.tags(c)
+                    assert {t: hashlib.sha1(b).hexdigest() for t, b in tg.items()} == {t: v[1] for t, v in ref_tags[k].items() if v[0]}, "stream %d: coded bytes differ from the reference's" % c
+                    checked["streams_sha1"] += 1
+        roundtrip = None
+        if args.config == 1 and not args.mixed:
+            ref_frames = golden_io.load("bench_BA_MW_D.264")
+            for c in (0, n_local - 1):
+                got = sess.picture(c, len(order[0]) - 1)
+                assert [golden_io.crc(g) for g in got] == ref_frames[len(order[0]) - 1].crc_fin, "bench output differs from the reference"
+            tags = coder.tags(n_local - 1)
+            coded = sum(len(v) for v in tags.values())
+            assert len(mains[0]) + coded == 53739, "compressed size differs from the reference's 53,739 bytes"
+            roundtrip = {"ratio": (len(mains[0]) + coded) / len(datas[0]), "reference_ratio": 53739 / 55885, "roundtrip_ok": lh.restore(mains[0], tags) == datas[0]}
+            assert roundtrip["roundtrip_ok"], "restore(compress(stream)) differs from the stream"
         else:
-            ref_tags.append(None)
-        ref_tagged.append(None if ref_tags[-1] is None else sum(v[0] for v in ref_tags[-1].values()))
-    # every batch that was coded in the timed steps: both sets of buffers when two batches are in flight
-    checked = {"batches": 0, "streams_sizes": 0, "streams_sha1": 0}
-    from losslessh264_amd.coder import TAG_OF_SLOT
-    for cd in coders:
-        ln = cd.d_len.cpu().numpy().reshape(n_local, L.N_TAG_SLOTS + 1)
-        assert not ln[:, L.N_TAG_SLOTS].any(), "device coder status %s" % sorted(set(ln[:, L.N_TAG_SLOTS].tolist()))
-        checked["batches"] += 1
-        for c in range(n_local):
-            want = ref_tags[(my_kinds[0] + c) % len(distinct)]
-            if want is None:
-                continue
-            got = {TAG_OF_SLOT[sl]: int(ln[c, sl]) for sl in range(35) if ln[c, sl]}
-            assert got == {t: v[0] for t, v in want.items() if v[0]}, "stream %d: tag sizes %s, the reference wrote %s" % (c, got, {t: v[0] for t, v in want.items()})
-            checked["streams_sizes"] += 1
-        for k in range(len(distinct)):                  # the bytes of the first and the last replica of every distinct stream
-            if ref_tags[k] is None:
-                continue
-            reps = [i for i in range(n_local) if (my_kinds[0] + i) % len(distinct) == k]
-            for c in sorted({reps[0], reps[-1]}) if reps else []:
-                tg = cd.tags(c)
-                assert {t: hashlib.sha1(b).hexdigest() for t, b in tg.items()} == {t: v[1] for t, v in ref_tags[k].items() if v[0]}, "stream %d: coded bytes differ from the reference's" % c
-                checked["streams_sha1"] += 1
-    roundtrip = None
-    if args.config == 1 and not args.mixed:
-        ref_frames = golden_io.load("bench_BA_MW_D.264")
-        for c in (0, n_local - 1):
-            got = sess.picture(c, len(order[0]) - 1)
-            assert [golden_io.crc(g) for g in got] == ref_frames[len(order[0]) - 1].crc_fin, "bench output differs from the reference"
-        tags = coder.tags(n_local - 1)
-        coded = sum(len(v) for v in tags.values())
-        assert len(mains[0]) + coded == 53739, "compressed size differs from the reference's 53,739 bytes"
-        roundtrip = {"ratio": (len(mains[0]) + coded) / len(datas[0]), "reference_ratio": 53739 / 55885, "roundtrip_ok": lh.restore(mains[0], tags) == datas[0]}
-        assert roundtrip["roundtrip_ok"], "restore(compress(stream)) differs from the stream"
-    else:
-        # ratio of what was coded: the tagged streams against the share of the input they stand for (the default stream is per file)
-        roundtrip = {"tagged_bytes_per_input_byte": float(coded_local.sum()) / max(1.0, local_bytes),
-                     "coded_bytes_equal_reference_files": [w is not None for w in ref_tagged]}
-        if all(w is not None for w in ref_tagged) and all(whole):
-            # whole streams: size and round trip of one replica of every distinct stream, as for configs[1]
-            ok = True
-            for k in range(len(distinct)):
-                c = next(i for i in range(n_local) if (my_kinds[0] + i) % len(distinct) == k)
-                ok = ok and lh.restore(mains[k], coder.tags(c)) == datas[k]
-            # the reference's sizes: its console application's files (fixture), or the sweep's record of them
-            def ref_size(name):
-                q = os.path.join(ROOT, "tests", "golden", "cli_" + name + ".npz")
-                if os.path.exists(q):
-                    zz = np.load(q)
-                    return sum(len(zz[f]) for f in zz.files)
-                return sum(v[0] for v in sweep[name]["files"].values())
-            roundtrip.update({"ratio": sum(len(m) + w for m, w in zip(mains, ref_tagged)) / sum(len(d) for d in datas),
-                              "reference_ratio": sum(ref_size(name) for name in cfg["streams"]) / sum(len(d) for d in datas), "roundtrip_ok": ok})
-            assert ok, "restore(compress(stream)) differs from the stream"
+            # ratio of what was coded: the tagged streams against the share of the input they stand for (the default stream is per file)
+            roundtrip = {"tagged_bytes_per_input_byte": float(coded_local.sum()) / max(1.0, local_bytes),
+                         "coded_bytes_equal_reference_files": [w is not None for w in ref_tagged]}
+            if all(w is not None for w in ref_tagged) and all(whole):
+                # whole streams: size and round trip of one replica of every distinct stream, as for configs[1]
+                ok = True
+                for k in range(len(distinct)):
+                    c = next(i for i in range(n_local) if (my_kinds[0] + i) % len(distinct) == k)
+                    ok = ok and lh.restore(mains[k], coder.tags(c)) == datas[k]
+                # the reference's sizes: its console application's files (fixture), or the sweep's record of them
+                def ref_size(name):
+                    q = os.path.join(ROOT, "tests", "golden", "cli_" + name + ".npz")
+                    if os.path.exists(q):
+                        zz = np.load(q)
+                        return sum(len(zz[f]) for f in zz.files)
+                    return sum(v[0] for v in sweep[name]["files"].values())
+                roundtrip.update({"ratio": sum(len(m) + w for m, w in zip(mains, ref_tagged)) / sum(len(d) for d in datas),
+                                  "reference_ratio": sum(ref_size(name) for name in cfg["streams"]) / sum(len(d) for d in datas), "roundtrip_ok": ok})
+                assert ok, "restore(compress(stream)) differs from the stream"
 
-    # ---- multi-GPU: the per-stream result records of every rank, gathered and checked once on rank 0 ---------------------------------------
-    outv = coder.d_out.view(n_local, -1)
-    sums = torch.cat([outv[i:i + 8].sum(dim=1, dtype=torch.int64) for i in range(0, n_local, 8)]).cpu().numpy() if n_local else np.zeros(0, np.int64)
-    records = np.stack([np.arange(g0, g1, dtype=np.int64), coded_local, sums], axis=1) if n_local else np.zeros((0, 3), np.int64)
-    n_records = n_local
-    if dist is not None:
-        allrec = shard.gather_records(records, dist, device=coll_dev)
-        n_records = len(allrec)
-        if rank == 0:
-            assert sorted(allrec[:, 0].tolist()) == list(range(n_global)), "a stream was compressed twice or not at all"
-            for k in range(len(distinct)):
-                rows = allrec[np.array([kind_of[int(g)] == k for g in allrec[:, 0]])]
-                assert len(set(map(tuple, rows[:, 1:].tolist()))) == 1, "replicas of one stream differ between ranks"
+        # ---- multi-GPU: the per-stream result records of every rank, gathered and checked once on rank 0 ---------------------------------------
+        outv = coder.d_out.view(n_local, -1)
+        sums = torch.cat([outv[i:i + 8].sum(dim=1, dtype=torch.int64) for i in range(0, n_local, 8)]).cpu().numpy() if n_local else np.zeros(0, np.int64)
+        records = np.stack([np.arange(g0, g1, dtype=np.int64), coded_local, sums], axis=1) if n_local else np.zeros((0, 3), np.int64)
+        n_records = n_local
+        if dist is not None:
+            allrec = shard.gather_records(records, dist, device=coll_dev)
+            n_records = len(allrec)
+            if rank == 0:
+                assert sorted(allrec[:, 0].tolist()) == list(range(n_global)), "a stream was compressed twice or not at all"
+                for k in range(len(distinct)):
+                    rows = allrec[np.array([kind_of[int(g)] == k for g in allrec[:, 0]])]
+                    assert len(set(map(tuple, rows[:, 1:].tolist()))) == 1, "replicas of one stream differ between ranks"
 
-    host_stages = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.no_host and args.config == 1 and not args.mixed:
-        # host stages on this box's cores (rows f1 / f2): the front end (parse + default stream + syntax symbols) and the restore
-        # direction (adaptive decode + CAVLC writer), one stream per thread, bounded to a few seconds each; and the whole compress
-        # direction behind one C call, host bytes in -> host bytes out (parse, staging, PCIe, kernels, download)
-        data = datas[0]
-        tags = coder.tags(n_local - 1)
-        ncpu = min(16, len(os.sched_getaffinity(0)))      # a one-GPU box's CPU share is 16 cores
-        nb = 8 * ncpu
-        pt, npic = lh.parse_batch_time([data] * nb, ncpu, keep=False)
-        assert npic == nb * len(order[0])
-        t1 = time.perf_counter()
-        outs = lh.restore_batch([(mains[0], tags)] * nb, ncpu)
-        rt = time.perf_counter() - t1
-        assert all(o == data for o in outs)
-        # each size twice: the first call of a size also grows the device and page-locked arenas (reported apart), the second is the
-        # steady state of a service that keeps them
-        e2e_times = {}
-        for mult in (4, 16):                              # 512 streams: four groups already overlap parsing with the device stage
-            first = None
-            for attempt in range(2):
-                # the C call (host bytes in, handles to host bytes out); every stream's status and a few streams' bytes are checked
-                e2e = lh.compress_batch_handles([data] * (mult * nb), ncpu)
-                et = e2e.seconds
-                assert all(e2e.status(i) == 0 for i in range(e2e.n))
-                for i in (0, e2e.n // 2, e2e.n - 1):
-                    m_i, t_i, err_i = e2e.result(i)
-                    assert err_i is None and t_i == tags and m_i == mains[0]
-                e2e.free()
-                if attempt == 0:
-                    first = et
-            e2e_times[mult * nb] = (et, first)
-        host_stages = {"threads": ncpu, "front_end_MB_per_s": nb * len(data) / pt / 1e6, "restore_MB_per_s": nb * len(data) / rt / 1e6}
-        for ns, (et, first) in e2e_times.items():
-            host_stages["compress_batch_end_to_end_%d_streams_MB_per_s" % ns] = ns * len(data) / et / 1e6
-            host_stages["compress_batch_end_to_end_%d_streams_first_call_MB_per_s" % ns] = ns * len(data) / first / 1e6
+        host_stages = None
+        if rank == 0 and world == 1 and not args.no_cpu and not args.no_host and args.config == 1 and not args.mixed:
+            # host stages on this box's cores (rows f1 / f2): the front end (parse + default stream + syntax symbols) and the restore
+            # direction (adaptive decode + CAVLC writer), one stream per thread, bounded to a few seconds each; and the whole compress
+            # direction behind one C call, host bytes in -> host bytes out (parse, staging, PCIe, kernels, download)
+            data = datas[0]
+            tags = coder.tags(n_local - 1)
+            ncpu = min(16, len(os.sched_getaffinity(0)))      # a one-GPU box's CPU share is 16 cores
+            nb = 8 * ncpu
+            pt, npic = lh.parse_batch_time([data] * nb, ncpu, keep=False)
+            assert npic == nb * len(order[0])
+            t1 = time.perf_counter()
+            outs = lh.restore_batch([(mains[0], tags)] * nb, ncpu)
+            rt = time.perf_counter() - t1
+            assert all(o == data for o in outs)
+            # each size twice: the first call of a size also grows the device and page-locked arenas (reported apart), the second is the
+            # steady state of a service that keeps them
+            e2e_times = {}
+            for mult in (4, 16):                              # 512 streams: four groups already overlap parsing with the device stage
+                first = None
+                for attempt in range(2):
+                    # the C call (host bytes in, handles to host bytes out); every stream's status and a few streams' bytes are checked
+                    e2e = lh.compress_batch_handles([data] * (mult * nb), ncpu)
+                    et = e2e.seconds
+                    assert all(e2e.status(i) == 0 for i in range(e2e.n))
+                    for i in (0, e2e.n // 2, e2e.n - 1):
+                        m_i, t_i, err_i = e2e.result(i)
+                        assert err_i is None and t_i == tags and m_i == mains[0]
+                    e2e.free()
+                    if attempt == 0:
+                        first = et
+                e2e_times[mult * nb] = (et, first)
+            host_stages = {"threads": ncpu, "front_end_MB_per_s": nb * len(data) / pt / 1e6, "restore_MB_per_s": nb * len(data) / rt / 1e6}
+            for ns, (et, first) in e2e_times.items():
+                host_stages["compress_batch_end_to_end_%d_streams_MB_per_s" % ns] = ns * len(data) / et / 1e6
+                host_stages["compress_batch_end_to_end_%d_streams_first_call_MB_per_s" % ns] = ns * len(data) / first / 1e6
 
     if rank == 0:
         ms = dt / args.steps * 1e3
         total_bytes = local_bytes * world * args.steps        # every rank holds the same mix (weak scaling)
-        a18 = k_ms["recon"] + k_ms["ctx"]
         what = cfg["what"] % ((per_gpu,) if args.config == 1 else (len(order[0]), per_gpu))
-        mixed = None
-        if args.mixed:
-            # how much of the launch is the longest stream's own chain: one workgroup (or one (stream, partition) wave) cannot go faster
-            lone = lh.ReconSession([order[0]], device=local_rank)
-            lone.run(); torch.cuda.synchronize(dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); lone.run(); e1.record(); torch.cuda.synchronize(dev)
-            mbs = [sum(f.mb_w * f.mb_h for f in fr) for fr in order]
-            mixed = {"streams": cfg["streams"], "macroblocks_per_stream": mbs, "order": "the longest stream first within every group of %d consecutive workgroups" % len(order),
-                     "recon_chain_kernel_ms_longest_stream_alone": e0.elapsed_time(e1),
-                     "note": "one workgroup per stream: the launch cannot end before its longest stream's chain does; compare with stage_ms.a1_a7_recon_chain_kernel"}
         out = {
             "metric": "MB/s .264 recompressed (bit-exact roundtrip) + ratio, 1/2/4/8 MI355X",
             "value": total_bytes / dt / 1e6, "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -614,24 +655,41 @@ def main():
                                       "second HIP stream beside the context-index and coder kernels; streams sharded across GPUs",
                        "coder_form": ("stream per workgroup" if (os.environ.get("LH264_CODER_PATH") == "sw" or (os.environ.get("LH264_CODER_PATH") != "wave" and 384 <= n_local < 1024
                                                                          and sess.n_mbs_total / max(1, n_local) <= 12288)) else "wave per (stream, partition)"),
-                       "stage_ms_note": "stage times are from steps run on one stream; in the timed steps the stages overlap, ms_per_step is less than their sum",
                        "pipeline": ("two batches in flight: the context-index kernels (row a8) of the next batch run on a third HIP stream beside the second half of "
                                     "this batch's coder; every step launches every kernel of rows a1-a10 once" if pipeline else "none: every batch on its own"),
-                       "ms_per_step_one_batch_in_flight": unpipelined_ms,
-                       "stage_ms": {"a1_a7_recon_chain_kernel": k_ms["recon"], "a8_ctx_kernels": k_ms["ctx"], "a9_a10_coder_kernels": k_ms["coder"]},
-                       "a1_a8_only_MB_per_s": local_bytes / (a18 * 1e-3) / 1e6,
-                       "compression": roundtrip, "parity_checked": checked, "mixed_batch": mixed, "host_stages": host_stages,
-                       "multi_gpu": {"result_records_gathered": n_records, "global_streams": n_global, "collectives": collectives,
+                       "multi_gpu": {"global_streams": n_global, "collectives": collectives,
                                      "work_list": "no scatter: every rank derives its share of the global stream list locally (partition_by_work); one gather of result records",
                                      "measured_on_hardware": ("rehearsal: all ranks on GPU 0, gloo collectives - not a scaling measurement" if rehearse
                                                               else "this line" if world > 1 else "single GPU; N > 1 unmeasured in this run")}},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_note, "kernel": "recon_chain_kernel", "kernel_ms": recon_ms, "kernel_ms_alone": k_ms["recon"], "algorithmic_bytes_per_launch": alg_bytes,
-                         "coder_stage": {"bound": "hbm", "achieved": coder_bytes / (k_ms["coder"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                         "frac": coder_bytes / (k_ms["coder"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": k_ms["coder"], "algorithmic_bytes": coder_bytes, "traffic": coder_traffic,
-                                         "note": "symbols read twice + 8-byte decision words and 2-byte list entries written and read once + output; "
-                                                 "the stage is bound by two serial chains (per adaptive probability, per tag), not by HBM"}},
+                         "traffic": traffic, "traffic_source": traffic_note, "kernel": "recon_chain_kernel", "kernel_ms": recon_ms, "algorithmic_bytes_per_launch": alg_bytes},
         }
+    if rank == 0 and args.full:
+        a18 = k_ms["recon"] + k_ms["ctx"]
+        mixed = None
+        if args.mixed:
+            # how much of the launch is the longest stream's own chain: one workgroup (or one (stream, partition) wave) cannot go faster
+            lone = lh.ReconSession([order[0]], device=local_rank)
+            lone.run(); torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); lone.run(); e1.record(); torch.cuda.synchronize(dev)
+            mbs = [sum(f.mb_w * f.mb_h for f in fr) for fr in order]
+            mixed = {"streams": cfg["streams"], "macroblocks_per_stream": mbs, "order": "the longest stream first within every group of %d consecutive workgroups" % len(order),
+                     "recon_chain_kernel_ms_longest_stream_alone": e0.elapsed_time(e1),
+                     "note": "one workgroup per stream: the launch cannot end before its longest stream's chain does; compare with stage_ms.a1_a7_recon_chain_kernel"}
+        out["config"].update({
+            "stage_ms_note": "stage times are from steps run on one stream; in the timed steps the stages overlap, ms_per_step is less than their sum",
+            "ms_per_step_one_batch_in_flight": unpipelined_ms,
+            "stage_ms": {"a1_a7_recon_chain_kernel": k_ms["recon"], "a8_ctx_kernels": k_ms["ctx"], "a9_a10_coder_kernels": k_ms["coder"]},
+            "a1_a8_only_MB_per_s": local_bytes / (a18 * 1e-3) / 1e6,
+            "compression": roundtrip, "parity_checked": checked, "mixed_batch": mixed, "host_stages": host_stages})
+        out["config"]["multi_gpu"]["result_records_gathered"] = n_records
+        out["roofline"].update({
+            "kernel_ms_alone": k_ms["recon"],
+            "coder_stage": {"bound": "hbm", "achieved": coder_bytes / (k_ms["coder"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": coder_bytes / (k_ms["coder"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": k_ms["coder"], "algorithmic_bytes": coder_bytes, "traffic": coder_traffic,
+                            "note": "symbols read twice + 8-byte decision words and 2-byte list entries written and read once + output; "
+                                    "the stage is bound by two serial chains (per adaptive probability, per tag), not by HBM"}})
         if world == 1 and not args.no_cpu:
             ncpu = min(16, len(os.sched_getaffinity(0)))
             v, reps, secs = cpu_baseline(order[0], stream_bytes[0], args.cpu_seconds, ncpu)
@@ -647,6 +705,7 @@ def main():
             ref = reference_cli_baseline(os.path.join(ROOT, "tests", "golden", "streams", cfg["streams"][0]), len(datas[0]), nproc)
             if ref is not None:
                 out["cpu_baseline"]["reference_cli"] = ref
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

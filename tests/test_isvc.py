@@ -1,7 +1,8 @@
 """The coarse boundary (include/lh264_isvc.h): an ISVCDecoder-compatible object in liblh264.so.
 
-CPU part: exported symbols, structure layouts (against the reference's codec_api.h when /root/reference is present, and
-against the committed numbers always), virtual-table order through the C view of the interface, loud failure without a GPU.
+CPU part: exported symbols, structure layouts (against the committed numbers, and those against what the same probe printed
+for the reference's codec_api.h where oracle/Makefile built it), virtual-table order through the C view of the interface, loud
+failure without a GPU.
 GPU part: a client application (tests/isvc_client.cpp) decodes the golden streams through the vtable and its YUV must hash to
 the reference's decoder-test SHA-1 table (tests/golden/decoder_sha1.json, from test/api/decoder_test.cpp:82-126)."""
 import ctypes
@@ -17,25 +18,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
 SO_DIR = os.path.join(ROOT, "losslessh264_amd")
-REF_API = "/root/reference/codec/api/svc"
 
-LAYOUT_PROBE = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include HEADER
-int main() {
-  printf("%zu %zu %zu %zu %zu %zu %zu ", sizeof(SDecodingParam), sizeof(SBufferInfo), sizeof(SSysMEMBuffer), sizeof(SDecoderCapability),
-         sizeof(SParserBsInfo), sizeof(SDecoderStatistics), sizeof(OpenH264Version));
-  printf("%zu %zu %zu %zu %zu %zu ", offsetof(SDecodingParam, eOutputColorFormat), offsetof(SDecodingParam, uiTargetDqLayer),
-         offsetof(SDecodingParam, eEcActiveIdc), offsetof(SDecodingParam, bParseOnly), offsetof(SDecodingParam, sVideoProperty),
-         offsetof(SBufferInfo, UsrData));
-  printf("%zu %zu %zu ", offsetof(SBufferInfo, uiOutYuvTimeStamp), offsetof(SParserBsInfo, pDstBuff), offsetof(SDecoderStatistics, iAvgLumaQp));
-  printf("%d %d %d %d %d %d %d\n", (int)dsInitialOptExpected, (int)dsDstBufNeedExpan, (int)DECODER_OPTION_GET_STATISTICS,
-         (int)ERROR_CON_SLICE_MV_COPY_CROSS_IDR_FREEZE_RES_CHANGE, (int)videoFormatI420, (int)cmUnsupportedData, (int)FEEDBACK_UNKNOWN_NAL);
-  return 0;
-}
-'''
-# the numbers the probe prints for the reference's codec_api.h on x86-64 (regenerate: run the probe with REF_API)
+LAYOUT_PROBE = os.path.join(ROOT, "tests", "isvc_layout_probe.cpp")
+# the numbers the probe prints for the reference's codec_api.h on x86-64 (oracle/Makefile writes them to oracle/_ref/isvc_layout_refhdr.txt)
 LAYOUT_EXPECTED = "40 48 20 36 552 84 16 8 16 20 24 28 24 16 520 56 8192 32768 12 7 23 5 2"
 
 
@@ -51,10 +36,8 @@ def _compile(src_path, out, extra=()):
 
 
 def _probe(tmp_path, header, incdir):
-    src = tmp_path / "probe.cpp"
-    src.write_text(LAYOUT_PROBE.replace("HEADER", '"%s"' % header))
     exe = str(tmp_path / "probe")
-    subprocess.check_call(["g++", "-std=c++11", "-I", incdir, str(src), "-o", exe])
+    subprocess.check_call(["g++", "-std=c++11", '-DLH264_PROBE_HEADER="%s"' % header, "-I", incdir, LAYOUT_PROBE, "-o", exe])
     return subprocess.check_output([exe]).decode().strip()
 
 
@@ -74,9 +57,13 @@ def test_layouts_match_committed_numbers(tmp_path):
     assert _probe(tmp_path, "lh264_isvc.h", INC) == LAYOUT_EXPECTED
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_API, "codec_api.h")), reason="reference tree not present")
-def test_layouts_match_reference_header(tmp_path):
-    assert _probe(tmp_path, "codec_api.h", REF_API) == LAYOUT_EXPECTED
+def test_layouts_match_reference_header():
+    """the probe compiled against the reference's own codec_api.h (oracle/Makefile, built where the reference's sources are) printed
+    the committed numbers"""
+    out = os.path.join(ROOT, "oracle", "_ref", "isvc_layout_refhdr.txt")
+    if not os.path.exists(out):
+        pytest.skip("oracle/_ref/isvc_layout_refhdr.txt not built")
+    assert open(out).read().strip() == LAYOUT_EXPECTED
 
 
 C_VTABLE_CLIENT = r'''

@@ -6,7 +6,7 @@ P=$1
 cd /tmp; export TMPDIR=/tmp
 for c in 2 3 4; do
   OUT=$R/gpurun_out/${P}_cfg$c; mkdir -p $OUT
-  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --config $c --steps 3 --warmup 1 --no-cpu > $OUT/bench.log 2>&1 || { echo "config $c failed"; tail -5 $OUT/bench.log; exit 1; }
+  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --config $c --steps 3 --warmup 1 --no-cpu > $OUT/bench.log 2>&1 || { echo "config $c failed"; tail -5 $OUT/bench.log; exit 1; }
   cp $(ls $OUT/stats/*/*kernel_stats.csv | head -1) $OUT/${P}_cfg${c}_kernel_stats.csv
   grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
   rm -rf $OUT/stats

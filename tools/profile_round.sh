@@ -9,7 +9,7 @@ C=${2:-1}
 cd /tmp; export TMPDIR=/tmp
 OUT=$R/gpurun_out/$N; mkdir -p $OUT
 T=${N}_cfg$C
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats$C -- python3 $R/bench.py --config $C --steps 5 --warmup 2 --no-cpu --no-host > $OUT/$T.bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats$C -- python3 $R/bench.py --full --config $C --steps 5 --warmup 2 --no-cpu --no-host > $OUT/$T.bench.log 2>&1
 grep '^{' $OUT/$T.bench.log | tail -1 > $OUT/${T}_bench.json
 cp $(ls $OUT/stats$C/*/*kernel_stats.csv | head -1) $OUT/${T}_kernel_stats.csv
 rm -rf $OUT/stats$C

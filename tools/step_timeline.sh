@@ -3,7 +3,7 @@
 cd /tmp; export TMPDIR=/tmp
 R=/root/repo
 OUT=$R/gpurun_out/$1; mkdir -p $OUT; shift
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu --no-host "$@" > $OUT/bench.log 2>&1 || { tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu --no-host "$@" > $OUT/bench.log 2>&1 || { tail -5 $OUT/bench.log; exit 1; }
 python3 - $OUT <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/tr/*/*kernel_trace.csv')[0]
