@@ -35,7 +35,7 @@ __global__ void coder_emit_kernel (const lh264_code_job_t* jobs, const uint32_t*
                                    const uint32_t* seg_doff, const uint32_t* seg_cnt, const uint32_t* seg_part, const uint8_t* chain_map, const uint32_t* chain_info, uint64_t* D);
 __global__ void coder_resolve_kernel (const lh264_code_stream_t* streams, uint32_t* chain_info, const uint32_t* seg0, const int32_t* chain_first,
                                       const uint32_t* seg_doff, const uint32_t* seg_part, const uint64_t* D, uint16_t* Q, int n_chains, int log2p, uint32_t* progress, int window);
-__global__ void coder_chunkmap_kernel (const uint32_t* chain_info, int n_pairs, uint32_t* pair_chunk0, uint32_t* pair_coarse0, uint32_t* cand_list);
+__global__ void coder_chunkmap_kernel (uint32_t* chain_info, int n_pairs, uint32_t* pair_chunk0, uint32_t* pair_coarse0, uint32_t* cand_list);
 __global__ void coder_range_seed_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_coarse0, int n_pairs, uint32_t* cand, uint32_t* cand_list, uint32_t long_list);
 __global__ void coder_range_first_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_chunk0, const uint32_t* pair_coarse0, int n_pairs, int groups,
                                           unsigned n_cand, unsigned n_later, const uint32_t* cand, const uint32_t* cand_list, uint8_t* cand_end, uint8_t* cmap, uint32_t* chunk_rec, uint32_t* coarse_bits);
@@ -682,22 +682,51 @@ long long lh264_debug_coder_seeds (uint32_t* out, long long cap) {
 }
 #endif
 // tuning aid (not declared in lh264.h): decisions per partition of stream `chain` of the last wave-form coder call on the current device;
-// returns the number of partitions, -1 if there is nothing to read
+// returns the number of partitions, -1 if the last call took the sw form, -2 if there is nothing to read
 int lh264_debug_coder_parts (int chain, unsigned long long* out, int cap) {
   int dev = 0; (void)hipGetDevice (&dev);
   CoderWs& W = g_coder_ws[dev];
-  if (W.sw || !W.seg_part || !W.seg0 || !W.chain_first) return -1;
+  if (W.sw) return -1;
+  if (!W.seg_part || !W.seg0 || !W.chain_first) return -2;
   (void)hipDeviceSynchronize();
   int32_t cf[2]; uint32_t sg[2];
-  if (hipMemcpy (cf, W.chain_first + chain, 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (hipMemcpy (&sg[0], W.seg0 + cf[0], 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy (&sg[1], W.seg0 + cf[1], 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy (cf, W.chain_first + chain, 8, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hipMemcpy (&sg[0], W.seg0 + cf[0], 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy (&sg[1], W.seg0 + cf[1], 4, hipMemcpyDeviceToHost) != hipSuccess) return -2;
   const int P = 1 << W.log2p;
-  if (P > cap) return -1;
+  if (P > cap) return -2;
   std::vector<uint32_t> rows ((size_t) (sg[1] - sg[0]) * (size_t) (P + 1));
-  if (hipMemcpy (rows.data(), W.seg_part + (size_t)sg[0] * (size_t) (P + 1), rows.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy (rows.data(), W.seg_part + (size_t)sg[0] * (size_t) (P + 1), rows.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -2;
   for (int p = 0; p < P; p++) out[p] = 0;
   for (size_t g = 0; g < sg[1] - sg[0]; g++) for (int p = 0; p < P; p++) out[p] += rows[g * (P + 1) + p + 1] - rows[g * (P + 1) + p];
   return P;
+}
+// tuning aid (not declared in lh264.h): the coarse chunks of the range walk of the last coder call on the current device, by the way
+// coder_range_seed_kernel left them (lh264_coder.hip): out[0] first chunk of a list, [1] walked on from the chunk before (list up to
+// long_list), [2] one candidate start state, [3] 2 .. CODE_CANDS candidates, [4] the whole state map (CODE_MAPPED).  Returns the number of
+// coarse chunks, -1 if there is nothing to read.  Reads what the call left; changes nothing.
+int lh264_debug_coder_range_paths (unsigned long long out[5]) {
+  int dev = 0; (void)hipGetDevice (&dev);
+  CoderWs& W = g_coder_ws[dev];
+  if (!out || !W.pair_coarse0 || !W.cand || W.n_pairs_last <= 0) return -1;
+  (void)hipDeviceSynchronize();
+  std::vector<uint32_t> pc ((size_t)W.n_pairs_last + 1);
+  if (hipMemcpy (pc.data(), W.pair_coarse0, pc.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const uint32_t total = pc.back();
+  if (total > W.coarse_bound) return -1;
+  std::vector<uint32_t> cw ((size_t)total * 2 + 1);
+  if (total && hipMemcpy (cw.data(), W.cand, (size_t)total * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  for (int k = 0; k < 5; k++) out[k] = 0;
+  size_t p = 0;
+  for (uint32_t G = 0; G < total; G++) {
+    while (p + 1 < pc.size() - 1 && pc[p + 1] <= G) p++;                  // the pair G belongs to (pairs without chunks are skipped)
+    const uint32_t lo = cw[2 * (size_t)G], hi = cw[2 * (size_t)G + 1];
+    if (G == pc[p]) out[0]++;
+    else if (hi == 0xffffffffu && lo == 0u) out[4]++;
+    else if (lo == 0u && hi == 0u) out[1]++;
+    else if ((lo >> 8) == 0u && hi == 0u) out[2]++;
+    else out[3]++;
+  }
+  return (int)total;
 }
 #ifdef LH264_STAMP
 // diagnostic builds only (not declared in lh264.h)

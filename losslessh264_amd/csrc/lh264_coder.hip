@@ -1170,9 +1170,12 @@ __device__ __forceinline__ PairInfo pair_info (const uint32_t* chain_info, const
   return P;
 }
 
-// kernel 6: chunks per (stream, tag) pair and their running sum (one workgroup)
+// kernel 6: chunks per (stream, tag) pair and their running sum (one workgroup).  A stream whose status is already set (its resolve did
+// not run - hash_cap invalid - or did not finish its lists) is not coded: the tag lists of such a stream hold whatever the work memory
+// held before, and a walk over them shifts out any number of bits - the zeroing of its sums in coder_range_scan_kernel then wrote far
+// beyond them.  Its lists are dropped here (counts and touch mask cleared), so every later kernel sees a stream without tags.
 __global__ void __launch_bounds__ (CODER_ONE_WG)
-coder_chunkmap_kernel (const uint32_t* __restrict__ chain_info, int n_pairs, uint32_t* __restrict__ pair_chunk0, uint32_t* __restrict__ pair_coarse0, uint32_t* __restrict__ cand_list) {
+coder_chunkmap_kernel (uint32_t* __restrict__ chain_info, int n_pairs, uint32_t* __restrict__ pair_chunk0, uint32_t* __restrict__ pair_coarse0, uint32_t* __restrict__ cand_list) {
   if (threadIdx.x == 0) cand_list[0] = 0;                  // the walks from candidate start states the seed kernel will ask for
   __shared__ uint32_t wsum[16], wsum2[16];
   __shared__ uint32_t carry, carry2;
@@ -1184,10 +1187,14 @@ coder_chunkmap_kernel (const uint32_t* __restrict__ chain_info, int n_pairs, uin
     uint32_t v = 0, v2 = 0;
     if (p < n_pairs) {
       const uint32_t chain = (uint32_t)p / LH264_N_TAG_SLOTS, slot = (uint32_t)p % LH264_N_TAG_SLOTS;
-      const uint32_t* I = chain_info + (size_t)chain * LH264_CODER_INFO_WORDS;
-      const uint32_t n = slot < 35u ? I[LH264_CODER_INFO_TAGCNT + slot] : 0u;
-      const unsigned long long tm = (unsigned long long)I[LH264_CODER_INFO_TOUCH] | (unsigned long long)I[LH264_CODER_INFO_TOUCH + 1] << 32;
-      if (slot < 35u && (n > 0u || ((tm >> slot) & 1ull))) { v = (n + 32u + CODE_CHUNK - 1u) / CODE_CHUNK; v2 = (n + 32u + CODE_COARSE - 1u) / CODE_COARSE; }
+      uint32_t* I = chain_info + (size_t)chain * LH264_CODER_INFO_WORDS;
+      const bool dead = I[LH264_CODER_INFO_STATUS] != 0u;
+      if (dead) { I[LH264_CODER_INFO_TAGCNT + slot] = 0u; if (slot == 0u) { I[LH264_CODER_INFO_TOUCH] = 0u; I[LH264_CODER_INFO_TOUCH + 1] = 0u; } }
+      else {                                               // (the touch mask is read only by the lanes of live streams: nothing here clears it)
+        const uint32_t n = slot < 35u ? I[LH264_CODER_INFO_TAGCNT + slot] : 0u;
+        const unsigned long long tm = (unsigned long long)I[LH264_CODER_INFO_TOUCH] | (unsigned long long)I[LH264_CODER_INFO_TOUCH + 1] << 32;
+        if (slot < 35u && (n > 0u || ((tm >> slot) & 1ull))) { v = (n + 32u + CODE_CHUNK - 1u) / CODE_CHUNK; v2 = (n + 32u + CODE_COARSE - 1u) / CODE_COARSE; }
+      }
     }
     const uint32_t incl = (uint32_t)wave_scan_add ((int)v), incl2 = (uint32_t)wave_scan_add ((int)v2);
     if (lane == 63) { wsum[wave] = incl; wsum2[wave] = incl2; }

@@ -42,7 +42,7 @@ def test_device_coder_equals_reference_bytes(path, monkeypatch):
             assert got[t] == refs[c][t], "%s tag %d: %d bytes, reference %d" % (name, t, len(got[t]), len(refs[c][t]))
 
 
-@pytest.mark.parametrize("log2p,window", [(0, 3), (2, 0), (4, 1), (5, 3), (7, 0)])
+@pytest.mark.parametrize("log2p,window", [(0, 3), (2, 0), (3, 3), (4, 1), (5, 3), (7, 0)])
 def test_wave_form_partitions_and_window_do_not_change_the_bytes(log2p, window, monkeypatch):
     """the wave form with 1 .. 128 partitions per stream (buckets of cells dealt to the partitions by coder_balance_kernel; 128 = the
     buckets themselves) and with / without the hint that keeps a stream's waves together: ten streams, so that the workgroups of the

@@ -51,3 +51,22 @@ def test_synthetic_levels_batch():
     sess.run(); sess.synchronize()
     for c in range(sess.n_chains):
         _check_stream(sess, c, streams[c % 3], False)
+
+
+def test_synthetic_full_macroblocks_at_int16_extremes():
+    """density 1.0, amplitude 32767, 8x8 transform: macroblocks with every coefficient symbol and levels at the ends of int16 through
+    the context-index kernels and the compact pool"""
+    import losslessh264_amd as lh
+    import synth
+    fr = synth.make_stream(seed=77, mb_w=6, mb_h=5, n_frames=3, t8=True, density=1.0, amp=32767)
+    for j, f in enumerate(fr):
+        f.levels = f.coeffs
+        f.frame_num = j
+    lv = np.concatenate([np.asarray(f.levels, dtype=np.int16).reshape(-1) for f in fr])
+    assert lv.max() >= 32000 and lv.min() <= -32000
+    sess = lh.CtxSession([fr], replicate=2)
+    sess.run(); sess.synchronize()
+    for c in range(sess.n_chains):
+        _check_stream(sess, c, fr, False)
+    most = max(int(sess.frame_symbols(0, i)[0].max()) for i in range(len(fr)))
+    assert most >= 400, most                    # (at most LH264_CTX_MAX_SYMS = 432 per macroblock)
