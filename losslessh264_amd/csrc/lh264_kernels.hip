@@ -821,25 +821,24 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
     } else lrow[0] = lrow[1] = lrow[3] = lrow[4] = lrow[5] = (v4u) (0u);     // never read (every strip has fy == 0)
 #endif
   }
-  v2u crow[2][2];                                   // [pair h][row]
-  int cinfo[2], csh[2], crb[2];
-  if (lane < 32) {
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int cx = cx0 + 2 * h;
-      crb[h] = (cy >> 1) * 4 + (cx >> 1);
-      cinfo[h] = L.mvi[crb[h]][2];
-      const GLB uint8_t* plane = (const GLB uint8_t*)L.refp[(cinfo[h] >> 12) & 15][1 + cp];
-      const uintptr_t a0 = (uintptr_t) (plane + L.mvi[crb[h]][1] + (cy & 1) * F.sc);
-      csh[h] = (int) (a0 & 3);
-      const GLB uint8_t* q = (const GLB uint8_t*) (a0 & ~ (uintptr_t)3);
+  // chroma: lane l and lane l + 32 share the 4-sample strip of lane l < 32; half h = l >> 5 takes the pair at columns
+  // cx0 + 2h, cx0 + 2h + 1 (one motion vector: a 4x4 luma block is a 2x2 chroma block)
+  const int ch = lane >> 5, cx = cx0 + 2 * ch;
+  const int crb = (cy >> 1) * 4 + (cx >> 1);
+  const int cinfo = L.mvi[crb][2];
+  v2u crow[2];                                      // [row]
+  int csh;
+  {
+    const GLB uint8_t* plane = (const GLB uint8_t*)L.refp[(cinfo >> 12) & 15][1 + cp];
+    const uintptr_t a0 = (uintptr_t) (plane + L.mvi[crb][1] + (cy & 1) * F.sc);
+    csh = (int) (a0 & 3);
+    const GLB uint8_t* q = (const GLB uint8_t*) (a0 & ~ (uintptr_t)3);
 #ifdef LH264_ABL_NOMC
-      crow[h][0] = crow[h][1] = (v2u) ((uint32_t) (uintptr_t)q);
+    crow[0] = crow[1] = (v2u) ((uint32_t) (uintptr_t)q);
 #else
-      crow[h][0] = * (const GLB v2u*)q;
-      crow[h][1] = * (const GLB v2u*) (q + F.sc);
+    crow[0] = * (const GLB v2u*)q;
+    crow[1] = * (const GLB v2u*) (q + F.sc);
 #endif
-    }
   }
   // ---- luma ------------------------------------------------------------------------------------------------------
   int pr[4], res[4];
@@ -857,33 +856,28 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
   res[0] = res[1] = res[2] = res[3] = 0;
   if (has_res) load_res4 (L.R, lane, res);
   * (LDS uint32_t*)&L.T[tY (ly, lx0)] = pack_add4 (pr, res);
-  // ---- chroma strip: plane cp, row cy, cols cx0..cx0+3 = two luma 4x4 blocks wide ----------------------------------
-  if (lane < 32) {
-    int cpr[4], cres[4];
+  // ---- chroma pair: plane cp, row cy, cols cx, cx+1 --------------------------------------------------------------
+  {
+    int cpr[2];
+    const uint32_t a = __builtin_amdgcn_alignbyte (crow[0].y, crow[0].x, csh);
+    const uint32_t bb = __builtin_amdgcn_alignbyte (crow[1].y, crow[1].x, csh);
+    mc_chroma_rows (a, bb, (cinfo >> 4) & 7, (cinfo >> 8) & 7, cpr[0], cpr[1]);
+    if (wp) {
+      // reference quirk (rec_mb.cpp:309-311): only the top-left (w>>2)x(h>>2) samples of the chroma block are weighted
+      const int geo = L.mvi[crb][3];
+      const int pox = (geo & 0xff) >> 1, poy = ((geo >> 8) & 0xff) >> 1, pw = (geo >> 16) & 0xff, ph = (geo >> 24) & 0xff;
+      const int ri = (cinfo >> 16) & 15, ld = sl.chroma_denom(), wt = sl.chroma_weight (ri, cp), of = sl.chroma_offset (ri, cp);
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int cx = cx0 + 2 * h;
-      const int info = cinfo[h];
-      const uint32_t a = __builtin_amdgcn_alignbyte (crow[h][0].y, crow[h][0].x, csh[h]);
-      const uint32_t bb = __builtin_amdgcn_alignbyte (crow[h][1].y, crow[h][1].x, csh[h]);
-      mc_chroma_rows (a, bb, (info >> 4) & 7, (info >> 8) & 7, cpr[2 * h], cpr[2 * h + 1]);
-      if (wp) {
-        // reference quirk (rec_mb.cpp:309-311): only the top-left (w>>2)x(h>>2) samples of the chroma block are weighted
-        const int geo = L.mvi[crb[h]][3];
-        const int pox = (geo & 0xff) >> 1, poy = ((geo >> 8) & 0xff) >> 1, pw = (geo >> 16) & 0xff, ph = (geo >> 24) & 0xff;
-        const int ri = (info >> 16) & 15, ld = sl.chroma_denom(), wt = sl.chroma_weight (ri, cp), of = sl.chroma_offset (ri, cp);
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-          if (cx + i - pox < (pw >> 2) && cy - poy < (ph >> 2)) {
-            const int v = cpr[2 * h + i];
-            cpr[2 * h + i] = clip_u8 (ld >= 1 ? ((v * wt + (1 << (ld - 1))) >> ld) + of : v * wt + of);
-          }
+      for (int i = 0; i < 2; i++) {
+        if (cx + i - pox < (pw >> 2) && cy - poy < (ph >> 2)) {
+          const int v = cpr[i];
+          cpr[i] = clip_u8 (ld >= 1 ? ((v * wt + (1 << (ld - 1))) >> ld) + of : v * wt + of);
         }
       }
     }
-    cres[0] = cres[1] = cres[2] = cres[3] = 0;
-    if (has_res) load_res4 (L.R + 256, lane, cres);
-    * (LDS uint32_t*)&L.C[cp][tC (cy, cx0)] = pack_add4 (cpr, cres);
+    // residual of the pair: int16 values 2h, 2h + 1 of the strip's 4 (load_res4 layout)
+    const int cr = has_res ? * (const LDS int32_t*) (L.R + 256 + 4 * (lane & 31) + 2 * ch) : 0;
+    * (LDS uint16_t*)&L.C[cp][tC (cy, cx)] = (uint16_t) (clip_u8 (cpr[0] + sext16 (cr)) | clip_u8 (cpr[1] + (cr >> 16)) << 8);
   }
 }
 
@@ -947,25 +941,25 @@ __device__ __forceinline__ void filter_edge (int& rp3, int& rp2, int& rp1, int& 
   const bool on = bs != 0 && d < alpha && absd (p1, p0) < beta && absd (q1, q0) < beta;
   const bool ap = !chroma && absd (p2, p0) < beta, aq = !chroma && absd (q2, q0) < beta;
   // bS < 4
-  const int t = chroma ? tc0 + 1 : tc0 + (ap ? 1 : 0) + (aq ? 1 : 0);
+  const int t = tc0 + (ap ? 1 : 0) + (aq ? 1 : 0) + (chroma ? 1 : 0);    // (ap, aq are false on chroma lines)
   const int dl = clip3 ((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3, -t, t);
   const int avg = (p0 + q0 + 1) >> 1;
-  int np0 = clip_u8 (p0 + dl), nq0 = clip_u8 (q0 - dl);
-  int np1 = ap ? p1 + clip3 ((p2 + avg - (p1 << 1)) >> 1, -tc0, tc0) : p1;
-  int nq1 = aq ? q1 + clip3 ((q2 + avg - (q1 << 1)) >> 1, -tc0, tc0) : q1;
-  int np2 = p2, nq2 = q2;
-  if (__ballot (on && bs == 4)) {                   // wave-uniform
+  const int np0 = clip_u8 (p0 + dl), nq0 = clip_u8 (q0 - dl);
+  const int np1 = p1 + (ap ? clip3 ((p2 + avg - (p1 << 1)) >> 1, -tc0, tc0) : 0);
+  const int nq1 = q1 + (aq ? clip3 ((q2 + avg - (q1 << 1)) >> 1, -tc0, tc0) : 0);
+  // p2 / q2 change under bS 4 only: the normal filter selects four samples, the strong one overrides up to six
+  rp0 = on ? np0 : p0; rq0 = on ? nq0 : q0; rp1 = on ? np1 : p1; rq1 = on ? nq1 : q1;
+  const bool on4 = on && bs == 4;
+  if (__ballot (on4)) {                             // wave-uniform
     const bool small = !chroma && d < ((alpha >> 2) + 2);
     const bool sp = small && ap, sq = small && aq;
-    const int s4 = bs == 4;
     const int wp0 = (2 * p1 + p0 + q1 + 2) >> 2, wq0 = (2 * q1 + q0 + p1 + 2) >> 2;
     const int xp0 = sp ? (p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3 : wp0;
     const int xq0 = sq ? (p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3 : wq0;
     const int xp1 = sp ? (p2 + p1 + p0 + q0 + 2) >> 2 : p1, xq1 = sq ? (p0 + q0 + q1 + q2 + 2) >> 2 : q1;
     const int xp2 = sp ? (2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3 : p2, xq2 = sq ? (2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3 : q2;
-    np0 = s4 ? xp0 : np0; nq0 = s4 ? xq0 : nq0; np1 = s4 ? xp1 : np1; nq1 = s4 ? xq1 : nq1; np2 = s4 ? xp2 : np2; nq2 = s4 ? xq2 : nq2;
+    rp0 = on4 ? xp0 : rp0; rq0 = on4 ? xq0 : rq0; rp1 = on4 ? xp1 : rp1; rq1 = on4 ? xq1 : rq1; rp2 = on4 ? xp2 : p2; rq2 = on4 ? xq2 : q2;
   }
-  rp0 = on ? np0 : p0; rq0 = on ? nq0 : q0; rp1 = on ? np1 : p1; rq1 = on ? nq1 : q1; rp2 = on ? np2 : p2; rq2 = on ? nq2 : q2;
 }
 
 // WelsDeblockingMb (deblocking.cpp:815-862) + FilteringEdgeLumaHV / FilteringEdgeChromaHV (:568-700): the macroblock's
