@@ -419,6 +419,26 @@ typedef struct lh264_restore_item {
 } lh264_restore_item_t;
 int lh264_pip_restore_batch (lh264_restore_item_t* items, int n, int threads);
 
+/* ---- restore direction on the device (csrc/lh264_restore.hip) ------------------------------------------------------------
+ * lh264_pip_restore_batch_device: the same n restores, with the same status, out and out_len per item as lh264_pip_restore_batch
+ * (LH264_E_ARG with out_len = the size needed included), synchronously on the current device.  Host pass 1 reads the slice headers
+ * of each default stream (`threads` host threads, 0 = all); one single-wave workgroup per CAVLC stream runs the adaptive decode and
+ * the CAVLC macroblock writer; host pass 2 splices the slices' bits behind their headers.  path_out[i] (may be NULL) tells how item
+ * i was restored.  Without a device: LH264_E_NODEVICE, the items untouched.  Device and page-locked buffers are kept between calls
+ * (lh264_restore_release frees them); concurrent calls on one device are serialised by a lock. */
+#define LH264_RESTORE_PATH_DEVICE   0   /* restored by the kernel                                                               */
+#define LH264_RESTORE_PATH_HOST     1   /* the stream has CABAC slices: the host restore, beside the kernel                      */
+#define LH264_RESTORE_PATH_FALLBACK 2   /* the device path stopped (capacity, corrupt input, I_PCM without samples): lh264_pip_restore */
+int lh264_pip_restore_batch_device (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+void lh264_restore_release (void);
+/* milliseconds of the last lh264_pip_restore_batch_device call in this process: ms[0] host pass 1 and staging, ms[1] the device
+ * stage (upload, kernel, download; the CABAC streams on the host meanwhile), ms[2] the kernel alone (HIP events), ms[3] host pass 2
+ * and the fallbacks */
+int lh264_restore_last_timing (double* ms);
+/* the kernel's code (csrc/lh264_restore.hip) stepped on the host threads over host memory, with the same plan, capacities and
+ * results as lh264_pip_restore_batch_device: a check of the device chain where no device is present; not a restore path */
+int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+
 #define LH264_OK            0
 #define LH264_E_NODEVICE   -1
 #define LH264_E_ARG        -2

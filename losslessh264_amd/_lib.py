@@ -161,4 +161,9 @@ CODE_STREAM_DTYPE = np.dtype([("hash_keys", "<u8"), ("hash_cells", "<u8"), ("out
 N_TAG_SLOTS = 40
 assert CODE_JOB_DTYPE.itemsize == 56 and CODE_STREAM_DTYPE.itemsize == 40
 _SIGS["lh264_code_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p])
+# ---- restore direction on the device
+_SIGS["lh264_pip_restore_batch_device"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_SIGS["lh264_debug_restore_cpu"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_SIGS["lh264_restore_release"] = (None, [])
+_SIGS["lh264_restore_last_timing"] = (C.c_int, [C.POINTER(C.c_double)])
 EXPORTS = sorted(_SIGS)

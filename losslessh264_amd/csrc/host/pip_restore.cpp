@@ -9,6 +9,7 @@
 #include "h264_tables.h"
 #include "h264_vlc_tables.h"
 #include "h264_cabac_tables.h"
+#include "../lh264_restore.h"
 
 namespace lh264host {
 namespace {
@@ -204,24 +205,97 @@ struct MbDec {                        // one decoded macroblock
   int16_t lev[384];
 };
 
-class Restorer {
+// the default stream, chunk by chunk as the console application feeds it back (h264dec.cpp:246-272, DC:658-860): everything but the
+// slice data is copied through, each slice header is parsed and written, and on_slice (H) writes the slice data behind it
+// (false: stop).  One walk serves the host restore (Restorer::decode_slice) and the two host passes of the device restore.
+class Walker {
  public:
-  Restorer (const uint8_t* const* tags, const size_t* tag_len, int n_tags, std::string& err) : err_ (err) {
+  explicit Walker (std::string& err) : err_ (err) {}
+ protected:
+  std::string& err_;
+  bool failed_ = false;
+  Parser hdr_;
+  MainStreamWriter w_;
+  void fail (const std::string& m) { if (!failed_) { failed_ = true; err_ = m; } }
+  template <class OnSlice> int walk (const uint8_t* d, size_t n, std::vector<uint8_t>& out, OnSlice on_slice);
+};
+
+template <class OnSlice> int Walker::walk (const uint8_t* d, size_t n, std::vector<uint8_t>& out, OnSlice on_slice) {
+  size_t pos = 0;
+  std::vector<uint8_t> nal;
+  auto at = [&] (size_t i) -> int { return i < n ? d[i] : (i == n + 3 ? 1 : 0); };
+  while (pos < n && !failed_) {
+    size_t i;
+    for (i = 0; i < n; i++) {
+      if (i > 0 && at (pos + i) == 0 && at (pos + i + 1) == 0 && ((at (pos + i + 2) == 0 && at (pos + i + 3) == 1) || at (pos + i + 2) == 1)) break;
+    }
+    const size_t len = i;
+    if (len < 4) { w_.append_bytes (d + pos, std::min (len, n - pos)); pos += len; continue; }
+    const uint8_t* c = d + pos;
+    pos += len;
+    size_t off = 0; bool found = false;
+    for (size_t q = 0, zeros = 0; q < len; q++) {
+      if (c[q] == 0) { zeros++; continue; }
+      if (c[q] == 1 && zeros >= 2) { off = q + 1; found = true; break; }
+      zeros = 0;
+    }
+    if (!found) continue;
+    w_.append_bytes (c, off);
+    Parser::unescape (c + off, len - off, nal);
+    w_.start_escape();
+    size_t tz = 0;
+    while (tz < nal.size() && nal[nal.size() - 1 - tz] == 0) tz++;
+    if (!nal.empty() && !(nal[0] & 0x80)) {
+      const int type = nal[0] & 31;
+      w_.append_byte (nal[0]);
+      std::vector<uint8_t> esc (c + off, c + len);            // the NAL as it stands in the stream, without trailing zero bytes
+      while (!esc.empty() && esc.back() == 0) esc.pop_back();
+      if (type == 1 || type == 5) {
+        Parser::HeaderInfo H;
+        // (a CABAC slice leaves only its header in the default stream, zero-padded to the byte: trailing zero bytes are header bits)
+        std::vector<uint8_t> hb (c + off, c + len);
+        hb.insert (hb.end(), 4, 0);
+        if (hdr_.parse_headers (hb.data(), hb.size(), H) < 0 || !H.is_slice) { fail ("cannot parse a slice header of the default stream (" + hdr_.error() + ")"); break; }
+        if (H.cabac) {
+          // The header of a CABAC slice is all its NAL keeps in the default stream, zero-padded to the byte.  When it ends in zero
+          // bytes, cutting the stream at start codes hands those to the following chunk as if they were zeros before a start
+          // code (the reference then writes them in the wrong place and cannot restore such streams): take them back.
+          size_t need = 1 + ((size_t)H.hdr_bits + 7) / 8;
+          for (size_t have = nal.size(); have < need && pos < n && d[pos] == 0; have++) pos++;
+        }
+        const std::vector<uint8_t>& rb = hdr_.last_rbsp();
+        for (int b = 0; b < H.hdr_bits; b++) w_.emit_bit ((rb[(size_t)b >> 3] >> (7 - (b & 7))) & 1);
+        if (!on_slice (H)) break;
+      } else {
+        if (type == 7 || type == 8) { Parser::HeaderInfo H; hdr_.parse_headers (esc.data(), esc.size(), H); }
+        if (nal.size() > 1 + tz) w_.append_bytes (nal.data() + 1, nal.size() - 1 - tz);
+        for (size_t q = 0; q < tz; q++) w_.append_byte (0);
+      }
+    }
+    w_.stop_escape();
+  }
+  if (failed_) return -1;
+  w_.pad_to_byte();
+  out.swap (w_.buffer);
+  return 0;
+}
+
+class Restorer : public Walker {
+ public:
+  Restorer (const uint8_t* const* tags, const size_t* tag_len, int n_tags, std::string& err) : Walker (err) {
     if (n_tags > LH264_TAG_PCM && tags[LH264_TAG_PCM]) { pcm_ = tags[LH264_TAG_PCM]; pcm_end_ = pcm_ + tag_len[LH264_TAG_PCM]; }
     for (int t = 0; t < N_TAGS && t < n_tags; t++) if (t != LH264_TAG_PCM && tags[t]) { rd_[t].p = tags[t]; rd_[t].end = tags[t] + tag_len[t]; rd_[t].present = true; rd_[t].fill(); }
     build_vlc();
   }
-  int run (const uint8_t* d, size_t n, std::vector<uint8_t>& out);
+  int run (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
+    return walk (d, n, out, [this] (const Parser::HeaderInfo& H) { return decode_slice (H); });
+  }
 
  private:
-  std::string& err_;
-  bool failed_ = false;
   BoolReader rd_[N_TAGS];
   const uint8_t* pcm_ = nullptr; const uint8_t* pcm_end_ = nullptr;     // samples of the I_PCM macroblocks still to be written
   DynProb test_prob_;                 // ArithmeticCodedInput::TEST_PROB: one adaptive probability shared by the raw bits of all tags
   PriorStore store_;
-  Parser hdr_;
-  MainStreamWriter w_;
   // model state (as csrc/host/pip_symbols.cpp keeps it on the compress side)
   std::vector<Cell> img_[2];
   int img_w_ = 0, img_h_ = 0, cur_ = 0, last_frame_id_ = 0;
@@ -232,8 +306,6 @@ class Restorer {
   int ws_n_ = 0, sid_ = 0;
   // coeff_token by (table, total_coeff, trailing_ones) -> length, code
   uint8_t tok_len_[5][17][4]; uint16_t tok_code_[5][17][4];
-
-  void fail (const std::string& m) { if (!failed_) { failed_ = true; err_ = m; } }
 
   // ---- scan primitives (the inverses of ArithmeticCodedOutput::emit*, CS:289-351 and CompressionStream::scanInt / scanUEGkInt :607-676)
   inline int scan_bit (int tag, DynProb* p) {
@@ -1124,66 +1196,46 @@ bool Restorer::decode_slice (const Parser::HeaderInfo& H) {
   return !failed_;
 }
 
-// the default stream, chunk by chunk as the console application feeds it back (h264dec.cpp:246-272, DC:658-860)
-int Restorer::run (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
-  size_t pos = 0;
-  std::vector<uint8_t> nal;
-  auto at = [&] (size_t i) -> int { return i < n ? d[i] : (i == n + 3 ? 1 : 0); };
-  while (pos < n && !failed_) {
-    size_t i;
-    for (i = 0; i < n; i++) {
-      if (i > 0 && at (pos + i) == 0 && at (pos + i + 1) == 0 && ((at (pos + i + 2) == 0 && at (pos + i + 3) == 1) || at (pos + i + 2) == 1)) break;
-    }
-    const size_t len = i;
-    if (len < 4) { w_.append_bytes (d + pos, std::min (len, n - pos)); pos += len; continue; }
-    const uint8_t* c = d + pos;
-    pos += len;
-    size_t off = 0; bool found = false;
-    for (size_t q = 0, zeros = 0; q < len; q++) {
-      if (c[q] == 0) { zeros++; continue; }
-      if (c[q] == 1 && zeros >= 2) { off = q + 1; found = true; break; }
-      zeros = 0;
-    }
-    if (!found) continue;
-    w_.append_bytes (c, off);
-    Parser::unescape (c + off, len - off, nal);
-    w_.start_escape();
-    size_t tz = 0;
-    while (tz < nal.size() && nal[nal.size() - 1 - tz] == 0) tz++;
-    if (!nal.empty() && !(nal[0] & 0x80)) {
-      const int type = nal[0] & 31;
-      w_.append_byte (nal[0]);
-      std::vector<uint8_t> esc (c + off, c + len);            // the NAL as it stands in the stream, without trailing zero bytes
-      while (!esc.empty() && esc.back() == 0) esc.pop_back();
-      if (type == 1 || type == 5) {
-        Parser::HeaderInfo H;
-        // (a CABAC slice leaves only its header in the default stream, zero-padded to the byte: trailing zero bytes are header bits)
-        std::vector<uint8_t> hb (c + off, c + len);
-        hb.insert (hb.end(), 4, 0);
-        if (hdr_.parse_headers (hb.data(), hb.size(), H) < 0 || !H.is_slice) { fail ("cannot parse a slice header of the default stream (" + hdr_.error() + ")"); break; }
-        if (H.cabac) {
-          // The header of a CABAC slice is all its NAL keeps in the default stream, zero-padded to the byte.  When it ends in zero
-          // bytes, cutting the stream at start codes hands those to the following chunk as if they were zeros before a start
-          // code (the reference then writes them in the wrong place and cannot restore such streams): take them back.
-          size_t need = 1 + ((size_t)H.hdr_bits + 7) / 8;
-          for (size_t have = nal.size(); have < need && pos < n && d[pos] == 0; have++) pos++;
-        }
-        const std::vector<uint8_t>& rb = hdr_.last_rbsp();
-        for (int b = 0; b < H.hdr_bits; b++) w_.emit_bit ((rb[(size_t)b >> 3] >> (7 - (b & 7))) & 1);
-        if (!decode_slice (H)) break;
-      } else {
-        if (type == 7 || type == 8) { Parser::HeaderInfo H; hdr_.parse_headers (esc.data(), esc.size(), H); }
-        if (nal.size() > 1 + tz) w_.append_bytes (nal.data() + 1, nal.size() - 1 - tz);
-        for (size_t q = 0; q < tz; q++) w_.append_byte (0);
-      }
-    }
-    w_.stop_escape();
+// ---- the host passes of the device restore (csrc/lh264_restore.hip) --------------------------------------------------------------
+// pass 1: the slice descriptors, in stream order (no tag data needed); stops at the first CABAC slice
+class SliceDescriber : public Walker {
+ public:
+  using Walker::Walker;
+  int run (const uint8_t* d, size_t n, std::vector<lh264r::RestoreSlice>& slices, bool& cabac) {
+    std::vector<uint8_t> out;
+    return walk (d, n, out, [&] (const Parser::HeaderInfo& H) {
+      if (H.cabac) { cabac = true; return false; }
+      lh264r::RestoreSlice s;
+      s.mb_w = H.mb_w; s.mb_h = H.mb_h; s.first_mb = H.sh.first_mb; s.slice_type = H.sh.slice_type; s.frame_num = H.sh.frame_num;
+      s.slice_qp = H.sh.slice_qp; s.num_ref_idx_l0 = H.sh.num_ref_idx_l0;
+      s.transform_8x8 = H.transform_8x8; s.constrained_intra_pred = H.constrained_intra_pred; s.cabac = 0;
+      s.phase = (uint8_t)w_.bits_in_byte();                  // hdr_bits & 7: the writer starts each NAL on a byte
+      slices.push_back (s);
+      return true;
+    });
   }
-  if (failed_) return -1;
-  w_.pad_to_byte();
-  out.swap (w_.buffer);
-  return 0;
-}
+};
+// pass 2: the same walk with the device's bits of each slice behind its header: the first byte holds the slice's first 8 - phase
+// bits, the rest are whole bytes, escaped on the way as decode_slice's bits are
+class SliceSplicer : public Walker {
+ public:
+  using Walker::Walker;
+  int run (const uint8_t* d, size_t n, const lh264r::RestoreSlice* slices, size_t n_slices, const uint8_t* bits, const uint32_t* slice_end,
+           std::vector<uint8_t>& out) {
+    size_t i = 0;
+    uint32_t start = 0;
+    return walk (d, n, out, [&] (const Parser::HeaderInfo&) {
+      if (i >= n_slices) { fail ("more slices than pass 1 saw"); return false; }
+      const uint32_t end = slice_end[i];
+      const int phase = slices[i].phase;
+      if (end <= start || w_.bits_in_byte() != phase) { fail ("the device's slice does not fit"); return false; }
+      w_.emit_bits (bits[start] & ((1u << (8 - phase)) - 1u), 8 - phase);
+      w_.append_bytes (bits + start + 1, end - start - 1);
+      start = end; i++;
+      return true;
+    });
+  }
+};
 
 }  // namespace
 
@@ -1198,6 +1250,62 @@ int pip_restore (const uint8_t* main_stream, size_t main_len, const uint8_t* con
     err = std::string ("internal: ") + e.what();
     return -1;
   }
+}
+
+int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err) {
+  err.clear(); slices.clear(); cabac = false;
+  if (!main_stream) { err = "null argument"; return -1; }
+  try {
+    SliceDescriber w (err);
+    return w.run (main_stream, main_len, slices, cabac);
+  } catch (const std::exception& e) {
+    err = std::string ("internal: ") + e.what();
+    return -1;
+  }
+}
+
+int pip_restore_splice (const uint8_t* main_stream, size_t main_len, const lh264r::RestoreSlice* slices, size_t n_slices, const uint8_t* bits,
+                        const uint32_t* slice_end, std::vector<uint8_t>& out, std::string& err) {
+  err.clear();
+  try {
+    SliceSplicer w (err);
+    return w.run (main_stream, main_len, slices, n_slices, bits, slice_end, out);
+  } catch (const std::exception& e) {
+    err = std::string ("internal: ") + e.what();
+    return -1;
+  }
+}
+
+void restore_tables (lh264r::RestoreTables& T) {
+  memset (&T, 0, sizeof (T));
+  for (int t = 0; t < LH264_TB_COUNT; t++) { T.cell[t] = kCell[t]; T.tree_bits[t] = kTreeBits[t]; }
+  for (int t = 0; t < 5; t++) {
+    if (t == 3) continue;
+    for (int i = 0; i < kCoeffTokenCount[t]; i++) {
+      const VlcTok& v = kCoeffToken[t][i];
+      T.tok_len[t][v.total_coeff][v.trailing_ones] = v.len; T.tok_code[t][v.total_coeff][v.trailing_ones] = v.code;
+    }
+  }
+  // the writer takes the first entry whose symbol matches
+  for (int total = 1; total < 16; total++)
+    for (int i = 0; i < kTotalZerosCount[total]; i++) {
+      const VlcSym& v = kTotalZeros[total][i];
+      if (!T.tz_len[total][v.sym]) { T.tz_len[total][v.sym] = v.len; T.tz_code[total][v.sym] = v.code; }
+    }
+  for (int total = 1; total < 4; total++)
+    for (int i = 0; i < kTotalZerosChromaDcCount[total]; i++) {
+      const VlcSym& v = kTotalZerosChromaDc[total][i];
+      if (!T.tzc_len[total][v.sym]) { T.tzc_len[total][v.sym] = v.len; T.tzc_code[total][v.sym] = (uint8_t)v.code; }
+    }
+  for (int zl = 1; zl < 8; zl++)
+    for (int i = 0; i < kRunBeforeCount[zl]; i++) {
+      const VlcSym& v = kRunBefore[zl][i];
+      if (!T.rb_len[zl][v.sym]) { T.rb_len[zl][v.sym] = v.len; T.rb_code[zl][v.sym] = v.code; }
+    }
+  for (int ci = 47; ci >= 0; ci--) { T.cbp_code[0][kCbpIntra[ci]] = (uint8_t)ci; T.cbp_code[1][kCbpInter[ci]] = (uint8_t)ci; }
+  memcpy (T.zz4, kZigzag4x4, 16); memcpy (T.zz8, kZigzag8x8, 64); memcpy (T.zz16, kZz16, 16); memcpy (T.zz64, kZz64, 64);
+  memcpy (T.scan8, kScan8, 16); memcpy (T.cache30, kCache30, 16); memcpy (T.z2raster, kZ2Raster, 16);
+  for (int p = 0; p < 2; p++) for (int j = 0; j < 4; j++) T.chroma_nzc[p][j] = (uint8_t)kChromaNzc[p][j];
 }
 
 }  // namespace lh264host

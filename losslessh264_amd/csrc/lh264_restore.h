@@ -1,0 +1,57 @@
+// lh264_restore.h - what the host passes of the device restore (csrc/host/pip_restore.cpp) and its kernel (lh264_restore.hip)
+// share: the slice descriptor pass 1 records, the CAVLC tables, and the per-stream job of one kernel workgroup.
+#pragma once
+#include <stdint.h>
+
+namespace lh264r {
+
+// what the model and the CAVLC writer read of a slice header (Parser::HeaderInfo), in stream order
+struct RestoreSlice {
+  int32_t mb_w, mb_h, first_mb, slice_type, frame_num, slice_qp, num_ref_idx_l0;
+  uint8_t transform_8x8, constrained_intra_pred, cabac;
+  uint8_t phase;                       // hdr_bits & 7: where the slice data starts in its byte
+};
+static_assert (sizeof (RestoreSlice) == 32, "RestoreSlice layout");
+
+// the tables of pip_restore.cpp's Restorer, flattened for the device (built by lh264host::restore_tables); a length of 0 = the
+// host's lookup finds nothing and writes nothing
+struct RestoreTables {
+  int32_t cell[18], tree_bits[18];     // kCell / kTreeBits by LH264_TB_*
+  uint16_t tok_code[5][17][4];         // coeff_token by (table, total_coeff, trailing_ones)
+  uint16_t tz_code[16][16];            // total_zeros by (total_coeff, zeros_left)
+  uint16_t rb_code[8][16];             // run_before by (min (zeros_left, 7), run)
+  uint8_t tok_len[5][17][4];
+  uint8_t tz_len[16][16];
+  uint8_t tzc_code[4][4], tzc_len[4][4];   // chroma DC total_zeros
+  uint8_t rb_len[8][16];
+  uint8_t cbp_code[2][48];             // coded_block_pattern -> codeNum: [0] intra, [1] inter
+  uint8_t zz4[16], zz8[64];            // kZigzag4x4 / kZigzag8x8 (the writer's scans)
+  uint8_t zz16[16], zz64[64];          // kZz16 / kZz64 (the model's scan position -> level index)
+  uint8_t scan8[16], cache30[16], z2raster[16], chroma_nzc[2][4];
+};
+static_assert (sizeof (RestoreTables) % 4 == 0, "RestoreTables is copied by words");
+
+// status of one stream after the kernel; anything but RS_OK sends the stream to the host restore (LH264_RESTORE_PATH_FALLBACK)
+enum { RS_OK = 0, RS_CORRUPT = 1, RS_STORE_FULL = 2, RS_OUT_FULL = 3 };
+
+// one stream: its inputs, its work memory (sized by the host from pass 1) and its outputs, all in device memory
+struct RestoreJob {
+  const uint8_t* tags;                 // the tag streams, concatenated
+  uint32_t tag_off[72], tag_len[72];
+  uint32_t tag_present[3];             // bit t: tags[t] exists (tag LH264_TAG_PCM: the I_PCM samples)
+  uint32_t n_slices, n_max;            // slices; the largest picture in macroblocks
+  const RestoreSlice* slices;
+  uint8_t* cells;                      // 2 x n_max Cell
+  uint8_t* ws;                         // n_max WState
+  int8_t* ipm;                         // n_max x 8
+  uint8_t* nxn;                        // n_max
+  uint32_t* hash;                      // slots x {key + 1, pool offset}; zeroed before the launch
+  uint32_t* pool;                      // pool_cap packed DynProbs
+  uint32_t slots, pool_cap;            // slots: a power of two
+  uint8_t* out;                        // the slices' bits, each slice from a fresh byte and `phase` zero bits
+  uint32_t out_cap;
+  uint32_t* slice_end;                 // per slice: its end in out (bytes)
+  int32_t* status;                     // [0] RS_*; [1] prior keys, [2] pool words, [3] output bytes used
+};
+
+}  // namespace lh264r

@@ -67,6 +67,65 @@ def restore_batch(items, threads=0, out_cap=None):
     return [keep[i][2].raw[:arr[i].out_len] if arr[i].status == 0 else None for i in range(len(items))]
 
 
+PATH_DEVICE, PATH_HOST, PATH_FALLBACK = 0, 1, 2
+
+
+def _restore_items(items, out_cap):
+    Item = _item_type()
+    arr = (Item * len(items))()
+    keep = []
+    for i, (main, tags) in enumerate(items):
+        ptrs = (C.c_char_p * N_TAG_IDS)()
+        lens = (C.c_size_t * N_TAG_IDS)()
+        for t, b in tags.items():
+            if 0 <= t < N_TAG_IDS:
+                ptrs[t] = bytes(b)
+                lens[t] = len(b)
+        cap = out_cap or (4 * (len(main) + sum(len(b) for b in tags.values())) + 4096)
+        buf = C.create_string_buffer(cap)
+        keep.append((ptrs, lens, buf))
+        it = arr[i]
+        it.main_stream, it.main_len, it.tags, it.tag_len, it.n_tags = bytes(main), len(main), ptrs, lens, N_TAG_IDS
+        it.out, it.out_cap = C.addressof(buf), cap
+    return arr, keep
+
+
+def _restore_batch_paths(fn, items, threads, out_cap, statuses):
+    arr, keep = _restore_items(items, out_cap)
+    paths = (C.c_int32 * max(1, len(items)))()
+    L.check(fn(C.byref(arr), len(items), threads, paths))
+    outs = [keep[i][2].raw[:arr[i].out_len] if arr[i].status == 0 else None for i in range(len(items))]
+    if statuses:
+        return outs, [paths[i] for i in range(len(items))], [(arr[i].status, arr[i].out_len) for i in range(len(items))]
+    return outs, [paths[i] for i in range(len(items))]
+
+
+def restore_batch_device(items, threads=0, out_cap=None, statuses=False):
+    """restore_batch on the current device (C ABI lh264_pip_restore_batch_device): CAVLC streams are decoded and written by the
+    kernel, streams with CABAC slices by the host restore beside it.  Returns (outs, paths): outs as restore_batch gives them, paths[i]
+    one of PATH_DEVICE / PATH_HOST / PATH_FALLBACK.  statuses=True adds a third list of (status, out_len) per item.  Raises without a
+    device."""
+    return _restore_batch_paths(L.lib().lh264_pip_restore_batch_device, items, threads, out_cap, statuses)
+
+
+def restore_batch_cpu_check(items, threads=0, out_cap=None, statuses=False):
+    """the kernel's code stepped on the host (lh264_debug_restore_cpu): the same plan and results as restore_batch_device, for checking
+    the device chain without a device"""
+    return _restore_batch_paths(L.lib().lh264_debug_restore_cpu, items, threads, out_cap, statuses)
+
+
+def restore_timing():
+    """(pass 1, device stage, kernel, pass 2) in ms of the last restore_batch_device call"""
+    ms = (C.c_double * 4)()
+    L.check(L.lib().lh264_restore_last_timing(ms))
+    return tuple(ms)
+
+
+def restore_release():
+    """frees the device and page-locked buffers restore_batch_device keeps between calls"""
+    L.lib().lh264_restore_release()
+
+
 VERBATIM = 1
 
 
