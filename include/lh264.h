@@ -299,6 +299,38 @@ int lh264_code_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_fi
 int lh264_code_binarise_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
                                 int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* hip_stream);
 int lh264_code_finish_chains (const lh264_code_stream_t* streams_dev, int n_chains, void* hip_stream);
+/* ---- resumable calls: a stream of any length, coded in SEGMENTS of whole pictures, one call after another ----------------------
+ * lh264_code_chains_resume codes the pictures of chain c as the NEXT segment of stream c; what the stream's coders have to remember
+ * between two calls lies in carry_dev[c], an opaque block of lh264_code_carry_bytes (hash_cap) bytes of device memory that the caller
+ * zero-fills before the stream's first segment and keeps until its last: every adaptive probability the stream has touched with its
+ * exact counters (the block holds the stream's spill table; streams_dev[c].hash_cells_dev is not used, hash_cap must be the same in
+ * every segment), and per tag whether the stream exists, the coder's range, the bits shifted out and the decisions coded so far.
+ * flags_dev[c]: LH264_CODE_SEG_FIRST - the stream starts here (the block's header is initialised by the call) -, LH264_CODE_SEG_LAST -
+ * the bool coders are stopped (the 32 padding decisions and the trailing-zero rule happen here and only here).  A call may mix streams
+ * in their first, a middle and their last segment; FIRST | LAST gives what lh264_code_chains gives.  out_dev / out_cap are the same
+ * buffer in every segment and are appended to: after the LAST segment out_len_dev holds the lengths as lh264_code_chains leaves them;
+ * after any other it holds, per tag, how many bytes are FINAL (a carry out of a later segment's bytes can still run back through a
+ * run of 0xff bytes and into the byte in front of it: the call applies it; the two bytes behind the written ones are work space).
+ * The bytes do not depend on where the cuts fall.  Status bits as in lh264_code_chains, per segment and sticky: a stream that failed
+ * fails in every later segment - except status 8, which the count pass gives before anything is coded: the carry stands as it was and
+ * the caller sends a shorter segment.  The 2^32 / 2^27 limits are limits of ONE segment; both count the decisions of ALL tag lists of
+ * the stream together (a decision word addresses the stream's lists as one array), not those of one tag.  Always the wave-per-partition form; calls on one
+ * stream's carry must be ordered (one HIP stream, or the caller's events).  device memory only, all pointers. */
+#define LH264_CODE_SEG_FIRST 1u
+#define LH264_CODE_SEG_LAST  2u
+size_t lh264_code_carry_bytes (uint32_t hash_cap);
+int lh264_code_chains_resume (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
+                              void* const* carry_dev, const uint32_t* flags_dev,
+                              int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* hip_stream);
+/* decisions coded into every tag slot's list of the stream so far (LH264_N_TAG_SLOTS x uint64, host memory), summed over its segments;
+ * synchronises hip_stream */
+int lh264_code_carry_decisions (const void* carry_dev, uint64_t* decisions_out, void* hip_stream);
+/* decisions per tag slot of chains first_chain .. first_chain + n_chains - 1 of the last coder call on the current device (n_chains x
+ * LH264_N_TAG_SLOTS values, host memory; of a resumable call: of that segment).  Synchronises the device.  A stream whose status is not
+ * 0 reads 0 for the tags its range stage dropped.  "The last call" is per device, not per caller: a thread that wants its own call's
+ * counts must keep other coder calls off the device between the call and this read (lh264_compress_batch does, for its own groups, by
+ * its per-device lock; direct coder calls from other threads are the caller's to order). */
+int lh264_code_last_decisions (int first_chain, int n_chains, uint64_t* decisions_out);
 /* sizes of the last lh264_code_chains call on the current device: 64-bit decision words written and read between its stages (one
  * per binary decision, each stream's count rounded up to 64) and 16-bit tag-list entries (one per decision, each tag's list padded
  * to 8): what the coder's memory traffic is computed from (bench.py). */
@@ -325,6 +357,15 @@ int   lh264_parser_feed (lh264_parser_t* p, const uint8_t* data, size_t len, int
  * the recompressor's default stream (stream id 0x7fffffff, the ".pip" file itself: the input minus its slice data,
  * decoder.cpp:658-860, au_parser.cpp:143,588, decode_slice.cpp:2974-2980), returned by lh264_parser_main_stream */
 int   lh264_parser_feed_file (lh264_parser_t* p, const uint8_t* data, size_t len);
+/* the same file in pieces, for streams of any length: lh264_parser_begin_file, then lh264_parser_feed_file_some until it returns 1 (the
+ * file is finished: last picture completed, default stream whole; 0: there is more; < 0: bad argument).  A call returns as soon as the
+ * parser holds MORE than want_mbs macroblocks in completed pictures; the caller takes pictures from the front and releases them with
+ * lh264_parser_drop_frames (p, n) - the pictures that remain are renumbered from 0, their records are what the whole parse gives -, so
+ * the parser's memory follows want_mbs and not the file's length.  data must stay valid until the file is finished; a parse error
+ * is reported by lh264_parser_error as ever. */
+int   lh264_parser_begin_file (lh264_parser_t* p, const uint8_t* data, size_t len);
+int   lh264_parser_feed_file_some (lh264_parser_t* p, uint64_t want_mbs);
+int   lh264_parser_drop_frames (lh264_parser_t* p, int n);
 const uint8_t* lh264_parser_main_stream (const lh264_parser_t* p, size_t* len);
 /* the samples of the stream's I_PCM macroblocks (384 bytes each, decoding order): stream LH264_TAG_PCM of the container, see
  * lh264_pip_restore */
@@ -394,6 +435,25 @@ int lh264_compress_batch (const uint8_t* const* data, const size_t* len, int n, 
  * lh264_compress_batch there (the streams are independent: nothing is exchanged between devices) */
 int lh264_compress_batch_devices (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,
                                   lh264_compressed_t** out);
+/* the same with options.  segment_mbs: a stream of more macroblocks than this is cut at picture boundaries into segments of at most
+ * that many (one picture at least); its segments go through successive groups, in order, coded by lh264_code_chains_resume with the
+ * stream's state carried in device memory, and its pictures are parsed a segment ahead and released segment by segment, so that host
+ * and device memory follow the segment's size and not the stream's length (the final bytes of every tag go to the host segment by
+ * segment; what grows with the stream is the result itself).  0 = the default, the group budget (1,300,000 macroblocks): no stream that fits a group is cut.  A segment that is
+ * over one of the coder's per-call limits (status 8: 2^27 decisions in all tags of the stream together) is sent again with half the
+ * pictures - a whole stream that is over them becomes a long one -, and segments are cut by an estimate of their decisions first, so
+ * that this is rare; status 8 reaches the caller only for a single picture.  A long stream that fails in any segment has the error as
+ * its result and no tags.  The bytes do not depend on where the cuts fall.  A struct_bytes this library does not know: LH264_E_ARG. */
+typedef struct lh264_compress_opts { uint32_t struct_bytes; uint32_t reserved; uint64_t segment_mbs; } lh264_compress_opts_t;
+int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_compress_opts_t* opts, lh264_compressed_t** out);
+int lh264_compress_batch_devices_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,
+                                       const lh264_compress_opts_t* opts, lh264_compressed_t** out);
+/* in how many segments the stream was coded (1: whole; 0: not coded), and the decisions coded into a tag's list, summed over them */
+int lh264_compressed_segments (const lh264_compressed_t* c);
+uint64_t lh264_compressed_decisions (const lh264_compressed_t* c, int tag);
+/* what the buffers lh264_compress_batch keeps on the current device hold after a call: device memory (with the most the long streams of
+ * the last call held beside them) and page-locked host memory, in bytes */
+int lh264_compress_arena_bytes (size_t* device, size_t* pinned);
 int lh264_compressed_status (const lh264_compressed_t* c);
 const char* lh264_compressed_error (const lh264_compressed_t* c);
 const uint8_t* lh264_compressed_main (const lh264_compressed_t* c, size_t* len);

@@ -7,6 +7,9 @@
                                                             restored and compared before it is written, and a stream the round trip
                                                             cannot carry (I_PCM, damaged or unsupported syntax) is stored verbatim
     python -m losslessh264_amd in.lhp  out.264              restore from the container
+    python -m losslessh264_amd --segment-mbs N in.264 out.pip   compress through lh264_compress_batch_opts: a stream of more than N
+                                                            macroblocks is coded in segments of whole pictures (a stream of any
+                                                            length: memory follows the segment, the bytes are the same)
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -60,6 +63,24 @@ def restore_single(src, dst):
     print("%s -> %s: %d bytes" % (src, dst, len(out)))
 
 
+def compress_segmented(src, dst, segment_mbs):
+    import losslessh264_amd as lh
+    data = open(src, "rb").read()
+    b = lh.compress_batch_handles([data], segment_mbs=segment_mbs)
+    main, tags, err = b.result(0)
+    segs = b.segments(0)
+    b.free()
+    if err:
+        raise SystemExit("cannot compress %s: %s" % (src, err))
+    with open(dst, "wb") as f:
+        f.write(main)
+    for t, x in tags.items():
+        with open("%s.%d" % (dst, t), "wb") as f:
+            f.write(x)
+    total = len(main) + sum(len(x) for x in tags.values())
+    print("%s: %d bytes -> %d bytes (%.4f), %d segments" % (src, len(data), total, total / max(1, len(data)), segs))
+
+
 def compress(src, dst, yuv=None):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
@@ -108,6 +129,9 @@ def restore(src, dst):
 
 
 def main(argv):
+    if len(argv) >= 5 and argv[1] == "--segment-mbs":
+        compress_segmented(argv[3], argv[4], int(argv[2]))
+        return 0
     if len(argv) < 3:
         print(__doc__)
         return 2

@@ -106,6 +106,22 @@ _SIGS["lh264_code_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_
 _SIGS["lh264_code_binarise_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p])
 _SIGS["lh264_code_finish_chains"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p])
 _SIGS["lh264_code_last_totals"] = (C.c_int, [C.c_void_p, C.c_void_p])
+# resumable calls (a stream coded in segments): flags per stream, the size of a stream's carry block, its decision counts
+CODE_SEG_FIRST, CODE_SEG_LAST = 1, 2
+_SIGS["lh264_code_carry_bytes"] = (C.c_size_t, [C.c_uint32])
+_SIGS["lh264_code_chains_resume"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p])
+_SIGS["lh264_parser_begin_file"] = (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t])
+_SIGS["lh264_parser_feed_file_some"] = (C.c_int, [C.c_void_p, C.c_uint64])
+_SIGS["lh264_parser_drop_frames"] = (C.c_int, [C.c_void_p, C.c_int])
+_SIGS["lh264_code_last_decisions"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p])
+class CompressOpts(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("segment_mbs", C.c_uint64)]
+_SIGS["lh264_compress_batch_opts"] = (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(CompressOpts), C.POINTER(C.c_void_p)])
+_SIGS["lh264_compress_batch_devices_opts"] = (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(CompressOpts), C.POINTER(C.c_void_p)])
+_SIGS["lh264_compressed_segments"] = (C.c_int, [C.c_void_p])
+_SIGS["lh264_compressed_decisions"] = (C.c_uint64, [C.c_void_p, C.c_int])
+_SIGS["lh264_compress_arena_bytes"] = (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
+_SIGS["lh264_code_carry_decisions"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS = sorted(_SIGS)
 
 

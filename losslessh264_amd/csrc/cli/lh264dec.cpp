@@ -7,6 +7,7 @@
 //   lh264dec in.264 out.lhp             compress into ONE container file; restored and compared before it is written, a
 //                                       stream the round trip cannot carry is stored verbatim
 //   lh264dec in.lhp out.264             restore from the container
+//   lh264dec --segment-mbs N ...               (first) streams of more than N macroblocks are coded in segments of whole pictures
 //   lh264dec --batch out_dir a.264 b.264 ...   many streams in one lh264_compress_batch call -> out_dir/<name>.lhp
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
@@ -83,12 +84,15 @@ static int dump_yuv (const Bytes& bs, const std::string& path) {
   return 0;
 }
 
+// --segment-mbs N: streams of more macroblocks are coded in segments of at most N (whole pictures); 0: the library's default
+static lh264_compress_opts_t g_opts = {sizeof (lh264_compress_opts_t), 0, 0};
+
 static int compress_files (const std::string& src, const std::string& dst, const char* yuv) {
   Bytes in;
   if (!load (src, in)) { perror (src.c_str()); return 2; }
   const uint8_t* d = in.data(); const size_t n = in.size();
   Compressed c;
-  if (lh264_compress_batch (&d, &n, 1, 0, &c.h) != LH264_OK || lh264_compressed_status (c.h) != LH264_OK) {
+  if (lh264_compress_batch_opts (&d, &n, 1, 0, &g_opts, &c.h) != LH264_OK || lh264_compressed_status (c.h) != LH264_OK) {
     fprintf (stderr, "cannot compress %s: %s\n", src.c_str(), c.h ? lh264_compressed_error (c.h) : lh264_last_error());
     return 1;
   }
@@ -150,8 +154,8 @@ static int compress_single (const std::vector<std::string>& srcs, const std::vec
   const int nd = lh264_device_count();
   std::vector<int> devs;
   for (int i = 0; i < nd && i < n; i++) devs.push_back (i);
-  const int rc = devs.size() > 1 ? lh264_compress_batch_devices (d.data(), l.data(), n, 0, devs.data(), (int)devs.size(), h.data())
-                                 : lh264_compress_batch (d.data(), l.data(), n, 0, h.data());
+  const int rc = devs.size() > 1 ? lh264_compress_batch_devices_opts (d.data(), l.data(), n, 0, devs.data(), (int)devs.size(), &g_opts, h.data())
+                                 : lh264_compress_batch_opts (d.data(), l.data(), n, 0, &g_opts, h.data());
   int ret = 0;
   for (int i = 0; i < n; i++) {
     Bytes blob; std::string why;
@@ -177,13 +181,14 @@ static int restore_single (const std::string& src, const std::string& dst) {
 }
 
 int main (int argc, char** argv) {
+  if (argc >= 3 && !strcmp (argv[1], "--segment-mbs")) { g_opts.segment_mbs = strtoull (argv[2], nullptr, 10); argv[2] = argv[0]; argv += 2; argc -= 2; }
   if (argc >= 4 && !strcmp (argv[1], "--batch")) {
     std::vector<std::string> srcs, dsts;
     for (int i = 3; i < argc; i++) { srcs.push_back (argv[i]); dsts.push_back (std::string (argv[2]) + "/" + base_name (argv[i]) + ".lhp"); }
     return compress_single (srcs, dsts);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

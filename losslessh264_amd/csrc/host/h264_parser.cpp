@@ -1718,9 +1718,24 @@ void MainStreamWriter::stop_escape() {
 // zero bytes (au_parser.cpp:588), one zero byte per trailing zero byte (decoder.cpp:610-627), for a slice the bits of its
 // header (decode_slice.cpp:2974-2980) and, for CAVLC, a single 1 bit (decoder.cpp:837-845); zero bits up to the byte.
 int Parser::feed_file (const uint8_t* d, size_t n) {
-  struct Scope { StreamArena*& slot; StreamArena* prev; Scope (StreamArena* a) : slot (current_stream_arena()), prev (slot) { slot = a; } ~Scope() { slot = prev; } } scope (arena_.get());
-  int rc = 0;
-  size_t pos = 0;
+  begin_file (d, n);
+  feed_file_some ((size_t)-1);
+  return file_rc_;
+}
+void Parser::begin_file (const uint8_t* d, size_t n) { file_d_ = d; file_n_ = n; file_pos_ = 0; file_rc_ = 0; file_done_ = false; }
+size_t Parser::held_mbs() const {
+  size_t m = 0;
+  for (auto& f : frames_) m += (size_t)f->mb_w * f->mb_h;
+  return m;
+}
+// the loop of feed_file, left as soon as frames() holds more than want_mbs macroblocks in completed pictures (looked at whenever a
+// picture completes); the end of the file completes the last picture and the default stream
+bool Parser::feed_file_some (size_t want_mbs) {
+  if (file_done_) return true;
+  const uint8_t* d = file_d_; const size_t n = file_n_;
+  size_t& pos = file_pos_; int& rc = file_rc_;
+  size_t seen = frames_.size(), held = held_mbs();
+  struct Scope { StreamArena*& slot; StreamArena* prev; Scope (StreamArena* a) : slot (current_stream_arena()), prev (slot) { slot = a; } ~Scope() { slot = prev; } } scope (arena_paused_ ? nullptr : arena_.get());
   std::vector<uint8_t> nal;
   auto at = [&] (size_t i) -> int { return i < n ? d[i] : (i == n + 3 ? 1 : 0); };   // the application appends 00 00 00 01
   while (pos < n) {
@@ -1767,10 +1782,15 @@ int Parser::feed_file (const uint8_t* d, size_t n) {
       if (!d_->last_cabac) main_.emit_bit (1);
     }
     main_.stop_escape();
+    if (frames_.size() != seen) {
+      for (; seen < frames_.size(); seen++) held += (size_t)frames_[seen]->mb_w * frames_[seen]->mb_h;
+      if (want_mbs != (size_t)-1 && held > want_mbs) return false;
+    }
   }
   flush();
   main_.pad_to_byte();
-  return rc;
+  file_done_ = true;
+  return true;
 }
 
 }  // namespace lh264host

@@ -221,6 +221,15 @@ class Parser {
   // a whole Annex-B file, cut and fed the way the reference's console application does (h264dec.cpp:246-272, one
   // DecodeFrameNoDelay per start-code-delimited chunk); also builds the recompressor's default stream, main_stream()
   int feed_file (const uint8_t* data, size_t len);
+  // the same file in pieces, for streams of any length: begin_file, then feed_file_some until it returns true (the file is finished: last
+  // picture completed, default stream padded).  A call returns as soon as frames() holds MORE than want_mbs macroblocks in completed
+  // pictures, so that the caller can take pictures from the front of frames() (erase them: the parser does not look at completed
+  // pictures again) while the default stream and the I_PCM samples keep growing.  data must stay valid until the file is finished.
+  void begin_file (const uint8_t* data, size_t len);
+  bool feed_file_some (size_t want_mbs);
+  bool file_finished() const { return file_done_; }
+  int file_status() const { return file_rc_; }            // what feed_file returns: < 0 when a NAL unit did not parse
+  size_t held_mbs() const;                                 // macroblocks of the pictures in frames()
   // headers only (the restore direction reads them from the default stream): SPS / PPS are remembered, for a slice NAL the
   // header is parsed and described; no picture is started.  nal = one NAL unit without start code.  <0: not parseable
   struct HeaderInfo {
@@ -257,6 +266,9 @@ class Parser {
   void set_sparse_levels (bool sparse) { sparse_levels_ = sparse; }
   // on: the per-picture arrays come from chunks owned by this parser (see StreamArena)
   void set_stream_arena (bool on) { if (on && !arena_) arena_.reset (new StreamArena()); else if (!on) arena_.reset(); }
+  // later pictures come from the per-thread cache again and are returned to it when they are destroyed; the arena itself lives on with
+  // the pictures it holds (a stream that turned out to be long: an arena only grows)
+  void pause_stream_arena() { arena_paused_ = true; }
   long pictures_done() const { return pictures_done_; }
   // a completed picture had macroblocks no slice covers (lost slices): the reference conceals them (error_concealment.cpp), which is not
   // modelled - the recompressed form of such a stream does not restore; callers that promise a round trip store it verbatim
@@ -272,6 +284,7 @@ class Parser {
   bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false; long pictures_done_ = 0; bool damaged_ = false;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;
+  const uint8_t* file_d_ = nullptr; size_t file_n_ = 0, file_pos_ = 0; int file_rc_ = 0; bool file_done_ = false, arena_paused_ = false;      // begin_file .. feed_file_some
   friend struct Impl;
 };
 

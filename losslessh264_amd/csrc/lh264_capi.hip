@@ -36,19 +36,26 @@ __global__ void coder_emit_kernel (const lh264_code_job_t* jobs, const uint32_t*
 __global__ void coder_resolve_kernel (const lh264_code_stream_t* streams, uint32_t* chain_info, const uint32_t* seg0, const int32_t* chain_first,
                                       const uint32_t* seg_doff, const uint32_t* seg_part, const uint64_t* D, uint16_t* Q, int n_chains, int log2p, uint32_t* progress, int window);
 __global__ void coder_chunkmap_kernel (uint32_t* chain_info, int n_pairs, uint32_t* pair_chunk0, uint32_t* pair_coarse0, uint32_t* cand_list);
-__global__ void coder_range_seed_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_coarse0, int n_pairs, uint32_t* cand, uint32_t* cand_list, uint32_t long_list);
+__global__ void coder_range_seed_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_coarse0, int n_pairs, uint32_t* cand, uint32_t* cand_list, uint32_t long_list, const uint32_t* pair_start);
 __global__ void coder_range_first_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_chunk0, const uint32_t* pair_coarse0, int n_pairs, int groups,
                                           unsigned n_cand, unsigned n_later, const uint32_t* cand, const uint32_t* cand_list, uint8_t* cand_end, uint8_t* cmap, uint32_t* chunk_rec, uint32_t* coarse_bits);
-__global__ void coder_range_link_kernel (const uint32_t* pair_coarse0, int n_pairs, const uint32_t* cand, const uint8_t* cand_end, const uint8_t* cmap, uint32_t* seed, uint32_t* chain_info);
+__global__ void coder_range_link_kernel (const uint32_t* pair_coarse0, int n_pairs, const uint32_t* cand, const uint8_t* cand_end, const uint8_t* cmap, uint32_t* seed, uint32_t* chain_info, const uint32_t* pair_start);
 __global__ void coder_range_walk_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_chunk0, const uint32_t* pair_coarse0, int n_pairs,
                                          const uint32_t* cand, const uint32_t* seed, uint32_t* chunk_rec, uint32_t* coarse_bits);
 __global__ void coder_range_scan_kernel (const uint32_t* pair_coarse0, int n_pairs, uint32_t* coarse_bits, uint32_t* pair_bits, const uint32_t* chain_info,
-                                         const uint16_t* Q, uint32_t* acc);
+                                         const uint16_t* Q, uint32_t* acc, const uint32_t* pair_start, const lh264_code_stream_t* streams);
 __global__ void coder_accum_kernel (const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_chunk0, const uint32_t* pair_coarse0, int n_pairs,
                                     const uint32_t* chunk_rec, const uint32_t* coarse_bits, const uint32_t* pair_bits, uint32_t* acc);
 __global__ void coder_bytes_kernel (const lh264_code_stream_t* streams, const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_bits,
                                     const uint32_t* acc, int n_pairs);
 __global__ void coder_status_kernel (const lh264_code_stream_t* streams, const uint32_t* chain_info, int n_chains);
+__global__ void coder_resolve_carry_kernel (const lh264_code_stream_t* streams, uint32_t* chain_info, const uint32_t* seg0, const int32_t* chain_first,
+                                            const uint32_t* seg_doff, const uint32_t* seg_part, const uint64_t* D, uint16_t* Q, int n_chains, int log2p, uint32_t* progress, int window,
+                                            uint8_t* const* carry);
+__global__ void coder_bytes_carry_kernel (const lh264_code_stream_t* streams, const uint32_t* chain_info, const uint16_t* Q, const uint32_t* pair_bits,
+                                          const uint32_t* acc, int n_pairs, const uint32_t* pair_start, const uint32_t* pair_chunk0, const uint32_t* chunk_rec, uint8_t* const* carry);
+__global__ void coder_carry_in_kernel (uint8_t* const* carry, const uint32_t* flags, uint32_t* chain_info, int n_pairs, uint32_t* pair_start);
+__global__ void coder_carry_out_kernel (const lh264_code_stream_t* streams, uint8_t* const* carry, const uint32_t* pair_start, int n_pairs);
 size_t wave_lds_bytes();
 size_t wg_lds_bytes();
 #ifdef LH264_CODER_DEBUG
@@ -277,6 +284,7 @@ struct CoderWs {
   uint32_t* pair_coarse0 = nullptr; uint32_t* seed = nullptr; uint32_t* coarse_bits = nullptr; size_t coarse_bound = 0; int n_pairs_last = 0;
   uint32_t* cand = nullptr; uint8_t* cand_end = nullptr; uint8_t* cmap = nullptr; uint32_t* cand_list = nullptr;
   const uint32_t* seg0 = nullptr; const uint32_t* seg_doff = nullptr; const uint32_t* seg_part = nullptr; const int32_t* chain_first = nullptr; int log2p = 3; bool sw = false;
+  uint32_t* pair_start = nullptr;                  // resumable calls: where every (stream, tag) pair's coder stands
   uint32_t* progress = nullptr; int window = 0;    // the resolve kernel's waves of a stream keep within `window` segments of one another
 };
 CoderWs g_coder_ws[16];
@@ -295,7 +303,7 @@ size_t up256 (size_t v) { return (v + 255) & ~ (size_t)255; }
 // the two halves of lh264_code_chains: binarise (count, scan, bases, one synchronisation for the sizes, emit) and code (resolve, range,
 // accumulate, bytes).  What the second half needs of the first is kept in the device's work space.
 static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
-                          int n_chains, int n_jobs, long long total_mbs, hipStream_t st) {
+                          int n_chains, int n_jobs, long long total_mbs, hipStream_t st, bool resumable = false) {
   W.ready_chains = -1;
   if (W.enter (st)) return fail (LH264_E_HIP, "hipStreamWaitEvent (coder work memory)");
   if (!W.totals_host) HIPCHK (hipHostMalloc ((void**)&W.totals_host, 2 * sizeof (unsigned long long), hipHostMallocDefault));
@@ -309,6 +317,7 @@ static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const in
   // LH264_CODER_PATH=sw|wave overrides, for the tests (both forms must give the same bytes) and for experiments.
   bool sw = n_chains >= 384 && n_chains < 1024 && total_mbs / n_chains <= 12288;
   if (const char* e = getenv ("LH264_CODER_PATH")) { if (!strcmp (e, "sw")) sw = true; else if (!strcmp (e, "wave")) sw = false; }
+  if (resumable) sw = false;                               // (a stream's DynProbs outlive the call in the wave form only)
   W.sw = sw;
   // the partitions of a stream's DynProbs (each resolved by a wave of its own): as few as fill the machine with waves - a partition's
   // runs of decision words get shorter with their number, and a run costs its wave a look at the segment tables
@@ -381,13 +390,14 @@ static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const in
   const size_t o_q = up256 ((size_t)n_words * 8 + 512), o_pc0 = o_q + up256 ((size_t)n_q * 2 + 256), o_pbits = o_pc0 + up256 ((size_t) (n_pairs + 1) * 4),
                o_crec = o_pbits + up256 ((size_t)n_pairs * 4), o_pco0 = o_crec + up256 (chunk_bound * 8), o_seed = o_pco0 + up256 ((size_t) (n_pairs + 1) * 4),
                o_cand = o_seed + up256 (coarse_bound * 4), o_cend = o_cand + up256 (coarse_bound * 12), o_cmap = o_cend + up256 (coarse_bound * 8), o_clist = o_cmap + up256 (coarse_bound * 128), o_cbits = o_clist + up256 (coarse_bound * 32 + 4),
-               o_acc = o_cbits + up256 (coarse_bound * 4 + 4);
+               o_pstart = o_cbits + up256 (coarse_bound * 4 + 4), o_acc = o_pstart + up256 (resumable ? (size_t)n_pairs * LH264_PAIR_START_WORDS * 4 : 4);
   if (int rc = grow (&W.big, &W.big_cap, o_acc + n_acc * 4 + 256)) return rc;
   uint8_t* bg = (uint8_t*)W.big;
   uint64_t* D = (uint64_t*)bg; uint16_t* Q = (uint16_t*) (bg + o_q);
   uint32_t* pair_chunk0 = (uint32_t*) (bg + o_pc0); uint32_t* pair_bits = (uint32_t*) (bg + o_pbits);
   uint32_t* chunk_rec = (uint32_t*) (bg + o_crec); uint32_t* acc = (uint32_t*) (bg + o_acc);
   W.pair_coarse0 = (uint32_t*) (bg + o_pco0); W.seed = (uint32_t*) (bg + o_seed); W.coarse_bits = (uint32_t*) (bg + o_cbits); W.coarse_bound = coarse_bound; W.n_pairs_last = n_pairs;
+  W.pair_start = resumable ? (uint32_t*) (bg + o_pstart) : nullptr;
   W.cand = (uint32_t*) (bg + o_cand); W.cand_end = (uint8_t*) (bg + o_cend); W.cmap = bg + o_cmap; W.cand_list = (uint32_t*) (bg + o_clist);
   W.seg0 = seg0; W.seg_doff = seg_doff; W.seg_part = seg_part; W.chain_first = chain_first_dev;
   W.progress = (uint32_t*) (sm + o_prog); W.window = 3;
@@ -404,7 +414,7 @@ static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const in
   return LH264_OK;
 }
 
-static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int n_chains, hipStream_t st) {
+static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int n_chains, hipStream_t st, uint8_t* const* carry_dev = nullptr, const uint32_t* flags_dev = nullptr) {
   if (W.ready_chains != n_chains || W.ready_streams != streams_dev) return fail (LH264_E_ARG, "lh264_code_finish_chains without the matching lh264_code_binarise_chains");
   uint32_t* info = W.info; uint64_t* D = W.D; uint16_t* Q = W.Q; uint32_t* pair_chunk0 = W.pair_chunk0; uint32_t* pair_bits = W.pair_bits;
   uint32_t* chunk_rec = W.chunk_rec; uint32_t* acc = W.acc;
@@ -412,8 +422,17 @@ static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int 
   W.ready_chains = -1;
   if (W.enter (st)) return fail (LH264_E_HIP, "hipStreamWaitEvent (coder work memory)");
   if (!W.sw && W.progress) HIPCHK (hipMemsetAsync (W.progress, 0, ((size_t)n_chains << W.log2p) * 4, st));
+  uint32_t* const pstart = carry_dev ? W.pair_start : nullptr;
+  if (carry_dev && (W.sw || !pstart)) return fail (LH264_E_ARG, "resumable call on a binarisation that is not");
+  const dim3 resolve_grid ((unsigned) ((((size_t)n_chains + 7) / 8) * 8 * (((size_t)1 << W.log2p) >= LH264_CODER_WG_WAVES ? ((size_t)1 << W.log2p) / LH264_CODER_WG_WAVES : 1)));
+  if (carry_dev) {
+    hipLaunchKernelGGL (lh264::coder_carry_in_kernel, dim3 ((unsigned) ((n_pairs + 255) / 256)), dim3 (256), 0, st, carry_dev, flags_dev, info, n_pairs, pstart);
+    HIPCHK (hipGetLastError());
+    hipLaunchKernelGGL (lh264::coder_resolve_carry_kernel, resolve_grid, dim3 (64 * LH264_CODER_WG_WAVES), 0, st, streams_dev, info, W.seg0, W.chain_first,
+                        W.seg_doff, W.seg_part, D, Q, n_chains, W.log2p, W.progress, W.window, carry_dev);
+  } else
   if (W.sw) hipLaunchKernelGGL (lh264sw::coder_resolve_kernel, dim3 (n_chains), dim3 (LH264_CODER_RESOLVE_THREADS), 0, st, streams_dev, info, D, Q, n_chains);
-  else hipLaunchKernelGGL (lh264::coder_resolve_kernel, dim3 ((unsigned) ((((size_t)n_chains + 7) / 8) * 8 * (((size_t)1 << W.log2p) >= LH264_CODER_WG_WAVES ? ((size_t)1 << W.log2p) / LH264_CODER_WG_WAVES : 1))), dim3 (64 * LH264_CODER_WG_WAVES), 0, st,
+  else hipLaunchKernelGGL (lh264::coder_resolve_kernel, resolve_grid, dim3 (64 * LH264_CODER_WG_WAVES), 0, st,
                            streams_dev, info, W.seg0, W.chain_first,
                            W.seg_doff, W.seg_part, D, Q, n_chains, W.log2p, W.progress, W.window);
   HIPCHK (hipGetLastError());
@@ -426,7 +445,7 @@ static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int 
   // every list is one of thousands and candidates are wasted walks; with large streams (5 - 23 M decisions) the lists of 65 - 262 k
   // decisions were the longest lanes of the launch (1080p batch 18.4 -> 14.5 ms, QCIF batch 1.2 -> 1.4 ms the other way)
   const uint32_t long_list = n_chains > 0 && W.last_q / (unsigned long long)n_chains > 4000000ull ? (uint32_t)LH264_CODER_CODE_COARSE : 262144u;
-  hipLaunchKernelGGL (lh264::coder_range_seed_kernel, dim3 ((unsigned) ((W.coarse_bound + 3) / 4)), dim3 (256), 0, st, info, Q, W.pair_coarse0, n_pairs, W.cand, W.cand_list, long_list);
+  hipLaunchKernelGGL (lh264::coder_range_seed_kernel, dim3 ((unsigned) ((W.coarse_bound + 3) / 4)), dim3 (256), 0, st, info, Q, W.pair_coarse0, n_pairs, W.cand, W.cand_list, long_list, pstart);
   HIPCHK (hipGetLastError());
   const int groups = (n_chains + 63) / 64;
   {
@@ -435,16 +454,21 @@ static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int 
                         n_pairs, groups, n_cand, n_later, W.cand, W.cand_list, W.cand_end, W.cmap, chunk_rec, W.coarse_bits);
     HIPCHK (hipGetLastError());
   }
-  hipLaunchKernelGGL (lh264::coder_range_link_kernel, dim3 ((unsigned) ((n_pairs + 63) / 64)), dim3 (64), 0, st, W.pair_coarse0, n_pairs, W.cand, W.cand_end, W.cmap, W.seed, info);
+  hipLaunchKernelGGL (lh264::coder_range_link_kernel, dim3 ((unsigned) ((n_pairs + 63) / 64)), dim3 (64), 0, st, W.pair_coarse0, n_pairs, W.cand, W.cand_end, W.cmap, W.seed, info, pstart);
   HIPCHK (hipGetLastError());
   hipLaunchKernelGGL (lh264::coder_range_walk_kernel, dim3 ((unsigned) ((W.coarse_bound + 63) / 64)), dim3 (64), 0, st, info, Q, pair_chunk0, W.pair_coarse0, n_pairs,
                       W.cand, W.seed, chunk_rec, W.coarse_bits);
   HIPCHK (hipGetLastError());
-  hipLaunchKernelGGL (lh264::coder_range_scan_kernel, dim3 ((unsigned) ((n_pairs + 3) / 4)), dim3 (256), 0, st, W.pair_coarse0, n_pairs, W.coarse_bits, pair_bits, info, Q, acc);
+  hipLaunchKernelGGL (lh264::coder_range_scan_kernel, dim3 ((unsigned) ((n_pairs + 3) / 4)), dim3 (256), 0, st, W.pair_coarse0, n_pairs, W.coarse_bits, pair_bits, info, Q, acc, pstart, streams_dev);
   HIPCHK (hipGetLastError());
   hipLaunchKernelGGL (lh264::coder_accum_kernel, dim3 ((unsigned) ((chunk_bound + 255) / 256)), dim3 (256), 0, st, info, Q, pair_chunk0, W.pair_coarse0, n_pairs,
                       chunk_rec, W.coarse_bits, pair_bits, acc);
   HIPCHK (hipGetLastError());
+  if (carry_dev) {
+    hipLaunchKernelGGL (lh264::coder_bytes_carry_kernel, dim3 ((unsigned) ((n_pairs + 3) / 4)), dim3 (256), 0, st, streams_dev, info, Q, pair_bits, acc, n_pairs, pstart, pair_chunk0, chunk_rec, carry_dev);
+    HIPCHK (hipGetLastError());
+    hipLaunchKernelGGL (lh264::coder_carry_out_kernel, dim3 ((unsigned) ((n_pairs + 255) / 256)), dim3 (256), 0, st, streams_dev, carry_dev, pstart, n_pairs);
+  } else
   hipLaunchKernelGGL (lh264::coder_bytes_kernel, dim3 ((unsigned) ((n_pairs + 3) / 4)), dim3 (256), 0, st, streams_dev, info, Q, pair_bits, acc, n_pairs);
   HIPCHK (hipGetLastError());
   // tag slots 35 .. LH264_N_TAG_SLOTS-1 do not exist: their lengths read 0
@@ -475,6 +499,30 @@ int lh264_code_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_fi
   if (int rc = code_binarise (*W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream)) return rc;
   return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream);
 }
+size_t lh264_code_carry_bytes (uint32_t hash_cap) { return (size_t)LH264_CARRY_TABLE_BYTES + (size_t)hash_cap * 64; }
+int lh264_code_chains_resume (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
+                              void* const* carry_dev, const uint32_t* flags_dev,
+                              int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* stream) {
+  CoderWs* W = nullptr;
+  if (int rc = coder_ws (&W)) return rc;
+  if (!code_args_ok (jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, max_mbs_per_frame) || !carry_dev || !flags_dev) return fail (LH264_E_ARG, "bad argument");
+  if (n_chains == 0) return LH264_OK;
+  std::lock_guard<std::mutex> lock (W->mu);
+  if (int rc = code_binarise (*W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream, true)) return rc;
+  return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream, (uint8_t* const*)carry_dev, flags_dev);
+}
+int lh264_code_carry_decisions (const void* carry_dev, uint64_t* decisions_out, void* stream) {
+  if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
+  if (!carry_dev || !decisions_out) return fail (LH264_E_ARG, "bad argument");
+  uint32_t rec[LH264_N_TAG_SLOTS * LH264_CARRY_TAG_WORDS];
+  HIPCHK (hipMemcpyAsync (rec, (const uint8_t*)carry_dev + LH264_CARRY_HDR_WORDS * 4, sizeof (rec), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK (hipStreamSynchronize ((hipStream_t)stream));
+  for (int t = 0; t < LH264_N_TAG_SLOTS; t++) {
+    const uint32_t* r = rec + t * LH264_CARRY_TAG_WORDS;
+    decisions_out[t] = r[LH264_CARRY_TAG_EXISTS] ? (uint64_t)r[LH264_CARRY_TAG_NDEC] | (uint64_t)r[LH264_CARRY_TAG_NDEC + 1] << 32 : 0;
+  }
+  return LH264_OK;
+}
 int lh264_code_binarise_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
                                 int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* stream) {
   CoderWs* W = nullptr;
@@ -493,6 +541,17 @@ int lh264_code_finish_chains (const lh264_code_stream_t* streams_dev, int n_chai
   return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream);
 }
 
+int lh264_code_last_decisions (int first_chain, int n_chains, uint64_t* decisions_out) {
+  CoderWs* W = nullptr;
+  if (int rc = coder_ws (&W)) return rc;
+  std::lock_guard<std::mutex> lock (W->mu);
+  if (!decisions_out || first_chain < 0 || n_chains < 0 || !W->info || first_chain + n_chains > W->n_pairs_last / LH264_N_TAG_SLOTS) return fail (LH264_E_ARG, "bad argument");
+  std::vector<uint32_t> info ((size_t)n_chains * LH264_CODER_INFO_WORDS);
+  if (n_chains) HIPCHK (hipMemcpy (info.data(), W->info + (size_t)first_chain * LH264_CODER_INFO_WORDS, info.size() * 4, hipMemcpyDeviceToHost));
+  for (int c = 0; c < n_chains; c++)
+    for (int t = 0; t < LH264_N_TAG_SLOTS; t++) decisions_out[(size_t)c * LH264_N_TAG_SLOTS + t] = t < 35 ? info[(size_t)c * LH264_CODER_INFO_WORDS + LH264_CODER_INFO_TAGCNT + t] : 0;
+  return LH264_OK;
+}
 int lh264_code_last_totals (unsigned long long* decision_words, unsigned long long* list_entries) {
   int dev = 0;
   if (lh264_device_count() <= 0 || hipGetDevice (&dev) != hipSuccess || dev < 0 || dev >= 16) return fail (LH264_E_NODEVICE, "no HIP device visible");
@@ -624,6 +683,20 @@ int lh264_pip_restore_batch (lh264_restore_item_t* items, int n, int threads) {
 int lh264_parser_feed_file (lh264_parser_t* p, const uint8_t* data, size_t len) {
   if (!p || (!data && len)) return LH264_E_ARG;
   return p->p.feed_file (data, len) < 0 ? LH264_E_UNSUPPORTED : LH264_OK;
+}
+int lh264_parser_begin_file (lh264_parser_t* p, const uint8_t* data, size_t len) {
+  if (!p || (!data && len)) return LH264_E_ARG;
+  p->p.begin_file (data, len);
+  return LH264_OK;
+}
+int lh264_parser_feed_file_some (lh264_parser_t* p, uint64_t want_mbs) {
+  if (!p) return LH264_E_ARG;
+  return p->p.feed_file_some ((size_t)want_mbs) ? 1 : 0;
+}
+int lh264_parser_drop_frames (lh264_parser_t* p, int n) {
+  if (!p || n < 0 || (size_t)n > p->p.frames().size()) return LH264_E_ARG;
+  p->p.frames().erase (p->p.frames().begin(), p->p.frames().begin() + n);
+  return LH264_OK;
 }
 const uint8_t* lh264_parser_main_stream (const lh264_parser_t* p, size_t* len) {
   if (!p) return nullptr;

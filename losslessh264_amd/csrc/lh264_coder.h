@@ -25,6 +25,7 @@
 #define LH264_CODER_INFO_DBASE   (2 * LH264_N_TAG_SLOTS + 4)         /* 64-bit: first decision word of the stream                      */
 #define LH264_CODER_INFO_QBASE   (2 * LH264_N_TAG_SLOTS + 6)         /* 64-bit: first list entry of the stream                         */
 #define LH264_CODER_INFO_STATUS  (2 * LH264_N_TAG_SLOTS + 8)
+#define LH264_CODER_INFO_FLAGS   (2 * LH264_N_TAG_SLOTS + 9)         /* bit 0: the tag lists of this call end without the 32 stop decisions   */
 #define LH264_CODER_INFO_WORDS   96
 
 // threads of a coder_resolve_kernel workgroup (one workgroup per stream)
@@ -43,6 +44,24 @@
 #ifndef LH264_CODER_CODE_COARSE
 #define LH264_CODER_CODE_COARSE 65536
 #endif
+
+// ---- the carry of a resumable call (lh264_code_chains_resume): one block per stream in device memory, 32-bit words --------------------
+// header: [0] status so far (sticky: a stream that failed in one segment fails in all later ones), [1] segments coded;
+// then one record per tag slot; then, LH264_CARRY_TABLE_BYTES behind the block's start, the stream's spill table (hash_cap x 64 bytes).
+// All zero = a stream that has not coded anything yet.
+#define LH264_CARRY_HDR_WORDS 16
+#define LH264_CARRY_TAG_WORDS 8
+#define LH264_CARRY_TAG_BITS   0      /* 64-bit: bits the tag's bool coder has shifted out so far                                       */
+#define LH264_CARRY_TAG_NDEC   2      /* 64-bit: decisions coded into the tag's list so far                                            */
+#define LH264_CARRY_TAG_RANGE  4      /* the coder's range behind the last decision (0: none yet = 255)                                */
+#define LH264_CARRY_TAG_EXISTS 5      /* the tag's stream exists                                                                       */
+#define LH264_CARRY_TAG_CIN    6      /* the last segment's sums carry into the bytes in front of them (applied by coder_carry_out_kernel) */
+#define LH264_CARRY_TABLE_BYTES 2048
+// per (stream, tag slot) pair of a resumable call, from the carry (coder_carry_in_kernel): 4 words
+#define LH264_PAIR_START_WORDS 4      /* [0] range at the list's start, [1] bit offset of its first decision inside [2], the output byte its sums start at, [3] flags */
+#define LH264_PAIR_EXISTED 1u
+#define LH264_PAIR_LAST    2u
+#define LH264_PAIR_FIRST   4u
 
 // status bits reported in out_len_dev[LH264_N_TAG_SLOTS]
 #define LH264_CODER_ST_TABLE_FULL 1

@@ -344,7 +344,7 @@ coder_jobs_kernel (const lh264_code_job_t* __restrict__ jobs, const int32_t* __r
   for (int c = tid; c < n_chains; c += CODER_ONE_WG) {
     for (int j = chain_first[c]; j < chain_first[c + 1]; j++) job_chain[j] = (uint32_t)c;
     chain_info[(size_t)c * LH264_CODER_INFO_WORDS + LH264_CODER_INFO_STATUS] = st0;
-    for (int q = 90; q < 96; q++) chain_info[(size_t)c * LH264_CODER_INFO_WORDS + q] = 0;
+    for (int q = LH264_CODER_INFO_FLAGS; q < 96; q++) chain_info[(size_t)c * LH264_CODER_INFO_WORDS + q] = 0;
   }
 }
 
@@ -904,10 +904,16 @@ struct RoundGen {
   }
 };
 
-__global__ void __launch_bounds__ (R2_WAVES * 64)
-coder_resolve_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t* __restrict__ chain_info, const uint32_t* __restrict__ seg0,
-                      const int32_t* __restrict__ chain_first, const uint32_t* __restrict__ seg_doff, const uint32_t* __restrict__ seg_part,
-                      const uint64_t* __restrict__ D, uint16_t* __restrict__ Q, int n_chains, int log2p, uint32_t* __restrict__ progress, int window) {
+// CARRY (lh264_code_chains_resume): the stream's DynProbs outlive the call.  Its spill table is the one in the stream's carry block, ONE
+// table for all partitions - where a DynProb lies there must not depend on how this call cuts the stream's cells into partitions, the
+// next call may cut them differently (another log2p, other bucket counts) -; every new DynProb asks the table from the first round on,
+// and at the end what the wave's cache holds goes to the table.  Waves of one stream then share a table, but never a key: inserting is
+// a compare-and-swap on a free entry, everything else touches entries of the wave's own keys.
+template <bool CARRY> __device__ __forceinline__ void
+resolve_body (const lh264_code_stream_t* __restrict__ streams, uint32_t* __restrict__ chain_info, const uint32_t* __restrict__ seg0,
+              const int32_t* __restrict__ chain_first, const uint32_t* __restrict__ seg_doff, const uint32_t* __restrict__ seg_part,
+              const uint64_t* __restrict__ D, uint16_t* __restrict__ Q, int n_chains, int log2p, uint32_t* __restrict__ progress, int window,
+              uint8_t* const* __restrict__ carry) {
   __shared__ ResolveLds Sg[R2_WAVES];
   const int lane = threadIdx.x & 63, wave = uniform ((int) (threadIdx.x >> 6));
   LDS ResolveLds& S = * (LDS ResolveLds*) (uintptr_t) (uint32_t) (uintptr_t)&Sg[wave];
@@ -929,12 +935,13 @@ coder_resolve_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t*
   uint32_t* I = chain_info + (size_t)chain * LH264_CODER_INFO_WORDS;
   // the partition's share of the stream's spill table (hash_cap cells of 64 bytes = 8 entries each)
   const uint32_t hc = streams[chain].hash_cap;
-  if (hc == 0u || (hc & (hc - 1u)) != 0u || hc > (1u << 20) || ((hc * 8u) >> log2p) < 64u) {
+  if (hc == 0u || (hc & (hc - 1u)) != 0u || hc > (1u << 20) || ((hc * 8u) >> (CARRY ? 0 : log2p)) < 64u) {
     if (lane == 0) atomicOr (&I[LH264_CODER_INFO_STATUS], (uint32_t)LH264_CODER_ST_TABLE_FULL);
     return;
   }
-  const uint32_t tsize = (hc * 8u) >> log2p, tmask = tsize - 1u;
-  GLB u64* T = glb<u64> (streams[chain].hash_cells_dev) + (size_t)part * tsize;
+  if (CARRY && (I[LH264_CODER_INFO_STATUS] & LH264_CODER_ST_COUNT)) return;      // a segment over a counter's limit leaves the carry as it was: the caller sends a shorter one
+  const uint32_t tsize = (hc * 8u) >> (CARRY ? 0 : log2p), tmask = tsize - 1u;
+  GLB u64* T = CARRY ? glb<u64> (carry[chain] + LH264_CARRY_TABLE_BYTES) : glb<u64> (streams[chain].hash_cells_dev) + (size_t)part * tsize;
   GLB uint16_t* Qc = glb<uint16_t> (Q) + ((unsigned long long)I[LH264_CODER_INFO_QBASE] | (unsigned long long)I[LH264_CODER_INFO_QBASE + 1] << 32);
   const GLB uint64_t* Dg = glb<const uint64_t> (D);
   for (int i = lane; i < R2_SLOTS; i += 64) S.ent[i] = 0ull;
@@ -971,10 +978,11 @@ coder_resolve_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t*
   // words loaded above have arrived: otherwise it puts "s_waitcnt vmcnt(0)" in front of their first use INSIDE the loop - the loop
   // carries them - and every round drains the requests under way, i.e. waits for memory once per round)
   __builtin_amdgcn_s_waitcnt (0x0F70);                     // vmcnt(0), gfx9 encoding
-  bool spilled = false;
+  bool spilled = CARRY;
   SlotRef e0, e1;
-  rs_lookup (S, T, tmask, (uint32_t)w0, (uint32_t) (w0 >> 32), (uint32_t)lane < n0, false, e0);
-  rs_lookup (S, T, tmask, (uint32_t)w1, (uint32_t) (w1 >> 32), (uint32_t)lane < n1, false, e1);
+  rs_lookup (S, T, tmask, (uint32_t)w0, (uint32_t) (w0 >> 32), (uint32_t)lane < n0, CARRY, e0);
+  rs_lookup (S, T, tmask, (uint32_t)w1, (uint32_t) (w1 >> 32), (uint32_t)lane < n1, CARRY, e1);
+  if (CARRY) { rs_land (S, T, tmask, (uint32_t)w0, (uint32_t) (w0 >> 32), e0); wsync(); }
   uint32_t nres = (uint32_t)__popcll (__ballot (e0.inserted)) + (uint32_t)__popcll (__ballot (e1.inserted));
   bool pend_ok = false; uint32_t pend_q = 0, pend_v = 0;
   // The waves of a stream keep near one another (a hint, never waited for beyond a bounded number of looks): a sector of a tag list is
@@ -1101,7 +1109,24 @@ coder_resolve_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t*
   }
   if (pend_ok) Qc[pend_q] = (uint16_t)pend_v;
   if (prog && lane == 0) __hip_atomic_store (prog + part, 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (CARRY) {                                             // the DynProbs of the cache to the carry's table: the next segment starts from there
+    wsync();
+    if (!rs_flush (S, T, tmask, lane)) atomicOr (&I[LH264_CODER_INFO_STATUS], (uint32_t)LH264_CODER_ST_TABLE_FULL);
+  }
   RS_STAMP_FLUSH
+}
+__global__ void __launch_bounds__ (R2_WAVES * 64)
+coder_resolve_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t* __restrict__ chain_info, const uint32_t* __restrict__ seg0,
+                      const int32_t* __restrict__ chain_first, const uint32_t* __restrict__ seg_doff, const uint32_t* __restrict__ seg_part,
+                      const uint64_t* __restrict__ D, uint16_t* __restrict__ Q, int n_chains, int log2p, uint32_t* __restrict__ progress, int window) {
+  resolve_body<false> (streams, chain_info, seg0, chain_first, seg_doff, seg_part, D, Q, n_chains, log2p, progress, window, nullptr);
+}
+__global__ void __launch_bounds__ (R2_WAVES * 64)
+coder_resolve_carry_kernel (const lh264_code_stream_t* __restrict__ streams, uint32_t* __restrict__ chain_info, const uint32_t* __restrict__ seg0,
+                            const int32_t* __restrict__ chain_first, const uint32_t* __restrict__ seg_doff, const uint32_t* __restrict__ seg_part,
+                            const uint64_t* __restrict__ D, uint16_t* __restrict__ Q, int n_chains, int log2p, uint32_t* __restrict__ progress, int window,
+                            uint8_t* const* __restrict__ carry) {
+  resolve_body<true> (streams, chain_info, seg0, chain_first, seg_doff, seg_part, D, Q, n_chains, log2p, progress, window, carry);
 }
 #ifdef LH264_CODER_DEBUG
 void read_rs_stamps (unsigned long long* out, bool reset) {
@@ -1163,7 +1188,7 @@ __device__ __forceinline__ PairInfo pair_info (const uint32_t* chain_info, const
   P.n = slot < 35u ? I[LH264_CODER_INFO_TAGCNT + slot] : 0u;
   const unsigned long long tm = (unsigned long long)I[LH264_CODER_INFO_TOUCH] | (unsigned long long)I[LH264_CODER_INFO_TOUCH + 1] << 32;
   P.used = slot < 35u && (P.n > 0u || ((tm >> slot) & 1ull));
-  P.total = P.used ? P.n + 32u : 0u;
+  P.total = P.used ? P.n + ((I[LH264_CODER_INFO_FLAGS] & 1u) ? 0u : 32u) : 0u;      // (a segment that is not the stream's last ends without the stop decisions)
   const unsigned long long q0 = ((unsigned long long)I[LH264_CODER_INFO_QBASE] | (unsigned long long)I[LH264_CODER_INFO_QBASE + 1] << 32) + I[LH264_CODER_INFO_TAGBASE + (slot < 35u ? slot : 0u)];
   P.list = glb<const uint16_t> (Q) + q0;
   P.acc0 = q0 + 48ull * pair;                        // the pair's sums: fewer than n + 40 positions (a decision shifts out 7 bits at most)
@@ -1193,7 +1218,8 @@ coder_chunkmap_kernel (uint32_t* __restrict__ chain_info, int n_pairs, uint32_t*
       else {                                               // (the touch mask is read only by the lanes of live streams: nothing here clears it)
         const uint32_t n = slot < 35u ? I[LH264_CODER_INFO_TAGCNT + slot] : 0u;
         const unsigned long long tm = (unsigned long long)I[LH264_CODER_INFO_TOUCH] | (unsigned long long)I[LH264_CODER_INFO_TOUCH + 1] << 32;
-        if (slot < 35u && (n > 0u || ((tm >> slot) & 1ull))) { v = (n + 32u + CODE_CHUNK - 1u) / CODE_CHUNK; v2 = (n + 32u + CODE_COARSE - 1u) / CODE_COARSE; }
+        const uint32_t tot = n + ((I[LH264_CODER_INFO_FLAGS] & 1u) ? 0u : 32u);
+        if (slot < 35u && (n > 0u || ((tm >> slot) & 1ull))) { v = (tot + CODE_CHUNK - 1u) / CODE_CHUNK; v2 = (tot + CODE_COARSE - 1u) / CODE_COARSE; }
       }
     }
     const uint32_t incl = (uint32_t)wave_scan_add ((int)v), incl2 = (uint32_t)wave_scan_add ((int)v2);
@@ -1246,12 +1272,12 @@ __device__ __forceinline__ uint32_t coarse_pair (const uint32_t* __restrict__ pa
 #define CODE_MAPPED 0xffffffff00000000ull      // candidate words of a chunk with more than CODE_CANDS possible start states
 __global__ void __launch_bounds__ (256)
 coder_range_seed_kernel (const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q, const uint32_t* __restrict__ pair_coarse0, int n_pairs,
-                         uint32_t* __restrict__ cand, uint32_t* __restrict__ cand_list, uint32_t long_list) {
+                         uint32_t* __restrict__ cand, uint32_t* __restrict__ cand_list, uint32_t long_list, const uint32_t* __restrict__ pair_start) {
   const uint32_t G = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (G >= pair_coarse0[n_pairs]) return;
   const uint32_t pair = (uint32_t)uniform ((int)coarse_pair (pair_coarse0, (uint32_t)n_pairs, G));
   const uint32_t c = G - pair_coarse0[pair];
-  if (c == 0u) { if (lane < 2u) cand[2 * (size_t)G + lane] = lane == 0u ? 255u : 0u; return; }
+  if (c == 0u) { if (lane < 2u) cand[2 * (size_t)G + lane] = lane == 0u ? (pair_start ? pair_start[LH264_PAIR_START_WORDS * (size_t)pair] : 255u) : 0u; return; }      // (a resumed list starts from the carried state)
   const PairInfo P = pair_info (chain_info, Q, pair);
   // a list of moderate length (the host's choice, lh264_capi.hip) is walked whole by the lane of its first chunk - candidates cost
   // several walks per chunk, which only pays where one lane would take longer than the rest of the coder
@@ -1441,10 +1467,10 @@ coder_range_first_kernel (const uint32_t* __restrict__ chain_info, const uint16_
 // walked by the lane of the chunk in front of them)
 __global__ void __launch_bounds__ (64)
 coder_range_link_kernel (const uint32_t* __restrict__ pair_coarse0, int n_pairs, const uint32_t* __restrict__ cand, const uint8_t* __restrict__ cand_end,
-                         const uint8_t* __restrict__ cmap, uint32_t* __restrict__ seed, uint32_t* __restrict__ chain_info) {
+                         const uint8_t* __restrict__ cmap, uint32_t* __restrict__ seed, uint32_t* __restrict__ chain_info, const uint32_t* __restrict__ pair_start) {
   const uint32_t pair = blockIdx.x * 64u + threadIdx.x;
   if (pair >= (uint32_t)n_pairs) return;
-  uint32_t s = 255u;
+  uint32_t s = pair_start ? pair_start[LH264_PAIR_START_WORDS * (size_t)pair] : 255u;
   bool lost = false;
   for (uint32_t G = pair_coarse0[pair]; G < pair_coarse0[pair + 1]; G++) {
     const unsigned long long cs = (unsigned long long)cand[2 * (size_t)G] | (unsigned long long)cand[2 * (size_t)G + 1] << 32;
@@ -1473,11 +1499,14 @@ coder_range_walk_kernel (const uint32_t* __restrict__ chain_info, const uint16_t
 // pair_bits[pair] all the bits the list shifts out
 __global__ void __launch_bounds__ (256)
 coder_range_scan_kernel (const uint32_t* __restrict__ pair_coarse0, int n_pairs, uint32_t* __restrict__ coarse_bits, uint32_t* __restrict__ pair_bits,
-                         const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q, uint32_t* __restrict__ acc) {
+                         const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q, uint32_t* __restrict__ acc,
+                         const uint32_t* __restrict__ pair_start, const lh264_code_stream_t* __restrict__ streams) {
   const uint32_t pair = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (pair >= (uint32_t)n_pairs) return;
   const uint32_t G0 = pair_coarse0[pair], G1 = pair_coarse0[pair + 1];
-  uint32_t carry = 0;
+  // a resumed list: its positions count from the output byte the carried bits end in (the bits of that byte in front of the list)
+  const uint32_t* ps = pair_start ? pair_start + LH264_PAIR_START_WORDS * (size_t)pair : nullptr;
+  uint32_t carry = ps ? ps[1] : 0u;
   for (uint32_t g = G0; g < G1; g += 64u) {
     const uint32_t v = g + lane < G1 ? coarse_bits[g + lane] : 0u;
     const uint32_t incl = (uint32_t)wave_scan_add ((int)v);
@@ -1492,6 +1521,12 @@ coder_range_scan_kernel (const uint32_t* __restrict__ pair_coarse0, int n_pairs,
     GLB uint32_t* A = glb<uint32_t> (acc) + P.acc0;
     const uint32_t n = (carry >> 3) + 8u;
     for (uint32_t k = lane; k < n; k += 64u) A[k] = 0u;
+    // ... and its first two sums start from what the segments before left there: the last two bytes they wrote
+    if (ps && (ps[3] & LH264_PAIR_EXISTED) && lane < 2u) {
+      const lh264_code_stream_t* S = streams + pair / LH264_N_TAG_SLOTS;
+      const uint32_t at = ps[2] + lane;
+      if (at < S->out_cap) A[lane] = glb<const uint8_t> (S->out_dev)[(size_t) (pair % LH264_N_TAG_SLOTS) * S->out_cap + at];
+    }
   }
 }
 
@@ -1600,9 +1635,14 @@ coder_accum_kernel (const uint32_t* __restrict__ chain_info, const uint16_t* __r
 // div 256 - and from there on a carry is one bit: a position generates one (C >= 256), passes one on (C == 255) or ends it.  The
 // carries into the 64 positions of a step are then ONE 64-bit addition of the two lane masks (the adder's own carry chain does the
 // work: carries = ((G | P) + G + carry_in) ^ P), and the carry out of the step goes into the next.
-__global__ void __launch_bounds__ (256)
-coder_bytes_kernel (const lh264_code_stream_t* __restrict__ streams, const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q,
-                    const uint32_t* __restrict__ pair_bits, const uint32_t* __restrict__ acc, int n_pairs) {
+// CARRY (lh264_code_chains_resume): the pair's sums start at output byte p0 (pair_start), the bytes in front of it were written by the
+// segments before.  A segment that is not the stream's last writes every byte its bits have reached AND the two behind them - the
+// sums later addends still add to, brought down to one byte each: they are where the next segment's sums start (coder_range_scan_kernel).
+// A carry out of the segment's first position is noted in the carry block and applied to the bytes in front by coder_carry_out_kernel.
+template <bool CARRY> __device__ __forceinline__ void
+bytes_body (const lh264_code_stream_t* __restrict__ streams, const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q,
+            const uint32_t* __restrict__ pair_bits, const uint32_t* __restrict__ acc, int n_pairs,
+            const uint32_t* __restrict__ pair_start, const uint32_t* __restrict__ pair_chunk0, const uint32_t* __restrict__ chunk_rec, uint8_t* const* __restrict__ carry) {
   const uint32_t pair = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (pair >= (uint32_t)n_pairs) return;
   const uint32_t chain = pair / LH264_N_TAG_SLOTS, slot = pair % LH264_N_TAG_SLOTS;
@@ -1610,11 +1650,20 @@ coder_bytes_kernel (const lh264_code_stream_t* __restrict__ streams, const uint3
   const lh264_code_stream_t* S = streams + chain;
   GLB uint32_t* lens = glb<uint32_t> (S->out_len_dev);
   const PairInfo P = pair_info (chain_info, Q, pair);
-  if (!P.used) { if (lane == 0u) lens[slot] = 0; return; }
-  const uint32_t bits = pair_bits[pair], cap = S->out_cap;
-  uint32_t nbytes = bits >= 24u ? ((bits - 24u) >> 3) + 1u : 0u;
+  const uint32_t* ps = CARRY ? pair_start + LH264_PAIR_START_WORDS * (size_t)pair : nullptr;
+  GLB uint32_t* rec = CARRY ? glb<uint32_t> (carry[chain]) + LH264_CARRY_HDR_WORDS + slot * LH264_CARRY_TAG_WORDS : (GLB uint32_t*)nullptr;
+  if (!P.used) {
+    if (lane == 0u) lens[slot] = 0;
+    if (CARRY && lane < LH264_CARRY_TAG_WORDS && (ps[3] & LH264_PAIR_FIRST)) rec[lane] = 0u;
+    return;
+  }
+  const uint32_t bits = pair_bits[pair], pbase = CARRY ? ps[2] : 0u;
+  const bool last_seg = !CARRY || (ps[3] & LH264_PAIR_LAST);
+  const uint32_t cap = CARRY ? (S->out_cap > pbase ? S->out_cap - pbase : 0u) : S->out_cap;
+  // (bytes from pbase on.  The whole list has shifted out 8 pbase + bits bits: with the stop decisions among them bits >= 31 here)
+  uint32_t nbytes = !last_seg ? (bits >> 3) + 2u : bits >= 24u ? ((bits - 24u) >> 3) + 1u : 0u;
   const GLB uint32_t* A = glb<const uint32_t> (acc) + P.acc0;
-  GLB uint8_t* o = glb<uint8_t> (S->out_dev) + (size_t)slot * cap;
+  GLB uint8_t* o = glb<uint8_t> (S->out_dev) + (size_t)slot * S->out_cap + pbase;
   const bool wide = (((uintptr_t)o) & 3u) == 0u;
   const uint32_t last = (bits >> 3) + 2u;                      // no addend lies behind this position (the sums behind it read zero)
   uint32_t cin = 0, final_byte = 0;
@@ -1660,10 +1709,114 @@ coder_bytes_kernel (const lh264_code_stream_t* __restrict__ streams, const uint3
   }
   final_byte = (uint32_t)__builtin_amdgcn_readlane (wave_scan_add ((int)final_byte), 63);      // (one lane held it)
   if (lane == 0u) {
-    if (nbytes > 0u && (final_byte & 0xe0u) == 0xc0u) { if (nbytes < cap) o[nbytes] = 0; nbytes++; }
-    lens[slot] = nbytes;
+    if (last_seg && nbytes > 0u && (final_byte & 0xe0u) == 0xc0u) { if (nbytes < cap) o[nbytes] = 0; nbytes++; }
+    lens[slot] = pbase + nbytes;                          // (not the last segment: coder_carry_out_kernel puts the number of final bytes here)
     if (nbytes > cap) atomicOr ((uint32_t*) (uintptr_t) (lens + LH264_N_TAG_SLOTS), (uint32_t)LH264_CODER_ST_OUT_FULL);
+    if (CARRY) {
+      // the range behind the list's last decision: the walk of its last chunk again, from the noted state (one lane, <= CODE_CHUNK decisions)
+      uint32_t range = ps[0];
+      const uint32_t g0 = pair_chunk0[pair], g1 = pair_chunk0[pair + 1];
+      if (!last_seg && g1 > g0) {
+        range = chunk_rec[2 * (size_t) (g1 - 1u)] & 0xffu;
+        ListReader L; L.init (P.list, P.n);
+        for (uint32_t i = (g1 - 1u - g0) * CODE_CHUNK; i < P.total; i++) code_step (range, L.at (i));
+      }
+      const bool first = (ps[3] & LH264_PAIR_FIRST) != 0u;
+      const unsigned long long b = 8ull * pbase + bits, nd = (first ? 0ull : ((unsigned long long)rec[LH264_CARRY_TAG_NDEC] | (unsigned long long)rec[LH264_CARRY_TAG_NDEC + 1] << 32)) + P.n;
+      rec[LH264_CARRY_TAG_BITS] = (uint32_t)b; rec[LH264_CARRY_TAG_BITS + 1] = (uint32_t) (b >> 32);
+      rec[LH264_CARRY_TAG_NDEC] = (uint32_t)nd; rec[LH264_CARRY_TAG_NDEC + 1] = (uint32_t) (nd >> 32);
+      // what leaves the segment's first position upwards: the carry of the walk above, what the first position's digit holds beyond a
+      // byte, and the high bytes of the first three sums (in an unsegmented list all of these are zero - the coder's sum stays below
+      // one -, here the sums start in the middle of the number)
+      rec[LH264_CARRY_TAG_RANGE] = range; rec[LH264_CARRY_TAG_EXISTS] = 1u; rec[7] = 0u;
+      const uint32_t b0 = (A[0] & 255u) + ((A[1] >> 8) & 255u) + ((A[2] >> 16) & 255u) + (A[3] >> 24);      // the first position's digit before the walk's carries
+      rec[LH264_CARRY_TAG_CIN] = pbase ? cin + (b0 >> 8) + (A[0] >> 8) + (A[1] >> 16) + (A[2] >> 24) : 0u;
+    }
   }
+}
+__global__ void __launch_bounds__ (256)
+coder_bytes_kernel (const lh264_code_stream_t* __restrict__ streams, const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q,
+                    const uint32_t* __restrict__ pair_bits, const uint32_t* __restrict__ acc, int n_pairs) {
+  bytes_body<false> (streams, chain_info, Q, pair_bits, acc, n_pairs, nullptr, nullptr, nullptr, nullptr);
+}
+__global__ void __launch_bounds__ (256)
+coder_bytes_carry_kernel (const lh264_code_stream_t* __restrict__ streams, const uint32_t* __restrict__ chain_info, const uint16_t* __restrict__ Q,
+                          const uint32_t* __restrict__ pair_bits, const uint32_t* __restrict__ acc, int n_pairs,
+                          const uint32_t* __restrict__ pair_start, const uint32_t* __restrict__ pair_chunk0, const uint32_t* __restrict__ chunk_rec, uint8_t* const* __restrict__ carry) {
+  bytes_body<true> (streams, chain_info, Q, pair_bits, acc, n_pairs, pair_start, pair_chunk0, chunk_rec, carry);
+}
+
+// ---- the carry of a resumable call: in front of the range stage and behind the bytes ---------------------------------------------------
+// One thread per (stream, tag slot) pair: where the tag's coder stands (range, bits shifted out: pair_start), tags that exist from
+// earlier segments into the stream's touch mask, "no stop decisions" unless the stream ends here, an earlier segment's failure into
+// this one's status.  In front of the resolve kernel (which adds a full table to the status word) and of coder_status_kernel; a stream
+// that failed in an earlier segment is still resolved - its table is of no use any more - and dropped by coder_chunkmap_kernel.
+__global__ void __launch_bounds__ (256)
+coder_carry_in_kernel (uint8_t* const* __restrict__ carry, const uint32_t* __restrict__ flags, uint32_t* __restrict__ chain_info, int n_pairs, uint32_t* __restrict__ pair_start) {
+  const uint32_t pair = blockIdx.x * 256u + threadIdx.x;
+  if (pair >= (uint32_t)n_pairs) return;
+  const uint32_t chain = pair / LH264_N_TAG_SLOTS, slot = pair % LH264_N_TAG_SLOTS;
+  GLB uint32_t* hdr = glb<uint32_t> (carry[chain]);
+  const GLB uint32_t* rec = hdr + LH264_CARRY_HDR_WORDS + slot * LH264_CARRY_TAG_WORDS;
+  uint32_t* I = chain_info + (size_t)chain * LH264_CODER_INFO_WORDS;
+  const uint32_t fl = flags[chain];
+  const bool first = (fl & LH264_CODE_SEG_FIRST) != 0u, live = !first && slot < 35u;
+  const unsigned long long bits = live ? (unsigned long long)rec[LH264_CARRY_TAG_BITS] | (unsigned long long)rec[LH264_CARRY_TAG_BITS + 1] << 32 : 0ull;
+  const uint32_t range = live ? rec[LH264_CARRY_TAG_RANGE] : 0u, exists = live && rec[LH264_CARRY_TAG_EXISTS] != 0u ? 1u : 0u;
+  uint32_t* ps = pair_start + LH264_PAIR_START_WORDS * (size_t)pair;
+  ps[0] = range >= 128u && range <= 255u ? range : 255u; ps[1] = (uint32_t) (bits & 7ull); ps[2] = (uint32_t) (bits >> 3);
+  ps[3] = (exists ? LH264_PAIR_EXISTED : 0u) | ((fl & LH264_CODE_SEG_LAST) ? LH264_PAIR_LAST : 0u) | (first ? LH264_PAIR_FIRST : 0u);
+  if (exists) atomicOr (&I[LH264_CODER_INFO_TOUCH + (slot >> 5)], 1u << (slot & 31u));
+  if (slot == 0u) {
+    if (!(fl & LH264_CODE_SEG_LAST)) I[LH264_CODER_INFO_FLAGS] = 1u;
+    if (first) { hdr[0] = 0u; hdr[1] = 0u; }
+    else if (hdr[0]) atomicOr (&I[LH264_CODER_INFO_STATUS], hdr[0]);
+  }
+}
+// One thread per pair, behind the bytes: a carry out of the segment's sums runs back through the 0xff bytes in front of them (rare, and
+// then mostly a byte or two; the walk is serial); a segment that is not the last reports how many of the tag's bytes are FINAL - those in
+// front of the last byte that is not 0xff, which a later carry can still reach.  The stream's status is kept in the carry.
+__global__ void __launch_bounds__ (256)
+coder_carry_out_kernel (const lh264_code_stream_t* __restrict__ streams, uint8_t* const* __restrict__ carry, const uint32_t* __restrict__ pair_start, int n_pairs) {
+  const uint32_t pair = blockIdx.x * 256u + threadIdx.x;
+  if (pair >= (uint32_t)n_pairs) return;
+  const uint32_t chain = pair / LH264_N_TAG_SLOTS, slot = pair % LH264_N_TAG_SLOTS;
+  const lh264_code_stream_t* S = streams + chain;
+  GLB uint32_t* lens = glb<uint32_t> (S->out_len_dev);
+  GLB uint32_t* hdr = glb<uint32_t> (carry[chain]);
+  const uint32_t* ps = pair_start + LH264_PAIR_START_WORDS * (size_t)pair;
+  if (slot < 35u && lens[slot] != 0u) {
+    GLB uint32_t* rec = hdr + LH264_CARRY_HDR_WORDS + slot * LH264_CARRY_TAG_WORDS;
+    GLB uint8_t* o = glb<uint8_t> (S->out_dev) + (size_t)slot * S->out_cap;
+    const uint32_t cap = S->out_cap;
+    if (const uint32_t n = rec[LH264_CARRY_TAG_CIN]) {
+      bool ok = n == 1u;                               // (one at most: the coder's sum stays below one)
+      if (ok) {
+        ok = false;
+        for (uint32_t k = ps[2]; k > 0u && !ok; ) {
+          k--;
+          if (k >= cap) continue;                      // (the output has overflowed: reported already)
+          const uint32_t b = o[k];
+          o[k] = (uint8_t) (b + 1u);
+          ok = b != 0xffu;
+        }
+        ok = ok || ps[2] > cap;
+      }
+      if (!ok) atomicOr ((uint32_t*) (uintptr_t) (lens + LH264_N_TAG_SLOTS), (uint32_t)LH264_CODER_ST_HANDOFF);
+      rec[LH264_CARRY_TAG_CIN] = 0u;
+    }
+    if (!(ps[3] & LH264_PAIR_LAST)) {
+      const unsigned long long bits = (unsigned long long)rec[LH264_CARRY_TAG_BITS] | (unsigned long long)rec[LH264_CARRY_TAG_BITS + 1] << 32;
+      uint32_t k = (uint32_t)min (bits >> 3, (unsigned long long)cap);
+      while (k > 0u && o[k - 1u] == 0xffu) k--;
+      lens[slot] = k > 0u ? k - 1u : 0u;
+    }
+  }
+  // (the other threads of the stream may still be adding their bit: whoever adds one to the status word adds it to the carry too.
+  // Not the counter overflow: that segment was not coded and the carry stands as it was)
+  const uint32_t st = __hip_atomic_load (lens + LH264_N_TAG_SLOTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (slot == 0u && !(st & LH264_CODER_ST_COUNT)) hdr[1] += 1u;
+  if (st & ~ (uint32_t)LH264_CODER_ST_COUNT) atomicOr ((uint32_t*) (uintptr_t)hdr, st & ~ (uint32_t)LH264_CODER_ST_COUNT);
 }
 
 // the status word of every stream, before the coding kernel adds its own bit

@@ -42,6 +42,34 @@ def parse_batch_time(datas, threads=0, keep=True):
     return dt, pics
 
 
+def _read_frame(lib, p, i):
+    """picture i of parser p as a ParsedFrame"""
+    info = np.zeros(1, dtype=L.FRAME_INFO_DTYPE)
+    L.check(lib.lh264_parser_frame_info(p, i, info.ctypes.data_as(C.c_void_p)))
+    fi = info[0]
+    f = ParsedFrame()
+    f.id, f.mb_w, f.mb_h, f.frame_num = int(fi["id"]), int(fi["mb_w"]), int(fi["mb_h"]), int(fi["frame_num"])
+    f.crop_x, f.crop_y, f.crop_w, f.crop_h = int(fi["crop_x"]), int(fi["crop_y"]), int(fi["crop_w"]), int(fi["crop_h"])
+    f.is_ref, f.idr = bool(fi["is_ref"]), bool(fi["idr"])
+    f.ref_ids = [int(x) for x in fi["ref_ids"][:int(fi["n_refs"])]]
+    n, ns = f.mb_w * f.mb_h, int(fi["n_slices"])
+
+    def arr(ptr, nbytes, dtype):
+        return np.frombuffer(C.string_at(ptr, nbytes), dtype=dtype).copy()
+    f.mbs = arr(lib.lh264_parser_frame_mbs(p, i), n * 128, L.MB_DTYPE)
+    f.coeffs = arr(lib.lh264_parser_frame_coeffs(p, i), n * 768, "<i2").reshape(n, 384)
+    f.levels = arr(lib.lh264_parser_frame_levels(p, i), n * 768, "<i2").reshape(n, 384)
+    f.slices = arr(lib.lh264_parser_frame_slices(p, i), ns * 232, L.SLICE_DTYPE)
+    f.covered = arr(lib.lh264_parser_frame_covered(p, i), n, np.uint8)
+    f.syn = arr(lib.lh264_parser_frame_syntax(p, i), n * 116, L.MBSYN_DTYPE)
+    f.slice_syn = arr(lib.lh264_parser_frame_slice_syntax(p, i), ns * 16, "<i4").reshape(ns, 4)
+    cnt = C.c_int(0)
+    ptr = lib.lh264_parser_frame_syn_symbols(p, i, C.byref(cnt))
+    f.syn_syms = arr(ptr, cnt.value * 8, L.CTX_SYM_DTYPE) if cnt.value else np.zeros(0, L.CTX_SYM_DTYPE)
+    f.syn_off = arr(lib.lh264_parser_frame_syn_offsets(p, i), (n + 1) * 4, "<u4")
+    return f
+
+
 def parse_stream(data, strict=False, _file=False, _pcm=False):
     """-> (frames, error_text).  frames have the attributes ReconSession / CtxSession expect."""
     lib = L.lib()
@@ -54,32 +82,7 @@ def parse_stream(data, strict=False, _file=False, _pcm=False):
         err = lib.lh264_parser_error(p).decode()
         if rc != 0 and strict:
             raise RuntimeError("h264 parse error: " + err)
-        frames = []
-        info = np.zeros(1, dtype=L.FRAME_INFO_DTYPE)
-        for i in range(lib.lh264_parser_frame_count(p)):
-            L.check(lib.lh264_parser_frame_info(p, i, info.ctypes.data_as(C.c_void_p)))
-            fi = info[0]
-            f = ParsedFrame()
-            f.id, f.mb_w, f.mb_h, f.frame_num = int(fi["id"]), int(fi["mb_w"]), int(fi["mb_h"]), int(fi["frame_num"])
-            f.crop_x, f.crop_y, f.crop_w, f.crop_h = int(fi["crop_x"]), int(fi["crop_y"]), int(fi["crop_w"]), int(fi["crop_h"])
-            f.is_ref, f.idr = bool(fi["is_ref"]), bool(fi["idr"])
-            f.ref_ids = [int(x) for x in fi["ref_ids"][:int(fi["n_refs"])]]
-            n, ns = f.mb_w * f.mb_h, int(fi["n_slices"])
-
-            def arr(ptr, nbytes, dtype):
-                return np.frombuffer(C.string_at(ptr, nbytes), dtype=dtype).copy()
-            f.mbs = arr(lib.lh264_parser_frame_mbs(p, i), n * 128, L.MB_DTYPE)
-            f.coeffs = arr(lib.lh264_parser_frame_coeffs(p, i), n * 768, "<i2").reshape(n, 384)
-            f.levels = arr(lib.lh264_parser_frame_levels(p, i), n * 768, "<i2").reshape(n, 384)
-            f.slices = arr(lib.lh264_parser_frame_slices(p, i), ns * 232, L.SLICE_DTYPE)
-            f.covered = arr(lib.lh264_parser_frame_covered(p, i), n, np.uint8)
-            f.syn = arr(lib.lh264_parser_frame_syntax(p, i), n * 116, L.MBSYN_DTYPE)
-            f.slice_syn = arr(lib.lh264_parser_frame_slice_syntax(p, i), ns * 16, "<i4").reshape(ns, 4)
-            cnt = C.c_int(0)
-            ptr = lib.lh264_parser_frame_syn_symbols(p, i, C.byref(cnt))
-            f.syn_syms = arr(ptr, cnt.value * 8, L.CTX_SYM_DTYPE) if cnt.value else np.zeros(0, L.CTX_SYM_DTYPE)
-            f.syn_off = arr(lib.lh264_parser_frame_syn_offsets(p, i), (n + 1) * 4, "<u4")
-            frames.append(f)
+        frames = [_read_frame(lib, p, i) for i in range(lib.lh264_parser_frame_count(p))]
         if _file:
             ln = C.c_size_t(0)
             ptr = lib.lh264_parser_main_stream(p, C.byref(ln))
@@ -89,5 +92,39 @@ def parse_stream(data, strict=False, _file=False, _pcm=False):
                 return frames, err, main, (C.string_at(ptr, ln.value) if ln.value else b"")
             return frames, err, main
         return frames, err
+    finally:
+        lib.lh264_parser_destroy(p)
+
+
+def parse_file_segments(data, segment_mbs):
+    """a file parsed in pieces (lh264_parser_begin_file / lh264_parser_feed_file_some / lh264_parser_drop_frames): yields lists of
+    frames - whole pictures, at most segment_mbs macroblocks a list but one picture at least - and at last the tuple
+    (error text, default stream).  The parser never holds more than a segment and a picture"""
+    lib = L.lib()
+    p = lib.lh264_parser_create()
+    data = bytes(data)
+    try:
+        L.check(lib.lh264_parser_begin_file(p, data, len(data)))
+        done = False
+        while True:
+            if not done:
+                done = lib.lh264_parser_feed_file_some(p, segment_mbs) == 1
+            n = lib.lh264_parser_frame_count(p)
+            if n == 0:
+                if done:
+                    break
+                continue
+            seg, m = [], 0
+            for i in range(n):
+                f = _read_frame(lib, p, i)
+                if seg and m + f.mb_w * f.mb_h > segment_mbs:
+                    break
+                seg.append(f)
+                m += f.mb_w * f.mb_h
+            L.check(lib.lh264_parser_drop_frames(p, len(seg)))
+            yield seg
+        ln = C.c_size_t(0)
+        ptr = lib.lh264_parser_main_stream(p, C.byref(ln))
+        yield lib.lh264_parser_error(p).decode(), (C.string_at(ptr, ln.value) if ln.value else b"")
     finally:
         lib.lh264_parser_destroy(p)

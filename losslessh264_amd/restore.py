@@ -187,6 +187,17 @@ class CompressedBatch:
     def status(self, i):
         return L.lib().lh264_compressed_status(self._h[i])
 
+    def pictures(self, i):
+        return L.lib().lh264_compressed_pictures(self._h[i])
+
+    def segments(self, i):
+        """in how many segments stream i was coded (1: whole; more: it was longer than segment_mbs)"""
+        return L.lib().lh264_compressed_segments(self._h[i])
+
+    def decisions(self, i, tag):
+        """binary decisions coded into stream i's tag `tag`, summed over its segments"""
+        return int(L.lib().lh264_compressed_decisions(self._h[i], tag))
+
     def free(self):
         lib = L.lib()
         for i in range(self.n):
@@ -202,8 +213,9 @@ class CompressedBatch:
             pass
 
 
-def compress_batch_handles(datas, threads=0, devices=None):
-    """lh264_compress_batch / lh264_compress_batch_devices -> CompressedBatch (call .free() when done)"""
+def compress_batch_handles(datas, threads=0, devices=None, segment_mbs=None):
+    """lh264_compress_batch_opts / lh264_compress_batch_devices_opts -> CompressedBatch (call .free() when done).  segment_mbs: streams of
+    more macroblocks are coded in segments of at most that many (whole pictures); None: the library's default"""
     import time
     lib = L.lib()
     n = len(datas)
@@ -211,21 +223,22 @@ def compress_batch_handles(datas, threads=0, devices=None):
     lens = (C.c_size_t * n)(*[len(d) for d in datas])
     outs = (C.c_void_p * n)()
     t0 = time.perf_counter()
+    opts = L.CompressOpts(C.sizeof(L.CompressOpts), 0, int(segment_mbs or 0))
     if devices:
         devs = (C.c_int * len(devices))(*devices)
-        rc = lib.lh264_compress_batch_devices(ptrs, lens, n, threads, devs, len(devices), outs)
+        rc = lib.lh264_compress_batch_devices_opts(ptrs, lens, n, threads, devs, len(devices), C.byref(opts), outs)
     else:
-        rc = lib.lh264_compress_batch(ptrs, lens, n, threads, outs)
+        rc = lib.lh264_compress_batch_opts(ptrs, lens, n, threads, C.byref(opts), outs)
     dt = time.perf_counter() - t0
     L.check(rc)
     return CompressedBatch(outs, n, dt)
 
 
-def compress_batch(datas, threads=0, devices=None):
+def compress_batch(datas, threads=0, devices=None, segment_mbs=None):
     """the whole compress direction behind one C call (lh264_compress_batch): list of Annex-B byte strings ->
     list of (main bytes, {tag: bytes}, error text or None).  devices: list of device indices to shard the batch over
-    (lh264_compress_batch_devices); default: the current device"""
-    b = compress_batch_handles(datas, threads, devices)
+    (lh264_compress_batch_devices); default: the current device.  segment_mbs: see compress_batch_handles"""
+    b = compress_batch_handles(datas, threads, devices, segment_mbs)
     res = [b.result(i) for i in range(b.n)]
     b.free()
     return res
