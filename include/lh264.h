@@ -375,6 +375,12 @@ int   lh264_parser_frame_info (const lh264_parser_t* p, int idx, lh264_frame_inf
 const lh264_mb_t*    lh264_parser_frame_mbs (const lh264_parser_t* p, int idx);
 const int16_t*       lh264_parser_frame_coeffs (const lh264_parser_t* p, int idx);
 const int16_t*       lh264_parser_frame_levels (const lh264_parser_t* p, int idx);
+/* sparse coefficients (set before the first byte is fed): lh264_parser_frame_coeffs is NULL and the picture's nonzero dequantised
+ * coefficients - of an I_PCM macroblock its nonzero samples - come as a list, ascending:
+ * (picture-relative macroblock * 384 + position) << 16 | (uint16_t) value.  What lh264_decode_batch uploads instead of 768 bytes per
+ * macroblock; a kernel scatters it into planes cleared on the device */
+int                  lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on);
+const uint64_t*      lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count);
 const lh264_slice_t* lh264_parser_frame_slices (const lh264_parser_t* p, int idx);
 const uint8_t*       lh264_parser_frame_covered (const lh264_parser_t* p, int idx);
 /* row a10: the macroblock syntax the recompressor codes beyond lh264_mb_t (the reference's DecodedMacroblock fields,
@@ -498,6 +504,71 @@ int lh264_restore_last_timing (double* ms);
 /* the kernel's code (csrc/lh264_restore.hip) stepped on the host threads over host memory, with the same plan, capacities and
  * results as lh264_pip_restore_batch_device: a check of the device chain where no device is present; not a restore path */
 int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+
+/* ---- the decode direction behind one call (csrc/lh264_decode.hip) -------------------------------------------------------------
+ * n independent Annex-B files in host memory -> per stream its pictures in decode order (= output order: I and P slices only, as in
+ * the reference), each cropped to the SPS window and tightly packed - LH264_FMT_I420: w*h Y, then w/2 * h/2 Cb, then Cr;
+ * LH264_FMT_NV12: Y, then Cb / Cr interleaved - one behind the other with nothing between them: in I420 exactly the file the
+ * reference's console application writes (h264dec.cpp Write2File).  offset counts from the stream's first byte; a stream may change
+ * resolution, width / height are per picture.
+ * The work runs in ROUNDS: every stream that takes part contributes its next round_pictures pictures at most, one
+ * lh264_recon_chains launch reconstructs them (a chain per stream) into a per-stream pool of padded pictures (round_pictures + the
+ * references the parser's DPB still holds), a pack kernel crops them into the round's output buffer, and the download runs on a
+ * second HIP stream while the host threads (`threads`, 0 = all) parse and stage the next round: host and device memory follow the
+ * round, not the streams' length.  group_mbs bounds the macroblocks of one round (streams wait their turn in the order given).
+ * A reference slot a picture does not fill, or whose picture is not held any more, holds a picture of 128s (no concealment): what a
+ * stream that has lost its references reads there is defined and the same on every run.
+ * Every out[i] is a handle to free.  A failure stays with its stream: LH264_E_UNSUPPORTED with the text of the front end for syntax it
+ * does not parse; a picture with macroblocks no slice covers (no concealment), an incomplete slice or a NAL unit that does not parse
+ * stops the stream THERE - the pictures in front of it are delivered and valid, the text names the picture.  A stream without a
+ * picture and without an error is LH264_OK with no pictures.
+ * sink: the handles keep no bytes; the sink is called with runs of consecutive pictures of one stream (pics[k].offset as above,
+ * bytes = the first picture's first byte), in order within a stream, never from two threads at once, bytes valid for the call only;
+ * a non-zero return stops that stream (LH264_E_ARG, text "sink").
+ * The bytes do not depend on threads, round_pictures, group_mbs, the sink or on which other streams share the batch.
+ * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a format out of range, sink together with
+ * LH264_DECODE_DEVICE_OUT, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
+ * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
+#define LH264_FMT_I420 0
+#define LH264_FMT_NV12 1
+#define LH264_DECODE_DEVICE_OUT 1u   /* the pictures stay in device memory owned by the handle */
+typedef struct lh264_decoded lh264_decoded_t;
+typedef struct lh264_decoded_pic { int32_t width, height, frame_num, idr; uint64_t offset, bytes; } lh264_decoded_pic_t;
+typedef int (*lh264_decode_sink_fn) (void* user, int stream, int first_picture, int n_pictures,
+                                     const lh264_decoded_pic_t* pics, const uint8_t* bytes, size_t len);
+typedef struct lh264_decode_opts {
+  uint32_t struct_bytes, format;        /* LH264_FMT_*                                                          */
+  uint32_t flags;                       /* LH264_DECODE_*                                                       */
+  uint32_t round_pictures;              /* pictures of one stream per launch at most; 0 = the default (8)       */
+  uint64_t group_mbs;                   /* macroblocks of one round at most; 0 = the default (1,000,000)        */
+  lh264_decode_sink_fn sink; void* user;
+} lh264_decode_opts_t;
+int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads,
+                        const lh264_decode_opts_t* opts /* NULL = defaults */, lh264_decoded_t** out);
+int lh264_decoded_status (const lh264_decoded_t* d);
+const char* lh264_decoded_error (const lh264_decoded_t* d);
+int lh264_decoded_pictures (const lh264_decoded_t* d);
+int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
+const uint8_t* lh264_decoded_bytes (const lh264_decoded_t* d, size_t* len);       /* host pointer; NULL in DEVICE_OUT and sink mode */
+const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len);   /* device pointer in DEVICE_OUT mode, else NULL  */
+/* DEVICE_OUT mode: the stream's bytes copied into the caller's device memory (cap >= their length), complete on return */
+int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap);
+void lh264_decoded_free (lh264_decoded_t* d);
+int lh264_decode_arena_bytes (size_t* device, size_t* pinned);
+void lh264_decode_release (void);
+/* milliseconds of the last lh264_decode_batch call in this process: ms[0] the call, ms[1] parsing and picking the rounds' pictures
+ * (host threads), ms[2] staging, ms[3] enqueueing the device stage, ms[4] the main thread's wait for the device (the download
+ * included), ms[5] delivery (copies into the handles, or the sink).  LH264_TRACE_DECODE=1 prints the same to stderr. */
+int lh264_decode_last_timing (double* ms);
+/* one picture to crop and pack (decode_pack_kernel): the planes' pixel (0,0) in a padded picture, the window, where the packed
+ * picture begins.  crop_x/y/w/h are even.  lh264_debug_pack_cpu steps the kernel's code over HOST memory: a check of the crop / format
+ * arithmetic where no device is present; not a decode path */
+typedef struct lh264_pack_job {
+  const uint8_t* y; const uint8_t* u; const uint8_t* v;
+  uint8_t* dst;
+  int32_t stride_y, stride_c, crop_x, crop_y, crop_w, crop_h, format, reserved;
+} lh264_pack_job_t;
+int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
 
 #define LH264_OK            0
 #define LH264_E_NODEVICE   -1

@@ -10,6 +10,8 @@
     python -m losslessh264_amd --segment-mbs N in.264 out.pip   compress through lh264_compress_batch_opts: a stream of more than N
                                                             macroblocks is coded in segments of whole pictures (a stream of any
                                                             length: memory follows the segment, the bytes are the same)
+    python -m losslessh264_amd --decode [--nv12] out_dir in.264...   decode through ONE lh264_decode_batch call: out_dir/<name>.yuv holds
+                                                            the cropped pictures as I420 (or NV12), appended by a sink run by run
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -128,7 +130,24 @@ def restore(src, dst):
     print("%s (+%d tagged streams) -> %s: %d bytes" % (src, len(tags), dst, len(out)))
 
 
+def decode(argv):
+    import losslessh264_amd as lh
+    nv12 = argv[0] == "--nv12"
+    if nv12:
+        argv = argv[1:]
+    if len(argv) < 2:
+        print(__doc__)
+        return 2
+    ret = 0
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420"):
+        print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
+        ret = ret or (1 if status else 0)
+    return ret
+
+
 def main(argv):
+    if len(argv) >= 4 and argv[1] == "--decode":
+        return decode(argv[2:])
     if len(argv) >= 5 and argv[1] == "--segment-mbs":
         compress_segmented(argv[3], argv[4], int(argv[2]))
         return 0

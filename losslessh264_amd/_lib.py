@@ -122,6 +122,37 @@ _SIGS["lh264_compressed_segments"] = (C.c_int, [C.c_void_p])
 _SIGS["lh264_compressed_decisions"] = (C.c_uint64, [C.c_void_p, C.c_int])
 _SIGS["lh264_compress_arena_bytes"] = (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
 _SIGS["lh264_code_carry_decisions"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
+# ---- the decode direction behind one call
+FMT_I420, FMT_NV12 = 0, 1
+DECODE_DEVICE_OUT = 1
+E_NODEVICE, E_ARG, E_HIP, E_UNSUPPORTED = -1, -2, -3, -4
+DECODED_PIC_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("frame_num", "<i4"), ("idr", "<i4"), ("offset", "<u8"), ("bytes", "<u8")])
+DECODE_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+class DecodeOpts(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("round_pictures", C.c_uint32),
+                ("group_mbs", C.c_uint64), ("sink", DECODE_SINK_FN), ("user", C.c_void_p)]
+class PackJob(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("dst", C.c_void_p),
+                ("stride_y", C.c_int32), ("stride_c", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
+                ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32)]
+assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 40 and C.sizeof(PackJob) == 64
+_SIGS.update({
+    "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodeOpts), C.POINTER(C.c_void_p)]),
+    "lh264_decoded_status": (C.c_int, [C.c_void_p]),
+    "lh264_decoded_error": (C.c_char_p, [C.c_void_p]),
+    "lh264_decoded_pictures": (C.c_int, [C.c_void_p]),
+    "lh264_decoded_picture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lh264_decoded_bytes": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "lh264_decoded_bytes_dev": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "lh264_decoded_copy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "lh264_decoded_free": (None, [C.c_void_p]),
+    "lh264_decode_arena_bytes": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lh264_decode_release": (None, []),
+    "lh264_decode_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
+    "lh264_debug_pack_cpu": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_set_sparse_coeffs": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_frame_sparse_coeffs": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
+})
 EXPORTS = sorted(_SIGS)
 
 

@@ -9,6 +9,8 @@
 //   lh264dec in.lhp out.264             restore from the container
 //   lh264dec --segment-mbs N ...               (first) streams of more than N macroblocks are coded in segments of whole pictures
 //   lh264dec --batch out_dir a.264 b.264 ...   many streams in one lh264_compress_batch call -> out_dir/<name>.lhp
+//   lh264dec --decode [--nv12] out_dir a.264 b.264 ...   many streams in one lh264_decode_batch call -> out_dir/<name>.yuv: the
+//                                       cropped pictures as I420 (or NV12), appended by a sink run by run (the file's size bounds nothing)
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
 #include <stdio.h>
@@ -167,6 +169,42 @@ static int compress_single (const std::vector<std::string>& srcs, const std::vec
   return ret;
 }
 
+// --decode: one lh264_decode_batch over all inputs, a sink that appends every run of pictures to its stream's file
+struct DecodeFiles { std::vector<FILE*> f; std::vector<size_t> bytes; };
+static int decode_sink (void* user, int stream, int, int, const lh264_decoded_pic_t*, const uint8_t* bytes, size_t len) {
+  DecodeFiles& d = * (DecodeFiles*)user;
+  if (len && fwrite (bytes, 1, len, d.f[stream]) != len) return 1;
+  d.bytes[stream] += len;
+  return 0;
+}
+static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12) {
+  const int n = (int)srcs.size();
+  std::vector<Bytes> in (n);
+  std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
+  for (int i = 0; i < n; i++) { if (!load (srcs[i], in[i])) { perror (srcs[i].c_str()); return 2; } d[i] = in[i].data(); l[i] = in[i].size(); }
+  DecodeFiles files; files.f.assign (n, nullptr); files.bytes.assign (n, 0);
+  std::vector<std::string> dsts (n);
+  for (int i = 0; i < n; i++) {
+    dsts[i] = out_dir + "/" + base_name (srcs[i]) + ".yuv";
+    files.f[i] = fopen (dsts[i].c_str(), "wb");
+    if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
+  }
+  lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files;
+  std::vector<lh264_decoded_t*> h (n, nullptr);
+  const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
+  for (FILE* f : files.f) fclose (f);
+  if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
+  int ret = 0;
+  for (int i = 0; i < n; i++) {
+    const int st = lh264_decoded_status (h[i]);
+    printf ("%s -> %s: %d pictures, %zu bytes%s%s\n", srcs[i].c_str(), dsts[i].c_str(), lh264_decoded_pictures (h[i]), files.bytes[i], st == LH264_OK ? "" : "  [stopped: ", st == LH264_OK ? "" : (std::string (lh264_decoded_error (h[i])) + "]").c_str());
+    if (st != LH264_OK) ret = 1;
+    lh264_decoded_free (h[i]);
+  }
+  return ret;
+}
+
 static int restore_single (const std::string& src, const std::string& dst) {
   Bytes f;
   if (!load (src, f)) { perror (src.c_str()); return 2; }
@@ -187,8 +225,16 @@ int main (int argc, char** argv) {
     for (int i = 3; i < argc; i++) { srcs.push_back (argv[i]); dsts.push_back (std::string (argv[2]) + "/" + base_name (argv[i]) + ".lhp"); }
     return compress_single (srcs, dsts);
   }
+  if (argc >= 4 && !strcmp (argv[1], "--decode")) {
+    const bool nv12 = !strcmp (argv[2], "--nv12");
+    const int first = nv12 ? 3 : 2;
+    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--nv12] out_dir in.264...\n", argv[0]); return 2; }
+    std::vector<std::string> srcs;
+    for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
+    return decode_files (argv[first], srcs, nv12);
+  }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

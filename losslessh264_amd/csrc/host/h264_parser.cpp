@@ -214,11 +214,36 @@ struct Parser::Impl {
     }
     cur->lev_nonzero[k] = any ? 1 : 0;
   }       // the slice NAL just handled: header length in bits, entropy mode
+  // sparse coefficients: the macroblock in hand writes its dequantised coefficients (an I_PCM macroblock its samples) here; when it is done
+  // the nonzero ones become list entries (picture-relative index << 16 | value) and the scratch is zero again
+  alignas (8) int16_t coef_scratch[384] = {};
+  bool coef_unsorted = false;                            // an entry went in below the one before it (slices out of order, a macroblock parsed twice)
+  void finish_coeffs (int k) {
+    if (!self->sparse_coeffs_) return;
+    for (int w = 0; w < 96; w++) {
+      uint64_t q; memcpy (&q, coef_scratch + 4 * w, 8);
+      if (!q) continue;
+      for (int j = 4 * w; j < 4 * w + 4; j++) if (coef_scratch[j]) {
+        const uint64_t e = ((uint64_t) ((size_t)k * 384 + (size_t)j) << 16) | (uint16_t)coef_scratch[j];
+        if (!cur->sparse_coeffs.empty() && (cur->sparse_coeffs.back() >> 16) >= (e >> 16)) coef_unsorted = true;
+        cur->sparse_coeffs.push_back (e);
+        coef_scratch[j] = 0;
+      }
+    }
+  }
+  // what the dense planes hold when macroblocks were written out of order or twice: sorted by index, the later value of a position wins
+  void sort_coeffs() {
+    auto& v = cur->sparse_coeffs;
+    std::stable_sort (v.begin(), v.end(), [] (uint64_t a, uint64_t b) { return (a >> 16) < (b >> 16); });
+    size_t n = 0;
+    for (size_t i = 0; i < v.size(); i++) if (i + 1 == v.size() || (v[i + 1] >> 16) != (v[i] >> 16)) v[n++] = v[i];
+    v.resize (n);
+  }
 
   explicit Impl (Parser* s) : self (s) {}
 
   // ---- helpers -------------------------------------------------------------------------------------------------
-  void fail (const std::string& m) { if (self->err_.empty()) self->err_ = m; }
+  void fail (const std::string& m) { if (self->err_.empty()) { self->err_ = m; self->err_pictures_ = self->pictures_done_; } }
 
   static void unescape (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
     out.clear(); out.reserve (n);
@@ -549,6 +574,7 @@ struct Parser::Impl {
       else { cur->syn_off.assign ((size_t)cur->mb_w * cur->mb_h + 1, 0); cur->syn_syms.clear(); }
     }
     for (uint8_t c : cur->covered) if (!c) { self->damaged_ = true; break; }
+    if (coef_unsorted) { sort_coeffs(); coef_unsorted = false; }
     cur->complete = true;
     self->pictures_done_++;
     if (self->keep_frames_) self->frames_.push_back (std::move (cur));
@@ -565,7 +591,8 @@ struct Parser::Impl {
     cur->crop_w = S.mb_w * 16 - 2 * (S.crop_l + S.crop_r); cur->crop_h = S.mb_h * 16 - 2 * (S.crop_t + S.crop_b);
     const size_t n = (size_t)S.mb_w * S.mb_h;
     cur->mbs.assign (n, lh264_mb_t()); memset (cur->mbs.data(), 0, n * sizeof (lh264_mb_t));
-    if (self->want_coeffs_) cur->coeffs.assign_zero ((size_t)n * 384);
+    if (self->want_coeffs_ && !self->sparse_coeffs_) cur->coeffs.assign_zero ((size_t)n * 384);
+    coef_unsorted = false;
     if (!self->sparse_levels_) cur->levels.assign_zero ((size_t)n * 384, !self->lazy_levels_);
     cur->lev_nonzero.assign (n, 0); cur->covered.assign (n, 0);
     cur->syn.assign (n, MbSyn()); memset (cur->syn.data(), 0, n * sizeof (MbSyn));
@@ -846,7 +873,7 @@ bool Parser::Impl::parse_mb_cavlc (BitReader& br, SliceCtx& c, int k, int& qp_pr
   cur->covered[k] = 1;
   for (int i = 0; i < 16; i++) { s.ipm[i] = 2; s.mv[i][0] = s.mv[i][1] = 0; }
   for (int i = 0; i < 4; i++) { s.ref[i] = -1; m.ref_idx[i] = -1; }
-  int16_t* coef = self->want_coeffs_ ? &cur->coeffs[(size_t)k * 384] : no_coef;
+  int16_t* coef = self->sparse_coeffs_ ? coef_scratch : self->want_coeffs_ ? &cur->coeffs[(size_t)k * 384] : no_coef;
   int16_t* lev = self->sparse_levels_ ? lev_scratch : &cur->levels[(size_t)k * 384];
   if (self->lazy_levels_ && !self->sparse_levels_ && !is_skip) memset (lev, 0, 768);     // (the sparse scratch is left zero by finish_levels)
   const bool use_sl = S.scaling_matrix_present || P.scaling_matrix_present;
@@ -891,7 +918,7 @@ bool Parser::Impl::parse_mb_cavlc (BitReader& br, SliceCtx& c, int k, int& qp_pr
       y.delta_qp = (int)m.qp_y - d->slice_cached_qp;
       d->slice_cached_qp = m.qp_y;
       // (a destructor: an allocation failure in here must not escape - it would end the process - but fail the stream)
-      try { if (m.mb_type != LH264_MB_IPCM) d->finish_levels (k); } catch (const std::exception& e) { d->fail (std::string ("internal: ") + e.what()); }
+      try { if (m.mb_type != LH264_MB_IPCM) d->finish_levels (k); d->finish_coeffs (k); } catch (const std::exception& e) { d->fail (std::string ("internal: ") + e.what()); }
     }
   } syn_done = {this, y, m, k};
   uint32_t mbt = br.ue();
@@ -1196,7 +1223,7 @@ bool Parser::Impl::parse_mb_cabac (Cabac& cb, SliceCtx& c, int k, int& qp_prev, 
   for (int i = 0; i < 16; i++) { s.ipm[i] = 2; s.mv[i][0] = s.mv[i][1] = 0; s.mvd[i][0] = s.mvd[i][1] = 0; }
   for (int i = 0; i < 4; i++) { s.ref[i] = -1; m.ref_idx[i] = -1; }
   s.skip = 0; s.pcm = 0; s.t8 = 0; s.cbp = 0; s.chroma_pred = 0; s.cbf = 0;
-  int16_t* coef = self->want_coeffs_ ? &cur->coeffs[(size_t)k * 384] : no_coef;
+  int16_t* coef = self->sparse_coeffs_ ? coef_scratch : self->want_coeffs_ ? &cur->coeffs[(size_t)k * 384] : no_coef;
   int16_t* lev = self->sparse_levels_ ? lev_scratch : &cur->levels[(size_t)k * 384];
   if (self->lazy_levels_ && !self->sparse_levels_ && !is_skip) memset (lev, 0, 768);     // (the sparse scratch is left zero by finish_levels)
   const bool use_sl = S.scaling_matrix_present || P.scaling_matrix_present;
@@ -1244,7 +1271,7 @@ bool Parser::Impl::parse_mb_cabac (Cabac& cb, SliceCtx& c, int k, int& qp_prev, 
       y.delta_qp = (int)m.qp_y - d->slice_cached_qp;
       d->slice_cached_qp = m.qp_y;
       // (a destructor: an allocation failure in here must not escape - it would end the process - but fail the stream)
-      try { if (m.mb_type != LH264_MB_IPCM) d->finish_levels (k); } catch (const std::exception& e) { d->fail (std::string ("internal: ") + e.what()); }
+      try { if (m.mb_type != LH264_MB_IPCM) d->finish_levels (k); d->finish_coeffs (k); } catch (const std::exception& e) { d->fail (std::string ("internal: ") + e.what()); }
     }
   } syn_done = {this, y, m, k};
 

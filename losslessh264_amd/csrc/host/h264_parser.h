@@ -189,6 +189,7 @@ struct FrameOut {
   PoolVec<uint32_t> syn_off;               // mb_w*mb_h + 1 offsets
   PoolVec<uint8_t> lev_nonzero;            // per macroblock: it has a nonzero level (FreqImage's 'zeroed' test)
   PoolVec<uint64_t> sparse;                // sparse mode instead of `levels`: (macroblock * 384 + position) << 16 | level, nonzero levels only
+  PoolVec<uint64_t> sparse_coeffs;         // sparse mode instead of `coeffs`: the same entries for the nonzero dequantised coefficients, ascending
 };
 
 // The recompressor's default stream (".pip" itself, stream id 0x7fffffff): the Annex-B input minus its slice data.
@@ -251,6 +252,8 @@ class Parser {
   std::vector<std::unique_ptr<FrameOut>>& frames() { return frames_; }
   const std::string& error() const { return err_; }       // first error since construction / clear_error()
   void clear_error() { err_.clear(); }
+  // how many pictures were complete when error() was set: the pictures in front of that one do not depend on how the stream was cut into feeds
+  long error_pictures() const { return err_pictures_; }
   int unsupported_count() const { return n_unsupported_; }
   // keep == false: a completed picture is counted and released at once (its buffers go back to the per-thread cache), as a
   // pipeline does after handing the records to the device; frames() then stays empty
@@ -264,6 +267,9 @@ class Parser {
   // sparse == true: FrameOut::levels stays empty and FrameOut::sparse lists the nonzero levels (a few per macroblock instead of
   // 768 bytes: what travels to the device, where lh264_compress_batch expands it)
   void set_sparse_levels (bool sparse) { sparse_levels_ = sparse; }
+  // sparse == true: FrameOut::coeffs stays empty and FrameOut::sparse_coeffs lists the nonzero dequantised coefficients (of an I_PCM
+  // macroblock: its nonzero samples), sorted by index: what lh264_decode_batch uploads and expands on the device
+  void set_sparse_coeffs (bool sparse) { sparse_coeffs_ = sparse; }
   // on: the per-picture arrays come from chunks owned by this parser (see StreamArena)
   void set_stream_arena (bool on) { if (on && !arena_) arena_.reset (new StreamArena()); else if (!on) arena_.reset(); }
   // later pictures come from the per-thread cache again and are returned to it when they are destroyed; the arena itself lives on with
@@ -281,7 +287,7 @@ class Parser {
   std::vector<std::unique_ptr<FrameOut>> frames_;
   std::string err_;
   int n_unsupported_ = 0;
-  bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false; long pictures_done_ = 0; bool damaged_ = false;
+  bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false, sparse_coeffs_ = false; long pictures_done_ = 0, err_pictures_ = 0; bool damaged_ = false;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;
   const uint8_t* file_d_ = nullptr; size_t file_n_ = 0, file_pos_ = 0; int file_rc_ = 0; bool file_done_ = false, arena_paused_ = false;      // begin_file .. feed_file_some

@@ -725,6 +725,12 @@ int lh264_parser_frame_info (const lh264_parser_t* p, int idx, lh264_frame_info_
 }
 const lh264_mb_t* lh264_parser_frame_mbs (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->mbs.data() : nullptr; }
 const int16_t* lh264_parser_frame_coeffs (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->coeffs.data() : nullptr; }
+int lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_sparse_coeffs (on != 0); return LH264_OK; }
+const uint64_t* lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count) {
+  auto f = pf (p, idx);
+  if (count) *count = f ? f->sparse_coeffs.size() : 0;
+  return f ? f->sparse_coeffs.data() : nullptr;
+}
 const int16_t* lh264_parser_frame_levels (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->levels.data() : nullptr; }
 const lh264_slice_t* lh264_parser_frame_slices (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->slices.data() : nullptr; }
 const uint8_t* lh264_parser_frame_covered (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->covered.data() : nullptr; }

@@ -1,0 +1,678 @@
+// lh264_decode.hip - the decode direction behind one C call (include/lh264.h: lh264_decode_batch): n Annex-B streams in host memory ->
+// their pictures, cropped and packed as I420 or NV12, in host memory, in device memory or through a sink.  What the reference's console
+// application does picture by picture (h264dec.cpp:246-330: DecodeFrameNoDelay, then Write2File of the cropped planes), here per batch
+// of independent streams in ROUNDS: every stream of the round contributes its next few pictures, one lh264_recon_chains launch
+// reconstructs them (one chain per stream), decode_pack_kernel behind it crops and packs them into the round's output buffer, and the
+// download of that buffer runs on a second HIP stream while the host threads parse and stage the next round.  DESIGN.md section 4.6.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <chrono>
+#include <deque>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+#include "../../include/lh264.h"
+#include "host/h264_parser.h"
+#include "host/capi_internal.h"
+
+// ---- the pack step: crop + I420 / NV12, host and device from one source ------------------------------------------------------------
+// A picture is cut into bands of 16 luma rows (and the 8 chroma rows that belong to them); a band's rows are cut into PIECES: the
+// 16-byte blocks of the DESTINATION, counted from the aligned address at or below the row's first byte.  Destinations are tight, so a
+// row starts wherever the row before ended: a whole piece is one aligned 16-byte store fed by an unaligned 16-byte load (crop_x is
+// even, not 16-aligned), the pieces at a row's head and tail go byte by byte and touch nothing outside the row.
+namespace lh264pack {
+
+constexpr int kBandRows = 16;
+
+__host__ __device__ inline uint32_t interleave_lo (uint32_t u, uint32_t v) {      // u0 v0 u1 v1
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm (v, u, 0x05010400u);
+#else
+  return (u & 0xffu) | (v & 0xffu) << 8 | (u & 0xff00u) << 8 | (v & 0xff00u) << 16;
+#endif
+}
+__host__ __device__ inline uint32_t interleave_hi (uint32_t u, uint32_t v) {      // u2 v2 u3 v3
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm (v, u, 0x07030602u);
+#else
+  return (u >> 16 & 0xffu) | (v >> 16 & 0xffu) << 8 | (u >> 24) << 16 | (v >> 24) << 24;
+#endif
+}
+
+// piece p of a row of w bytes copied from s to d
+__host__ __device__ inline void piece_copy (uint8_t* d, const uint8_t* s, int w, int p) {
+  int a = p * 16 - (int) ((uintptr_t)d & 15u), b = a + 16;
+  if (a >= 0 && b <= w) {
+    uint4 x;
+    __builtin_memcpy (&x, s + a, 16);
+    * (uint4*) (d + a) = x;
+    return;
+  }
+  if (a < 0) a = 0;
+  if (b > w) b = w;
+  for (int k = a; k < b; k++) d[k] = s[k];
+}
+// piece p of a row of w bytes: Cb and Cr (w / 2 bytes each) interleaved
+__host__ __device__ inline void piece_interleave (uint8_t* d, const uint8_t* u, const uint8_t* v, int w, int p) {
+  int a = p * 16 - (int) ((uintptr_t)d & 15u), b = a + 16;
+  if (a >= 0 && b <= w && !(a & 1)) {
+    uint2 x, y;
+    __builtin_memcpy (&x, u + (a >> 1), 8);
+    __builtin_memcpy (&y, v + (a >> 1), 8);
+    uint4 o;
+    o.x = interleave_lo (x.x, y.x); o.y = interleave_hi (x.x, y.x); o.z = interleave_lo (x.y, y.y); o.w = interleave_hi (x.y, y.y);
+    * (uint4*) (d + a) = o;
+    return;
+  }
+  if (a < 0) a = 0;
+  if (b > w) b = w;
+  for (int k = a; k < b; k++) d[k] = (k & 1) ? v[k >> 1] : u[k >> 1];
+}
+
+// band `band` of one job, worked on by item t of nt (the lanes of a workgroup; the host steps it with t = 0, nt = 1)
+__host__ __device__ inline void pack_band (const lh264_pack_job_t& j, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h, cw = w >> 1, ch = h >> 1;
+  const int r0 = band * kBandRows, r1 = r0 + kBandRows < h ? r0 + kBandRows : h;
+  if (r1 > r0) {
+    const int pieces = (w + 30) >> 4, items = (r1 - r0) * pieces;
+    const uint8_t* s = j.y + (size_t)j.crop_y * j.stride_y + j.crop_x;
+    for (int it = t; it < items; it += nt) {
+      const int r = r0 + it / pieces, p = it % pieces;
+      piece_copy (j.dst + (size_t)r * w, s + (size_t)r * j.stride_y, w, p);
+    }
+  }
+  const int c0 = band * (kBandRows / 2), c1 = c0 + kBandRows / 2 < ch ? c0 + kBandRows / 2 : ch;
+  if (c1 <= c0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  uint8_t* dc = j.dst + (size_t)w * h;
+  if (j.format == LH264_FMT_NV12) {
+    const int pieces = (w + 30) >> 4, items = (c1 - c0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = c0 + it / pieces, p = it % pieces;
+      piece_interleave (dc + (size_t)r * w, j.u + co + (size_t)r * j.stride_c, j.v + co + (size_t)r * j.stride_c, w, p);
+    }
+  } else {
+    const int pieces = (cw + 30) >> 4, per_plane = (c1 - c0) * pieces;
+    for (int it = t; it < 2 * per_plane; it += nt) {
+      const int plane = it >= per_plane, q = it - plane * per_plane;
+      const int r = c0 + q / pieces, p = q % pieces;
+      piece_copy (dc + (size_t)plane * cw * ch + (size_t)r * cw, (plane ? j.v : j.u) + co + (size_t)r * j.stride_c, cw, p);
+    }
+  }
+}
+
+}  // namespace lh264pack
+
+// one workgroup per (picture, band)
+__global__ void __launch_bounds__ (256) decode_pack_kernel (const lh264_pack_job_t* __restrict__ jobs) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if ((int)blockIdx.y * lh264pack::kBandRows >= j.crop_h) return;
+  lh264pack::pack_band (j, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+
+// the dequantised coefficients travel as a list of the nonzero ones: (index into the round's coefficient planes) << 16 | value; the
+// planes are cleared on the device in front of this
+__global__ void __launch_bounds__ (256) expand_coeffs_kernel (const uint64_t* __restrict__ ents, size_t n, int16_t* __restrict__ dense) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) { const uint64_t e = ents[i]; dense[e >> 16] = (int16_t) (uint16_t) (e & 0xffffu); }
+}
+
+struct lh264_decoded {
+  int status = LH264_OK;
+  std::string error;
+  std::vector<lh264_decoded_pic_t> pics;
+  std::vector<uint8_t> bytes;                   // host mode
+  uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
+  ~lh264_decoded() {
+    if (!dev) return;
+    int cur = 0;
+    hipGetDevice (&cur);
+    if (cur != device) hipSetDevice (device);
+    hipFree (dev);
+    if (cur != device) hipSetDevice (cur);
+  }
+};
+
+namespace {
+
+using lh264host::FrameOut;
+using lh264host::Parser;
+
+bool trace_on() { static const bool t = getenv ("LH264_TRACE_DECODE") != nullptr; return t; }
+double now_s() { return std::chrono::duration<double> (std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct DevBuf {                       // device memory, grown when a round needs more, reused otherwise
+  void* p = nullptr; size_t cap = 0;
+  ~DevBuf() { if (p) hipFree (p); }
+  bool alloc (size_t bytes) {
+    if (bytes < 16) bytes = 16;
+    if (bytes <= cap) return true;
+    if (p) { hipFree (p); p = nullptr; cap = 0; }
+    const size_t want = bytes + bytes / 8;
+    if (hipMalloc (&p, want) != hipSuccess) { p = nullptr; return false; }
+    cap = want;
+    return true;
+  }
+  template <typename T> T* as() const { return (T*)p; }
+};
+struct PinBuf {                       // page-locked staging memory
+  void* p = nullptr; size_t cap = 0;
+  ~PinBuf() { if (p) hipHostFree (p); }
+  bool alloc (size_t bytes) {
+    if (bytes < 16) bytes = 16;
+    if (bytes <= cap) return true;
+    if (p) { hipHostFree (p); p = nullptr; cap = 0; }
+    const size_t want = bytes + bytes / 8;
+    if (hipHostMalloc (&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
+    cap = want;
+    return true;
+  }
+  template <typename T> T* as() const { return (T*)p; }
+};
+
+// padded pictures, handed out one by one and taken back when a stream is through; allocated in slabs of one picture size
+struct PicCache {
+  std::map<size_t, std::vector<uint8_t*>> free_;
+  std::vector<void*> slabs;
+  size_t bytes = 0;
+  ~PicCache() { for (void* s : slabs) hipFree (s); }
+  uint8_t* get (size_t pic_bytes, hipStream_t st) {
+    std::vector<uint8_t*>& v = free_[pic_bytes];
+    if (v.empty()) {
+      const size_t n = std::min<size_t> (64, std::max<size_t> (1, ((size_t)32 << 20) / pic_bytes));
+      void* s = nullptr;
+      if (hipMalloc (&s, n * pic_bytes) != hipSuccess) return nullptr;
+      slabs.push_back (s); bytes += n * pic_bytes;
+      for (size_t k = n; k-- > 0; ) v.push_back ((uint8_t*)s + k * pic_bytes);
+    }
+    uint8_t* p = v.back(); v.pop_back();
+    return p;
+  }
+  void put (size_t pic_bytes, uint8_t* p) { free_[pic_bytes].push_back (p); }
+  // one picture per size that nothing ever writes: every sample 128, padding included.  It stands in for a reference a picture names
+  // no picture for (see where the job tables are written)
+  std::map<size_t, uint8_t*> grey_;
+  const uint8_t* grey (size_t pic_bytes, hipStream_t st) {
+    auto it = grey_.find (pic_bytes);
+    if (it != grey_.end()) return it->second;
+    uint8_t* p = get (pic_bytes, st);
+    if (!p) return nullptr;
+    if (hipMemsetAsync (p, 128, pic_bytes, st) != hipSuccess) { put (pic_bytes, p); return nullptr; }
+    grey_[pic_bytes] = p;
+    return p;
+  }
+};
+
+// two of everything the host writes or reads while the device works on the round before
+struct Arena {
+  DevBuf d_mbs, d_coef, d_sparse, d_sl, d_jobs, d_first, d_pack, d_out[2];
+  PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
+  PicCache pics;
+  hipStream_t s_run = nullptr, s_down = nullptr;
+  hipEvent_t e_run[2] = {nullptr, nullptr}, e_down[2] = {nullptr, nullptr};
+  bool ready = false;
+  bool init() {
+    if (ready) return true;
+    bool ok = hipStreamCreateWithFlags (&s_run, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags (&s_down, hipStreamNonBlocking) == hipSuccess;
+    for (int b = 0; b < 2 && ok; b++) ok = hipEventCreateWithFlags (&e_run[b], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags (&e_down[b], hipEventDisableTiming) == hipSuccess;
+    ready = ok;
+    return ok;
+  }
+  ~Arena() {
+    for (int b = 0; b < 2; b++) { if (e_run[b]) hipEventDestroy (e_run[b]); if (e_down[b]) hipEventDestroy (e_down[b]); }
+    if (s_run) hipStreamDestroy (s_run);
+    if (s_down) hipStreamDestroy (s_down);
+  }
+  size_t device_bytes() const {
+    size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack}) n += b->cap;
+    return n;
+  }
+  size_t pinned_bytes() const {
+    size_t n = 0;
+    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap;
+    return n;
+  }
+};
+
+struct Geo {
+  int mb_w = 0, mb_h = 0, stride_y = 0, stride_c = 0;
+  size_t off[3] = {0, 0, 0}, bytes = 0;
+};
+struct Slot { uint8_t* base; int pic_id; };       // pic_id < 0: free
+
+// a stream of the batch while it is being decoded
+struct DStream {
+  int i = 0;
+  std::unique_ptr<Parser> parser;
+  std::deque<std::unique_ptr<FrameOut>> pending;     // parsed, not yet in a round
+  long next_picture = 0;                             // the stream's pictures in rounds so far
+  uint64_t out_off = 0;                              // ... and their packed bytes
+  size_t pic_mbs = 0;                                // macroblocks of the stream's last picture (0: none seen yet)
+  Geo geo;
+  const uint8_t* grey = nullptr;                     // the arena's 128 picture of this geometry
+  std::vector<Slot> pool;
+  // set by select(): the stream ends behind the pictures selected
+  bool ending = false; int end_code = LH264_OK; std::string end_text;
+  bool stopped = false;                              // the sink refused, or the device stage failed: nothing more is delivered
+  std::vector<std::unique_ptr<FrameOut>> sel;        // the pictures of the round in preparation
+};
+
+// one chain of a round that is on the device: what its delivery needs
+struct RoundChain {
+  DStream* s = nullptr;
+  int first_picture = 0;
+  std::vector<lh264_decoded_pic_t> pics;
+  size_t at = 0, bytes = 0;                          // in the round's output buffer
+};
+struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0; bool live = false; };
+
+std::string refuse_picture (const FrameOut& f) {
+  const size_t n = (size_t)f.mb_w * f.mb_h;
+  if (f.covered.size() != n || f.mbs.size() != n) return "an incomplete picture";
+  for (size_t k = 0; k < n; k++) if (!f.covered[k]) return "macroblocks no slice covers (the reference conceals them, which is not modelled)";
+  if (f.slices.empty() || f.slice_syn.size() != f.slices.size()) return "an incomplete slice";
+  if (f.crop_w <= 0 || f.crop_h <= 0 || (f.crop_w & 1) || (f.crop_h & 1) || f.crop_x < 0 || f.crop_y < 0 || (f.crop_x & 1) || (f.crop_y & 1) ||
+      f.crop_x + f.crop_w > f.mb_w * 16 || f.crop_y + f.crop_h > f.mb_h * 16) return "a crop window outside the picture";
+  return "";
+}
+
+enum { kMaxDevices = 16 };
+std::unique_ptr<Arena> g_arena[kMaxDevices];
+std::mutex g_arena_mutex[kMaxDevices];
+double g_timing[6] = {0, 0, 0, 0, 0, 0};
+
+const uint32_t kDefaultRoundPictures = 8;
+const uint64_t kDefaultGroupMbs = 1000000;
+
+}  // namespace
+
+extern "C" {
+
+int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n) {
+  if (!jobs || n < 0) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) {
+    const lh264_pack_job_t& j = jobs[k];
+    if (!j.y || !j.u || !j.v || !j.dst || j.crop_w <= 0 || j.crop_h <= 0 || ((j.crop_w | j.crop_h | j.crop_x | j.crop_y) & 1) || j.crop_x < 0 || j.crop_y < 0 ||
+        (j.format != LH264_FMT_I420 && j.format != LH264_FMT_NV12)) return LH264_E_ARG;
+    for (int band = 0; band * lh264pack::kBandRows < j.crop_h; band++) lh264pack::pack_band (j, band, 0, 1);
+  }
+  return LH264_OK;
+}
+
+int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
+  if (!data || !len || !out || n < 0) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_decode_opts_t) || opts->format > LH264_FMT_NV12 || (opts->flags & ~LH264_DECODE_DEVICE_OUT) ||
+               (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)))) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  const int format = opts ? (int)opts->format : LH264_FMT_I420;
+  const bool device_out = opts && (opts->flags & LH264_DECODE_DEVICE_OUT);
+  const lh264_decode_sink_fn sink = opts ? opts->sink : nullptr;
+  void* const sink_user = opts ? opts->user : nullptr;
+  const size_t R = opts && opts->round_pictures ? opts->round_pictures : kDefaultRoundPictures;
+  const size_t group_mbs = opts && opts->group_mbs ? (size_t)opts->group_mbs : (size_t)kDefaultGroupMbs;
+  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+  if (threads < 1) threads = 1;
+  int device = 0;
+  if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= kMaxDevices) return LH264_E_ARG;
+  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; }
+  std::lock_guard<std::mutex> arena_lock (g_arena_mutex[device]);
+  if (!g_arena[device]) g_arena[device].reset (new Arena());
+  Arena& A = *g_arena[device];
+  if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
+  const double t_call = now_s();
+  double t_parse = 0, t_stage = 0, t_enqueue = 0, t_wait = 0, t_deliver = 0;
+
+  std::vector<std::unique_ptr<DStream>> active;
+  std::vector<std::unique_ptr<DStream>> retired;   // streams that are through (a round on the device still names them)
+  int next_stream = 0;
+  const int kWave = std::max (8, 4 * threads);
+  Round rounds[2];
+  int rb = 0;                                       // the buffers the next round takes
+  bool device_failed = false;
+  std::string device_error;
+
+  auto release_pool = [&] (DStream& s) {
+    for (Slot& sl : s.pool) A.pics.put (s.geo.bytes, sl.base);
+    s.pool.clear();
+  };
+  auto finish = [&] (DStream& s) {                  // the stream leaves: its result stands, its memory goes back
+    lh264_decoded_t& r = *out[s.i];
+    if (r.status == LH264_OK && device_failed) { r.status = LH264_E_HIP; r.error = device_error; }
+    if (r.status == LH264_OK && s.end_code != LH264_OK) { r.status = s.end_code; r.error = s.end_text; }
+    release_pool (s);
+    s.parser.reset(); s.pending.clear(); s.sel.clear();
+  };
+
+  // host threads: parse until the stream has a round's pictures (or ends), then pick the round's pictures
+  auto fill_and_select = [&] (DStream& s) {
+    Parser& P = *s.parser;
+    while (s.pending.size() < R && !P.file_finished()) {
+      const size_t want = s.pic_mbs ? (R - s.pending.size()) * s.pic_mbs - 1 : 0;
+      P.feed_file_some (want);
+      for (auto& f : P.frames()) { s.pic_mbs = (size_t)f->mb_w * f->mb_h; s.pending.push_back (std::move (f)); }
+      P.frames().clear();
+    }
+    s.ending = false; s.end_code = LH264_OK; s.end_text.clear();
+    const bool has_err = !P.error().empty();
+    const long limit = has_err ? P.error_pictures() : 0x7fffffffffffffffl;
+    while (s.sel.size() < R) {
+      const long idx = s.next_picture + (long)s.sel.size();
+      if (idx >= limit) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + P.error(); break; }
+      if (s.pending.empty()) {
+        if (P.file_finished()) { s.ending = true; if (has_err) { s.end_code = LH264_E_UNSUPPORTED; s.end_text = P.error(); } }
+        break;
+      }
+      FrameOut& f = *s.pending.front();
+      const std::string why = refuse_picture (f);
+      if (!why.empty()) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + why; break; }
+      // a change of resolution ends the round: the next one starts with a new pool
+      if (!s.sel.empty() && (f.mb_w != s.sel[0]->mb_w || f.mb_h != s.sel[0]->mb_h)) break;
+      s.sel.push_back (std::move (s.pending.front())); s.pending.pop_front();
+    }
+  };
+  auto unselect = [&] (DStream& s) {                // the round was full: the pictures wait for the next one
+    for (size_t q = s.sel.size(); q-- > 0; ) s.pending.push_front (std::move (s.sel[q]));
+    s.sel.clear(); s.ending = false;
+  };
+
+  auto fail_device = [&] (const std::string& what) {
+    device_failed = true; device_error = what;
+    const char* he = hipGetErrorString (hipGetLastError());
+    if (he && *he) device_error += std::string (" (") + he + ")";
+  };
+
+  // a round that is on the device: wait for its bytes and hand them on
+  auto deliver = [&] (Round& rd, int b) {
+    if (!rd.live) return;
+    rd.live = false;
+    const double t0 = now_s();
+    if (!device_failed && hipEventSynchronize (device_out ? A.e_run[b] : A.e_down[b]) != hipSuccess) fail_device ("the device stage failed");
+    const double t1 = now_s();
+    t_wait += t1 - t0;
+    if (device_failed) {
+      for (RoundChain& c : rd.chains) { c.s->stopped = true; lh264_decoded_t& r = *out[c.s->i]; if (r.status == LH264_OK) { r.status = LH264_E_HIP; r.error = device_error; } }
+      return;
+    }
+    const uint8_t* hb = A.h_out[b].as<uint8_t>();
+    if (sink) {
+      for (RoundChain& c : rd.chains) {
+        if (c.s->stopped) continue;
+        lh264_decoded_t& r = *out[c.s->i];
+        if (sink (sink_user, c.s->i, c.first_picture, (int)c.pics.size(), c.pics.data(), hb + c.at, c.bytes) != 0) {
+          c.s->stopped = true; r.status = LH264_E_ARG; r.error = "sink";
+          continue;
+        }
+        r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
+      }
+    } else {
+      run_parallel ((int)rd.chains.size(), threads, [&] (int k) {
+        RoundChain& c = rd.chains[k];
+        if (c.s->stopped) return;
+        lh264_decoded_t& r = *out[c.s->i];
+        if (!device_out) r.bytes.insert (r.bytes.end(), hb + c.at, hb + c.at + c.bytes);
+        r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
+      });
+    }
+    t_deliver += now_s() - t1;
+  };
+
+  for (;;) {
+    // ---- who takes part: streams that are through leave, new ones are admitted while the round has room
+    for (size_t k = 0; k < active.size(); ) {
+      DStream& s = *active[k];
+      if (s.stopped || s.ending) { finish (s); retired.push_back (std::move (active[k])); active.erase (active.begin() + (long)k); } else k++;
+    }
+    if (device_failed) break;
+    {
+      size_t known = 0, known_mbs = 0;
+      for (auto& s : active) if (s->pic_mbs) { known++; known_mbs += s->pic_mbs; }
+      const size_t avg = known ? std::max<size_t> (1, known_mbs / known) : 396;
+      size_t used = 0;
+      for (auto& s : active) used += (s->pic_mbs ? s->pic_mbs : avg) * R;
+      int admitted = 0;
+      while (next_stream < n && (active.empty() || used + avg * R <= group_mbs) && (known || admitted < kWave)) {
+        std::unique_ptr<DStream> s (new DStream());
+        s->i = next_stream++;
+        s->parser.reset (new Parser());
+        s->parser->set_sparse_coeffs (true);
+        s->parser->set_sparse_levels (true);       // (the parser has no mode without levels: their list is the cheapest form)
+        s->parser->begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
+        active.push_back (std::move (s));
+        used += avg * R; admitted++;
+      }
+    }
+    if (active.empty()) break;
+    const double t_a = now_s();
+    run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k]); });
+    const double t_b = now_s();
+    t_parse += t_b - t_a;
+
+    // ---- the round: which streams fit, where their records and bytes go, which picture slots they take
+    // (the buffers `rb` were last used by the round before the one that is on the device now: it has been delivered)
+    Round& rd = rounds[rb];
+    rd.chains.clear(); rd.out_bytes = 0;
+    struct Place { size_t mb0, sl0, sp0, job0; };
+    std::vector<Place> place;
+    size_t n_mbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0;
+    int max_w = 1, max_h = 1, max_bands = 1;
+    bool alloc_ok = true;
+    for (auto& sp : active) {
+      DStream& s = *sp;
+      if (s.sel.empty()) continue;
+      size_t m = 0, sl = 0, ents = 0, bytes = 0;
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; }
+      if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
+      const FrameOut& f0 = *s.sel[0];
+      if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
+        release_pool (s);                           // (the kernels that still read the old pictures are in front of whatever takes them next)
+        s.geo.mb_w = f0.mb_w; s.geo.mb_h = f0.mb_h;
+        s.geo.bytes = (lh264_pic_bytes (f0.mb_w, f0.mb_h, &s.geo.stride_y, &s.geo.stride_c, &s.geo.off[0], &s.geo.off[1], &s.geo.off[2]) + 255) & ~ (size_t)255;
+      }
+      RoundChain c;
+      c.s = &s; c.first_picture = (int)s.next_picture; c.at = rd.out_bytes; c.bytes = bytes;
+      place.push_back ({n_mbs, n_sl, n_sp, n_jobs});
+      n_mbs += m; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
+      rd.out_bytes += (bytes + 15) & ~ (size_t)15;
+      max_w = std::max (max_w, f0.mb_w); max_h = std::max (max_h, f0.mb_h);
+      rd.chains.push_back (std::move (c));
+    }
+    if (rd.chains.empty()) {
+      // nothing to reconstruct (streams that ended without a picture): the round on the device is still owed
+      deliver (rounds[rb ^ 1], rb ^ 1);
+      continue;
+    }
+    const int n_chains = (int)rd.chains.size();
+    alloc_ok = A.d_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_mbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
+               A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_chains + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
+               A.d_out[rb].alloc (rd.out_bytes) && (device_out || A.h_out[rb].alloc (rd.out_bytes)) &&
+               A.h_mbs[rb].alloc (n_mbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
+               A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_chains + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
+    // picture slots (serial: the cache is shared).  A picture takes a slot that was free when the round began; a slot becomes free
+    // behind the round when its picture is in no DPB any more - the round's pictures are all packed by then
+    std::vector<std::vector<int>> slot_of (n_chains);
+    for (int c = 0; c < n_chains && alloc_ok; c++) {
+      DStream& s = *rd.chains[c].s;
+      s.grey = A.pics.grey (s.geo.bytes, A.s_run);
+      if (!s.grey) { alloc_ok = false; break; }
+      for (auto& f : s.sel) {
+        int at = -1;
+        for (size_t q = 0; q < s.pool.size(); q++) if (s.pool[q].pic_id < 0) { at = (int)q; break; }
+        if (at < 0) {
+          uint8_t* p = A.pics.get (s.geo.bytes, A.s_run);
+          if (!p) { alloc_ok = false; break; }
+          s.pool.push_back ({p, -1});
+          at = (int)s.pool.size() - 1;
+        }
+        s.pool[at].pic_id = f->id;
+        slot_of[c].push_back (at);
+      }
+    }
+    if (!alloc_ok) { fail_device ("device allocation failed"); for (auto& s : active) s->sel.clear(); deliver (rounds[rb ^ 1], rb ^ 1); continue; }
+    // ---- staging (host threads): records to the page-locked buffers, the job tables
+    lh264_mb_t* h_mbs = A.h_mbs[rb].as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse[rb].as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl[rb].as<lh264_slice_t>();
+    lh264_frame_job_t* h_jobs = A.h_jobs[rb].as<lh264_frame_job_t>(); int32_t* h_first = A.h_first[rb].as<int32_t>(); lh264_pack_job_t* h_pack = A.h_pack[rb].as<lh264_pack_job_t>();
+    uint8_t* const d_out = A.d_out[rb].as<uint8_t>();
+    run_parallel (n_chains, threads, [&] (int c) {
+      RoundChain& rc = rd.chains[c];
+      DStream& s = *rc.s;
+      size_t mo = place[c].mb0, so = place[c].sl0, po = place[c].sp0, j = place[c].job0, at = rc.at;
+      h_first[c] = (int32_t)j;
+      uint64_t off = s.out_off;
+      for (size_t q = 0; q < s.sel.size(); q++) {
+        FrameOut& f = *s.sel[q];
+        const size_t nm = (size_t)f.mb_w * f.mb_h;
+        memcpy (&h_mbs[mo], f.mbs.data(), nm * sizeof (lh264_mb_t));
+        memcpy (&h_sl[so], f.slices.data(), f.slices.size() * sizeof (lh264_slice_t));
+        { const uint64_t add = (uint64_t) (mo * 384) << 16; const size_t ns = f.sparse_coeffs.size(); for (size_t e = 0; e < ns; e++) h_sparse[po + e] = f.sparse_coeffs[e] + add; po += ns; }
+        const Slot& me = s.pool[slot_of[c][q]];
+        auto pic_at = [&] (const uint8_t* base) { lh264_pic_t p; p.y_dev = (uint8_t*)base + s.geo.off[0]; p.u_dev = (uint8_t*)base + s.geo.off[1]; p.v_dev = (uint8_t*)base + s.geo.off[2]; return p; };
+        lh264_frame_job_t& jb = h_jobs[j];
+        memset (&jb, 0, sizeof (jb));
+        jb.mbs_dev = A.d_mbs.as<lh264_mb_t>() + mo; jb.coeffs_dev = A.d_coef.as<int16_t>() + mo * 384; jb.slices_dev = A.d_sl.as<lh264_slice_t>() + so;
+        jb.dst = pic_at (me.base);
+        for (size_t k = 0; k < LH264_MAX_REFS; k++) {
+          // A slot the picture does not fill, or whose picture is not held, points at the 128 picture.  recon_chain_kernel reads job slot
+          // 0 for a partition whose slice has no reference list entry (a P picture whose references are lost); the oracle predicts nothing
+          // there and leaves its fresh picture's 128: the same samples.  The picture itself in that slot (what the ISVC object does) would
+          // be read while it is being written, in wavefront order: not the oracle's result, and not a defined one.
+          const uint8_t* base = s.grey;
+          if (k < f.ref_ids.size()) for (const Slot& sl : s.pool) if (sl.pic_id == f.ref_ids[k] && sl.base != me.base) { base = sl.base; break; }
+          jb.ref[k] = pic_at (base);
+        }
+        jb.mb_w = f.mb_w; jb.mb_h = f.mb_h; jb.stride_y = s.geo.stride_y; jb.stride_c = s.geo.stride_c;
+        jb.n_slices = (int32_t)f.slices.size();
+        jb.flags = f.is_ref ? 0 : LH264_JOB_NO_EXPAND;
+        lh264_pack_job_t& pj = h_pack[j];
+        memset (&pj, 0, sizeof (pj));
+        pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
+        pj.dst = d_out + at;
+        pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
+        pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
+        const size_t bytes = (size_t)f.crop_w * f.crop_h * 3 / 2;
+        lh264_decoded_pic_t dp;
+        dp.width = f.crop_w; dp.height = f.crop_h; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
+        rc.pics.push_back (dp);
+        at += bytes; off += bytes;
+        mo += nm; so += f.slices.size(); j++;
+      }
+    });
+    h_first[n_chains] = (int32_t)n_jobs;
+    for (int c = 0; c < n_chains; c++) {
+      DStream& s = *rd.chains[c].s;
+      for (auto& f : s.sel) max_bands = std::max (max_bands, (f->crop_h + lh264pack::kBandRows - 1) / lh264pack::kBandRows);
+      // the slots the round leaves free: pictures the DPB behind the round's last picture does not hold
+      const std::vector<int>& dpb = s.sel.back()->dpb_ids;
+      for (Slot& sl : s.pool) if (sl.pic_id >= 0 && std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end()) sl.pic_id = -1;
+      s.next_picture += (long)s.sel.size();
+      s.out_off += rd.chains[c].bytes;
+      s.sel.clear();                                  // the pictures' records are staged: their memory goes back
+    }
+    const double t_c = now_s();
+    t_stage += t_c - t_b;
+    // ---- the device stage, asynchronous: upload, clear + expand the coefficients, reconstruct, pack; the download behind an event
+    {
+      hipStream_t st = A.s_run;
+      auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
+      bool ok = up (A.d_mbs, h_mbs, n_mbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
+                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_chains + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
+                hipMemsetAsync (A.d_coef.p, 0, n_mbs * 768, st) == hipSuccess;
+      if (ok && n_sp) { hipLaunchKernelGGL (expand_coeffs_kernel, dim3 ((unsigned) ((n_sp + 255) / 256)), dim3 (256), 0, st, A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>()); ok = hipGetLastError() == hipSuccess; }
+      if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
+      if (ok) { hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>()); ok = hipGetLastError() == hipSuccess; }
+      if (ok && device_out) {
+        // the pictures stay on the device: every stream's run goes behind what its handle holds (the buffer grows by doubling)
+        for (RoundChain& c : rd.chains) {
+          lh264_decoded_t& r = *out[c.s->i];
+          if (r.dev_len + c.bytes > r.dev_cap) {
+            const size_t cap = std::max<size_t> (4 * (r.dev_len + c.bytes), (size_t)1 << 16);
+            uint8_t* p = nullptr;
+            if (hipMalloc ((void**)&p, cap) != hipSuccess) { ok = false; break; }
+            if (r.dev_len && hipMemcpyAsync (p, r.dev, r.dev_len, hipMemcpyDeviceToDevice, st) != hipSuccess) { hipFree (p); ok = false; break; }
+            if (r.dev) { hipStreamSynchronize (st); hipFree (r.dev); }
+            r.dev = p; r.dev_cap = cap;
+          }
+          if (hipMemcpyAsync (r.dev + r.dev_len, d_out + c.at, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) { ok = false; break; }
+          r.dev_len += c.bytes;
+        }
+      }
+      ok = ok && hipEventRecord (A.e_run[rb], st) == hipSuccess;
+      if (ok && !device_out) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
+                                  hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess &&
+                                  hipEventRecord (A.e_down[rb], A.s_down) == hipSuccess;
+      if (!ok) { const char* le = lh264_last_error(); fail_device (std::string ("launching the device stage failed") + (le && *le ? std::string (": ") + le : std::string())); for (RoundChain& c : rd.chains) c.s->stopped = true; }
+      else rd.live = true;
+    }
+    t_enqueue += now_s() - t_c;
+    // ---- the round before: its bytes arrive while this one reconstructs
+    deliver (rounds[rb ^ 1], rb ^ 1);
+    rb ^= 1;
+  }
+  deliver (rounds[0], 0);
+  deliver (rounds[1], 1);
+  hipStreamSynchronize (A.s_run);
+  hipStreamSynchronize (A.s_down);
+  for (auto& s : active) finish (*s);
+  active.clear(); retired.clear();
+  // (streams that were complete before a failure of the device stage keep their result; the others carry the error)
+  if (device_failed) for (int i = next_stream; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = device_error; }
+  g_timing[0] = (now_s() - t_call) * 1e3; g_timing[1] = t_parse * 1e3; g_timing[2] = t_stage * 1e3; g_timing[3] = t_enqueue * 1e3; g_timing[4] = t_wait * 1e3; g_timing[5] = t_deliver * 1e3;
+  if (trace_on()) fprintf (stderr, "[lh264 decode] %d streams: %.3f s (parse %.3f, staging %.3f, enqueue %.3f, waiting for the device %.3f, delivery %.3f); arena %.1f MB device, %.1f MB pinned\n",
+                           n, g_timing[0] / 1e3, t_parse, t_stage, t_enqueue, t_wait, t_deliver, A.device_bytes() / 1e6, A.pinned_bytes() / 1e6);
+  return LH264_OK;
+}
+
+int lh264_decode_last_timing (double* ms) {
+  if (!ms) return LH264_E_ARG;
+  for (int k = 0; k < 6; k++) ms[k] = g_timing[k];
+  return LH264_OK;
+}
+int lh264_decoded_status (const lh264_decoded_t* d) { return d ? d->status : LH264_E_ARG; }
+const char* lh264_decoded_error (const lh264_decoded_t* d) { return d ? d->error.c_str() : ""; }
+int lh264_decoded_pictures (const lh264_decoded_t* d) { return d ? (int)d->pics.size() : 0; }
+int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* o) {
+  if (!d || !o || idx < 0 || (size_t)idx >= d->pics.size()) return LH264_E_ARG;
+  *o = d->pics[idx];
+  return LH264_OK;
+}
+const uint8_t* lh264_decoded_bytes (const lh264_decoded_t* d, size_t* len) {
+  if (len) *len = d ? d->bytes.size() : 0;
+  return d && !d->bytes.empty() ? d->bytes.data() : nullptr;
+}
+const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len) {
+  if (len) *len = d ? d->dev_len : 0;
+  return d ? d->dev : nullptr;
+}
+int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap) {
+  if (!d || !dst_dev || cap < d->dev_len) return LH264_E_ARG;
+  if (d->dev_len && hipMemcpy (dst_dev, d->dev, d->dev_len, hipMemcpyDeviceToDevice) != hipSuccess) return LH264_E_HIP;
+  return LH264_OK;
+}
+void lh264_decoded_free (lh264_decoded_t* d) { delete d; }
+int lh264_decode_arena_bytes (size_t* device, size_t* pinned) {
+  int d = 0;
+  if (lh264_device_count() <= 0 || hipGetDevice (&d) != hipSuccess || d < 0 || d >= kMaxDevices) return LH264_E_NODEVICE;
+  std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
+  if (device) *device = g_arena[d] ? g_arena[d]->device_bytes() : 0;
+  if (pinned) *pinned = g_arena[d] ? g_arena[d]->pinned_bytes() : 0;
+  return LH264_OK;
+}
+void lh264_decode_release (void) {
+  if (lh264_device_count() <= 0) return;
+  int cur = 0;
+  hipGetDevice (&cur);
+  for (int d = 0; d < kMaxDevices; d++) {
+    std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
+    if (g_arena[d]) { hipSetDevice (d); g_arena[d].reset(); }
+  }
+  hipSetDevice (cur);
+}
+
+}

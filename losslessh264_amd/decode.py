@@ -1,0 +1,156 @@
+"""The decode direction behind one C call (lh264_decode_batch): Annex-B streams -> their pictures, cropped and packed as I420 or
+NV12, as host bytes, as device tensors or through a sink.  ctypes only; torch is device-buffer plumbing."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib as L
+
+_FORMATS = {"i420": L.FMT_I420, "nv12": L.FMT_NV12}
+
+
+class _DevSpan:
+    """a run of device bytes owned by a decode handle, described the way torch.as_tensor reads it"""
+
+    def __init__(self, ptr, n, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
+
+
+class DecodedBatch:
+    """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
+
+    def __init__(self, lib, handles, device_out, sink_keepalive=None):
+        self._lib, self._h, self.device_out, self._keep = lib, handles, device_out, sink_keepalive
+
+    def __len__(self):
+        return len(self._h)
+
+    def status(self, i):
+        return self._lib.lh264_decoded_status(self._h[i])
+
+    def error(self, i):
+        return self._lib.lh264_decoded_error(self._h[i]).decode()
+
+    def pictures(self, i):
+        """[(width, height, frame_num, idr, offset, bytes)] of stream i, in decode order"""
+        n = self._lib.lh264_decoded_pictures(self._h[i])
+        out = []
+        rec = np.zeros(1, dtype=L.DECODED_PIC_DTYPE)
+        for k in range(n):
+            L.check(self._lib.lh264_decoded_picture(self._h[i], k, rec.ctypes.data_as(C.c_void_p)))
+            r = rec[0]
+            out.append((int(r["width"]), int(r["height"]), int(r["frame_num"]), int(r["idr"]), int(r["offset"]), int(r["bytes"])))
+        return out
+
+    def data(self, i):
+        """the packed pictures of stream i as bytes (empty with device_out=True or a sink)"""
+        ln = C.c_size_t(0)
+        ptr = self._lib.lh264_decoded_bytes(self._h[i], C.byref(ln))
+        return C.string_at(ptr, ln.value) if ptr and ln.value else b""
+
+    def tensor(self, i):
+        """device_out=True: the packed pictures of stream i as a torch.uint8 tensor on the device.  Zero-copy where torch.as_tensor
+        takes __cuda_array_interface__ (it does on the torch this was written against, ROCm builds included): the tensor is a VIEW of
+        the handle's memory, valid until free() - clone() it to keep it longer.  Where torch refuses the interface the bytes are
+        copied device-to-device into a fresh tensor (lh264_decoded_copy_dev); `zero_copy` tells which happened last."""
+        import torch
+        if not self.device_out:
+            raise RuntimeError("decode_batch was not called with device_out=True")
+        ln = C.c_size_t(0)
+        ptr = self._lib.lh264_decoded_bytes_dev(self._h[i], C.byref(ln))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if not ptr or not ln.value:
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        try:
+            t = torch.as_tensor(_DevSpan(ptr, ln.value, self), device=dev)
+            self.zero_copy = t.data_ptr() == ptr
+            return t
+        except (TypeError, RuntimeError, ValueError):
+            t = torch.empty(ln.value, dtype=torch.uint8, device=dev)
+            L.check(self._lib.lh264_decoded_copy_dev(self._h[i], t.data_ptr(), ln.value))
+            self.zero_copy = False
+            return t
+
+    def free(self):
+        for h in self._h:
+            self._lib.lh264_decoded_free(h)
+        self._h = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None):
+    """decode a batch of Annex-B streams on the current device -> DecodedBatch.
+    fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
+    (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
+    DecodedBatch.pictures, data a bytes object); the handles then keep no bytes.  round_pictures / group_mbs: the cuts of the work
+    (None = the library's defaults); the bytes do not depend on them."""
+    lib = L.lib()
+    if fmt not in _FORMATS:
+        raise ValueError("fmt must be 'i420' or 'nv12'")
+    n = len(datas)
+    keep = [bytes(d) for d in datas]
+    ptrs = (C.c_char_p * n)(*keep)
+    lens = (C.c_size_t * n)(*[len(d) for d in keep])
+    opts = L.DecodeOpts()
+    opts.struct_bytes = C.sizeof(L.DecodeOpts)
+    opts.format = _FORMATS[fmt]
+    opts.flags = L.DECODE_DEVICE_OUT if device_out else 0
+    opts.round_pictures = int(round_pictures or 0)
+    opts.group_mbs = int(group_mbs or 0)
+    cb = None
+    if sink is not None:
+        def _cb(user, stream, first, count, pics, data, ln):
+            try:
+                recs = np.frombuffer(C.string_at(pics, count * L.DECODED_PIC_DTYPE.itemsize), dtype=L.DECODED_PIC_DTYPE)
+                lst = [(int(r["width"]), int(r["height"]), int(r["frame_num"]), int(r["idr"]), int(r["offset"]), int(r["bytes"])) for r in recs]
+                return 1 if sink(stream, first, lst, C.string_at(data, ln)) else 0
+            except Exception:      # an exception must not cross the C frames: the stream stops
+                import traceback
+                traceback.print_exc()
+                return 1
+        cb = L.DECODE_SINK_FN(_cb)
+        opts.sink = cb
+    outs = (C.c_void_p * n)()
+    rc = lib.lh264_decode_batch(ptrs, lens, n, threads, C.byref(opts), outs)
+    if rc == L.E_NODEVICE:
+        raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
+    if rc != 0:
+        raise RuntimeError("lh264_decode_batch: error %d" % rc)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb)
+
+
+def decode_arena_bytes():
+    """(device bytes, page-locked host bytes) the decode call keeps on the current device"""
+    d, p = C.c_size_t(0), C.c_size_t(0)
+    L.check(L.lib().lh264_decode_arena_bytes(C.byref(d), C.byref(p)))
+    return d.value, p.value
+
+
+def decode_to_files(paths, out_dir, fmt="i420"):
+    """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
+    pictures, bytes)]"""
+    datas = [open(p, "rb").read() for p in paths]
+    os.makedirs(out_dir, exist_ok=True)
+    names = [os.path.join(out_dir, os.path.basename(p) + ".yuv") for p in paths]
+    files = [open(q, "wb") for q in names]
+    total = [0] * len(paths)
+
+    def sink(stream, first, pics, data):
+        files[stream].write(data)
+        total[stream] += len(data)
+        return 0
+    try:
+        b = decode_batch(datas, fmt=fmt, sink=sink)
+    finally:
+        for f in files:
+            f.close()
+    res = [(names[i], b.status(i), b.error(i), len(b.pictures(i)), total[i]) for i in range(len(paths))]
+    b.free()
+    return res
