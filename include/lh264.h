@@ -402,6 +402,9 @@ const int32_t*       lh264_parser_frame_slice_syntax (const lh264_parser_t* p, i
 const lh264_ctx_sym_t* lh264_parser_frame_syn_symbols (const lh264_parser_t* p, int idx, int* count);
 const uint32_t*      lh264_parser_frame_syn_offsets (const lh264_parser_t* p, int idx);
 const char*          lh264_parser_error (const lh264_parser_t* p);
+/* "" or why lh264_compress_batch refuses the stream although it parses: the first syntax value met so far that the container's prior
+ * tables cannot carry ("mb_skip_run 687 is outside the container's range 0..511"); such a stream is stored verbatim */
+const char*          lh264_parser_out_of_range (const lh264_parser_t* p);
 
 /* ---- restore direction, host side ------------------------------------------------------------
  * The inverse of compress: the default stream (".pip") plus the tagged arithmetic-coded streams (".pip.<tag>") -> the
@@ -504,6 +507,10 @@ int lh264_restore_last_timing (double* ms);
 /* the kernel's code (csrc/lh264_restore.hip) stepped on the host threads over host memory, with the same plan, capacities and
  * results as lh264_pip_restore_batch_device: a check of the device chain where no device is present; not a restore path */
 int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+/* the restore kernel's adaptive-probability update ON THE DEVICE, alone: out[i] = the probability word (c0 bits 0-9, c1 bits 10-19,
+ * prob bits 20-27) that follows words[i] after the decision bits[i].  Its division by a reciprocal exists in device code only, so
+ * lh264_debug_restore_cpu never steps it; a test runs every reachable pair of counts through this.  Without a device: LH264_E_NODEVICE */
+int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t* out, int n);
 
 /* ---- the decode direction behind one call (csrc/lh264_decode.hip) -------------------------------------------------------------
  * n independent Annex-B files in host memory -> per stream its pictures in decode order (= output order: I and P slices only, as in

@@ -96,6 +96,7 @@ _SIGS.update({
     "lh264_parser_frame_syn_symbols": (C.c_void_p, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_parser_frame_syn_offsets": (C.c_void_p, [C.c_void_p, C.c_int]),
     "lh264_parser_error": (C.c_char_p, [C.c_void_p]),
+    "lh264_parser_out_of_range": (C.c_char_p, [C.c_void_p]),
 })
 CODE_JOB_DTYPE = np.dtype([("syn_syms", "<u8"), ("syn_off", "<u8"), ("ctx_syms", "<u8"), ("ctx_n_syms", "<u8"), ("n_mbs", "<i4"), ("reserved", "<i4"),
                            ("ctx_sym_off", "<u8"), ("ctx_sym_base", "<u8")])
@@ -211,6 +212,7 @@ _SIGS["lh264_code_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_
 # ---- restore direction on the device
 _SIGS["lh264_pip_restore_batch_device"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
 _SIGS["lh264_debug_restore_cpu"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_SIGS["lh264_debug_dp_update"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
 _SIGS["lh264_restore_release"] = (None, [])
 _SIGS["lh264_restore_last_timing"] = (C.c_int, [C.POINTER(C.c_double)])
 EXPORTS = sorted(_SIGS)

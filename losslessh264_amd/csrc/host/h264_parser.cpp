@@ -1715,12 +1715,17 @@ int Parser::parse_headers (const uint8_t* nal, size_t len, HeaderInfo& o) {
   return 0;
 }
 const std::vector<uint8_t>& Parser::last_rbsp() const { return d_->rbsp; }
+const std::string& Parser::out_of_range() const { return d_->symbolizer.out_of_range(); }
 void Parser::unescape (const uint8_t* d, size_t n, std::vector<uint8_t>& out) { Impl::unescape (d, n, out); }
 
 // ---- the recompressor's default stream ---------------------------------------------------------------------------
 void MainStreamWriter::append_byte (uint8_t x) {
   if (!escaping_) { buffer.push_back (x); return; }
-  if (x <= 3 && esc_n_ == 2 && esc_[0] == 0 && esc_[1] == 0) {
+  if (exact_ && x <= 3 && esc_n_ == 2 && esc_[0] == 0 && esc_[1] == 0) {
+    const uint8_t e[3] = {0, 0, 3};
+    buffer.insert (buffer.end(), e, e + 3);
+    esc_[0] = x; esc_n_ = 1;                               // x itself may begin the next pair of zeros
+  } else if (x <= 3 && esc_n_ == 2 && esc_[0] == 0 && esc_[1] == 0) {
     const uint8_t e[4] = {0, 0, 3, x};
     buffer.insert (buffer.end(), e, e + 4);
     esc_n_ = 0;

@@ -209,10 +209,14 @@ class MainStreamWriter {
   }
   int bits_in_byte() const { return n_bits_; }
   void start_escape() { escaping_ = true; }
+  // exact == false: the reference's escaping of its default stream, which forgets the byte it wrote behind an escape (00 00 00 00 00 becomes
+  // 00 00 03 00 | 00 00 03 ..., three zero bytes in a row).  exact == true: emulation prevention as 7.4.1 has it, for the restore direction,
+  // whose output is the stream an encoder wrote (I_PCM samples and coefficient escapes can hold any run of zero bytes)
+  void set_exact_escape (bool exact) { exact_ = exact; }
   void stop_escape();
   void pad_to_byte() { while (n_bits_ & 7) emit_bit (0); }
  private:
-  uint32_t bits_ = 0; int n_bits_ = 0; bool escaping_ = false; uint8_t esc_[2] = {0, 0}; int esc_n_ = 0;
+  uint32_t bits_ = 0; int n_bits_ = 0; bool escaping_ = false, exact_ = false; uint8_t esc_[2] = {0, 0}; int esc_n_ = 0;
 };
 
 class Parser {
@@ -279,6 +283,9 @@ class Parser {
   // a completed picture had macroblocks no slice covers (lost slices): the reference conceals them (error_concealment.cpp), which is not
   // modelled - the recompressed form of such a stream does not restore; callers that promise a round trip store it verbatim
   bool damaged() const { return damaged_; }
+  // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
+  // carry (Symbolizer::out_of_range: an mb_skip_run above 511, 16 active references).  Not an error of the stream: it parses and decodes
+  const std::string& out_of_range() const;
 
  private:
   struct Impl;

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <algorithm>
 #include "h264_parser.h"
+#include "pip_symbols.h"
 #include "h264_tables.h"
 #include "h264_vlc_tables.h"
 #include "h264_cabac_tables.h"
@@ -64,7 +65,6 @@ struct BoolReader {
 
 // ---- the adaptive priors: a cell per (table, index), created when first touched ------------------------------------------
 const int kCell[LH264_TB_COUNT] = {15, 14, 8, 9, 9, 8, 8, 13, 13, 511, 128, 255, 15, 3, 15, 1, 1, 15};
-const int kTreeBits[LH264_TB_COUNT] = {4, 0, 3, 0, 0, 0, 0, 0, 0, 9, 7, 8, 4, 2, 4, 0, 0, 4};
 
 class PriorStore {
  public:
@@ -210,7 +210,7 @@ struct MbDec {                        // one decoded macroblock
 // (false: stop).  One walk serves the host restore (Restorer::decode_slice) and the two host passes of the device restore.
 class Walker {
  public:
-  explicit Walker (std::string& err) : err_ (err) {}
+  explicit Walker (std::string& err) : err_ (err) { w_.set_exact_escape (true); }
  protected:
   std::string& err_;
   bool failed_ = false;

@@ -2,6 +2,7 @@
 // decoder/core/src/decode_slice.cpp (DS), decoder/core/src/macroblock_model.cpp (MM), decoder/core/inc/decoded_macroblock.h (DM).
 #include "pip_symbols.h"
 #include <string.h>
+#include <string>
 
 namespace lh264host {
 namespace {
@@ -20,9 +21,26 @@ int type_code (uint32_t t) {          // MacroblockModel::encodeMacroblockType M
 }
 uint32_t rd32 (const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
+const char* table_name (int table) {
+  switch (table) {
+  case LH264_TB_SKIPRUN: return "mb_skip_run";  case LH264_TB_NUMREF: return "num_ref_idx_l0_active";  case LH264_TB_QPL: return "mb_qp_delta";
+  case LH264_TB_SUBMB: return "sub_mb_type";  case LH264_TB_MBTYPE: return "mb_type";  case LH264_TB_CBPC: return "chroma cbp";
+  case LH264_TB_CBPL: return "luma cbp";  case LH264_TB_MODE8: return "intra 16x16 / chroma mode";  case LH264_TB_PREDMODE: return "intra 4x4 mode";
+  default: return "symbol";
+  }
+}
+
 struct Out {
   PoolVec<lh264_ctx_sym_t>& v;
+  std::string& out_of_range;
+  // a value its table's tree has no leaf for would be coded modulo 2^bits and restore as another stream: the stream is marked (the first
+  // such value names the reason) and lh264_compress_batch refuses it
   void put (int kind, int table, uint32_t index, int value, int tag) {
+    if (kind == LH264_SYM_TREE || kind == LH264_SYM_POW2) {
+      const int limit = (1 << kTreeBits[table]) - (kind == LH264_SYM_TREE ? 1 : 0);
+      if ((value < 0 || value > limit) && out_of_range.empty())
+        out_of_range = std::string (table_name (table)) + " " + std::to_string (value) + " is outside the container's range 0.." + std::to_string (limit);
+    }
     lh264_ctx_sym_t s; s.prior = LH264_PRIOR (table, index); s.value = (int16_t)value; s.kind = (uint8_t)kind; s.pad = (uint8_t)tag;
     v.push_back (s);
   }
@@ -78,7 +96,7 @@ void Symbolizer::picture (FrameOut& f) {
     const int end = S.first_mb + S.n_mbs;
     int skip_state = -1, mb_in_slice = 0, cached_qp = 0, last_nonzero_dqp = 0;
     for (int k = S.first_mb; k < end && k < n; k++, mb_in_slice++) {
-      Out o = {flat};
+      Out o = {flat, out_of_range_};
       start_[k] = (uint32_t)flat.size();
       struct Close { PoolVec<lh264_ctx_sym_t>& v; uint32_t& s; uint32_t& c; ~Close() { c = (uint32_t)v.size() - s; } } close_run = {flat, start_[k], cnt_[k]};
       const int x = k % w;
@@ -229,7 +247,7 @@ void Symbolizer::picture (FrameOut& f) {
     }
     // the alignment bits after the slice's stop bit go to the pad-byte tag, DS:3133-3148
     if (X.pad_bits && end - 1 < n && end - 1 >= S.first_mb && start_[end - 1] + cnt_[end - 1] == flat.size()) {
-      Out o = {flat}; o.raw (X.pad_value, X.pad_bits, TAG_PADBYTE); cnt_[end - 1]++;
+      Out o = {flat, out_of_range_}; o.raw (X.pad_value, X.pad_bits, TAG_PADBYTE); cnt_[end - 1]++;
     }
   }
   f.syn_off.assign ((size_t)n + 1, 0);

@@ -7,18 +7,27 @@
 // (decoder/core/inc/decoded_macroblock.h:106-192).
 #pragma once
 #include <stdint.h>
+#include <string>
 #include <vector>
 #include "../../../include/lh264.h"
 #include "h264_parser.h"
 
 namespace lh264host {
 
+// bits of each prior table's binary tree (Branch<n>), by LH264_TB_*; 0: the table has none.  A TREE symbol holds 0 .. 2^n - 1, a POW2
+// symbol (emitBitsZeroToPow2Inclusive<n>) 0 .. 2^n.  One table for the symbolizer's range guard and for both restorers
+constexpr int kTreeBits[LH264_TB_COUNT] = {4, 0, 3, 0, 0, 0, 0, 0, 0, 9, 7, 8, 4, 2, 4, 0, 0, 4};
+
 class Symbolizer {
  public:
   // appends the picture's symbols to f.syn_syms / f.syn_off (pictures of one stream, in decode order)
   void picture (FrameOut& f);
+  // empty, or the first value met that its prior table cannot carry ("mb_skip_run 687 is outside the container's range 0..511"): the
+  // symbols of such a stream do not restore it
+  const std::string& out_of_range() const { return out_of_range_; }
 
  private:
+  std::string out_of_range_;
   struct Cell {                       // what the model remembers of a macroblock (DecodedMacroblock, decoded_macroblock.h:4-34)
     uint8_t initialized = 0, zeroed = 0, cbp_c = 0, cbp_l = 0, chroma_mode = 0, luma16_mode = 0;
     uint16_t cached_skips = 0;

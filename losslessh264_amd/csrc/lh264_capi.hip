@@ -744,6 +744,7 @@ const lh264_ctx_sym_t* lh264_parser_frame_syn_symbols (const lh264_parser_t* p, 
 }
 const uint32_t* lh264_parser_frame_syn_offsets (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->syn_off.data() : nullptr; }
 const char* lh264_parser_error (const lh264_parser_t* p) { return p ? const_cast<lh264_parser_t*> (p)->p.error().c_str() : ""; }
+const char* lh264_parser_out_of_range (const lh264_parser_t* p) { return p ? p->p.out_of_range().c_str() : ""; }
 
 #ifdef LH264_CODER_DEBUG
 void lh264_debug_read_rs_stamps (unsigned long long* out16, int reset) { lh264::read_rs_stamps (out16, reset != 0); }

@@ -469,6 +469,7 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
     for (auto& f : fr) symbols = symbols && f->syn_off.size() == (size_t)f->mb_w * f->mb_h + 1 && (f->syn_off.back() == f->syn_syms.size());
     if (!P.error().empty()) why = P.error();
     else if (!symbols) why = "a picture with an incomplete slice";
+    else if (!P.out_of_range().empty()) why = P.out_of_range() + " (the stream would not restore)";
     else if (P.damaged()) why = "a picture with macroblocks no slice covers: the reference conceals them, which is not modelled (the stream would not restore)";
     return !why.empty();
   };

@@ -790,6 +790,12 @@ __global__ __launch_bounds__ (64) __attribute__ ((amdgpu_waves_per_eu (LH264_RES
   restore_stream (jobs[order[blockIdx.x]], *tables, S, (int)threadIdx.x, (int)blockDim.x);
 }
 
+// dp_update alone, one pair of counts per thread (lh264_debug_dp_update)
+__global__ __launch_bounds__ (256) void dp_update_kernel (const uint32_t* words, const uint8_t* bits, uint32_t* out, int n) {
+  const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < n) out[i] = dp_update (words[i], bits[i] & 1);
+}
+
 // the same chain on the host, one stream at a time (no device: the CPU check of the transliteration)
 void restore_stream_host (const RestoreJob& J, const RestoreTables& T) {
   static thread_local Shared S;
@@ -1078,6 +1084,22 @@ int lh264_pip_restore_batch_device (lh264_restore_item_t* items, int n, int thre
 }
 int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out) {
   return restore_batch (items, n, threads, path_out, false);
+}
+int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t* out, int n) {
+  if (!words || !bits || !out || n < 0) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  if (n == 0) return LH264_OK;
+  uint8_t* d = nullptr;                                  // [words] [out] [bits]
+  const size_t nw = 4 * (size_t)n;
+  if (hipMalloc ((void**)&d, 2 * nw + (size_t)n) != hipSuccess) return LH264_E_HIP;
+  bool ok = hipMemcpy (d, words, nw, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy (d + 2 * nw, bits, (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL (lh264r::dp_update_kernel, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, 0, (const uint32_t*)d, (const uint8_t*) (d + 2 * nw),
+                        (uint32_t*) (d + nw), n);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy (out, d + nw, nw, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  hipFree (d);
+  return ok ? LH264_OK : LH264_E_HIP;
 }
 int lh264_restore_last_timing (double* ms) {
   if (!ms) return LH264_E_ARG;

@@ -96,6 +96,18 @@ def parse_stream(data, strict=False, _file=False, _pcm=False):
         lib.lh264_parser_destroy(p)
 
 
+def out_of_range(data):
+    """'' or why compress_batch refuses a stream that parses: the first syntax value the container's prior tables cannot carry
+    (lh264_parser_out_of_range), e.g. "mb_skip_run 687 is outside the container's range 0..511".  No device is needed."""
+    lib = L.lib()
+    p = lib.lh264_parser_create()
+    try:
+        lib.lh264_parser_feed_file(p, bytes(data), len(data))
+        return lib.lh264_parser_out_of_range(p).decode()
+    finally:
+        lib.lh264_parser_destroy(p)
+
+
 def parse_file_segments(data, segment_mbs):
     """a file parsed in pieces (lh264_parser_begin_file / lh264_parser_feed_file_some / lh264_parser_drop_frames): yields lists of
     frames - whole pictures, at most segment_mbs macroblocks a list but one picture at least - and at last the tuple

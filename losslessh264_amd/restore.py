@@ -114,6 +114,17 @@ def restore_batch_cpu_check(items, threads=0, out_cap=None, statuses=False):
     return _restore_batch_paths(L.lib().lh264_debug_restore_cpu, items, threads, out_cap, statuses)
 
 
+def dp_update_device(words, bits):
+    """the restore kernel's probability update on the device (lh264_debug_dp_update): uint32 words and 0 / 1 decisions -> uint32 words"""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    assert w.shape == b.shape and w.ndim == 1
+    out = np.zeros(len(w), dtype=np.uint32)
+    L.check(L.lib().lh264_debug_dp_update(w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), len(w)))
+    return out
+
+
 def restore_timing():
     """(pass 1, device stage, kernel, pass 2) in ms of the last restore_batch_device call"""
     ms = (C.c_double * 4)()
