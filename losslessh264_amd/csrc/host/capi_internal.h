@@ -1,5 +1,7 @@
 // capi_internal.h - what the C ABI's opaque handles are, for the translation units of the library that share them
 #pragma once
+#include <stddef.h>
+#include <stdint.h>
 #include <atomic>
 #include <thread>
 #include <vector>
@@ -20,3 +22,6 @@ template <typename F> static void run_parallel (int n, int threads, F&& fn) {
   for (auto& t : pool) t.join();
 }
 
+// n entries of (index << 16 | 16-bit value) in device memory written into the dense planes (lh264_capi.hip: expand_sparse_kernel, one
+// thread per entry, enqueued on `stream`); n > 0.  The caller asks hipGetLastError() if it wants to know
+namespace lh264host { void expand_sparse (const uint64_t* ents_dev, size_t n, int16_t* dense_dev, void* stream); }

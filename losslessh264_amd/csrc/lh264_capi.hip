@@ -12,9 +12,9 @@
 #include "../../include/lh264.h"
 #include "host/h264_parser.h"
 #include "host/capi_internal.h"
+#include "host/device_mem.h"
 #include "host/pip_restore.h"
 #include "lh264_coder.h"
-#include <mutex>
 
 namespace lh264 {
 __global__ void recon_chain_kernel (const lh264_frame_job_t* jobs, const int32_t* chain_first, int n_chains, int line_bytes);
@@ -75,6 +75,19 @@ __global__ void coder_bases_kernel (uint32_t* chain_info, int n_chains, unsigned
 __global__ void coder_emit_kernel (const lh264_code_job_t* jobs, const uint32_t* seg0, const uint32_t* job_chain, int n_jobs,
                                    const uint32_t* seg_doff, const uint32_t* chain_info, uint64_t* D);
 __global__ void coder_resolve_kernel (const lh264_code_stream_t* streams, uint32_t* chain_info, const uint64_t* D, uint16_t* Q, int n_chains);
+}
+
+using lh264host::DevBuf;
+using lh264host::PerDevice;
+
+// Both pipelines send their 16-bit values (compress: the raw levels, decode: the dequantised coefficients) as a list of the nonzero
+// ones, (index into the call's planes) << 16 | value; the planes are cleared on the device in front of this
+__global__ void __launch_bounds__ (256) expand_sparse_kernel (const uint64_t* __restrict__ ents, size_t n, int16_t* __restrict__ dense) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) { const uint64_t e = ents[i]; dense[e >> 16] = (int16_t) (uint16_t) (e & 0xffffu); }
+}
+void lh264host::expand_sparse (const uint64_t* ents_dev, size_t n, int16_t* dense_dev, void* stream) {
+  hipLaunchKernelGGL (expand_sparse_kernel, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, (hipStream_t)stream, ents_dev, n, dense_dev);
 }
 
 static thread_local std::string g_err;
@@ -158,8 +171,19 @@ static int pick_waves (int max_mb_w, int max_mb_h, int slot_bytes, size_t* lds_o
   }
 }
 
+// per device: what the reconstruct launches keep between calls
+namespace {
+struct ReconDev {
+  bool attr_set = false;                  // the kernel's dynamic LDS limit has been raised on this device
+  DevBuf idx; size_t idx_n = 0;           // lh264_recon_frames: 0, 1, 2 .. (chains of length one)
+};
+// (this record and the two work spaces below are never destroyed: their memory stays until the process ends, and no hipFree runs
+// from a static destructor after the runtime has begun to shut down)
+PerDevice<ReconDev>& g_recon_dev = *new PerDevice<ReconDev>;
+}
+// held: the current device's record where the caller has it locked already; otherwise its lock is taken here, for the attribute only
 static int launch_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains,
-                          int max_mb_w, int max_mb_h, hipStream_t st) {
+                          int max_mb_w, int max_mb_h, hipStream_t st, ReconDev* held = nullptr) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
   if (!jobs_dev || !chain_first_dev || n_chains < 0 || max_mb_w <= 0 || max_mb_h <= 0) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
@@ -167,10 +191,18 @@ static int launch_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chai
   size_t lds = 0;
   const int nw = pick_waves (max_mb_w, max_mb_h, slot_bytes, &lds);
   if (lds > 160 * 1024) return fail (LH264_E_UNSUPPORTED, "picture too wide for the LDS line buffers");
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIPCHK (hipFuncSetAttribute ((const void*)lh264::recon_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
+  const auto raise_lds_limit = [] (ReconDev& R) {
+    if (!R.attr_set) {
+      HIPCHK (hipFuncSetAttribute ((const void*)lh264::recon_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      R.attr_set = true;
+    }
+    return (int)LH264_OK;
+  };
+  if (held) { if (int rc = raise_lds_limit (*held)) return rc; }
+  else {
+    const int dev = g_recon_dev.current();
+    if (dev < 0) return fail (LH264_E_ARG, "device index out of range");
+    if (int rc = raise_lds_limit (g_recon_dev.lock (dev).get())) return rc;
   }
   hipLaunchKernelGGL (lh264::recon_chain_kernel, dim3 (n_chains), dim3 (nw * 64), lds, st, jobs_dev, chain_first_dev, n_chains, slot_bytes);
   HIPCHK (hipGetLastError());
@@ -185,56 +217,49 @@ int lh264_recon_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chain_
 int lh264_recon_frames (const lh264_frame_job_t* jobs_dev, int n_jobs, int max_mb_w, int max_mb_h, void* stream) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
   if (n_jobs <= 0) return n_jobs == 0 ? LH264_OK : fail (LH264_E_ARG, "bad argument");
-  // independent frames = chains of length one; the index table lives in a small cached device buffer
-  static int32_t* idx_dev = nullptr;
-  static int idx_cap = 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_jobs + 1 > idx_cap) {
-    if (idx_dev) hipFree (idx_dev);
-    idx_cap = n_jobs + 1 + 1024;
-    HIPCHK (hipMalloc (&idx_dev, sizeof (int32_t) * idx_cap));
-    int32_t* h = new int32_t[idx_cap];
-    for (int i = 0; i < idx_cap; i++) h[i] = i;
-    hipError_t e = hipMemcpy (idx_dev, h, sizeof (int32_t) * idx_cap, hipMemcpyHostToDevice);
-    delete[] h;
-    if (e != hipSuccess) return fail (LH264_E_HIP, "hipMemcpy", e);
+  // independent frames = chains of length one; the index table lives in a small device buffer kept per device
+  const int dev = g_recon_dev.current();
+  if (dev < 0) return fail (LH264_E_ARG, "device index out of range");
+  auto lock = g_recon_dev.lock (dev);
+  ReconDev& R = lock.get();
+  if ((size_t)n_jobs + 1 > R.idx_n) {
+    const size_t n = (size_t)n_jobs + 1 + 1024;
+    R.idx_n = 0;
+    if (!R.idx.alloc (sizeof (int32_t) * n)) return fail (LH264_E_HIP, "hipMalloc", R.idx.err);
+    std::vector<int32_t> h (n);
+    for (size_t i = 0; i < n; i++) h[i] = (int32_t)i;
+    HIPCHK (hipMemcpy (R.idx.p, h.data(), sizeof (int32_t) * n, hipMemcpyHostToDevice));
+    R.idx_n = n;
   }
-  return launch_chains (jobs_dev, idx_dev, n_jobs, max_mb_w, max_mb_h, st);
+  return launch_chains (jobs_dev, R.idx.as<int32_t>(), n_jobs, max_mb_w, max_mb_h, (hipStream_t)stream, &R);
 }
 
 // per device: the pictures' symbol totals of the compact layout (n_jobs + 1 words), kept between calls
 namespace {
-struct CtxWs { std::mutex mu; void* totals = nullptr; size_t cap = 0; };
-CtxWs g_ctx_ws[16];
+struct CtxWs { DevBuf totals; };
+PerDevice<CtxWs>& g_ctx_ws = *new PerDevice<CtxWs>;
 }
 static int ctx_passes (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains, int n_jobs, int max_mbs_per_frame,
                        unsigned long long* total_dev, bool symbols, hipStream_t st) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
   if (!jobs_dev || !chain_first_dev || n_chains < 0 || n_jobs < 0 || max_mbs_per_frame <= 0) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0 || n_jobs == 0) { if (total_dev) HIPCHK (hipMemsetAsync (total_dev, 0, 8, st)); return LH264_OK; }
-  int dev = 0;
-  HIPCHK (hipGetDevice (&dev));
-  if (dev < 0 || dev >= 16) return fail (LH264_E_ARG, "device index out of range");
-  CtxWs& W = g_ctx_ws[dev];
-  std::lock_guard<std::mutex> lock (W.mu);
-  const size_t need = ((size_t)n_jobs + 2) * 8;
-  if (need > W.cap) {
-    if (W.totals) (void)hipFree (W.totals);            // (synchronises the device: nobody reads the old one any more)
-    W.totals = nullptr; W.cap = 0;
-    HIPCHK (hipMalloc (&W.totals, need + 4096));
-    W.cap = need + 4096;
-  }
+  const int dev = g_ctx_ws.current();
+  if (dev < 0) return fail (LH264_E_ARG, "device index out of range");
+  auto lock = g_ctx_ws.lock (dev);
+  CtxWs& W = lock.get();
+  if (!W.totals.alloc (((size_t)n_jobs + 2) * 8)) return fail (LH264_E_HIP, "hipMalloc (symbol totals)", W.totals.err);
   const int bpj = (max_mbs_per_frame + 3) / 4;
   hipLaunchKernelGGL (lh264::ctx_nnz_kernel, dim3 ((unsigned)n_jobs * bpj), dim3 (256), 0, st, jobs_dev, n_jobs, bpj);
   HIPCHK (hipGetLastError());
   hipLaunchKernelGGL (lh264::ctx_inherit_chain_kernel, dim3 (n_chains), dim3 (256), 0, st, jobs_dev, chain_first_dev, n_chains);
   HIPCHK (hipGetLastError());
   // the compact layout: where every macroblock's symbols go (pictures in the fixed layout count as empty)
-  hipLaunchKernelGGL (lh264::ctx_offsets_kernel, dim3 (n_jobs), dim3 (256), 0, st, jobs_dev, n_jobs, (unsigned long long*)W.totals);
+  hipLaunchKernelGGL (lh264::ctx_offsets_kernel, dim3 (n_jobs), dim3 (256), 0, st, jobs_dev, n_jobs, W.totals.as<unsigned long long>());
   HIPCHK (hipGetLastError());
-  hipLaunchKernelGGL (lh264::ctx_bases_kernel, dim3 (1), dim3 (256), 0, st, n_jobs, (unsigned long long*)W.totals, total_dev);
+  hipLaunchKernelGGL (lh264::ctx_bases_kernel, dim3 (1), dim3 (256), 0, st, n_jobs, W.totals.as<unsigned long long>(), total_dev);
   HIPCHK (hipGetLastError());
-  hipLaunchKernelGGL (lh264::ctx_scatter_kernel, dim3 ((unsigned) ((n_jobs + 255) / 256)), dim3 (256), 0, st, jobs_dev, n_jobs, (const unsigned long long*)W.totals);
+  hipLaunchKernelGGL (lh264::ctx_scatter_kernel, dim3 ((unsigned) ((n_jobs + 255) / 256)), dim3 (256), 0, st, jobs_dev, n_jobs, W.totals.as<const unsigned long long>());
   HIPCHK (hipGetLastError());
   if (symbols) {
     hipLaunchKernelGGL (lh264::ctx_symbols_kernel, dim3 ((unsigned)n_jobs * bpj), dim3 (256), 0, st, jobs_dev, n_jobs, bpj);
@@ -258,7 +283,6 @@ int lh264_ctx_count_chains (const lh264_ctx_job_t* jobs_dev, const int32_t* chai
 // of the previous call are still being read until then.  (Calls on one stream are ordered by the stream.)
 namespace {
 struct CoderWs {
-  std::mutex mu;
   hipEvent_t done = nullptr; hipStream_t last_stream = nullptr; bool busy = false;
   // before the first kernel of a coder call on `st`
   int enter (hipStream_t st) {
@@ -273,8 +297,8 @@ struct CoderWs {
     last_stream = st; busy = true;
     return 0;
   }
-  void* small = nullptr; size_t small_cap = 0;     // job / macroblock / stream tables
-  void* big = nullptr; size_t big_cap = 0;         // decision words + tag lists
+  DevBuf small;                                    // job / macroblock / stream tables
+  DevBuf big;                                      // decision words + tag lists
   unsigned long long* totals_host = nullptr;       // page-locked, 2 x u64
   unsigned long long last_words = 0, last_q = 0;   // of the last call: decisions (incl. per-stream padding to 64), list entries
   // what lh264_code_binarise_chains leaves for lh264_code_finish_chains
@@ -287,16 +311,7 @@ struct CoderWs {
   uint32_t* pair_start = nullptr;                  // resumable calls: where every (stream, tag) pair's coder stands
   uint32_t* progress = nullptr; int window = 0;    // the resolve kernel's waves of a stream keep within `window` segments of one another
 };
-CoderWs g_coder_ws[16];
-int grow (void** p, size_t* cap, size_t need) {
-  if (need <= *cap) return LH264_OK;
-  if (*p) { (void)hipFree (*p); *p = nullptr; *cap = 0; }
-  const size_t want = need + need / 8 + 4096;
-  hipError_t e = hipMalloc (p, want);
-  if (e != hipSuccess) return fail (LH264_E_HIP, "hipMalloc (coder work memory)", e);
-  *cap = want;
-  return LH264_OK;
-}
+PerDevice<CoderWs>& g_coder_ws = *new PerDevice<CoderWs>;
 size_t up256 (size_t v) { return (v + 255) & ~ (size_t)255; }
 }
 
@@ -337,8 +352,8 @@ static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const in
                o_sjob = o_doff + up256 (seg_bound * 4 + 4), o_cnt = o_sjob + up256 (seg_bound * 4 + 4), o_part = o_cnt + up256 (seg_bound * LH264_CODER_CNT_STRIDE * 4 + 4),
                o_bkt = o_part + up256 (sw ? 4 : seg_bound * pstride * 4 + 4), o_map = o_bkt + up256 (sw ? 4 : seg_bound * LH264_CODER_MAX_PARTS * 4),
                o_prog = o_map + up256 ((size_t)n_chains * LH264_CODER_MAX_PARTS), small_need = o_prog + up256 ((size_t)n_chains * LH264_CODER_MAX_PARTS * 4);
-  if (int rc = grow (&W.small, &W.small_cap, small_need)) return rc;
-  uint8_t* sm = (uint8_t*)W.small;
+  if (!W.small.alloc (small_need)) return fail (LH264_E_HIP, "hipMalloc (coder work memory)", W.small.err);
+  uint8_t* sm = W.small.as<uint8_t>();
   uint32_t* seg0 = (uint32_t*) (sm + o_seg0); uint32_t* job_chain = (uint32_t*) (sm + o_jobchain); uint32_t* info = (uint32_t*) (sm + o_info);
   unsigned long long* totals = (unsigned long long*) (sm + o_totals); uint32_t* seg_doff = (uint32_t*) (sm + o_doff); uint32_t* seg_cnt = (uint32_t*) (sm + o_cnt);
   uint32_t* seg_part = (uint32_t*) (sm + o_part); uint32_t* seg_job = (uint32_t*) (sm + o_sjob);
@@ -391,8 +406,8 @@ static int code_binarise (CoderWs& W, const lh264_code_job_t* jobs_dev, const in
                o_crec = o_pbits + up256 ((size_t)n_pairs * 4), o_pco0 = o_crec + up256 (chunk_bound * 8), o_seed = o_pco0 + up256 ((size_t) (n_pairs + 1) * 4),
                o_cand = o_seed + up256 (coarse_bound * 4), o_cend = o_cand + up256 (coarse_bound * 12), o_cmap = o_cend + up256 (coarse_bound * 8), o_clist = o_cmap + up256 (coarse_bound * 128), o_cbits = o_clist + up256 (coarse_bound * 32 + 4),
                o_pstart = o_cbits + up256 (coarse_bound * 4 + 4), o_acc = o_pstart + up256 (resumable ? (size_t)n_pairs * LH264_PAIR_START_WORDS * 4 : 4);
-  if (int rc = grow (&W.big, &W.big_cap, o_acc + n_acc * 4 + 256)) return rc;
-  uint8_t* bg = (uint8_t*)W.big;
+  if (!W.big.alloc (o_acc + n_acc * 4 + 256)) return fail (LH264_E_HIP, "hipMalloc (coder work memory)", W.big.err);
+  uint8_t* bg = W.big.as<uint8_t>();
   uint64_t* D = (uint64_t*)bg; uint16_t* Q = (uint16_t*) (bg + o_q);
   uint32_t* pair_chunk0 = (uint32_t*) (bg + o_pc0); uint32_t* pair_bits = (uint32_t*) (bg + o_pbits);
   uint32_t* chunk_rec = (uint32_t*) (bg + o_crec); uint32_t* acc = (uint32_t*) (bg + o_acc);
@@ -477,12 +492,11 @@ static int code_finish (CoderWs& W, const lh264_code_stream_t* streams_dev, int 
 }
 
 
-static int coder_ws (CoderWs** W) {
+// which device's work space a coder call uses (g_coder_ws.lock (*dev))
+static int coder_dev (int* dev) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
-  int dev = 0;
-  HIPCHK (hipGetDevice (&dev));
-  if (dev < 0 || dev >= 16) return fail (LH264_E_ARG, "device index out of range");
-  *W = &g_coder_ws[dev];
+  *dev = g_coder_ws.current();
+  if (*dev < 0) return fail (LH264_E_ARG, "device index out of range");
   return LH264_OK;
 }
 static bool code_args_ok (const void* jobs_dev, const void* chain_first_dev, const void* streams_dev, int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame) {
@@ -491,25 +505,27 @@ static bool code_args_ok (const void* jobs_dev, const void* chain_first_dev, con
 
 int lh264_code_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
                        int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* stream) {
-  CoderWs* W = nullptr;
-  if (int rc = coder_ws (&W)) return rc;
+  int dev = 0;
+  if (int rc = coder_dev (&dev)) return rc;
   if (!code_args_ok (jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, max_mbs_per_frame)) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
-  std::lock_guard<std::mutex> lock (W->mu);
-  if (int rc = code_binarise (*W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream)) return rc;
-  return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream);
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
+  if (int rc = code_binarise (W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream)) return rc;
+  return code_finish (W, streams_dev, n_chains, (hipStream_t)stream);
 }
 size_t lh264_code_carry_bytes (uint32_t hash_cap) { return (size_t)LH264_CARRY_TABLE_BYTES + (size_t)hash_cap * 64; }
 int lh264_code_chains_resume (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
                               void* const* carry_dev, const uint32_t* flags_dev,
                               int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* stream) {
-  CoderWs* W = nullptr;
-  if (int rc = coder_ws (&W)) return rc;
+  int dev = 0;
+  if (int rc = coder_dev (&dev)) return rc;
   if (!code_args_ok (jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, max_mbs_per_frame) || !carry_dev || !flags_dev) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
-  std::lock_guard<std::mutex> lock (W->mu);
-  if (int rc = code_binarise (*W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream, true)) return rc;
-  return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream, (uint8_t* const*)carry_dev, flags_dev);
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
+  if (int rc = code_binarise (W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream, true)) return rc;
+  return code_finish (W, streams_dev, n_chains, (hipStream_t)stream, (uint8_t* const*)carry_dev, flags_dev);
 }
 int lh264_code_carry_decisions (const void* carry_dev, uint64_t* decisions_out, void* stream) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
@@ -525,38 +541,39 @@ int lh264_code_carry_decisions (const void* carry_dev, uint64_t* decisions_out, 
 }
 int lh264_code_binarise_chains (const lh264_code_job_t* jobs_dev, const int32_t* chain_first_dev, const lh264_code_stream_t* streams_dev,
                                 int n_chains, int n_jobs, long long total_mbs, int max_mbs_per_frame, void* stream) {
-  CoderWs* W = nullptr;
-  if (int rc = coder_ws (&W)) return rc;
+  int dev = 0;
+  if (int rc = coder_dev (&dev)) return rc;
   if (!code_args_ok (jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, max_mbs_per_frame)) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
-  std::lock_guard<std::mutex> lock (W->mu);
-  return code_binarise (*W, jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream);
+  auto lock = g_coder_ws.lock (dev);
+  return code_binarise (lock.get(), jobs_dev, chain_first_dev, streams_dev, n_chains, n_jobs, total_mbs, (hipStream_t)stream);
 }
 int lh264_code_finish_chains (const lh264_code_stream_t* streams_dev, int n_chains, void* stream) {
-  CoderWs* W = nullptr;
-  if (int rc = coder_ws (&W)) return rc;
+  int dev = 0;
+  if (int rc = coder_dev (&dev)) return rc;
   if (!streams_dev || n_chains < 0) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
-  std::lock_guard<std::mutex> lock (W->mu);
-  return code_finish (*W, streams_dev, n_chains, (hipStream_t)stream);
+  auto lock = g_coder_ws.lock (dev);
+  return code_finish (lock.get(), streams_dev, n_chains, (hipStream_t)stream);
 }
 
 int lh264_code_last_decisions (int first_chain, int n_chains, uint64_t* decisions_out) {
-  CoderWs* W = nullptr;
-  if (int rc = coder_ws (&W)) return rc;
-  std::lock_guard<std::mutex> lock (W->mu);
-  if (!decisions_out || first_chain < 0 || n_chains < 0 || !W->info || first_chain + n_chains > W->n_pairs_last / LH264_N_TAG_SLOTS) return fail (LH264_E_ARG, "bad argument");
+  int dev = 0;
+  if (int rc = coder_dev (&dev)) return rc;
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
+  if (!decisions_out || first_chain < 0 || n_chains < 0 || !W.info || first_chain + n_chains > W.n_pairs_last / LH264_N_TAG_SLOTS) return fail (LH264_E_ARG, "bad argument");
   std::vector<uint32_t> info ((size_t)n_chains * LH264_CODER_INFO_WORDS);
-  if (n_chains) HIPCHK (hipMemcpy (info.data(), W->info + (size_t)first_chain * LH264_CODER_INFO_WORDS, info.size() * 4, hipMemcpyDeviceToHost));
+  if (n_chains) HIPCHK (hipMemcpy (info.data(), W.info + (size_t)first_chain * LH264_CODER_INFO_WORDS, info.size() * 4, hipMemcpyDeviceToHost));
   for (int c = 0; c < n_chains; c++)
     for (int t = 0; t < LH264_N_TAG_SLOTS; t++) decisions_out[(size_t)c * LH264_N_TAG_SLOTS + t] = t < 35 ? info[(size_t)c * LH264_CODER_INFO_WORDS + LH264_CODER_INFO_TAGCNT + t] : 0;
   return LH264_OK;
 }
 int lh264_code_last_totals (unsigned long long* decision_words, unsigned long long* list_entries) {
-  int dev = 0;
-  if (lh264_device_count() <= 0 || hipGetDevice (&dev) != hipSuccess || dev < 0 || dev >= 16) return fail (LH264_E_NODEVICE, "no HIP device visible");
-  CoderWs& W = g_coder_ws[dev];
-  std::lock_guard<std::mutex> lock (W.mu);
+  const int dev = lh264_device_count() <= 0 ? -1 : g_coder_ws.current();
+  if (dev < 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
   if (decision_words) *decision_words = W.last_words;
   if (list_entries) *list_entries = W.last_q;
   return LH264_OK;
@@ -752,8 +769,10 @@ void lh264_debug_read_rs_stamps (unsigned long long* out16, int reset) { lh264::
 #ifdef LH264_RANGE_PROBE
 // diagnostic builds only: the seed words of the last coder call on the current device
 long long lh264_debug_coder_seeds (uint32_t* out, long long cap) {
-  int dev = 0; (void)hipGetDevice (&dev);
-  CoderWs& W = g_coder_ws[dev];
+  const int dev = g_coder_ws.current();
+  if (dev < 0) return -1;
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
   uint32_t total = 0;                   // coarse chunks of the call: the probe words lie behind the seeds
   if (hipMemcpy (&total, W.pair_coarse0 + W.n_pairs_last, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   const long long n = (long long)total < cap ? (long long)total : cap;
@@ -764,8 +783,10 @@ long long lh264_debug_coder_seeds (uint32_t* out, long long cap) {
 // tuning aid (not declared in lh264.h): decisions per partition of stream `chain` of the last wave-form coder call on the current device;
 // returns the number of partitions, -1 if the last call took the sw form, -2 if there is nothing to read
 int lh264_debug_coder_parts (int chain, unsigned long long* out, int cap) {
-  int dev = 0; (void)hipGetDevice (&dev);
-  CoderWs& W = g_coder_ws[dev];
+  const int dev = g_coder_ws.current();
+  if (dev < 0) return -2;
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
   if (W.sw) return -1;
   if (!W.seg_part || !W.seg0 || !W.chain_first) return -2;
   (void)hipDeviceSynchronize();
@@ -785,8 +806,10 @@ int lh264_debug_coder_parts (int chain, unsigned long long* out, int cap) {
 // long_list), [2] one candidate start state, [3] 2 .. CODE_CANDS candidates, [4] the whole state map (CODE_MAPPED).  Returns the number of
 // coarse chunks, -1 if there is nothing to read.  Reads what the call left; changes nothing.
 int lh264_debug_coder_range_paths (unsigned long long out[5]) {
-  int dev = 0; (void)hipGetDevice (&dev);
-  CoderWs& W = g_coder_ws[dev];
+  const int dev = g_coder_ws.current();
+  if (dev < 0) return -1;
+  auto lock = g_coder_ws.lock (dev);
+  CoderWs& W = lock.get();
   if (!out || !W.pair_coarse0 || !W.cand || W.n_pairs_last <= 0) return -1;
   (void)hipDeviceSynchronize();
   std::vector<uint32_t> pc ((size_t)W.n_pairs_last + 1);

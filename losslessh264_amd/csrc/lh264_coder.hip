@@ -35,50 +35,18 @@
 #include <stdint.h>
 #include "../../include/lh264.h"
 #include "lh264_coder.h"
+#include "lh264_coder_dev.h"
 
 namespace lh264 {
 
-#define GLB __attribute__ ((address_space (1)))
-#define LDS __attribute__ ((address_space (3)))
-typedef uint32_t u32x4 __attribute__ ((ext_vector_type (4)));
-template <typename T> __device__ __forceinline__ GLB T* glb (const void* p) { return (GLB T*) (uintptr_t)p; }
-__device__ __forceinline__ int uniform (int v) { return __builtin_amdgcn_readfirstlane (v); }
+using namespace lh264dev;
 
-// ---- wave-wide inclusive scan over 64 lanes with DPP: Hillis-Steele inside each row of 16 (row_shr 1, 2, 4, 8), then lane 15
-// of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3 (row_bcast:31).  Lanes without a source add 0.
-template <int CTRL, int ROWS> __device__ __forceinline__ int dpp0 (int x) { return __builtin_amdgcn_update_dpp (0, x, CTRL, ROWS, 0xf, false); }
-__device__ __forceinline__ int wave_scan_add (int x) {
-  x += dpp0<0x111, 0xf> (x); x += dpp0<0x112, 0xf> (x); x += dpp0<0x114, 0xf> (x); x += dpp0<0x118, 0xf> (x);
-  x += dpp0<0x142, 0xa> (x); x += dpp0<0x143, 0xc> (x);
-  return x;
-}
-
-// ---- DynProb (compression_stream.h:87-115): the probability from the two counters -------------------------------------------
-// floor (256 (c0+1) / (c0+c1+2)) < 256: numerator < 2^18, divisor <= 516: a float quotient is within one of the exact one
-__device__ __forceinline__ uint32_t dp_ratio (uint32_t c0, uint32_t c1) {
-  const uint32_t num = 256u * (c0 + 1u), den = c0 + c1 + 2u;
-  uint32_t prob = (uint32_t) ((float)num * __builtin_amdgcn_rcpf ((float)den));
-  if (prob * den > num) prob--;
-  else if ((prob + 1u) * den <= num) prob++;
-  return prob;
-}
-
-__device__ __forceinline__ int tag_slot (int tag) { return tag == 69 ? 34 : tag; }
-
-// the tag of a coefficient / nonzero-count symbol: the context-index kernel leaves it in the symbol's pad byte (lh264_ctx.hip mk_sym);
-// symbols from elsewhere (pad 0) have it taken out of the prior: colour, first scan position and macroblock class (encode4x4)
-__device__ __forceinline__ int ac_tag_base (uint32_t prior, int kind, int pad) {
-  if (pad) return pad;
-  const uint32_t nco = kind == LH264_SYM_AC4 ? 16u : 64u;
-  const uint32_t outer = prior / 3125u;
-  const int emitted = (int) (outer % nco), color = (int) ((outer / nco) % 3u), code = (int) ((outer / nco / 3u) % 16u);
-  const int first = color == 0 && emitted == 0 && code != 1;
-  return color ? 29 : (first ? 19 : 24);
-}
-__device__ __forceinline__ int nz_tag (uint32_t prior, int pad) { return pad ? pad : (((prior / 27u) % 3u) ? 29 : 19); }
 // the key raw bits are filed under: the shared TEST_PROB (compression_stream.h:363,441-448) as a cell of its own
 #define CODER_RAW_KEY 0xf8000000u
-// ---- how many decisions a symbol becomes, per tag, without walking its binarisation (the walk: lh264_coder_sw.hip binarize) -------
+// ---- how many decisions a symbol becomes, per tag, without walking its binarisation (the walk: decision_at below) -------
+// The stream-per-workgroup form keeps a sym_count of its own (lh264_coder_sw.hip, a switch per kind, no raws / key): the same
+// reference arithmetic, so a change to the cases here is a change there.  This one in its place costs that form's count and emit
+// kernels 4 and 2 VGPRs and was no faster on the 512-stream batch.
 // n: all decisions; up to four (tag slot, count) pairs (-1: unused); tch: tag brought into existence; raws: how many of the decisions are
 // raw bits (the shared TEST_PROB); key: the cell the others use (trees over several cells: the first one).
 // The lanes of a wave hold symbols of all kinds: the integer-like ones (DC, nonzero count, coefficient, motion vector difference -
@@ -86,7 +54,6 @@ __device__ __forceinline__ int nz_tag (uint32_t prior, int pad) { return pad ? p
 // branch per kind (round-3 counters: 19 of 64 lanes were active on average in the per-kind version).
 struct SymCount { int n, s0, s1, s2, s3, n0, n1, n2, n3, tch, raws; uint32_t key; };
 template <bool CTX_ONLY = false> __device__ __forceinline__ SymCount sym_count (uint32_t prior, int value, int kind, int pad) {
-  enum { T_LDC = 17, T_CRDC = 18, T_LAC_0_EOB = 19, T_LAC_N_EOB = 24, T_CRAC_EOB = 29 };
   SymCount c; c.n = 0; c.s0 = c.s1 = c.s2 = c.s3 = -1; c.n0 = c.n1 = c.n2 = c.n3 = 0; c.tch = -1; c.raws = 0; c.key = prior;
   const int table = (int) (prior >> 27);
   // CTX_ONLY: the symbol is known to come from the context-index kernel (a coefficient, a nonzero count or a DC level)
@@ -176,7 +143,6 @@ __device__ __forceinline__ void tree_at (Decision& d, uint32_t prior, int groups
   d.bit = (int) ((data >> (nbits - 1 - j)) & 1u);
 }
 __device__ __forceinline__ Decision decision_at (uint32_t prior, int value, int kind, int pad, int j) {
-  enum { T_LDC = 17, T_CRDC = 18, T_LAC_0_EOB = 19, T_LAC_N_EOB = 24, T_CRAC_EOB = 29 };
   Decision d; d.key = prior; d.place = 0; d.bit = 0; d.tag = pad;
   const int table = (int) (prior >> 27);
   switch (kind) {
@@ -283,11 +249,6 @@ __device__ __forceinline__ void seg_layout (LDS SegLds& L, Seg& S, int lane) {
   if (lane == 63) L.sbase[S.n] = incl;
   wsync();
   S.total = L.sbase[S.n];
-}
-// where the coefficient symbols of macroblock k of a picture start (in symbols behind ctx_syms_dev): its fixed slot, or - compact
-// layout - the picture's first symbol in the pool + the macroblock's offset
-__device__ __forceinline__ size_t ctx_sym_at (const lh264_code_job_t* J, int k) {
-  return J->ctx_sym_off_dev ? (size_t)*glb<const unsigned long long> (J->ctx_sym_base_dev) + glb<const uint32_t> (J->ctx_sym_off_dev)[k] : (size_t)k * LH264_CTX_MAX_SYMS;
 }
 // symbols s0 + 64 q + lane, q = 0 .. 3, of the segment (0 beyond its end): the four searches advance together, so that a step waits for
 // LDS once, not four times, and the four loads are under way together
@@ -603,19 +564,6 @@ coder_bases_kernel (uint32_t* __restrict__ chain_info, int n_chains, unsigned lo
   }
   if (tid == 0) { totals[0] = cd; totals[1] = cq; }
 }
-
-// which lanes of the wave hold the same `nbits`-bit key as this lane (valid lanes only)
-template <int NBITS> __device__ __forceinline__ void wave_match (uint32_t key, unsigned long long valid, uint32_t& lo, uint32_t& hi) {
-  uint32_t dlo = 0, dhi = 0;
-#pragma unroll
-  for (int b = 0; b < NBITS; b++) {
-    const int xb = __builtin_amdgcn_sbfe ((int)key, b, 1);             // 0 or -1
-    const unsigned long long m = __ballot (xb != 0);
-    dlo |= (uint32_t)m ^ (uint32_t)xb; dhi |= (uint32_t) (m >> 32) ^ (uint32_t)xb;
-  }
-  lo = ~dlo & (uint32_t)valid; hi = ~dhi & (uint32_t) (valid >> 32);
-}
-__device__ __forceinline__ int below (uint32_t lo, uint32_t hi) { return (int)__builtin_amdgcn_mbcnt_hi (hi, __builtin_amdgcn_mbcnt_lo (lo, 0u)); }
 
 // ---- kernel 4: the decision words ------------------------------------------------------------------------------------------------
 // One wave per segment, a lane per DECISION: the wave takes 256 symbols of the segment at a time, lays their decision counts out as a

@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <memory>
 #include <mutex>
-#include <chrono>
 #include <deque>
 #include <atomic>
 #include <stdio.h>
@@ -19,6 +18,7 @@
 #include "../../include/lh264.h"
 #include "host/h264_parser.h"
 #include "host/capi_internal.h"
+#include "host/device_mem.h"
 #include "lh264_coder.h"
 
 struct lh264_compressed {
@@ -38,12 +38,6 @@ __global__ void __launch_bounds__ (256) pack_tags_kernel (const PackItem* __rest
   const PackItem it = items[blockIdx.x];
   const uint8_t* s = (const uint8_t*) (uintptr_t)it.src; uint8_t* d = packed + it.dst;
   for (uint32_t i = threadIdx.x; i < it.len; i += blockDim.x) d[i] = s[i];
-}
-
-// the raw levels travel as a list of the nonzero ones: (index into the group's level planes) << 16 | level
-__global__ void __launch_bounds__ (256) expand_levels_kernel (const uint64_t* __restrict__ ents, size_t n, int16_t* __restrict__ dense) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) { const uint64_t e = ents[i]; dense[e >> 16] = (int16_t) (uint16_t) (e & 0xffffu); }
 }
 
 // A long stream between two segments: the bytes of a tag that are final have gone to the host, what is left - the last byte that is not
@@ -72,39 +66,11 @@ __global__ void __launch_bounds__ (64) rebase_tags_kernel (const RebaseItem* __r
 
 namespace {
 
-static bool trace_on() { static const bool t = getenv ("LH264_TRACE_COMPRESS") != nullptr; return t; }
-static double now_s() { return std::chrono::duration<double> (std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using lh264host::DevBuf;
+using lh264host::PinBuf;
+using lh264host::now_s;
+bool trace_on() { static const bool t = lh264host::trace_on ("LH264_TRACE_COMPRESS"); return t; }
 
-struct DevBuf {                       // device memory, grown when a group needs more, reused otherwise
-  void* p = nullptr; size_t cap = 0;
-  ~DevBuf() { if (p) hipFree (p); }
-  bool alloc (size_t bytes, bool zero) {
-    if (bytes < 16) bytes = 16;
-    if (bytes > cap) {
-      if (p) { hipFree (p); p = nullptr; cap = 0; }
-      const size_t want = bytes + bytes / 8;
-      if (hipMalloc (&p, want) != hipSuccess) { p = nullptr; return false; }
-      cap = want;
-    }
-    if (zero && hipMemsetAsync (p, 0, bytes, nullptr) != hipSuccess) return false;
-    return true;
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-struct PinBuf {                       // page-locked staging memory (the upload runs at PCIe speed and asynchronously)
-  void* p = nullptr; size_t cap = 0;
-  ~PinBuf() { if (p) hipHostFree (p); }
-  bool alloc (size_t bytes) {
-    if (bytes < 16) bytes = 16;
-    if (bytes <= cap) return true;
-    if (p) { hipHostFree (p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 8;
-    if (hipHostMalloc (&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
 struct Arena {
   DevBuf d_mbs, d_lev, d_sl, d_nnz, d_syms, d_nsyms, d_symoff, d_symbase, d_cj, d_first, d_syn, d_off, d_kj, d_st, d_keys, d_cells, d_out, d_len, d_items, d_packed;
   PinBuf h_mbs, h_sparse, h_sl, h_syn, h_off, h_packed;
@@ -147,6 +113,10 @@ struct Part {
   LongStream* ls = nullptr;
   uint32_t flags = LH264_CODE_SEG_FIRST | LH264_CODE_SEG_LAST;
   bool again = false;                           // out: status 8 with more than one picture - nothing was coded, the pictures go back
+  // left by the staging of compress_group for where its results are read: the PAST policy behind the part's last picture (a long
+  // stream takes it over once the segment is coded) and the first macroblock of every picture in the group's buffers
+  int cur = 0, last_fn = 0; long slot[2] = {-1, -1};
+  std::vector<size_t> mb_at;
 };
 
 // which earlier picture the reference's FreqImage holds as PAST (decoded_macroblock.h:119-123): two buffers, flipped when
@@ -215,7 +185,8 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
         // (... and one call codes fewer than 2^27 decisions into a stream's lists, each of which shifts out 7 bits at most)
         out_cap[c] = (uint32_t)std::max<size_t> (1u << 16, std::min<size_t> ({want_cap, 400 * seg + 65536, ((size_t)7 << 24) + 65536}));
         ls->hash_cap = hc; ls->out_cap = out_cap[c];
-        if (!(ls->carry.alloc (lh264_code_carry_bytes (hc), true) && ls->outb.alloc ((size_t)35 * out_cap[c], false)      /* (the tag slots that exist) */ && ls->lens.alloc ((LH264_N_TAG_SLOTS + 1) * 4, true))) {
+        if (!(ls->carry.alloc (lh264_code_carry_bytes (hc)) && ls->carry.zero (lh264_code_carry_bytes (hc), nullptr) && ls->outb.alloc ((size_t)35 * out_cap[c])      /* (the tag slots that exist) */ &&
+              ls->lens.alloc ((LH264_N_TAG_SLOTS + 1) * 4) && ls->lens.zero ((LH264_N_TAG_SLOTS + 1) * 4, nullptr))) {
           fail_all (out, parts, LH264_E_HIP, "device allocation failed"); return;
         }
         ls->started = true;
@@ -228,15 +199,15 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   std::vector<uint32_t> h_flags (n_chains);
   const size_t keys_total = key0[n_chains], out_total = out0[n_chains];
   const double t_a = now_s();
-  const bool ok = A.d_mbs.alloc (n_mbs * sizeof (lh264_mb_t), false) && A.d_lev.alloc (n_mbs * 768, true) && A.d_sparse.alloc (n_sparse * 8, false) && A.d_sl.alloc (n_slices * sizeof (lh264_slice_t), false) &&
-                  A.d_nnz.alloc (n_mbs * 24, true) && A.d_nsyms.alloc (n_mbs * 2, true) && A.d_symoff.alloc (n_mbs * 4, false) && A.d_symbase.alloc ((n_jobs + 2) * 8, false) &&
-                  A.d_cj.alloc (n_jobs * sizeof (lh264_ctx_job_t), false) && A.d_first.alloc ((n_chains + 1) * 4, false) && A.d_syn.alloc (n_syn * sizeof (lh264_ctx_sym_t), false) &&
-                  A.d_off.alloc (n_off * 4, false) && A.d_kj.alloc (n_jobs * sizeof (lh264_code_job_t), false) && A.d_st.alloc (n_chains * sizeof (lh264_code_stream_t), false) &&
-                  A.d_keys.alloc (256, false) && A.d_cells.alloc (keys_total * 64, true) && A.d_out.alloc (out_total, false) &&
-                  A.d_len.alloc ((size_t)n_chains * (LH264_N_TAG_SLOTS + 1) * 4, true) &&
+  const bool ok = A.d_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.d_lev.alloc (n_mbs * 768) && A.d_lev.zero (n_mbs * 768, nullptr) && A.d_sparse.alloc (n_sparse * 8) && A.d_sl.alloc (n_slices * sizeof (lh264_slice_t)) &&
+                  A.d_nnz.alloc (n_mbs * 24) && A.d_nnz.zero (n_mbs * 24, nullptr) && A.d_nsyms.alloc (n_mbs * 2) && A.d_nsyms.zero (n_mbs * 2, nullptr) && A.d_symoff.alloc (n_mbs * 4) && A.d_symbase.alloc ((n_jobs + 2) * 8) &&
+                  A.d_cj.alloc (n_jobs * sizeof (lh264_ctx_job_t)) && A.d_first.alloc ((n_chains + 1) * 4) && A.d_syn.alloc (n_syn * sizeof (lh264_ctx_sym_t)) &&
+                  A.d_off.alloc (n_off * 4) && A.d_kj.alloc (n_jobs * sizeof (lh264_code_job_t)) && A.d_st.alloc (n_chains * sizeof (lh264_code_stream_t)) &&
+                  A.d_keys.alloc (256) && A.d_cells.alloc (keys_total * 64) && A.d_cells.zero (keys_total * 64, nullptr) && A.d_out.alloc (out_total) &&
+                  A.d_len.alloc ((size_t)n_chains * (LH264_N_TAG_SLOTS + 1) * 4) && A.d_len.zero ((size_t)n_chains * (LH264_N_TAG_SLOTS + 1) * 4, nullptr) &&
                   A.h_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.h_sparse.alloc (n_sparse * 8) && A.h_sl.alloc (n_slices * sizeof (lh264_slice_t)) &&
                   A.h_syn.alloc (n_syn * sizeof (lh264_ctx_sym_t)) && A.h_off.alloc (n_off * 4) &&
-                  (!resumable || (A.d_carry.alloc (n_chains * sizeof (void*), false) && A.d_flags.alloc (n_chains * 4, false)));
+                  (!resumable || (A.d_carry.alloc (n_chains * sizeof (void*)) && A.d_flags.alloc (n_chains * 4)));
   if (!ok) { fail_all (out, parts, LH264_E_HIP, "device allocation failed"); return; }
   const double t_b = now_s();
   lh264_mb_t* h_mbs = A.h_mbs.as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse.as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl.as<lh264_slice_t>();
@@ -248,12 +219,15 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     size_t mo = mb0[c], so = sl0[c], yo = sy0[c], oo = of0[c], j = jb0[c], po = sp0[c];
     h_first[c] = (int32_t)j;
     std::vector<long> past; std::vector<int> past_buf;
-    int pcur = 0, plast = 0; long pslot[2] = {-1, -1};
+    Part& pt = parts[c];
     const long base = ls ? ls->pics_done : 0;
-    // (a segment that has to be sent again must find the stream's policy as it was: the walk works on a copy, kept when the segment was coded)
-    if (ls) { pcur = ls->cur; plast = ls->last_fn; pslot[0] = ls->slot[0]; pslot[1] = ls->slot[1]; }
-    past_policy (fr, past, past_buf, base, pcur, plast, pslot);
-    std::vector<size_t> mb_at (fr.size());
+    // (a segment that has to be sent again must find the stream's policy as it was: the walk works on a copy in the part, which the
+    // stream takes over when the segment was coded)
+    pt.cur = 0; pt.last_fn = 0; pt.slot[0] = pt.slot[1] = -1;
+    if (ls) { pt.cur = ls->cur; pt.last_fn = ls->last_fn; pt.slot[0] = ls->slot[0]; pt.slot[1] = ls->slot[1]; }
+    past_policy (fr, past, past_buf, base, pt.cur, pt.last_fn, pt.slot);
+    std::vector<size_t>& mb_at = pt.mb_at;
+    mb_at.resize (fr.size());
     for (size_t i = 0; i < fr.size(); i++) {
       FrameOut& f = *fr[i];
       const size_t n = (size_t)f.mb_w * f.mb_h;
@@ -296,7 +270,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
         (!resumable || (up (A.d_carry, h_carry.data(), n_chains * sizeof (void*)) && up (A.d_flags, h_flags.data(), n_chains * 4))))) {
     fail_all (out, parts, LH264_E_HIP, "upload failed"); return;
   }
-  if (n_sparse) hipLaunchKernelGGL (expand_levels_kernel, dim3 ((unsigned) ((n_sparse + 255) / 256)), dim3 (256), 0, nullptr, A.d_sparse.as<uint64_t>(), n_sparse, A.d_lev.as<int16_t>());
+  if (n_sparse) lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sparse, A.d_lev.as<int16_t>(), nullptr);
   if (trace_on()) hipDeviceSynchronize();
   const double t_d = now_s();
   // the symbol pool: the count pass says how many symbols the group's pictures have (8 bytes each; the fixed layout took 3,456 bytes per
@@ -304,7 +278,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   unsigned long long n_syms_total = 0;
   int rc = n_jobs == 0 ? LH264_OK : lh264_ctx_count_chains (A.d_cj.as<lh264_ctx_job_t>(), A.d_first.as<int32_t>(), n_chains, (int)n_jobs, max_mbs, A.d_symbase.as<unsigned long long>() + n_jobs + 1, nullptr);
   if (rc == LH264_OK && n_jobs && hipMemcpy (&n_syms_total, A.d_symbase.as<unsigned long long>() + n_jobs + 1, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = LH264_E_HIP;
-  if (rc == LH264_OK && !A.d_syms.alloc ((size_t)n_syms_total * sizeof (lh264_ctx_sym_t), false)) rc = LH264_E_HIP;
+  if (rc == LH264_OK && !A.d_syms.alloc ((size_t)n_syms_total * sizeof (lh264_ctx_sym_t))) rc = LH264_E_HIP;
   if (rc == LH264_OK) {
     for (size_t j = 0; j < n_jobs; j++) { h_cj[j].syms_dev = A.d_syms.as<lh264_ctx_sym_t>(); h_cj[j].syms_cap = n_syms_total; h_kj[j].ctx_syms_dev = A.d_syms.as<lh264_ctx_sym_t>(); }
     if (hipMemcpy (A.d_cj.p, h_cj.data(), n_jobs * sizeof (lh264_ctx_job_t), hipMemcpyHostToDevice) != hipSuccess ||
@@ -326,6 +300,14 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   std::vector<PackItem> items;
   std::vector<RebaseItem> rebase;
   size_t packed_bytes = 0;
+  // the bytes of chain c's tags that the device has written (L: their lengths), from `bytes` (35 slots of out_cap[c]), go to the host
+  auto pack_chain = [&] (int c, const uint32_t* L, const uint8_t* bytes) {
+    for (int slot = 0; slot < 35; slot++) if (L[slot]) {
+      PackItem it; it.src = (uint64_t) (uintptr_t) (bytes + (size_t)slot * out_cap[c]); it.dst = packed_bytes; it.len = L[slot]; it.pad = (uint32_t)c << 8 | (uint32_t)slot;
+      items.push_back (it);
+      packed_bytes += (L[slot] + 15u) & ~15u;
+    }
+  };
   for (int c = 0; c < n_chains; c++) {
     lh264_compressed_t& r = *out[idx[c]];
     const uint32_t* L = &lens[(size_t)c * (LH264_N_TAG_SLOTS + 1)];
@@ -339,28 +321,21 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     }
     if (ls && L[LH264_N_TAG_SLOTS] == 0) {
       // the stream's PAST policy moves on, and the images its two buffers name now are kept for the segments to come
-      std::vector<long> past; std::vector<int> pb;
       const long base = ls->pics_done;
-      past_policy (parts[c].frames, past, pb, base, ls->cur, ls->last_fn, ls->slot);
+      ls->cur = parts[c].cur; ls->last_fn = parts[c].last_fn; ls->slot[0] = parts[c].slot[0]; ls->slot[1] = parts[c].slot[1];
       ls->pics_done += (long)parts[c].frames.size();
       if (!(parts[c].flags & LH264_CODE_SEG_LAST)) {
-        size_t mo = mb0[c];
-        std::vector<size_t> at (parts[c].frames.size());
-        for (size_t q = 0; q < at.size(); q++) { at[q] = mo; mo += (size_t)parts[c].frames[q]->mb_w * parts[c].frames[q]->mb_h; }
+        const std::vector<size_t>& at = parts[c].mb_at;
         for (int b = 0; b < 2; b++) if (ls->slot[b] >= base) {
           const size_t q = (size_t) (ls->slot[b] - base), bytes = (size_t)parts[c].frames[q]->mb_w * parts[c].frames[q]->mb_h * 24;
-          if (!ls->nnz[b].alloc (bytes, false) || hipMemcpy (ls->nnz[b].p, A.d_nnz.as<uint8_t>() + at[q] * 24, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+          if (!ls->nnz[b].alloc (bytes) || hipMemcpy (ls->nnz[b].p, A.d_nnz.as<uint8_t>() + at[q] * 24, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
             ls->fail (LH264_E_HIP, "device allocation failed");
           }
         }
         A.long_bytes = std::max (A.long_bytes, ls->device_bytes());
         if (!ls->failed) {
           // the bytes that are final go to the host now; what is left moves to the front of the buffers (rebase_tags_kernel below)
-          for (int slot = 0; slot < 35; slot++) if (L[slot]) {
-              PackItem it; it.src = (uint64_t) (uintptr_t) (ls->outb.as<uint8_t>() + (size_t)slot * out_cap[c]); it.dst = packed_bytes; it.len = L[slot]; it.pad = (uint32_t)c << 8 | (uint32_t)slot;
-              items.push_back (it);
-              packed_bytes += (L[slot] + 15u) & ~15u;
-            }
+          pack_chain (c, L, ls->outb.as<uint8_t>());
           RebaseItem rb; rb.out = ls->outb.as<uint8_t>(); rb.carry = ls->carry.as<uint32_t>(); rb.lens = ls->lens.as<uint32_t>(); rb.cap = out_cap[c]; rb.pad = 0;
           rebase.push_back (rb);
           continue;
@@ -378,14 +353,10 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     if (L[LH264_N_TAG_SLOTS] != 0) { const std::string text = "device coder status " + std::to_string (L[LH264_N_TAG_SLOTS]) + " (bits - 1: prior table full or invalid, 4: output overflow, 8: counter overflow, 16: internal hand-off; include/lh264.h)";
       if (ls) ls->fail (LH264_E_HIP, text); else { r.status = LH264_E_HIP; r.error = text; }
       continue; }
-    for (int slot = 0; slot < 35; slot++) if (L[slot]) {
-        PackItem it; it.src = (uint64_t) (uintptr_t) ((ls ? ls->outb.as<uint8_t>() : A.d_out.as<uint8_t>() + out0[c]) + (size_t)slot * out_cap[c]); it.dst = packed_bytes; it.len = L[slot]; it.pad = (uint32_t)c << 8 | (uint32_t)slot;
-        items.push_back (it);
-        packed_bytes += (L[slot] + 15u) & ~15u;
-      }
+    pack_chain (c, L, ls ? ls->outb.as<uint8_t>() : A.d_out.as<uint8_t>() + out0[c]);
   }
   if (!items.empty()) {
-    if (!(A.d_items.alloc (items.size() * sizeof (PackItem), false) && A.d_packed.alloc (packed_bytes, false) && A.h_packed.alloc (packed_bytes)) ||
+    if (!(A.d_items.alloc (items.size() * sizeof (PackItem)) && A.d_packed.alloc (packed_bytes) && A.h_packed.alloc (packed_bytes)) ||
         hipMemcpyAsync (A.d_items.p, items.data(), items.size() * sizeof (PackItem), hipMemcpyHostToDevice, nullptr) != hipSuccess) { fail_all (out, parts, LH264_E_HIP, "download failed"); return; }
     hipLaunchKernelGGL (pack_tags_kernel, dim3 ((unsigned)items.size()), dim3 (256), 0, nullptr, A.d_items.as<PackItem>(), A.d_packed.as<uint8_t>());
     if (hipMemcpy (A.h_packed.p, A.d_packed.p, packed_bytes, hipMemcpyDeviceToHost) != hipSuccess) { fail_all (out, parts, LH264_E_HIP, "download failed"); return; }
@@ -398,7 +369,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     });
   }
   if (!rebase.empty()) {
-    bool ok2 = A.d_rebase.alloc (rebase.size() * sizeof (RebaseItem), false) && hipMemcpy (A.d_rebase.p, rebase.data(), rebase.size() * sizeof (RebaseItem), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok2 = A.d_rebase.alloc (rebase.size() * sizeof (RebaseItem)) && hipMemcpy (A.d_rebase.p, rebase.data(), rebase.size() * sizeof (RebaseItem), hipMemcpyHostToDevice) == hipSuccess;
     if (ok2) { hipLaunchKernelGGL (rebase_tags_kernel, dim3 ((unsigned)rebase.size() * 35u), dim3 (64), 0, nullptr, A.d_rebase.as<RebaseItem>()); ok2 = hipDeviceSynchronize() == hipSuccess; }
     if (!ok2) for (Part& p : parts) if (p.ls && !(p.flags & LH264_CODE_SEG_LAST)) p.ls->fail (LH264_E_HIP, "moving a long stream's bytes failed");
   }
@@ -406,9 +377,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
                            t_b - t_a, t_c - t_b, t_d - t_c, t_e - t_d, now_s() - t_e);
 }
 
-enum { kMaxDevices = 16 };
-std::unique_ptr<Arena> g_arena[kMaxDevices];      // one per device: device and page-locked buffers kept between calls
-std::mutex g_arena_mutex[kMaxDevices];             // one compress call at a time per device
+lh264host::PerDevice<Arena> g_arena;      // device and page-locked buffers kept between calls; one compress call at a time per device
 
 }  // namespace
 
@@ -451,10 +420,9 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
   const int kWave = std::max (8, 4 * threads);
   // device and page-locked buffers live across calls (allocating and releasing ~20 GB costs more than a whole batch):
   // one arena per process, one compress call at a time; lh264_compress_release() gives the memory back
-  if (device < 0 || device >= kMaxDevices) return LH264_E_ARG;
-  std::lock_guard<std::mutex> arena_lock (g_arena_mutex[device]);
-  if (!g_arena[device]) g_arena[device].reset (new Arena());
-  Arena& arena = *g_arena[device];
+  if (device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
+  auto arena_lock = g_arena.lock (device);
+  Arena& arena = arena_lock.get();
   arena.long_bytes = 0;
   const double t_call = now_s();
   std::vector<std::unique_ptr<lh264host::Parser>> parsers (n);
@@ -604,22 +572,13 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
   return LH264_OK;
 }
 int lh264_compress_arena_bytes (size_t* device, size_t* pinned) {
-  int d = 0;
-  if (lh264_device_count() <= 0 || hipGetDevice (&d) != hipSuccess || d < 0 || d >= kMaxDevices) return LH264_E_NODEVICE;
-  std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
-  if (device) *device = g_arena[d] ? g_arena[d]->device_bytes() + g_arena[d]->long_bytes : 0;
-  if (pinned) *pinned = g_arena[d] ? g_arena[d]->pinned_bytes() : 0;
-  return LH264_OK;
+  const bool ok = lh264_device_count() > 0 && g_arena.read_current ([&] (const Arena* a) {
+    if (device) *device = a ? a->device_bytes() + a->long_bytes : 0;
+    if (pinned) *pinned = a ? a->pinned_bytes() : 0;
+  });
+  return ok ? LH264_OK : LH264_E_NODEVICE;
 }
-void lh264_compress_release (void) {
-  int cur = 0;
-  hipGetDevice (&cur);
-  for (int d = 0; d < kMaxDevices; d++) {
-    std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
-    if (g_arena[d]) { hipSetDevice (d); g_arena[d].reset(); }
-  }
-  hipSetDevice (cur);
-}
+void lh264_compress_release (void) { g_arena.release_all(); }
 
 // the same batch over several devices of the node: the streams are cut into contiguous shares of about equal input size, one
 // host thread per share drives lh264_compress_batch on its device (streams are independent: no exchange between devices)

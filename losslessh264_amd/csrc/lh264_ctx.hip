@@ -14,13 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/lh264.h"
+#include "lh264_coder_dev.h"
 
 namespace lh264 {
 
-#define LDS __attribute__ ((address_space (3)))
-#define GLB __attribute__ ((address_space (1)))
+using lh264dev::glb;
 typedef int v2i __attribute__ ((ext_vector_type (2)));
-template <typename T> __device__ __forceinline__ GLB T* as_glb (const void* p) { return (GLB T*) (uintptr_t)p; }
 
 __device__ __forceinline__ int mb_type_code (int t) {       // MacroblockModel::encodeMacroblockType, macroblock_model.cpp:647-679
   switch (t) {
@@ -63,10 +62,10 @@ ctx_nnz_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int blocks
   const int k = (blockIdx.x % blocks_per_job) * 4 + wave;
   if (k >= n) return;
   // the macroblock type and the levels are requested together (one memory round trip, not two)
-  const GLB int16_t* lv = as_glb<const int16_t> (J->levels_dev) + (size_t)k * 384;
-  GLB uint8_t* cur = as_glb<uint8_t> (J->nnz_cur_dev) + (size_t)k * 24;
-  GLB uint16_t* nout = as_glb<uint16_t> (J->n_syms_dev) + k;
-  const GLB uint32_t* rec = (const GLB uint32_t*) (as_glb<const lh264_mb_t> (J->mbs_dev) + k);
+  const GLB int16_t* lv = glb<const int16_t> (J->levels_dev) + (size_t)k * 384;
+  GLB uint8_t* cur = glb<uint8_t> (J->nnz_cur_dev) + (size_t)k * 24;
+  GLB uint16_t* nout = glb<uint16_t> (J->n_syms_dev) + k;
+  const GLB uint32_t* rec = (const GLB uint32_t*) (glb<const lh264_mb_t> (J->mbs_dev) + k);
   const uint32_t head_l = rec[0], flags_l = rec[1];             // mb_type | cbp << 16 | qp << 24 ; qp_c | flags << 16 | intra_avail << 24
   const v2i a = * (const GLB v2i*) (lv + 4 * lane);
   v2i b = {0, 0};
@@ -134,9 +133,9 @@ ctx_inherit_chain_kernel (const lh264_ctx_job_t* __restrict__ jobs, const int32_
   if (chain >= n_chains) return;
   for (int ji = chain_first[chain]; ji < chain_first[chain + 1]; ji++) {
     const lh264_ctx_job_t* J = jobs + ji;
-    const GLB lh264_mb_t* mbs = as_glb<const lh264_mb_t> (J->mbs_dev);
-    const GLB uint8_t* past = as_glb<const uint8_t> (J->nnz_past_dev);
-    GLB uint8_t* cur = as_glb<uint8_t> (J->nnz_cur_dev);
+    const GLB lh264_mb_t* mbs = glb<const lh264_mb_t> (J->mbs_dev);
+    const GLB uint8_t* past = glb<const uint8_t> (J->nnz_past_dev);
+    GLB uint8_t* cur = glb<uint8_t> (J->nnz_cur_dev);
     const int n = J->mb_w * J->mb_h;
     for (int k = threadIdx.x; k < n; k += blockDim.x) {
       const int type = mbs[k].mb_type;
@@ -223,8 +222,8 @@ ctx_offsets_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, unsign
   __syncthreads();
   if (!J->sym_off_dev) { if (tid == 0) job_total[ji] = 0; return; }
   const int n = J->mb_w * J->mb_h;
-  const GLB uint16_t* ns = as_glb<const uint16_t> (J->n_syms_dev);
-  GLB uint32_t* off = as_glb<uint32_t> (J->sym_off_dev);
+  const GLB uint16_t* ns = glb<const uint16_t> (J->n_syms_dev);
+  GLB uint32_t* off = glb<uint32_t> (J->sym_off_dev);
   for (int k0 = 0; k0 < n; k0 += 256) {
     const int k = k0 + tid;
     const uint32_t v = k < n ? ns[k] : 0u;
@@ -265,7 +264,7 @@ ctx_bases_kernel (int n_jobs, unsigned long long* __restrict__ job_total, unsign
 __global__ void __launch_bounds__ (256)
 ctx_scatter_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, const unsigned long long* __restrict__ job_total) {
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < n_jobs && jobs[j].sym_base_dev) *as_glb<unsigned long long> (jobs[j].sym_base_dev) = job_total[j];
+  if (j < n_jobs && jobs[j].sym_base_dev) *glb<unsigned long long> (jobs[j].sym_base_dev) = job_total[j];
 }
 
 __global__ void __launch_bounds__ (256)
@@ -279,16 +278,16 @@ ctx_symbols_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int bl
   const int k = (blockIdx.x % blocks_per_job) * 4 + wave;
   if (k >= n) return;
   LDS CtxWave& W = * (LDS CtxWave*) (uintptr_t) (uint32_t) (uintptr_t)&sm[wave];
-  const GLB lh264_mb_t* m = as_glb<const lh264_mb_t> (J->mbs_dev) + k;
-  const GLB int16_t* lv = as_glb<const int16_t> (J->levels_dev) + (size_t)k * 384;
-  const GLB uint8_t* cur = as_glb<const uint8_t> (J->nnz_cur_dev);
-  GLB uint16_t* nout = as_glb<uint16_t> (J->n_syms_dev) + k;
+  const GLB lh264_mb_t* m = glb<const lh264_mb_t> (J->mbs_dev) + k;
+  const GLB int16_t* lv = glb<const int16_t> (J->levels_dev) + (size_t)k * 384;
+  const GLB uint8_t* cur = glb<const uint8_t> (J->nnz_cur_dev);
+  GLB uint16_t* nout = glb<uint16_t> (J->n_syms_dev) + k;
   // where the macroblock's symbols go: its fixed slot, or (compact layout) behind its predecessors' in the pool - the count pass has
   // said how many there are (n_syms), the running sums where (sym_off, sym_base); a pool that is too small is not written to.
   // (requested here with the other reads of the macroblock, looked at when the symbols are copied out)
   const bool compact = J->sym_off_dev != nullptr;
   unsigned long long sym_base_v = 0; uint32_t sym_off_v = 0, n_syms_v = 0;
-  if (compact) { sym_base_v = *as_glb<const unsigned long long> (J->sym_base_dev); sym_off_v = as_glb<const uint32_t> (J->sym_off_dev)[k]; n_syms_v = *nout; }
+  if (compact) { sym_base_v = *glb<const unsigned long long> (J->sym_base_dev); sym_off_v = glb<const uint32_t> (J->sym_off_dev)[k]; n_syms_v = *nout; }
 
   // Every global read of the macroblock is issued before anything is looked at: the record (lanes 0..7 take a dword each),
   // the levels and the four nnz entries travel together, one memory round trip instead of a chain of three (a wave has
@@ -304,7 +303,7 @@ ctx_symbols_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int bl
     if (who == 0) nzv = ((const GLB uint32_t*) (cur + (size_t)k * 24))[q];
     else if (who == 1) { if (mbx > 0) nzv = ((const GLB uint32_t*) (cur + (size_t) (k - 1) * 24))[q]; }
     else if (who == 2) { if (k >= mb_w) nzv = ((const GLB uint32_t*) (cur + (size_t) (k - mb_w) * 24))[q]; }
-    else if (J->nnz_past_dev) nzv = ((const GLB uint32_t*) (as_glb<const uint8_t> (J->nnz_past_dev) + (size_t)k * 24))[q];
+    else if (J->nnz_past_dev) nzv = ((const GLB uint32_t*) (glb<const uint8_t> (J->nnz_past_dev) + (size_t)k * 24))[q];
   }
   // stage levels and the four nnz entries
   * (LDS v2i*) (W.lv + 4 * lane) = l0;
@@ -320,7 +319,7 @@ ctx_symbols_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int bl
   const int cbp = (head >> 16) & 0xff;
   const int t8 = (__builtin_amdgcn_readlane ((int)rec, 1) >> 16) & LH264_MBF_T8x8;                 // flags: byte 6
   const int sid = (int) ((uint32_t)__builtin_amdgcn_readlane ((int)rec, 6) >> 16);                // slice_id: bytes 26..27
-  const int st = as_glb<const lh264_slice_t> (J->slices_dev)[sid].slice_type;
+  const int st = glb<const lh264_slice_t> (J->slices_dev)[sid].slice_type;
   const int mbc = mb_type_code (type);
   asm volatile ("" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -419,8 +418,8 @@ ctx_symbols_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int bl
   if (compact) {
     const unsigned long long at = sym_base_v + sym_off_v;
     room = at + n_syms_v <= J->syms_cap && (int)n_syms_v == total;
-    out = (GLB uint64_t*) (as_glb<lh264_ctx_sym_t> (J->syms_dev) + at);
-  } else out = (GLB uint64_t*) (as_glb<lh264_ctx_sym_t> (J->syms_dev) + (size_t)k * LH264_CTX_MAX_SYMS);
+    out = (GLB uint64_t*) (glb<lh264_ctx_sym_t> (J->syms_dev) + at);
+  } else out = (GLB uint64_t*) (glb<lh264_ctx_sym_t> (J->syms_dev) + (size_t)k * LH264_CTX_MAX_SYMS);
   if (room) for (int i = lane; i < total; i += 64) out[i] = W.osym[i];
   if (lane == 0 && (!compact || !room)) *nout = room ? (uint16_t)total : (uint16_t)0;       // (compact layout: the count pass has written it)
 }

@@ -10,7 +10,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
-#include <chrono>
 #include <deque>
 #include <map>
 #include <memory>
@@ -21,6 +20,7 @@
 #include "../../include/lh264.h"
 #include "host/h264_parser.h"
 #include "host/capi_internal.h"
+#include "host/device_mem.h"
 
 // ---- the pack step: crop + I420 / NV12, host and device from one source ------------------------------------------------------------
 // A picture is cut into bands of 16 luma rows (and the 8 chroma rows that belong to them); a band's rows are cut into PIECES: the
@@ -117,13 +117,6 @@ __global__ void __launch_bounds__ (256) decode_pack_kernel (const lh264_pack_job
   lh264pack::pack_band (j, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
-// the dequantised coefficients travel as a list of the nonzero ones: (index into the round's coefficient planes) << 16 | value; the
-// planes are cleared on the device in front of this
-__global__ void __launch_bounds__ (256) expand_coeffs_kernel (const uint64_t* __restrict__ ents, size_t n, int16_t* __restrict__ dense) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) { const uint64_t e = ents[i]; dense[e >> 16] = (int16_t) (uint16_t) (e & 0xffffu); }
-}
-
 struct lh264_decoded {
   int status = LH264_OK;
   std::string error;
@@ -145,37 +138,10 @@ namespace {
 using lh264host::FrameOut;
 using lh264host::Parser;
 
-bool trace_on() { static const bool t = getenv ("LH264_TRACE_DECODE") != nullptr; return t; }
-double now_s() { return std::chrono::duration<double> (std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-struct DevBuf {                       // device memory, grown when a round needs more, reused otherwise
-  void* p = nullptr; size_t cap = 0;
-  ~DevBuf() { if (p) hipFree (p); }
-  bool alloc (size_t bytes) {
-    if (bytes < 16) bytes = 16;
-    if (bytes <= cap) return true;
-    if (p) { hipFree (p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 8;
-    if (hipMalloc (&p, want) != hipSuccess) { p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-struct PinBuf {                       // page-locked staging memory
-  void* p = nullptr; size_t cap = 0;
-  ~PinBuf() { if (p) hipHostFree (p); }
-  bool alloc (size_t bytes) {
-    if (bytes < 16) bytes = 16;
-    if (bytes <= cap) return true;
-    if (p) { hipHostFree (p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 8;
-    if (hipHostMalloc (&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
+using lh264host::DevBuf;
+using lh264host::PinBuf;
+using lh264host::now_s;
+bool trace_on() { static const bool t = lh264host::trace_on ("LH264_TRACE_DECODE"); return t; }
 
 // padded pictures, handed out one by one and taken back when a stream is through; allocated in slabs of one picture size
 struct PicCache {
@@ -284,9 +250,7 @@ std::string refuse_picture (const FrameOut& f) {
   return "";
 }
 
-enum { kMaxDevices = 16 };
-std::unique_ptr<Arena> g_arena[kMaxDevices];
-std::mutex g_arena_mutex[kMaxDevices];
+lh264host::PerDevice<Arena> g_arena;      // one decode call at a time per device
 double g_timing[6] = {0, 0, 0, 0, 0, 0};
 
 const uint32_t kDefaultRoundPictures = 8;
@@ -321,11 +285,10 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   if (threads < 1) threads = 1;
   int device = 0;
-  if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= kMaxDevices) return LH264_E_ARG;
+  if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
   for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; }
-  std::lock_guard<std::mutex> arena_lock (g_arena_mutex[device]);
-  if (!g_arena[device]) g_arena[device].reset (new Arena());
-  Arena& A = *g_arena[device];
+  auto arena_lock = g_arena.lock (device);
+  Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
   const double t_call = now_s();
   double t_parse = 0, t_stage = 0, t_enqueue = 0, t_wait = 0, t_deliver = 0;
@@ -584,7 +547,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       bool ok = up (A.d_mbs, h_mbs, n_mbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
                 up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_chains + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
                 hipMemsetAsync (A.d_coef.p, 0, n_mbs * 768, st) == hipSuccess;
-      if (ok && n_sp) { hipLaunchKernelGGL (expand_coeffs_kernel, dim3 ((unsigned) ((n_sp + 255) / 256)), dim3 (256), 0, st, A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>()); ok = hipGetLastError() == hipSuccess; }
+      if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
       if (ok) { hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>()); ok = hipGetLastError() == hipSuccess; }
       if (ok && device_out) {
@@ -657,22 +620,15 @@ int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap)
 }
 void lh264_decoded_free (lh264_decoded_t* d) { delete d; }
 int lh264_decode_arena_bytes (size_t* device, size_t* pinned) {
-  int d = 0;
-  if (lh264_device_count() <= 0 || hipGetDevice (&d) != hipSuccess || d < 0 || d >= kMaxDevices) return LH264_E_NODEVICE;
-  std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
-  if (device) *device = g_arena[d] ? g_arena[d]->device_bytes() : 0;
-  if (pinned) *pinned = g_arena[d] ? g_arena[d]->pinned_bytes() : 0;
-  return LH264_OK;
+  const bool ok = lh264_device_count() > 0 && g_arena.read_current ([&] (const Arena* a) {
+    if (device) *device = a ? a->device_bytes() : 0;
+    if (pinned) *pinned = a ? a->pinned_bytes() : 0;
+  });
+  return ok ? LH264_OK : LH264_E_NODEVICE;
 }
 void lh264_decode_release (void) {
   if (lh264_device_count() <= 0) return;
-  int cur = 0;
-  hipGetDevice (&cur);
-  for (int d = 0; d < kMaxDevices; d++) {
-    std::lock_guard<std::mutex> lock (g_arena_mutex[d]);
-    if (g_arena[d]) { hipSetDevice (d); g_arena[d].reset(); }
-  }
-  hipSetDevice (cur);
+  g_arena.release_all();
 }
 
 }

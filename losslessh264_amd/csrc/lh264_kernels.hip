@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/lh264.h"
+#include "lh264_coder_dev.h"
 
 namespace lh264 {
 
@@ -53,11 +54,9 @@ __device__ unsigned long long g_stamps[16];
 #define STAMP(i) do {} while (0)
 #define STAMP_FLUSH do {} while (0)
 #endif
-#define LDS __attribute__ ((address_space (3)))
-#define GLB __attribute__ ((address_space (1)))
+using lh264dev::glb;
 typedef int v2i __attribute__ ((ext_vector_type (2)));
 __device__ __forceinline__ v2i mk2 (int a, int b) { v2i r; r.x = a; r.y = b; return r; }
-template <typename T> __device__ __forceinline__ GLB T* to_glb (const void* p) { return (GLB T*) (uintptr_t)p; }
 
 // ---- tables (H.264 Tables 8-16/8-17; reference copies: deblocking.cpp:89-125) ----------------
 __constant__ uint8_t kTables[52 + 52 + 52 * 4] = {
@@ -1410,8 +1409,8 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
     if (ji >= last) break;
     if (ji != cur_ji) {                      // entering a new frame
       const lh264_frame_job_t* J = jobs + ji;
-      F.mbs = to_glb<const lh264_mb_t> (J->mbs_dev); F.coeffs = to_glb<const int16_t> (J->coeffs_dev); F.slices = to_glb<const lh264_slice_t> (J->slices_dev);
-      F.dy = to_glb<uint8_t> (J->dst.y_dev); F.du = to_glb<uint8_t> (J->dst.u_dev); F.dv = to_glb<uint8_t> (J->dst.v_dev);
+      F.mbs = glb<const lh264_mb_t> (J->mbs_dev); F.coeffs = glb<const int16_t> (J->coeffs_dev); F.slices = glb<const lh264_slice_t> (J->slices_dev);
+      F.dy = glb<uint8_t> (J->dst.y_dev); F.du = glb<uint8_t> (J->dst.u_dev); F.dv = glb<uint8_t> (J->dst.v_dev);
       F.mb_w = J->mb_w; F.mb_h = J->mb_h; F.sy = J->stride_y; F.sc = J->stride_c; F.flags = J->flags;
       B.LY = F.mb_w * 16 + 48; B.LC = F.mb_w * 8 + 24; B.FW = F.mb_w * 16;
       lu = B.LY + 2 * B.LC;

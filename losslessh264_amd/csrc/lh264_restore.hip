@@ -809,19 +809,19 @@ void restore_stream_host (const RestoreJob& J, const RestoreTables& T) {
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 #include "host/capi_internal.h"
+#include "host/device_mem.h"
 #include "host/pip_restore.h"
 
 namespace {
 using namespace lh264r;
 
-double now_ms() { return std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now().time_since_epoch()).count(); }
-bool trace_on() { static const bool t = getenv ("LH264_TRACE_RESTORE") != nullptr; return t; }
+double now_ms() { return 1e3 * lh264host::now_s(); }
+bool trace_on() { static const bool t = lh264host::trace_on ("LH264_TRACE_RESTORE"); return t; }
 // test-only capacity overrides (0 / unset: the host's estimate)
 uint32_t env_u32 (const char* name) { const char* e = getenv (name); return e ? (uint32_t)strtoul (e, nullptr, 10) : 0u; }
 inline size_t al256 (size_t v) { return (v + 255) & ~(size_t)255; }
@@ -836,23 +836,23 @@ struct Plan {
 
 // device and page-locked buffers kept between calls, one set per device; one call at a time per device
 struct RestoreArena {
-  uint8_t* dev = nullptr; size_t dev_cap = 0;
-  uint8_t* pin_in = nullptr; size_t pin_in_cap = 0;
-  uint8_t* pin_out = nullptr; size_t pin_out_cap = 0;
+  lh264host::DevBuf dev; lh264host::PinBuf pin_in, pin_out;
   hipStream_t stream = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
-  void release() {
-    if (dev) hipFree (dev);
-    if (pin_in) hipHostFree (pin_in);
-    if (pin_out) hipHostFree (pin_out);
+  bool init() {
+    if (stream) return true;
+    if (hipStreamCreateWithFlags (&stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate (&ev[0]) == hipSuccess && hipEventCreate (&ev[1]) == hipSuccess) return true;
+    drop_stream();
+    return false;
+  }
+  void drop_stream() {
     if (ev[0]) hipEventDestroy (ev[0]);
     if (ev[1]) hipEventDestroy (ev[1]);
     if (stream) hipStreamDestroy (stream);
-    *this = RestoreArena();
+    stream = nullptr; ev[0] = ev[1] = nullptr;
   }
+  ~RestoreArena() { drop_stream(); }
 };
-enum { kMaxDevices = 16 };
-std::unique_ptr<RestoreArena> g_arena[kMaxDevices];
-std::mutex g_mutex[kMaxDevices];
+lh264host::PerDevice<RestoreArena> g_arena;      // (the CPU check takes device 0's lock and no arena)
 std::mutex g_timing_mutex;
 double g_timing[4] = {0, 0, 0, 0};
 
@@ -894,9 +894,9 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   int dev = 0;
   if (device) {
     if (lh264_device_count() <= 0 || hipGetDevice (&dev) != hipSuccess) return LH264_E_NODEVICE;
-    if (dev < 0 || dev >= kMaxDevices) return LH264_E_ARG;
+    if (dev < 0 || dev >= lh264host::kMaxDevices) return LH264_E_ARG;
   }
-  std::lock_guard<std::mutex> lock (g_mutex[device ? dev : 0]);
+  auto lock = g_arena.lock (device ? dev : 0);
   double t[5]; t[0] = now_ms();
   // pass 1
   std::vector<Plan> plans (n);
@@ -953,31 +953,9 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   uint8_t* out_stage = nullptr;  // where the outputs arrive
   RestoreArena* A = nullptr;
   if (device) {
-    if (!g_arena[dev]) g_arena[dev].reset (new RestoreArena());
-    A = g_arena[dev].get();
-    if (!A->stream) {
-      if (hipStreamCreateWithFlags (&A->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate (&A->ev[0]) != hipSuccess ||
-          hipEventCreate (&A->ev[1]) != hipSuccess) { A->release(); return LH264_E_HIP; }
-    }
-    if (A->dev_cap < total) {
-      if (A->dev) hipFree (A->dev);
-      A->dev = nullptr; A->dev_cap = 0;
-      if (hipMalloc ((void**)&A->dev, total) != hipSuccess) return LH264_E_HIP;
-      A->dev_cap = total;
-    }
-    if (A->pin_in_cap < in_bytes) {
-      if (A->pin_in) hipHostFree (A->pin_in);
-      A->pin_in = nullptr; A->pin_in_cap = 0;
-      if (hipHostMalloc ((void**)&A->pin_in, in_bytes, 0) != hipSuccess) return LH264_E_HIP;
-      A->pin_in_cap = in_bytes;
-    }
-    if (A->pin_out_cap < out_bytes) {
-      if (A->pin_out) hipHostFree (A->pin_out);
-      A->pin_out = nullptr; A->pin_out_cap = 0;
-      if (hipHostMalloc ((void**)&A->pin_out, std::max<size_t> (out_bytes, 256), 0) != hipSuccess) return LH264_E_HIP;
-      A->pin_out_cap = std::max<size_t> (out_bytes, 256);
-    }
-    base = A->dev; in_stage = A->pin_in; out_stage = A->pin_out - off_outr;
+    A = &lock.get();
+    if (!A->init() || !A->dev.alloc (total) || !A->pin_in.alloc (in_bytes) || !A->pin_out.alloc (out_bytes)) return LH264_E_HIP;
+    base = A->dev.as<uint8_t>(); in_stage = A->pin_in.as<uint8_t>(); out_stage = A->pin_out.as<uint8_t>() - off_outr;
   } else {
     host_mem.assign (total, 0);
     base = host_mem.data(); in_stage = host_mem.data(); out_stage = host_mem.data();
@@ -1020,15 +998,15 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   double kernel_ms = 0;
   if (device) {
     hipStream_t s = A->stream;
-    bool ok = hipMemcpyAsync (A->dev, A->pin_in, in_bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-    ok = ok && (zero_bytes == 0 || hipMemsetAsync (A->dev + off_zero, 0, zero_bytes, s) == hipSuccess);
+    bool ok = hipMemcpyAsync (base, in_stage, in_bytes, hipMemcpyHostToDevice, s) == hipSuccess;
+    ok = ok && (zero_bytes == 0 || hipMemsetAsync (base + off_zero, 0, zero_bytes, s) == hipSuccess);
     if (ok && nd) {
       ok = ok && hipEventRecord (A->ev[0], s) == hipSuccess;
-      hipLaunchKernelGGL (restore_kernel, dim3 ((unsigned)nd), dim3 (64), 0, s, (const RestoreJob*) (A->dev + off_jobs), (const int32_t*) (A->dev + off_order), nd,
-                          (const RestoreTables*) (A->dev + off_tables));
+      hipLaunchKernelGGL (restore_kernel, dim3 ((unsigned)nd), dim3 (64), 0, s, (const RestoreJob*) (base + off_jobs), (const int32_t*) (base + off_order), nd,
+                          (const RestoreTables*) (base + off_tables));
       ok = ok && hipGetLastError() == hipSuccess;
       ok = ok && hipEventRecord (A->ev[1], s) == hipSuccess;
-      ok = ok && hipMemcpyAsync (A->pin_out, A->dev + off_outr, out_bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+      ok = ok && hipMemcpyAsync (A->pin_out.p, base + off_outr, out_bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
     }
     if (!ok) { hipStreamSynchronize (s); return LH264_E_HIP; }
     // the streams the host restores go while the device works
@@ -1107,16 +1085,5 @@ int lh264_restore_last_timing (double* ms) {
   for (int i = 0; i < 4; i++) ms[i] = g_timing[i];
   return LH264_OK;
 }
-void lh264_restore_release (void) {
-  int cur = 0;
-  hipGetDevice (&cur);
-  for (int d = 0; d < kMaxDevices; d++) {
-    std::lock_guard<std::mutex> lock (g_mutex[d]);
-    if (!g_arena[d]) continue;
-    hipSetDevice (d);
-    g_arena[d]->release();
-    g_arena[d].reset();
-  }
-  hipSetDevice (cur);
-}
+void lh264_restore_release (void) { g_arena.release_all(); }
 }
