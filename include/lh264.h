@@ -491,14 +491,24 @@ int lh264_pip_restore_batch (lh264_restore_item_t* items, int n, int threads);
 /* ---- restore direction on the device (csrc/lh264_restore.hip) ------------------------------------------------------------
  * lh264_pip_restore_batch_device: the same n restores, with the same status, out and out_len per item as lh264_pip_restore_batch
  * (LH264_E_ARG with out_len = the size needed included), synchronously on the current device.  Host pass 1 reads the slice headers
- * of each default stream (`threads` host threads, 0 = all); one single-wave workgroup per CAVLC stream runs the adaptive decode and
- * the CAVLC macroblock writer; host pass 2 splices the slices' bits behind their headers.  path_out[i] (may be NULL) tells how item
- * i was restored.  Without a device: LH264_E_NODEVICE, the items untouched.  Device and page-locked buffers are kept between calls
- * (lh264_restore_release frees them); concurrent calls on one device are serialised by a lock. */
+ * of each default stream (`threads` host threads, 0 = all); one single-wave workgroup per stream runs the adaptive decode and the
+ * macroblock writer of each slice - the CAVLC writer; the CABAC writer where the caller asks for it (LH264_RESTORE_CABAC_DEVICE),
+ * otherwise a stream with a CABAC slice is restored by the host beside the kernel -; host pass 2 splices the slices' bits behind
+ * their headers.  path_out[i] (may be NULL) tells how item i was restored.  Without a device: LH264_E_NODEVICE, the items untouched.
+ * Device and page-locked buffers are kept between calls (lh264_restore_release frees them); concurrent calls on one device are
+ * serialised by a lock. */
 #define LH264_RESTORE_PATH_DEVICE   0   /* restored by the kernel                                                               */
-#define LH264_RESTORE_PATH_HOST     1   /* the stream has CABAC slices: the host restore, beside the kernel                      */
+#define LH264_RESTORE_PATH_HOST     1   /* the stream has CABAC slices (and no LH264_RESTORE_CABAC_DEVICE): the host restore      */
 #define LH264_RESTORE_PATH_FALLBACK 2   /* the device path stopped (capacity, corrupt input, I_PCM without samples): lh264_pip_restore */
 int lh264_pip_restore_batch_device (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+/* the same with options; lh264_pip_restore_batch_device behaves as this call with zeroed flags.  LH264_RESTORE_CABAC_DEVICE: streams
+ * with CABAC slices are planned like the others (per slice: a stream may change between CAVLC and CABAC with its PPS) and the batch
+ * runs the kernel instance that has the CABAC writer (9.3.2 - 9.3.4) beside the CAVLC one; LH264_RESTORE_PATH_HOST is then reported
+ * for no item.  Opt-in: which side is faster for a batch is in DESIGN.md 4.5.  opts == NULL: zeroed flags and threads = 0.  A
+ * struct_bytes this library does not know or unknown flag bits: LH264_E_ARG, before the device is looked at. */
+#define LH264_RESTORE_CABAC_DEVICE 1u   /* streams with CABAC slices take the kernel too */
+typedef struct lh264_restore_opts { uint32_t struct_bytes; int32_t threads; uint32_t flags; } lh264_restore_opts_t;
+int lh264_pip_restore_batch_device_opts (lh264_restore_item_t* items, int n, const lh264_restore_opts_t* opts, int32_t* path_out);
 void lh264_restore_release (void);
 /* milliseconds of the last lh264_pip_restore_batch_device call in this process: ms[0] host pass 1 and staging, ms[1] the device
  * stage (upload, kernel, download; the CABAC streams on the host meanwhile), ms[2] the kernel alone (HIP events), ms[3] host pass 2
@@ -507,6 +517,7 @@ int lh264_restore_last_timing (double* ms);
 /* the kernel's code (csrc/lh264_restore.hip) stepped on the host threads over host memory, with the same plan, capacities and
  * results as lh264_pip_restore_batch_device: a check of the device chain where no device is present; not a restore path */
 int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out);
+int lh264_debug_restore_cpu_opts (lh264_restore_item_t* items, int n, const lh264_restore_opts_t* opts, int32_t* path_out);
 /* the restore kernel's adaptive-probability update ON THE DEVICE, alone: out[i] = the probability word (c0 bits 0-9, c1 bits 10-19,
  * prob bits 20-27) that follows words[i] after the decision bits[i].  Its division by a reciprocal exists in device code only, so
  * lh264_debug_restore_cpu never steps it; a test runs every reachable pair of counts through this.  Without a device: LH264_E_NODEVICE */

@@ -136,7 +136,10 @@ class PackJob(C.Structure):
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("dst", C.c_void_p),
                 ("stride_y", C.c_int32), ("stride_c", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
                 ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32)]
-assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 40 and C.sizeof(PackJob) == 64
+RESTORE_CABAC_DEVICE = 1
+class RestoreOpts(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
+assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 40 and C.sizeof(PackJob) == 64 and C.sizeof(RestoreOpts) == 12
 _SIGS.update({
     "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodeOpts), C.POINTER(C.c_void_p)]),
     "lh264_decoded_status": (C.c_int, [C.c_void_p]),
@@ -212,6 +215,8 @@ _SIGS["lh264_code_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_
 # ---- restore direction on the device
 _SIGS["lh264_pip_restore_batch_device"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
 _SIGS["lh264_debug_restore_cpu"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_SIGS["lh264_pip_restore_batch_device_opts"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+_SIGS["lh264_debug_restore_cpu_opts"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
 _SIGS["lh264_debug_dp_update"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
 _SIGS["lh264_restore_release"] = (None, [])
 _SIGS["lh264_restore_last_timing"] = (C.c_int, [C.POINTER(C.c_double)])

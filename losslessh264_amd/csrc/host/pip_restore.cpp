@@ -1197,26 +1197,29 @@ bool Restorer::decode_slice (const Parser::HeaderInfo& H) {
 }
 
 // ---- the host passes of the device restore (csrc/lh264_restore.hip) --------------------------------------------------------------
-// pass 1: the slice descriptors, in stream order (no tag data needed); stops at the first CABAC slice
+// pass 1: the slice descriptors, in stream order (no tag data needed); stops at the first CABAC slice unless the caller takes those
+// too (keep_cabac: per slice, a stream may change between the two with its PPS)
 class SliceDescriber : public Walker {
  public:
   using Walker::Walker;
-  int run (const uint8_t* d, size_t n, std::vector<lh264r::RestoreSlice>& slices, bool& cabac) {
+  int run (const uint8_t* d, size_t n, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, bool keep_cabac) {
     std::vector<uint8_t> out;
     return walk (d, n, out, [&] (const Parser::HeaderInfo& H) {
-      if (H.cabac) { cabac = true; return false; }
+      if (H.cabac) { cabac = true; if (!keep_cabac) return false; }
       lh264r::RestoreSlice s;
       s.mb_w = H.mb_w; s.mb_h = H.mb_h; s.first_mb = H.sh.first_mb; s.slice_type = H.sh.slice_type; s.frame_num = H.sh.frame_num;
       s.slice_qp = H.sh.slice_qp; s.num_ref_idx_l0 = H.sh.num_ref_idx_l0;
-      s.transform_8x8 = H.transform_8x8; s.constrained_intra_pred = H.constrained_intra_pred; s.cabac = 0;
-      s.phase = (uint8_t)w_.bits_in_byte();                  // hdr_bits & 7: the writer starts each NAL on a byte
+      s.transform_8x8 = H.transform_8x8; s.constrained_intra_pred = H.constrained_intra_pred;
+      s.cabac = H.cabac ? (uint8_t) (1 | ((H.sh.cabac_init_idc & 3) << 1)) : 0;
+      s.phase = H.cabac ? 0 : (uint8_t)w_.bits_in_byte();    // hdr_bits & 7: the writer starts each NAL on a byte
       slices.push_back (s);
       return true;
     });
   }
 };
 // pass 2: the same walk with the device's bits of each slice behind its header: the first byte holds the slice's first 8 - phase
-// bits, the rest are whole bytes, escaped on the way as decode_slice's bits are
+// bits, the rest are whole bytes, escaped on the way as decode_slice's bits are.  A CABAC slice's bytes follow the
+// cabac_alignment_one_bits that fill the header's last byte
 class SliceSplicer : public Walker {
  public:
   using Walker::Walker;
@@ -1228,9 +1231,15 @@ class SliceSplicer : public Walker {
       if (i >= n_slices) { fail ("more slices than pass 1 saw"); return false; }
       const uint32_t end = slice_end[i];
       const int phase = slices[i].phase;
-      if (end <= start || w_.bits_in_byte() != phase) { fail ("the device's slice does not fit"); return false; }
-      w_.emit_bits (bits[start] & ((1u << (8 - phase)) - 1u), 8 - phase);
-      w_.append_bytes (bits + start + 1, end - start - 1);
+      if (end <= start) { fail ("the device's slice does not fit"); return false; }
+      if (slices[i].cabac) {
+        while (w_.bits_in_byte()) w_.emit_bit (1);
+        w_.append_bytes (bits + start, end - start);
+      } else {
+        if (w_.bits_in_byte() != phase) { fail ("the device's slice does not fit"); return false; }
+        w_.emit_bits (bits[start] & ((1u << (8 - phase)) - 1u), 8 - phase);
+        w_.append_bytes (bits + start + 1, end - start - 1);
+      }
       start = end; i++;
       return true;
     });
@@ -1252,12 +1261,13 @@ int pip_restore (const uint8_t* main_stream, size_t main_len, const uint8_t* con
   }
 }
 
-int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err) {
+int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err,
+                          bool keep_cabac) {
   err.clear(); slices.clear(); cabac = false;
   if (!main_stream) { err = "null argument"; return -1; }
   try {
     SliceDescriber w (err);
-    return w.run (main_stream, main_len, slices, cabac);
+    return w.run (main_stream, main_len, slices, cabac, keep_cabac);
   } catch (const std::exception& e) {
     err = std::string ("internal: ") + e.what();
     return -1;
@@ -1306,6 +1316,16 @@ void restore_tables (lh264r::RestoreTables& T) {
   memcpy (T.zz4, kZigzag4x4, 16); memcpy (T.zz8, kZigzag8x8, 64); memcpy (T.zz16, kZz16, 16); memcpy (T.zz64, kZz64, 64);
   memcpy (T.scan8, kScan8, 16); memcpy (T.cache30, kCache30, 16); memcpy (T.z2raster, kZ2Raster, 16);
   for (int p = 0; p < 2; p++) for (int j = 0; j < 4; j++) T.chroma_nzc[p][j] = (uint8_t)kChromaNzc[p][j];
+}
+
+void restore_cabac_tables (lh264r::RestoreCabacTables& T) {
+  memset (&T, 0, sizeof (T));
+  static_assert (sizeof (T.init) == sizeof (kCabacInit) && sizeof (T.enc.range_lps) == sizeof (kCabacRangeLps), "the tables of h264_cabac_tables.h");
+  memcpy (T.init, kCabacInit, sizeof (kCabacInit));
+  memcpy (T.enc.range_lps, kCabacRangeLps, sizeof (kCabacRangeLps));
+  memcpy (T.enc.next_lps, kCabacNextLps, 64); memcpy (T.enc.next_mps, kCabacNextMps, 64);
+  memcpy (T.enc.sig8x8, kSig8x8, 63); memcpy (T.enc.last8x8, kLast8x8, 63);
+  for (int c = 0; c < 5; c++) { T.enc.cat_cbf[c] = (uint8_t)kCatCbf[c]; T.enc.cat_map[c] = (uint8_t)kCatMap[c]; T.enc.cat_abs[c] = (uint8_t)kCatAbs[c]; }
 }
 
 }  // namespace lh264host

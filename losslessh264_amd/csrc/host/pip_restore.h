@@ -10,7 +10,7 @@
 //   * a CAVLC macroblock-layer writer straight from ITU-T H.264 7.3.5 / 9.2 (the reference borrows its encoder's writer,
 //     encoder/core/src/svc_set_mb_syn_cavlc.cpp:266-320 via decoder/core/inc/encoder_from_decoder.h)
 // The adaptive decode is serial by nature (every prior depends on the values decoded before it); it runs here one stream per
-// thread, and for CAVLC streams also on the device (csrc/lh264_restore.hip, one wave per stream, between the two host passes below).  CABAC slices go through a CABAC macroblock writer (9.3.2-9.3.4, the mirror image of the
+// thread, and also on the device (csrc/lh264_restore.hip, one wave per stream, between the two host passes below).  CABAC slices go through a CABAC macroblock writer (9.3.2-9.3.4, the mirror image of the
 // front end's CABAC parser).  I_PCM macroblocks are reported as unsupported.
 #pragma once
 #include <stddef.h>
@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-namespace lh264r { struct RestoreSlice; struct RestoreTables; }
+namespace lh264r { struct RestoreSlice; struct RestoreTables; struct RestoreCabacTables; }
 
 namespace lh264host {
 
@@ -29,12 +29,15 @@ int pip_restore (const uint8_t* main_stream, size_t main_len, const uint8_t* con
 
 // The host passes of the device restore (csrc/lh264_restore.hip), over the same walk of the default stream as pip_restore.
 // Pass 1: the descriptor of every slice (csrc/lh264_restore.h RestoreSlice); cabac = the stream has a CABAC slice (the walk stops
-// there).  Pass 2: the restored stream, with the device's bits of slice i at bits[slice_end[i-1] .. slice_end[i]).
-// Both return 0, or < 0 with a message in err.
-int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err);
+// there, or with keep_cabac records such slices like the others).  Pass 2: the restored stream, with the device's bits of slice i at
+// bits[slice_end[i-1] .. slice_end[i]).  Both return 0, or < 0 with a message in err.
+int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err,
+                          bool keep_cabac = false);
 int pip_restore_splice (const uint8_t* main_stream, size_t main_len, const lh264r::RestoreSlice* slices, size_t n_slices, const uint8_t* bits,
                         const uint32_t* slice_end, std::vector<uint8_t>& out, std::string& err);
 // the CAVLC tables and prior sizes of the host restore, flattened for the kernel
 void restore_tables (lh264r::RestoreTables& T);
+// the CABAC writer's: context initialisation, the encoder's state transitions, the residual context maps
+void restore_cabac_tables (lh264r::RestoreCabacTables& T);
 
 }  // namespace lh264host

@@ -1,15 +1,16 @@
 // lh264_restore.h - what the host passes of the device restore (csrc/host/pip_restore.cpp) and its kernel (lh264_restore.hip)
-// share: the slice descriptor pass 1 records, the CAVLC tables, and the per-stream job of one kernel workgroup.
+// share: the slice descriptor pass 1 records, the CAVLC and CABAC tables, and the per-stream job of one kernel workgroup.
 #pragma once
 #include <stdint.h>
 
 namespace lh264r {
 
-// what the model and the CAVLC writer read of a slice header (Parser::HeaderInfo), in stream order
+// what the model and the writers read of a slice header (Parser::HeaderInfo), in stream order
 struct RestoreSlice {
   int32_t mb_w, mb_h, first_mb, slice_type, frame_num, slice_qp, num_ref_idx_l0;
-  uint8_t transform_8x8, constrained_intra_pred, cabac;
-  uint8_t phase;                       // hdr_bits & 7: where the slice data starts in its byte
+  uint8_t transform_8x8, constrained_intra_pred;
+  uint8_t cabac;                       // 0: a CAVLC slice; else 1 | cabac_init_idc << 1
+  uint8_t phase;                       // CAVLC: hdr_bits & 7, where the slice data starts in its byte; CABAC: 0 (the data starts on a byte)
 };
 static_assert (sizeof (RestoreSlice) == 32, "RestoreSlice layout");
 
@@ -31,6 +32,19 @@ struct RestoreTables {
 };
 static_assert (sizeof (RestoreTables) % 4 == 0, "RestoreTables is copied by words");
 
+// the tables of the CABAC writer (h264_cabac_tables.h and pip_restore.cpp's), as the CAVLC ones above; built by
+// lh264host::restore_cabac_tables.  The encoder reads `enc` for every bin (the kernel keeps a copy in LDS), `init` once per slice
+struct RestoreCabacEnc {
+  uint8_t range_lps[64][4], next_lps[64], next_mps[64];   // kCabacRangeLps / kCabacNextLps / kCabacNextMps
+  uint8_t sig8x8[64], last8x8[64];                        // kSig8x8 / kLast8x8 (63 used)
+  uint8_t cat_cbf[8], cat_map[8], cat_abs[8];             // kCatCbf / kCatMap / kCatAbs (5 used)
+};
+struct RestoreCabacTables {
+  RestoreCabacEnc enc;
+  int8_t init[460][4][2];              // kCabacInit: (m, n) by context and column (0: I slices, 1 + cabac_init_idc: P slices)
+};
+static_assert (sizeof (RestoreCabacEnc) % 4 == 0 && sizeof (RestoreCabacTables) % 4 == 0, "the CABAC tables are copied by words");
+
 // status of one stream after the kernel; anything but RS_OK sends the stream to the host restore (LH264_RESTORE_PATH_FALLBACK)
 enum { RS_OK = 0, RS_CORRUPT = 1, RS_STORE_FULL = 2, RS_OUT_FULL = 3 };
 
@@ -42,13 +56,13 @@ struct RestoreJob {
   uint32_t n_slices, n_max;            // slices; the largest picture in macroblocks
   const RestoreSlice* slices;
   uint8_t* cells;                      // 2 x n_max Cell
-  uint8_t* ws;                         // n_max WState
+  uint8_t* ws;                         // n_max WState (the kernel instance with the CABAC writer: its longer WState)
   int8_t* ipm;                         // n_max x 8
   uint8_t* nxn;                        // n_max
   uint32_t* hash;                      // slots x {key + 1, pool offset}; zeroed before the launch
   uint32_t* pool;                      // pool_cap packed DynProbs
   uint32_t slots, pool_cap;            // slots: a power of two
-  uint8_t* out;                        // the slices' bits, each slice from a fresh byte and `phase` zero bits
+  uint8_t* out;                        // the slices' bits, each slice from a fresh byte and `phase` zero bits (a CABAC slice: its bytes)
   uint32_t out_cap;
   uint32_t* slice_end;                 // per slice: its end in out (bytes)
   int32_t* status;                     // [0] RS_*; [1] prior keys, [2] pool words, [3] output bytes used

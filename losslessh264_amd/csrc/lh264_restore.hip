@@ -1,7 +1,9 @@
-// lh264_restore.hip - the restore direction on the device for CAVLC streams (include/lh264.h lh264_pip_restore_batch_device):
+// lh264_restore.hip - the restore direction on the device (include/lh264.h lh264_pip_restore_batch_device):
 // one single-wave workgroup per stream runs the adaptive decode of csrc/host/pip_restore.cpp (Restorer::decode_slice,
-// decode_coeffs, the scan primitives, update_frame) and its CAVLC macroblock writer, slice after slice, in the same decision
-// order.  The decode is a serial chain (every prior depends on what was decoded before it): lane 0 runs it; the wave clears
+// decode_coeffs, the scan primitives, update_frame) and its macroblock writers, slice after slice, in the same decision
+// order: the CAVLC writer, and in a kernel instance of its own (restore_cabac_kernel, for batches that ask for it) the CABAC writer
+// (CabacEnc, write_mb_cabac, cabac_residual), which feeds nothing back into the model.
+// The decode is a serial chain (every prior depends on what was decoded before it): lane 0 runs it; the wave clears
 // the work memory and runs update_frame's skip-run scan.  What the host keeps in growing containers lives in fixed regions
 // the host sized from pass 1 (lh264_restore.h RestoreJob); running out of one, or input the host would refuse, ends the
 // stream with a status and the host restores it instead.  Every loop is bounded.
@@ -76,6 +78,13 @@ struct WState {                         // the CAVLC part of pip_restore.cpp WSt
   int32_t slice; uint32_t mb_type; int8_t ipm[16]; uint8_t nzc[24]; uint8_t type_class, pad[3];
 };
 static_assert (sizeof (WState) == 52, "WState layout");
+struct WStateC {                        // pip_restore.cpp WState whole: the CAVLC part where WState has it, then the CABAC context selection (9.3.3.1.1)
+  int32_t slice; uint32_t mb_type; int8_t ipm[16]; uint8_t nzc[24]; uint8_t type_class, skip, t8, cbp;
+  uint8_t chroma_pred; int8_t ref[4]; uint8_t mvd[16][2]; uint8_t pad[3]; uint32_t cbf;
+};
+static_assert (sizeof (WStateC) == 96, "WStateC layout");
+template <bool kCabac> struct WSel { typedef WState type; };
+template <> struct WSel<true> { typedef WStateC type; };
 struct alignas (16) MbDec {
   uint32_t type; int cbp_c, cbp_l, luma_qp, num_ref, chroma_mode, luma16_mode, t8;
   int pred_mode[16]; int sub_type[4]; int ref_idx[4]; int mvd[16][2];
@@ -90,6 +99,11 @@ struct Shared {
   uint8_t zero[24];                     // the nnz of an absent neighbour
   uint32_t test_prob;
   int32_t status;
+};
+// and what the instance with the CABAC writer keeps there beside it
+struct CabacShared {
+  RestoreCabacEnc K;
+  uint8_t state[460];                   // pStateIdx << 1 | valMPS by context (CabacEnc::state)
 };
 
 inline LH_HD int type_code (uint32_t t) {
@@ -113,13 +127,19 @@ LH_HD inline int imin (int a, int b) { return a < b ? a : b; }
 LH_HD inline int z2x (int z) { return (z & 1) | ((z >> 2) & 1) << 1; }
 LH_HD inline int z2y (int z) { return ((z >> 1) & 1) | ((z >> 3) & 1) << 1; }
 
-// the serial chain of one stream: lane 0's part of the kernel
-struct Chain {
+// the state of the CABAC encoder (pip_restore.cpp CabacEnc): its bits go out through the chain's bits / nbits, its context states live
+// in C.  A base of the chain, empty without the CABAC writer: that chain is then the one the CAVLC kernel has always had
+template <bool kCabac> struct EncState {};
+template <> struct EncState<true> { CabacShared* C; uint32_t c_low, c_range; int c_out; bool c_first; };
+
+// the serial chain of one stream: lane 0's part of the kernel.  kCabac: with the CABAC writer (and the longer WState it needs)
+template <bool kCabac> struct Chain : EncState<kCabac> {
+  typedef typename WSel<kCabac>::type W;
   const RestoreJob& J;
   Shared& S;
   const RestoreTables& T;
   Cell* img[2];
-  WState* ws;
+  W* ws;
   const uint8_t* pcm; const uint8_t* pcm_end;
   uint32_t used, pool_used;
   int sid;
@@ -251,10 +271,62 @@ struct Chain {
   LH_HD void write_residual_block (const int* lv, int maxc, int nC, int& total_out);
   LH_HD void write_mb (const RestoreSlice& H, int k, const MbDec& m, int& qp_prev);
   LH_HD void decode_slice (const RestoreSlice& H, int cur_, bool prior_valid, int8_t* ipm, uint8_t* nxn);
+
+  // ---- CABAC arithmetic encoding engine, 9.3.4.2 (this->: the members of EncState, a dependent base)
+  LH_HD void ce_reset() { this->c_low = 0; this->c_range = 510; this->c_out = 0; this->c_first = true; }
+  LH_HD void ce_write_bit (uint32_t b) { bits = (bits << 1) | (b & 1u); if (++nbits == 8) { put_byte (bits); bits = 0; nbits = 0; } }
+  LH_HD void ce_put (uint32_t b) {                      // PutBit, figure 9-9
+    if (this->c_first) this->c_first = false; else ce_write_bit (b);
+    while (this->c_out > 0) { ce_write_bit (1u - b); this->c_out--; }
+  }
+  LH_HD void ce_renorm() {
+    while (this->c_range < 256) {                             // at most 7 steps
+      if (this->c_low < 256) ce_put (0);
+      else if (this->c_low >= 512) { this->c_low -= 512; ce_put (1); }
+      else { this->c_low -= 256; this->c_out++; }
+      this->c_range <<= 1; this->c_low <<= 1;
+    }
+  }
+  LH_HD void ce_encode (int ctx, int bin) {
+    const uint32_t s = this->C->state[ctx];
+    const uint32_t st = s >> 1; uint32_t mps = s & 1u;
+    const uint32_t lps = this->C->K.range_lps[st][(this->c_range >> 6) & 3];
+    this->c_range -= lps;
+    if ((uint32_t) (bin & 1) != mps) {
+      this->c_low += this->c_range; this->c_range = lps;
+      if (st == 0) mps ^= 1u;
+      this->C->state[ctx] = (uint8_t) ((this->C->K.next_lps[st] << 1) | mps);
+    } else this->C->state[ctx] = (uint8_t) ((this->C->K.next_mps[st] << 1) | mps);
+    ce_renorm();
+  }
+  LH_HD void ce_bypass (int bin) {
+    this->c_low <<= 1;
+    if (bin & 1) this->c_low += this->c_range;
+    if (this->c_low >= 1024) { ce_put (1); this->c_low -= 1024; }
+    else if (this->c_low < 512) ce_put (0);
+    else { this->c_low -= 512; this->c_out++; }
+  }
+  LH_HD void ce_terminate (int bin) {
+    this->c_range -= 2;
+    if (bin) {
+      this->c_low += this->c_range;
+      this->c_range = 2; ce_renorm();                         // EncodeFlush
+      ce_put ((this->c_low >> 9) & 1);
+      ce_write_bit ((this->c_low >> 8) & 1); ce_write_bit (1);   // the last bit is the rbsp stop bit
+      while (nbits) ce_write_bit (0);
+    } else ce_renorm();
+  }
+  LH_HD void ce_ueg_suffix (int rem, int kk) {          // the Exp-Golomb suffix of UEGk, bypass coded; rem < 2^28
+    while (kk < 30 && rem >= (1 << kk)) { ce_bypass (1); rem -= 1 << kk; kk++; }
+    ce_bypass (0);
+    while (kk--) ce_bypass ((rem >> kk) & 1);
+  }
+  LH_HD void cabac_residual (int w, int k, int cat, int blk, int plane, bool cur_intra, const int* lv, int maxc);
+  LH_HD void write_mb_cabac (const RestoreSlice& H, int k, const MbDec* m /* null: P_Skip */, int& qp_prev, int& last_dqp);
 };
 
 // pip_restore.cpp Restorer::decode_coeffs
-LH_HD void Chain::decode_coeffs (MbDec& m, int st, int mbc, const Cell* nl, const Cell* na, const Cell* np, Cell& e) {
+template <bool kCabac> LH_HD void Chain<kCabac>::decode_coeffs (MbDec& m, int st, int mbc, const Cell* nl, const Cell* na, const Cell* np, Cell& e) {
   const uint8_t* Lf = nl ? nl->nnz : S.zero; const uint8_t* Ab = na ? na->nnz : S.zero; const uint8_t* Pa = np ? np->nnz : S.zero;
   uint8_t* C = e.nnz;
   int16_t* lev = m.lev;
@@ -324,7 +396,7 @@ LH_HD void Chain::decode_coeffs (MbDec& m, int st, int mbc, const Cell* nl, cons
   }
 }
 
-LH_HD int Chain::pred_intra_mode (int k, int bx, int by, int w, int sid_, bool cip) const {
+template <bool kCabac> LH_HD int Chain<kCabac>::pred_intra_mode (int k, int bx, int by, int w, int sid_, bool cip) const {
   int modeA = 2, modeB = 2; bool dcpred = false;
   auto avail = [&] (int kk) { return kk >= 0 && ws[kk].slice == sid_ && (!cip || ws[kk].type_class == 1 || ws[kk].type_class == 2); };
   {
@@ -343,7 +415,7 @@ LH_HD int Chain::pred_intra_mode (int k, int bx, int by, int w, int sid_, bool c
 }
 
 // residual_block_cavlc, 7.3.5.3.2 / 9.2 (pip_restore.cpp Restorer::write_residual_block)
-LH_HD void Chain::write_residual_block (const int* lv, int maxc, int nC, int& total_out) {
+template <bool kCabac> LH_HD void Chain<kCabac>::write_residual_block (const int* lv, int maxc, int nC, int& total_out) {
   int coef[16], pos_of[16], total = 0;
   for (int i = maxc - 1; i >= 0; i--) if (lv[i]) { coef[total] = lv[i]; pos_of[total] = i; total++; }
   total_out = total;
@@ -392,10 +464,10 @@ LH_HD void Chain::write_residual_block (const int* lv, int maxc, int nC, int& to
 }
 
 // macroblock_layer, 7.3.5 (pip_restore.cpp Restorer::write_mb)
-LH_HD void Chain::write_mb (const RestoreSlice& H, int k, const MbDec& m, int& qp_prev) {
+template <bool kCabac> LH_HD void Chain<kCabac>::write_mb (const RestoreSlice& H, int k, const MbDec& m, int& qp_prev) {
   const int w = H.mb_w;
   const bool is_p = H.slice_type == 0;
-  WState& s = ws[k];
+  W& s = ws[k];
   s.slice = sid; for (int i = 0; i < 24; i++) s.nzc[i] = 0; for (int i = 0; i < 16; i++) s.ipm[i] = 2;
   const uint32_t type = m.type;
   s.mb_type = type;
@@ -509,14 +581,316 @@ LH_HD void Chain::write_mb (const RestoreSlice& H, int k, const MbDec& m, int& q
   }
 }
 
-// one CAVLC slice (pip_restore.cpp Restorer::decode_slice after its bookkeeping, which the whole wave did)
-LH_HD void Chain::decode_slice (const RestoreSlice& H, int cur_, bool prior_valid, int8_t* ipm_, uint8_t* nxn_) {
+// ---- the CABAC macroblock layer writer: 7.3.5 with the binarisations and context selection of 9.3.2 / 9.3.3 (pip_restore.cpp
+// Restorer::cabac_residual, Restorer::write_mb_cabac), instantiated in the kCabac chain only
+template <bool kCabac> LH_HD void Chain<kCabac>::cabac_residual (int w, int k, int cat, int blk, int plane, bool cur_intra, const int* lv, int maxc) {
+  const RestoreCabacEnc& K = this->C->K;
+  W& s = ws[k];
+  int last_nz = -1, n_sig = 0;
+  for (int i = 0; i < maxc; i++) if (lv[i]) { last_nz = i; n_sig++; }
+  if (cat != 5) {                                          // coded_block_flag, 9.3.3.1.1.9
+    int bit, bitA, bitB; int kA = k, kB = k;
+    if (cat == 0) { bit = bitA = bitB = 16; kA = -2; kB = -2; }
+    else if (cat == 3) { bit = bitA = bitB = 17 + plane; kA = -2; kB = -2; }
+    else if (cat == 4) {
+      const int cx = blk & 1, cy = blk >> 1;
+      bit = 19 + plane * 4 + blk;
+      if (cx == 0) { kA = -2; bitA = 19 + plane * 4 + cy * 2 + 1; } else bitA = bit - 1;
+      if (cy == 0) { kB = -2; bitB = 19 + plane * 4 + 2 + cx; } else bitB = bit - 2;
+    } else {
+      const int bx = blk & 3, by = blk >> 2;
+      bit = blk;
+      if (bx == 0) { kA = -2; bitA = by * 4 + 3; } else bitA = blk - 1;
+      if (by == 0) { kB = -2; bitB = 12 + bx; } else bitB = blk - 4;
+    }
+    if (kA == -2) kA = ((k % w) && ws[k - 1].slice == sid) ? k - 1 : -1;
+    if (kB == -2) kB = (k >= w && ws[k - w].slice == sid) ? k - w : -1;
+    const int cA = kA < 0 ? (cur_intra ? 1 : 0) : (int) ((ws[kA].cbf >> bitA) & 1);
+    const int cBf = kB < 0 ? (cur_intra ? 1 : 0) : (int) ((ws[kB].cbf >> bitB) & 1);
+    ce_encode (85 + K.cat_cbf[cat] + cA + 2 * cBf, n_sig != 0);
+    if (!n_sig) return;
+    s.cbf |= 1u << bit;
+  }
+  const int sig_base = cat == 5 ? 402 : 105 + K.cat_map[cat], last_base = cat == 5 ? 417 : 166 + K.cat_map[cat];
+  const int abs_base = cat == 5 ? 426 : 227 + K.cat_abs[cat];
+  for (int i = 0; i < maxc - 1; i++) {
+    const int inc_s = cat == 5 ? K.sig8x8[i] : cat == 3 ? imin (i, 2) : i;
+    const int inc_l = cat == 5 ? K.last8x8[i] : cat == 3 ? imin (i, 2) : i;
+    const int sig = lv[i] != 0;
+    ce_encode (sig_base + inc_s, sig);
+    if (sig) {
+      ce_encode (last_base + inc_l, i == last_nz);
+      if (i == last_nz) break;
+    }
+  }
+  int num_eq1 = 0, num_gt1 = 0;
+  for (int i = maxc - 1; i >= 0; i--) {
+    if (!lv[i]) continue;
+    const int mag = lv[i] < 0 ? -lv[i] : lv[i], v = mag - 1;
+    int inc = num_gt1 ? 0 : imin (4, 1 + num_eq1);
+    ce_encode (abs_base + inc, v > 0);
+    if (v > 0) {
+      inc = 5 + imin (4 - (cat == 3 ? 1 : 0), num_gt1);
+      int cnt = 1;
+      while (cnt < 14) { const int bin = v > cnt; ce_encode (abs_base + inc, bin); if (!bin) break; cnt++; }
+      if (v >= 14) ce_ueg_suffix (v - 14, 0);               // Exp-Golomb order 0 suffix
+    }
+    ce_bypass (lv[i] < 0);
+    if (mag == 1) num_eq1++; else num_gt1++;
+  }
+}
+
+template <bool kCabac> LH_HD void Chain<kCabac>::write_mb_cabac (const RestoreSlice& H, int k, const MbDec* mp, int& qp_prev, int& last_dqp) {
+  const int w = H.mb_w;
+  const bool is_p = H.slice_type == 0;
+  W& s = ws[k];
+  const int kA = ((k % w) && ws[k - 1].slice == sid) ? k - 1 : -1, kB = (k >= w && ws[k - w].slice == sid) ? k - w : -1;
+  if (is_p) ce_encode (11 + (kA >= 0 && !ws[kA].skip) + (kB >= 0 && !ws[kB].skip), mp == nullptr);     // mb_skip_flag
+  s.slice = sid; for (int i = 0; i < 24; i++) s.nzc[i] = 0; for (int i = 0; i < 16; i++) { s.ipm[i] = 2; s.mvd[i][0] = s.mvd[i][1] = 0; }
+  s.skip = 0; s.t8 = 0; s.cbp = 0; s.chroma_pred = 0; s.cbf = 0;
+  for (int i = 0; i < 4; i++) s.ref[i] = -1;
+  if (!mp) {
+    s.mb_type = LH264_MB_SKIP; s.type_class = 3; s.skip = 1;
+    for (int i = 0; i < 4; i++) s.ref[i] = 0;
+    last_dqp = 0;
+    return;
+  }
+  const MbDec& m = *mp;
+  const uint32_t type = m.type;
+  s.mb_type = type;
+  const bool intra = (type & LH264_MB_INTRA) != 0;
+  const bool i16 = type == LH264_MB_I16x16;
+  const int cbp = m.cbp_l | (m.cbp_c << 4);
+  auto i_type = [&] (bool islice, int mbt) {               // 9.3.2.5, Table 9-36
+    const int ctx0 = islice ? 3 + (kA >= 0 && ws[kA].type_class != 1) + (kB >= 0 && ws[kB].type_class != 1) : 17;
+    if (mbt == 0) { ce_encode (ctx0, 0); return; }
+    ce_encode (ctx0, 1);
+    ce_terminate (0);
+    const int v = mbt - 1, pm = v & 3, chroma = (v >> 2) % 3, luma = v >= 12;
+    const int base = islice ? 3 : 17;
+    ce_encode (base + (islice ? 3 : 1), luma);
+    ce_encode (base + (islice ? 4 : 2), chroma != 0);
+    if (chroma) ce_encode (base + (islice ? 5 : 2), chroma == 2);
+    ce_encode (base + (islice ? 6 : 3), pm >> 1);
+    ce_encode (base + (islice ? 7 : 3), pm & 1);
+  };
+  auto t8_flag = [&] (int v) { ce_encode (399 + (kA >= 0 && ws[kA].t8) + (kB >= 0 && ws[kB].t8), v); };
+  bool t8 = false;
+  if (type == LH264_MB_IPCM) {
+    // mb_type 25: the prefix bin, then the terminating bin set, which flushes the engine (9.3.4.5) and leaves the stream byte aligned;
+    // the samples follow as they are and the engine starts afresh behind them, the context states kept (9.3.1.2)
+    if (is_p) ce_encode (14, 1);
+    ce_encode (is_p ? 17 : 3 + (kA >= 0 && ws[kA].type_class != 1) + (kB >= 0 && ws[kB].type_class != 1), 1);
+    ce_terminate (1);
+    for (int i = 0; i < 384; i++) put_byte (pcm[i]);
+    pcm += 384;
+    ce_reset();
+    s.type_class = 2; s.cbf = 0xffffffffu; s.cbp = 0x2f;
+    for (int i = 0; i < 24; i++) s.nzc[i] = 16;
+    last_dqp = 0;
+    return;
+  }
+  if (intra) {
+    int mbt = 0;
+    if (i16) {
+      const int kRaw16[7] = {0, 1, 2, 3, 2, 2, 2};
+      mbt = 1 + kRaw16[imin (m.luma16_mode, 6)] + 4 * m.cbp_c + (m.cbp_l ? 12 : 0);
+      s.type_class = 2;
+    } else s.type_class = 1;
+    if (is_p) ce_encode (14, 1);
+    i_type (!is_p, mbt);
+    if (!i16) {
+      t8 = type == LH264_MB_I8x8;
+      if (H.transform_8x8) t8_flag (t8);
+      s.t8 = t8;
+      const int nblk = t8 ? 4 : 16;
+      for (int i = 0; i < nblk; i++) {
+        const int bx = t8 ? (i & 1) * 2 : z2x (i), by = t8 ? (i >> 1) * 2 : z2y (i);
+        const int pred = pred_intra_mode (k, bx, by, w, sid, H.constrained_intra_pred);
+        const int mode = m.pred_mode[i];
+        ce_encode (68, mode == pred);
+        if (mode != pred) { const int rem = mode < pred ? mode : mode - 1; ce_encode (69, rem & 1); ce_encode (69, (rem >> 1) & 1); ce_encode (69, (rem >> 2) & 1); }
+        const int n = t8 ? 2 : 1;
+        for (int yy = 0; yy < n; yy++) for (int x = 0; x < n; x++) s.ipm[(by + yy) * 4 + bx + x] = (int8_t)mode;
+      }
+    }
+    const int kRawChroma[7] = {0, 1, 2, 3, 0, 0, 0};
+    const int cm = kRawChroma[imin (m.chroma_mode, 6)];
+    {                                                        // intra_chroma_pred_mode, 9.3.3.1.1.8
+      const int cA = kA >= 0 && ws[kA].type_class != 3 && ws[kA].chroma_pred != 0;
+      const int cBn = kB >= 0 && ws[kB].type_class != 3 && ws[kB].chroma_pred != 0;
+      ce_encode (64 + cA + cBn, cm != 0);
+      if (cm) { ce_encode (67, cm != 1); if (cm != 1) ce_encode (67, cm == 3); }
+    }
+    s.chroma_pred = (uint8_t)cm;
+  } else {
+    s.type_class = 3;
+    const int nref = H.num_ref_idx_l0;
+    ce_encode (14, 0);
+    if (type == LH264_MB_P16x16) { ce_encode (15, 0); ce_encode (16, 0); }
+    else if (type == LH264_MB_P8x8 || type == LH264_MB_P8x8REF0) { ce_encode (15, 0); ce_encode (16, 1); }
+    else if (type == LH264_MB_P16x8) { ce_encode (15, 1); ce_encode (17, 1); }
+    else { ce_encode (15, 1); ce_encode (17, 0); }
+    auto ref_gt0 = [&] (int bx, int by) -> int {
+      int kk = k, x = bx, yy = by;
+      if (x < 0) { kk = kA; x = 3; } else if (yy < 0) { kk = kB; yy = 3; }
+      if (kk < 0) return 0;
+      const W& t = ws[kk];
+      if (t.type_class != 3 || t.skip) return 0;
+      return t.ref[(yy >> 1) * 2 + (x >> 1)] > 0;
+    };
+    auto put_ref = [&] (int bx, int by, int v) {
+      if (nref <= 1) return;
+      int inc = ref_gt0 (bx - 1, by) + 2 * ref_gt0 (bx, by - 1);
+      for (int i = 0; i < v; i++) { ce_encode (54 + inc, 1); inc = i == 0 ? 4 : 5; }
+      ce_encode (54 + inc, 0);
+    };
+    auto abs_mvd = [&] (int bx, int by, int comp) -> int {
+      int kk = k, x = bx, yy = by;
+      if (x < 0) { kk = kA; x = 3; } else if (yy < 0) { kk = kB; yy = 3; }
+      if (kk < 0) return 0;
+      return ws[kk].mvd[yy * 4 + x][comp];
+    };
+    auto put_mvd1 = [&] (int bx, int by, int comp, int d) {     // UEG3, uCoff 9, signed (9.3.2.3, 9.3.3.1.1.7)
+      const int base = comp ? 47 : 40;
+      const int sum = abs_mvd (bx - 1, by, comp) + abs_mvd (bx, by - 1, comp);
+      int inc = sum < 3 ? 0 : sum > 32 ? 2 : 1;
+      const int a = d < 0 ? -d : d;
+      if (a < 0 || a >= (1 << 28)) { fail (RS_CORRUPT); return; }     // no stream codes one; the suffix loop stays in range
+      ce_encode (base + inc, a != 0);
+      if (!a) return;
+      int v = 1;
+      inc = 3;
+      while (v < 9) { const int bin = a > v; ce_encode (base + inc, bin); if (!bin) break; v++; if (inc < 6) inc++; }
+      if (a >= 9) ce_ueg_suffix (a - 9, 3);
+      ce_bypass (d < 0);
+    };
+    auto part = [&] (int bx, int by, int bw, int bh) {          // the partition whose motion vector difference sits at (bx,by)
+      const int dx = m.mvd[by * 4 + bx][0], dy = m.mvd[by * 4 + bx][1];
+      put_mvd1 (bx, by, 0, dx); put_mvd1 (bx, by, 1, dy);
+      const uint8_t ax = (uint8_t)imin (255, dx < 0 ? -dx : dx), ay = (uint8_t)imin (255, dy < 0 ? -dy : dy);
+      for (int yy = by; yy < by + bh; yy++) for (int x = bx; x < bx + bw; x++) { s.mvd[yy * 4 + x][0] = ax; s.mvd[yy * 4 + x][1] = ay; }
+    };
+    if (type == LH264_MB_P16x16 || type == LH264_MB_P16x8 || type == LH264_MB_P8x16) {
+      const int mbt = type == LH264_MB_P16x16 ? 0 : type == LH264_MB_P16x8 ? 1 : 2;
+      const int np = mbt == 0 ? 1 : 2;
+      for (int i = 0; i < np; i++) {
+        const int bx = mbt == 2 ? i * 2 : 0, by = mbt == 1 ? i * 2 : 0;
+        put_ref (bx, by, m.ref_idx[i]);
+        for (int q = 0; q < 4; q++) {
+          const bool in = mbt == 0 || (mbt == 1 ? (q >> 1) == i : (q & 1) == i);
+          if (in) s.ref[q] = (int8_t)m.ref_idx[i];
+        }
+      }
+      for (int i = 0; i < np; i++) {
+        int bx = 0, by = 0, bw = 4, bh = 4;
+        if (mbt == 1) { bh = 2; by = i * 2; } else if (mbt == 2) { bw = 2; bx = i * 2; }
+        part (bx, by, bw, bh);
+      }
+    } else {
+      int sub[4];
+      for (int q = 0; q < 4; q++) {                           // sub_mb_type, Table 9-37
+        sub[q] = m.sub_type[q] == LH264_SUB_8x8 ? 0 : m.sub_type[q] == LH264_SUB_8x4 ? 1 : m.sub_type[q] == LH264_SUB_4x8 ? 2 : 3;
+        if (sub[q] == 0) ce_encode (21, 1);
+        else { ce_encode (21, 0); if (sub[q] == 1) ce_encode (22, 0); else { ce_encode (22, 1); ce_encode (23, sub[q] == 2); } }
+      }
+      for (int q = 0; q < 4; q++) { put_ref ((q & 1) * 2, (q >> 1) * 2, m.ref_idx[q]); s.ref[q] = (int8_t)m.ref_idx[q]; }
+      for (int q = 0; q < 4; q++) {
+        const int qx = (q & 1) * 2, qy = (q >> 1) * 2;
+        const int nsp = sub[q] == 0 ? 1 : sub[q] == 3 ? 4 : 2;
+        for (int j = 0; j < nsp; j++) {
+          int bx = qx, by = qy, bw = 2, bh = 2;
+          if (sub[q] == 1) { bh = 1; by += j; } else if (sub[q] == 2) { bw = 1; bx += j; } else if (sub[q] == 3) { bw = bh = 1; bx += j & 1; by += j >> 1; }
+          part (bx, by, bw, bh);
+        }
+      }
+    }
+  }
+  if (!i16) {                                                // coded_block_pattern, 9.3.2.6 / 9.3.3.1.1.4
+    auto luma_bit = [&] (int kk, int b8) -> int {
+      if (kk < 0) return 0;
+      if (ws[kk].skip) return 1;
+      return ((ws[kk].cbp >> b8) & 1) ? 0 : 1;
+    };
+    int cl = 0;
+    for (int b8 = 0; b8 < 4; b8++) {
+      const int cA = (b8 & 1) ? (((cl >> (b8 - 1)) & 1) ? 0 : 1) : luma_bit (kA, b8 + 1);
+      const int cBn = (b8 & 2) ? (((cl >> (b8 - 2)) & 1) ? 0 : 1) : luma_bit (kB, b8 + 2);
+      const int bit = (m.cbp_l >> b8) & 1;
+      ce_encode (73 + cA + 2 * cBn, bit);
+      cl |= bit << b8;
+    }
+    auto chroma_nz = [&] (int kk, int lvl) -> int {
+      if (kk < 0) return 0;
+      if (ws[kk].skip) return 0;
+      return (ws[kk].cbp >> 4) >= lvl;
+    };
+    ce_encode (77 + chroma_nz (kA, 1) + 2 * chroma_nz (kB, 1), m.cbp_c != 0);
+    if (m.cbp_c) ce_encode (77 + 4 + chroma_nz (kA, 2) + 2 * chroma_nz (kB, 2), m.cbp_c == 2);
+    if (!intra) {
+      bool no_sub_lt8 = true;
+      if (type == LH264_MB_P8x8 || type == LH264_MB_P8x8REF0) for (int q = 0; q < 4; q++) if (m.sub_type[q] != LH264_SUB_8x8) no_sub_lt8 = false;
+      if (m.cbp_l && H.transform_8x8 && no_sub_lt8) { t8 = m.t8 != 0; t8_flag (t8); }
+    }
+  }
+  s.cbp = (uint8_t)cbp;
+  if (t8) s.t8 = 1;
+  if (!(cbp || i16)) { last_dqp = 0; return; }
+  {                                                          // mb_qp_delta, 9.3.2.7 / 9.3.3.1.1.5
+    const int d = (((m.luma_qp - qp_prev) + 26 + 104) % 52) - 26;
+    const int v = d > 0 ? 2 * d - 1 : -2 * d;
+    ce_encode (60 + (last_dqp != 0 ? 1 : 0), v != 0);
+    if (v) {
+      ce_encode (62, v >= 2);
+      if (v >= 2) { for (int j = 2; j < v; j++) ce_encode (63, 1); ce_encode (63, 0); }
+    }
+    last_dqp = d;
+    qp_prev = m.luma_qp;
+  }
+  int lv[64];
+  if (i16) {
+    for (int i = 0; i < 16; i++) { const int r = T.zz4[i]; lv[i] = m.lev[(((r & 3) & 1) | (((r >> 2) & 1) << 1) | (((r & 3) >> 1) << 2) | (((r >> 2) >> 1) << 3)) * 16]; }
+    cabac_residual (w, k, 0, 0, 0, true, lv, 16);
+  }
+  for (int i8 = 0; i8 < 4; i8++) {
+    if (!((m.cbp_l >> i8) & 1)) continue;
+    if (t8) {
+      for (int i = 0; i < 64; i++) lv[i] = m.lev[i8 * 64 + T.zz8[i]];
+      cabac_residual (w, k, 5, i8, 0, intra, lv, 64);
+      for (int j = 0; j < 4; j++) { const int z = i8 * 4 + j; s.cbf |= 1u << (z2y (z) * 4 + z2x (z)); }
+      continue;
+    }
+    for (int j = 0; j < 4; j++) {
+      const int z = i8 * 4 + j, bx = z2x (z), by = z2y (z);
+      const int maxc = i16 ? 15 : 16;
+      for (int i = 0; i < maxc; i++) lv[i] = m.lev[z * 16 + T.zz4[i16 ? i + 1 : i]];
+      cabac_residual (w, k, i16 ? 1 : 2, by * 4 + bx, 0, intra, lv, maxc);
+    }
+  }
+  if (m.cbp_c) {
+    for (int p = 0; p < 2; p++) {
+      for (int i = 0; i < 4; i++) lv[i] = m.lev[256 + p * 64 + i * 16];
+      cabac_residual (w, k, 3, 0, p, intra, lv, 4);
+    }
+    if (m.cbp_c == 2) {
+      for (int p = 0; p < 2; p++) for (int j = 0; j < 4; j++) {
+          for (int i = 0; i < 15; i++) lv[i] = m.lev[256 + p * 64 + j * 16 + T.zz4[i + 1]];
+          cabac_residual (w, k, 4, j, p, intra, lv, 15);
+        }
+    }
+  }
+}
+
+// one slice (pip_restore.cpp Restorer::decode_slice after its bookkeeping, which the whole wave did)
+template <bool kCabac> LH_HD void Chain<kCabac>::decode_slice (const RestoreSlice& H, int cur_, bool prior_valid, int8_t* ipm_, uint8_t* nxn_) {
   const int w = H.mb_w, n = H.mb_w * H.mb_h;
   Cell* cur = img[cur_];
   Cell* last = img[1 - cur_];
   const bool is_p = H.slice_type == 0;
   const int st = H.slice_type;
-  int skip_state = -1, mb_in_slice = 0, cached_qp = 0, last_nonzero_dqp = 0, qp_prev = H.slice_qp;
+  const bool cabac = kCabac && H.cabac;
+  const uint32_t pos0 = pos;
+  int skip_state = -1, mb_in_slice = 0, cached_qp = 0, last_nonzero_dqp = 0, qp_prev = H.slice_qp, last_dqp = 0;
   uint32_t pending_skips = 0;
   MbDec& m = S.m;
   for (int k = H.first_mb; ; k++, mb_in_slice++) {      // ends at the stop flag; k < n bounds it
@@ -528,21 +902,25 @@ LH_HD void Chain::decode_slice (const RestoreSlice& H, int cur_, bool prior_vali
     const Cell* np = (prior_valid && last[k].initialized) ? &last[k] : nullptr;
     int mb_skip_run = 0;
     const uint32_t stop_idx = (uint32_t) (mb_in_slice < 2048 ? mb_in_slice : 2047);
-    if (skip_state == -1) {
+    if (skip_state == -1 || cabac) {                    // CABAC: a run of 0 or 1 for every macroblock
       const int pr = np ? np->cached_skips / 8 + (np->cached_skips % 8 ? 1 : 0) : 0;
       const int run = (int)tree (TAG_SKIP, LH264_TB_SKIPRUN, (uint32_t) (pr * 16 + 11));
-      if (is_p) skip_state = run; else mb_skip_run = run;
+      if (is_p && !cabac) skip_state = run; else mb_skip_run = run;
+      if (cabac && run > 1) { fail (RS_CORRUPT); return; }
     }
-    if (is_p) { mb_skip_run = skip_state; skip_state--; }
+    if (is_p && !cabac) { mb_skip_run = skip_state; skip_state--; }
     bool has_stop = false;
     if (mb_skip_run == 1) has_stop = scan_bit (TAG_SKIP_END, get (LH264_TB_STOP, stop_idx)) != 0;
     if (mb_skip_run != 0) {
       if (!is_p) { fail (RS_CORRUPT); return; }
       cur[k] = last[k];
       nxn_[k] = 0;
-      WState& s = ws[k];
+      W& s = ws[k];
       s.slice = sid; s.mb_type = LH264_MB_SKIP; s.type_class = 3; for (int i = 0; i < 24; i++) s.nzc[i] = 0; for (int i = 0; i < 16; i++) s.ipm[i] = 2;
-      pending_skips++;
+      if constexpr (kCabac) {
+        if (cabac) { write_mb_cabac (H, k, nullptr, qp_prev, last_dqp); ce_terminate (has_stop); }
+        else pending_skips++;
+      } else pending_skips++;
       if (has_stop) break;
       continue;
     }
@@ -680,10 +1058,23 @@ LH_HD void Chain::decode_slice (const RestoreSlice& H, int cur_, bool prior_vali
     e.zeroed = 1;
     for (int i = 0; i < 384; i++) if (m.lev[i]) { e.zeroed = 0; break; }
     cur[k] = e;
+    if constexpr (kCabac) if (cabac) {
+        write_mb_cabac (H, k, &m, qp_prev, last_dqp); ce_terminate (has_stop);
+        if (has_stop) break;
+        continue;
+      }
     if (is_p) { put_ue (pending_skips); pending_skips = 0; }
     write_mb (H, k, m, qp_prev);
     if (has_stop) break;
   }
+  if constexpr (kCabac) if (cabac) {
+      // the codeword ends with the rbsp stop bit on a byte; the low 7 bits of its last byte are what the compressor saw there
+      const unsigned pad_value = scan_raw_bits (TAG_PADBYTE, 7);
+      if (failed()) return;
+      if (pos == pos0) { fail (RS_CORRUPT); return; }
+      J.out[pos - 1] = (uint8_t) ((J.out[pos - 1] & 0x80u) | pad_value);     // (not failed: pos <= out_cap)
+      return;
+    }
   if (pending_skips) put_ue (pending_skips);
   // rbsp_slice_trailing_bits: the stop bit, then the alignment bits as the compressor saw them
   const int pad_bits = 7 - (nbits & 7);
@@ -699,11 +1090,18 @@ LH_HD void Chain::decode_slice (const RestoreSlice& H, int cur_, bool prior_vali
 #endif
 
 // one stream on `nl` lanes (the kernel: a wave; the CPU check: one); the bookkeeping of decode_slice on every lane, the chain on lane 0
-LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared& S, int lane, int nl) {
+template <bool kCabac>
+LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared& S, int lane, int nl, const RestoreCabacTables* CT, CabacShared* CS) {
+  typedef typename Chain<kCabac>::W W;
   {
     const uint32_t* src = (const uint32_t*)&Tg;
     uint32_t* dst = (uint32_t*)&S.T;
     for (unsigned i = (unsigned)lane; i < sizeof (RestoreTables) / 4; i += (unsigned)nl) dst[i] = src[i];
+  }
+  if constexpr (kCabac) {
+    const uint32_t* src = (const uint32_t*)&CT->enc;
+    uint32_t* dst = (uint32_t*)&CS->K;
+    for (unsigned i = (unsigned)lane; i < sizeof (RestoreCabacEnc) / 4; i += (unsigned)nl) dst[i] = src[i];
   }
   if (lane == 0) {
     S.status = RS_OK;
@@ -720,9 +1118,10 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
     }
   }
   RBAR();
-  Chain c (J, S);
+  Chain<kCabac> c (J, S);
+  if constexpr (kCabac) c.C = CS;
   c.img[0] = (Cell*)J.cells; c.img[1] = (Cell*)J.cells + J.n_max;
-  c.ws = (WState*)J.ws;
+  c.ws = (W*)J.ws;
   const bool have_pcm = (J.tag_present[LH264_TAG_PCM >> 5] >> (LH264_TAG_PCM & 31)) & 1u;
   c.pcm = have_pcm ? J.tags + J.tag_off[LH264_TAG_PCM] : nullptr;
   c.pcm_end = have_pcm ? c.pcm + J.tag_len[LH264_TAG_PCM] : nullptr;
@@ -735,7 +1134,7 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
     if (S.status != RS_OK) break;
     const RestoreSlice H = J.slices[si];
     const int n = H.mb_w * H.mb_h;
-    if (n <= 0 || H.first_mb < 0 || H.first_mb >= n || H.cabac) { if (lane == 0) c.fail (RS_CORRUPT); break; }
+    if (n <= 0 || H.first_mb < 0 || H.first_mb >= n || (!kCabac && H.cabac)) { if (lane == 0) c.fail (RS_CORRUPT); break; }
     if ((uint32_t)n > J.n_max) { if (lane == 0) c.fail (RS_STORE_FULL); break; }
     if (ipm_n != n * 8) {
       for (int i = lane; i < n * 2; i += nl) ((uint32_t*)J.ipm)[i] = 0;
@@ -743,7 +1142,8 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
       ipm_n = n * 8;
     }
     if (ws_n != n) {
-      for (int i = lane; i < n * 13; i += nl) ((uint32_t*)J.ws)[i] = (i % 13) == 0 ? 0xffffffffu : 0u;
+      const int ww = (int) (sizeof (W) / 4);
+      for (int i = lane; i < n * ww; i += nl) ((uint32_t*)J.ws)[i] = (i % ww) == 0 ? 0xffffffffu : 0u;
       ws_n = n;
     }
     c.sid++;
@@ -766,9 +1166,19 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
       img_w = H.mb_w; img_h = H.mb_h;
       for (int i = lane; i < n * 10; i += nl) { ((uint32_t*)c.img[0])[i] = 0; ((uint32_t*)c.img[1])[i] = 0; }
     }
+    if constexpr (kCabac) if (H.cabac) {                  // CabacEnc::init, a lane per context (9.3.1.1)
+        const int col = H.slice_type == 0 ? imin (3, 1 + (H.cabac >> 1)) : 0;
+        const int qp = H.slice_qp < 0 ? 0 : imin (51, H.slice_qp);
+        for (int i = lane; i < 460; i += nl) {
+          const int pre0 = ((CT->init[i][col][0] * qp) >> 4) + CT->init[i][col][1];
+          const int pre = pre0 < 1 ? 1 : imin (126, pre0);
+          CS->state[i] = pre <= 63 ? (uint8_t) ((63 - pre) << 1) : (uint8_t) (((pre - 64) << 1) | 1);
+        }
+      }
     RBAR();
     if (lane == 0) {
       c.nbits = H.phase; c.bits = 0;
+      if constexpr (kCabac) c.ce_reset();
       c.decode_slice (H, cur, prior_valid, J.ipm, J.nxn);
       J.slice_end[si] = c.pos;
     }
@@ -787,7 +1197,16 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
 __global__ __launch_bounds__ (64) __attribute__ ((amdgpu_waves_per_eu (LH264_RESTORE_WAVES))) void restore_kernel (const RestoreJob* jobs, const int32_t* order, int n, const RestoreTables* tables) {
   __shared__ Shared S;
   if ((int)blockIdx.x >= n) return;
-  restore_stream (jobs[order[blockIdx.x]], *tables, S, (int)threadIdx.x, (int)blockDim.x);
+  restore_stream<false> (jobs[order[blockIdx.x]], *tables, S, (int)threadIdx.x, (int)blockDim.x, nullptr, nullptr);
+}
+// the same with the CABAC writer beside the CAVLC one, for batches in which a stream has a CABAC slice; an instance of its own, so
+// that the CAVLC batches run the kernel above with its registers and LDS
+__global__ __launch_bounds__ (64) __attribute__ ((amdgpu_waves_per_eu (LH264_RESTORE_WAVES))) void restore_cabac_kernel (const RestoreJob* jobs, const int32_t* order, int n, const RestoreTables* tables,
+                                                                                                                   const RestoreCabacTables* ctables) {
+  __shared__ Shared S;
+  __shared__ CabacShared CS;
+  if ((int)blockIdx.x >= n) return;
+  restore_stream<true> (jobs[order[blockIdx.x]], *tables, S, (int)threadIdx.x, (int)blockDim.x, ctables, &CS);
 }
 
 // dp_update alone, one pair of counts per thread (lh264_debug_dp_update)
@@ -797,9 +1216,11 @@ __global__ __launch_bounds__ (256) void dp_update_kernel (const uint32_t* words,
 }
 
 // the same chain on the host, one stream at a time (no device: the CPU check of the transliteration)
-void restore_stream_host (const RestoreJob& J, const RestoreTables& T) {
+void restore_stream_host (const RestoreJob& J, const RestoreTables& T, const RestoreCabacTables* CT) {
   static thread_local Shared S;
-  restore_stream (J, T, S, 0, 1);
+  static thread_local CabacShared CS;
+  if (CT) restore_stream<true> (J, T, S, 0, 1, CT, &CS);
+  else restore_stream<false> (J, T, S, 0, 1, nullptr, nullptr);
 }
 
 }  // namespace lh264r
@@ -828,6 +1249,7 @@ inline size_t al256 (size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Plan {
   int path = LH264_RESTORE_PATH_FALLBACK;
+  bool cabac = false;                                   // a slice of the stream is a CABAC slice
   std::vector<RestoreSlice> slices;
   size_t tag_bytes = 0;
   uint32_t n_max = 0, slots = 0, pool_cap = 0, out_cap = 0;
@@ -873,7 +1295,8 @@ void size_plan (Plan& P, const lh264_restore_item_t& it) {
   if (uint32_t e = env_u32 ("LH264_RESTORE_POOL")) P.pool_cap = e;
   const size_t pcm = (it.n_tags > LH264_TAG_PCM && it.tags[LH264_TAG_PCM]) ? it.tag_len[LH264_TAG_PCM] : 0;
   // the slice data is at most 1.27 x the tags that code it on the reference's files; twice that, the I_PCM samples and a few bytes per
-  // slice and macroblock
+  // slice and macroblock.  CABAC slices, counted on their own (status[3] of the reference-written CABAC files): 1.055 x at most
+  // (test_cif_P_CABAC_slice.264, 4,200 slices), so 2 x the tags is 1.9 x the largest seen and serves them too
   P.out_cap = (uint32_t)std::min<size_t> (0xfffff000u, 2 * coded + 2 * pcm + 64 * P.slices.size() + 2 * (size_t)n_max + 4096);
   if (uint32_t e = env_u32 ("LH264_RESTORE_OUT_CAP")) P.out_cap = e;
 }
@@ -889,8 +1312,11 @@ void host_restore (lh264_restore_item_t& it) {
 }
 
 // device == false: the kernel's code stepped on the host threads over host memory (lh264_debug_restore_cpu)
-int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* path_out, bool device) {
+int restore_batch (lh264_restore_item_t* items, int n, const lh264_restore_opts_t* opts, int32_t* path_out, bool device) {
   if (!items || n < 0) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_restore_opts_t) || (opts->flags & ~LH264_RESTORE_CABAC_DEVICE))) return LH264_E_ARG;
+  const int threads = opts ? opts->threads : 0;
+  const bool cabac_device = opts && (opts->flags & LH264_RESTORE_CABAC_DEVICE);
   int dev = 0;
   if (device) {
     if (lh264_device_count() <= 0 || hipGetDevice (&dev) != hipSuccess) return LH264_E_NODEVICE;
@@ -906,9 +1332,8 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
     P.path = LH264_RESTORE_PATH_FALLBACK;
     if (!it.main_stream || !it.tags || !it.tag_len || it.n_tags < 0) return;      // lh264_pip_restore reports it
     std::string err;
-    bool cabac = false;
-    if (lh264host::pip_restore_describe (it.main_stream, it.main_len, P.slices, cabac, err) < 0) return;
-    if (cabac) { P.path = LH264_RESTORE_PATH_HOST; return; }
+    if (lh264host::pip_restore_describe (it.main_stream, it.main_len, P.slices, P.cabac, err, cabac_device) < 0) return;
+    if (P.cabac && !cabac_device) { P.path = LH264_RESTORE_PATH_HOST; return; }
     for (int q = 0; q < it.n_tags && q < 72; q++) if (it.tags[q]) P.tag_bytes += it.tag_len[q];
     if (P.tag_bytes >= 0xfffff000u) return;
     size_plan (P, it);
@@ -919,9 +1344,14 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   // the longest chains first: tag bytes stand for decisions
   std::stable_sort (dev_items.begin(), dev_items.end(), [&] (int a, int b) { return plans[a].tag_bytes > plans[b].tag_bytes; });
   const int nd = (int)dev_items.size();
+  // the kernel instance with the CABAC writer only where a stream of the batch needs it: its WState is the longer one
+  bool any_cabac = false;
+  for (int i : dev_items) any_cabac = any_cabac || plans[i].cabac;
+  const size_t ws_bytes = any_cabac ? sizeof (WStateC) : sizeof (WState);
   // layout: [inputs: tables, jobs, order, per stream slices + tags] [hash tables: zeroed] [work memory] [outputs: status, slice ends, bits]
   size_t off = 0;
   const size_t off_tables = off; off += al256 (sizeof (RestoreTables));
+  const size_t off_ctables = off; if (any_cabac) off += al256 (sizeof (RestoreCabacTables));
   const size_t off_jobs = off; off += al256 (sizeof (RestoreJob) * (size_t)nd);
   const size_t off_order = off; off += al256 (sizeof (int32_t) * (size_t)nd);
   for (int i : dev_items) {
@@ -936,7 +1366,7 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   for (int i : dev_items) {
     Plan& P = plans[i];
     P.off_work = off;
-    off += al256 ((size_t)P.n_max * (2 * 40 + 52 + 8 + 4)) + al256 ((size_t)P.pool_cap * 4);
+    off += al256 ((size_t)P.n_max * (2 * 40 + ws_bytes + 8 + 4)) + al256 ((size_t)P.pool_cap * 4);
   }
   const size_t off_outr = off;
   for (int i : dev_items) {
@@ -961,6 +1391,7 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
     base = host_mem.data(); in_stage = host_mem.data(); out_stage = host_mem.data();
   }
   lh264host::restore_tables (*(RestoreTables*) (in_stage + off_tables));
+  if (any_cabac) lh264host::restore_cabac_tables (*(RestoreCabacTables*) (in_stage + off_ctables));
   RestoreJob* jobs = (RestoreJob*) (in_stage + off_jobs);
   int32_t* order = (int32_t*) (in_stage + off_order);
   run_parallel (nd, threads, [&] (int j) {
@@ -983,10 +1414,10 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
     J.slices = (const RestoreSlice*) (base + P.off_slices);
     uint8_t* w = base + P.off_work;
     J.cells = w; w += (size_t)P.n_max * 80;
-    J.ws = w; w += (size_t)P.n_max * 52;
+    J.ws = w; w += (size_t)P.n_max * ws_bytes;
     J.ipm = (int8_t*)w; w += (size_t)P.n_max * 8;
     J.nxn = w;
-    J.pool = (uint32_t*) (base + P.off_work + al256 ((size_t)P.n_max * (2 * 40 + 52 + 8 + 4)));
+    J.pool = (uint32_t*) (base + P.off_work + al256 ((size_t)P.n_max * (2 * 40 + ws_bytes + 8 + 4)));
     J.hash = (uint32_t*) (base + P.off_hash);
     J.slots = P.slots; J.pool_cap = P.pool_cap;
     J.out = base + P.off_out; J.out_cap = P.out_cap;
@@ -1002,8 +1433,10 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
     ok = ok && (zero_bytes == 0 || hipMemsetAsync (base + off_zero, 0, zero_bytes, s) == hipSuccess);
     if (ok && nd) {
       ok = ok && hipEventRecord (A->ev[0], s) == hipSuccess;
-      hipLaunchKernelGGL (restore_kernel, dim3 ((unsigned)nd), dim3 (64), 0, s, (const RestoreJob*) (base + off_jobs), (const int32_t*) (base + off_order), nd,
-                          (const RestoreTables*) (base + off_tables));
+      if (any_cabac) hipLaunchKernelGGL (restore_cabac_kernel, dim3 ((unsigned)nd), dim3 (64), 0, s, (const RestoreJob*) (base + off_jobs), (const int32_t*) (base + off_order), nd,
+                                         (const RestoreTables*) (base + off_tables), (const RestoreCabacTables*) (base + off_ctables));
+      else hipLaunchKernelGGL (restore_kernel, dim3 ((unsigned)nd), dim3 (64), 0, s, (const RestoreJob*) (base + off_jobs), (const int32_t*) (base + off_order), nd,
+                               (const RestoreTables*) (base + off_tables));
       ok = ok && hipGetLastError() == hipSuccess;
       ok = ok && hipEventRecord (A->ev[1], s) == hipSuccess;
       ok = ok && hipMemcpyAsync (A->pin_out.p, base + off_outr, out_bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -1017,7 +1450,9 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
   } else {
     if (zero_bytes) memset (host_mem.data() + off_zero, 0, zero_bytes);
     run_parallel ((int)host_items.size(), threads, [&] (int j) { if (plans[host_items[j]].path == LH264_RESTORE_PATH_HOST) host_restore (items[host_items[j]]); });
-    run_parallel (nd, threads, [&] (int j) { restore_stream_host (jobs[j], *(const RestoreTables*) (host_mem.data() + off_tables)); });
+    run_parallel (nd, threads, [&] (int j) {
+      restore_stream_host (jobs[j], *(const RestoreTables*) (host_mem.data() + off_tables), any_cabac ? (const RestoreCabacTables*) (host_mem.data() + off_ctables) : nullptr);
+    });
   }
   t[2] = now_ms();
   // pass 2
@@ -1058,10 +1493,18 @@ int restore_batch (lh264_restore_item_t* items, int n, int threads, int32_t* pat
 
 extern "C" {
 int lh264_pip_restore_batch_device (lh264_restore_item_t* items, int n, int threads, int32_t* path_out) {
-  return restore_batch (items, n, threads, path_out, true);
+  const lh264_restore_opts_t o = {(uint32_t)sizeof (lh264_restore_opts_t), threads, 0u};
+  return restore_batch (items, n, &o, path_out, true);
+}
+int lh264_pip_restore_batch_device_opts (lh264_restore_item_t* items, int n, const lh264_restore_opts_t* opts, int32_t* path_out) {
+  return restore_batch (items, n, opts, path_out, true);
 }
 int lh264_debug_restore_cpu (lh264_restore_item_t* items, int n, int threads, int32_t* path_out) {
-  return restore_batch (items, n, threads, path_out, false);
+  const lh264_restore_opts_t o = {(uint32_t)sizeof (lh264_restore_opts_t), threads, 0u};
+  return restore_batch (items, n, &o, path_out, false);
+}
+int lh264_debug_restore_cpu_opts (lh264_restore_item_t* items, int n, const lh264_restore_opts_t* opts, int32_t* path_out) {
+  return restore_batch (items, n, opts, path_out, false);
 }
 int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t* out, int n) {
   if (!words || !bits || !out || n < 0) return LH264_E_ARG;

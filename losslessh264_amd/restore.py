@@ -90,28 +90,33 @@ def _restore_items(items, out_cap):
     return arr, keep
 
 
-def _restore_batch_paths(fn, items, threads, out_cap, statuses):
+def _restore_batch_paths(name, items, threads, out_cap, statuses, cabac_device):
+    """name: the C call without options, taken when no option is asked for; name + "_opts" otherwise"""
     arr, keep = _restore_items(items, out_cap)
     paths = (C.c_int32 * max(1, len(items)))()
-    L.check(fn(C.byref(arr), len(items), threads, paths))
+    if cabac_device:
+        opts = L.RestoreOpts(C.sizeof(L.RestoreOpts), threads, L.RESTORE_CABAC_DEVICE)
+        L.check(getattr(L.lib(), name + "_opts")(C.byref(arr), len(items), C.byref(opts), paths))
+    else:
+        L.check(getattr(L.lib(), name)(C.byref(arr), len(items), threads, paths))
     outs = [keep[i][2].raw[:arr[i].out_len] if arr[i].status == 0 else None for i in range(len(items))]
     if statuses:
         return outs, [paths[i] for i in range(len(items))], [(arr[i].status, arr[i].out_len) for i in range(len(items))]
     return outs, [paths[i] for i in range(len(items))]
 
 
-def restore_batch_device(items, threads=0, out_cap=None, statuses=False):
+def restore_batch_device(items, threads=0, out_cap=None, statuses=False, cabac_device=False):
     """restore_batch on the current device (C ABI lh264_pip_restore_batch_device): CAVLC streams are decoded and written by the
-    kernel, streams with CABAC slices by the host restore beside it.  Returns (outs, paths): outs as restore_batch gives them, paths[i]
-    one of PATH_DEVICE / PATH_HOST / PATH_FALLBACK.  statuses=True adds a third list of (status, out_len) per item.  Raises without a
-    device."""
-    return _restore_batch_paths(L.lib().lh264_pip_restore_batch_device, items, threads, out_cap, statuses)
+    kernel, streams with CABAC slices by the host restore beside it - or, with cabac_device=True (lh264_pip_restore_batch_device_opts
+    with LH264_RESTORE_CABAC_DEVICE), by the kernel too.  Returns (outs, paths): outs as restore_batch gives them, paths[i] one of
+    PATH_DEVICE / PATH_HOST / PATH_FALLBACK.  statuses=True adds a third list of (status, out_len) per item.  Raises without a device."""
+    return _restore_batch_paths("lh264_pip_restore_batch_device", items, threads, out_cap, statuses, cabac_device)
 
 
-def restore_batch_cpu_check(items, threads=0, out_cap=None, statuses=False):
-    """the kernel's code stepped on the host (lh264_debug_restore_cpu): the same plan and results as restore_batch_device, for checking
-    the device chain without a device"""
-    return _restore_batch_paths(L.lib().lh264_debug_restore_cpu, items, threads, out_cap, statuses)
+def restore_batch_cpu_check(items, threads=0, out_cap=None, statuses=False, cabac_device=False):
+    """the kernel's code stepped on the host (lh264_debug_restore_cpu, lh264_debug_restore_cpu_opts): the same plan and results as
+    restore_batch_device, for checking the device chain without a device"""
+    return _restore_batch_paths("lh264_debug_restore_cpu", items, threads, out_cap, statuses, cabac_device)
 
 
 def dp_update_device(words, bits):
