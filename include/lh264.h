@@ -405,6 +405,11 @@ const char*          lh264_parser_error (const lh264_parser_t* p);
 /* "" or why lh264_compress_batch refuses the stream although it parses: the first syntax value met so far that the container's prior
  * tables cannot carry ("mb_skip_run 687 is outside the container's range 0..511"); such a stream is stored verbatim */
 const char*          lh264_parser_out_of_range (const lh264_parser_t* p);
+/* what carries those values all the same: the escape stream of the pictures parsed so far (stream LH264_TAG_ESC of the container, see
+ * lh264_pip_restore for the format), runs still open closed; *len = 0 when no value was out of range, and also when one was that the
+ * escape stream cannot carry (17 or more active references, a value of another table): such a stream stays refused.  A finished copy at any time -
+ * lh264_parser_drop_frames does not touch it -, valid until the next call for this parser */
+const uint8_t*       lh264_parser_escapes (const lh264_parser_t* p, size_t* len);
 
 /* ---- restore direction, host side ------------------------------------------------------------
  * The inverse of compress: the default stream (".pip") plus the tagged arithmetic-coded streams (".pip.<tag>") -> the
@@ -414,8 +419,19 @@ const char*          lh264_parser_out_of_range (const lh264_parser_t* p);
  * I_PCM macroblocks: the reference's representation does not carry their samples (its own restore aborts on them); ours adds one
  * stream, tags[LH264_TAG_PCM] = the 384 samples of every I_PCM macroblock in decoding order, stored as they are.  With it streams
  * with I_PCM macroblocks restore (CAVLC: 7.3.5; CABAC: the engine is flushed before the samples and restarted behind them,
- * 9.3.1.2); without it the call gives LH264_E_UNSUPPORTED (lh264_restore_error: the text). */
+ * 9.3.1.2); without it the call gives LH264_E_UNSUPPORTED (lh264_restore_error: the text).
+ * Values above a prior table's tree: an mb_skip_run above 511 (SKIPRUN is a 9-bit tree) and num_ref_idx_l0_active 16 (NUMREF is a
+ * 4-bit tree) are coded modulo the tree, as the reference codes them; tags[LH264_TAG_ESC] carries what the tree drops.  It is a
+ * sequence of entries of four unsigned LEB128 varints {table, gap, high, repeat}: table is LH264_TB_SKIPRUN or LH264_TB_NUMREF; gap
+ * counts the tree symbols of that table, in coding order, between the end of the table's previous entry (or the stream's start) and
+ * the entry's first symbol (every SKIPRUN / NUMREF symbol counts: CABAC slices and I slices have one SKIPRUN per macroblock); high >= 1
+ * is the value >> the tree's bits; repeat >= 1 is how many consecutive symbols of the table carry this high.  Entries of one table
+ * are in order, those of the two tables interleave as their runs close; the runs open at the end are closed SKIPRUN first.  A stream
+ * without such a value has no such tag.  The tag is honoured whenever it is present, by this call and by the device restore alike; a
+ * malformed one (unknown table, high or repeat 0, a truncated varint or one wider than 64 bits, a restored num_ref_idx above 16, entries
+ * left over at the end of the default stream) is LH264_E_UNSUPPORTED with a text, never other bytes. */
 #define LH264_TAG_PCM 70
+#define LH264_TAG_ESC 71
 int lh264_pip_restore (const uint8_t* main_stream, size_t main_len, const uint8_t* const* tags, const size_t* tag_len, int n_tags,
                        uint8_t* out, size_t out_cap, size_t* out_len);
 const char* lh264_restore_error (void);       /* message of the calling thread's last failed lh264_pip_restore */
@@ -452,7 +468,13 @@ int lh264_compress_batch_devices (const uint8_t* const* data, const size_t* len,
  * over one of the coder's per-call limits (status 8: 2^27 decisions in all tags of the stream together) is sent again with half the
  * pictures - a whole stream that is over them becomes a long one -, and segments are cut by an estimate of their decisions first, so
  * that this is rare; status 8 reaches the caller only for a single picture.  A long stream that fails in any segment has the error as
- * its result and no tags.  The bytes do not depend on where the cuts fall.  A struct_bytes this library does not know: LH264_E_ARG. */
+ * its result and no tags.  The bytes do not depend on where the cuts fall.  A struct_bytes this library does not know: LH264_E_ARG.
+ * `reserved` is the flags word (the field keeps the name it was declared with; 0 as callers have always passed it = no flag):
+ * LH264_COMPRESS_ESCAPES - a stream that lh264_parser_out_of_range names, and nothing else stands against, is compressed and
+ * gets the escape stream lh264_parser_escapes as tag LH264_TAG_ESC (every other tag and the default stream are what they are without
+ * the flag's guard: the reference's own files); without the flag it is refused as ever.  Streams inside the range are not touched by
+ * the flag.  An unknown flag: LH264_E_ARG. */
+#define LH264_COMPRESS_ESCAPES 1u
 typedef struct lh264_compress_opts { uint32_t struct_bytes; uint32_t reserved; uint64_t segment_mbs; } lh264_compress_opts_t;
 int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_compress_opts_t* opts, lh264_compressed_t** out);
 int lh264_compress_batch_devices_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,

@@ -10,6 +10,9 @@
     python -m losslessh264_amd --segment-mbs N in.264 out.pip   compress through lh264_compress_batch_opts: a stream of more than N
                                                             macroblocks is coded in segments of whole pictures (a stream of any
                                                             length: memory follows the segment, the bytes are the same)
+    python -m losslessh264_amd --escapes ...                (first) a stream with an mb_skip_run above 511 or 16 active references is
+                                                            compressed with the escape stream, tag 71, beside it (out.pip.71, or in
+                                                            the container) instead of being refused or stored verbatim
     python -m losslessh264_amd --decode [--nv12] out_dir in.264...   decode through ONE lh264_decode_batch call: out_dir/<name>.yuv holds
                                                             the cropped pictures as I420 (or NV12), appended by a sink run by run
 
@@ -23,13 +26,13 @@ import sys
 import numpy as np
 
 
-def compress_single(src, dst):
+def compress_single(src, dst, escapes=False):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
     blob = None
     why = ""
     try:
-        frames, err, main, pcm = lh.parse_file(data, pcm=True)
+        frames, err, main, pcm, esc = lh.parse_file(data, pcm=True, escapes=True)
         if err:
             why = err
         elif frames:
@@ -41,6 +44,8 @@ def compress_single(src, dst):
             tags = coder.tags(0)
             if pcm:
                 tags[70] = pcm          # LH264_TAG_PCM: the samples of the I_PCM macroblocks travel as they are
+            if escapes and esc:
+                tags[71] = esc          # LH264_TAG_ESC (--escapes): what the SKIPRUN / NUMREF trees drop of a value above their range
             if lh.restore(main, tags) == data:
                 blob = lh.pack(main, tags)
             else:
@@ -65,10 +70,10 @@ def restore_single(src, dst):
     print("%s -> %s: %d bytes" % (src, dst, len(out)))
 
 
-def compress_segmented(src, dst, segment_mbs):
+def compress_segmented(src, dst, segment_mbs, escapes=False):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
-    b = lh.compress_batch_handles([data], segment_mbs=segment_mbs)
+    b = lh.compress_batch_handles([data], segment_mbs=segment_mbs, escapes=escapes)
     main, tags, err = b.result(0)
     segs = b.segments(0)
     b.free()
@@ -83,10 +88,10 @@ def compress_segmented(src, dst, segment_mbs):
     print("%s: %d bytes -> %d bytes (%.4f), %d segments" % (src, len(data), total, total / max(1, len(data)), segs))
 
 
-def compress(src, dst, yuv=None):
+def compress(src, dst, yuv=None, escapes=False):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
-    frames, err, main, pcm = lh.parse_file(data, pcm=True)
+    frames, err, main, pcm, esc = lh.parse_file(data, pcm=True, escapes=True)
     if err:
         raise SystemExit("cannot compress %s: %s" % (src, err))
     ctx = lh.CtxSession([frames])
@@ -97,6 +102,8 @@ def compress(src, dst, yuv=None):
     tags = coder.tags(0)
     if pcm:
         tags[70] = pcm                  # LH264_TAG_PCM (the reference writes no such file: its own restore fails on I_PCM streams)
+    if escapes and esc:
+        tags[71] = esc                  # LH264_TAG_ESC
     with open(dst, "wb") as f:
         f.write(main)
     for t, b in tags.items():
@@ -146,10 +153,13 @@ def decode(argv):
 
 
 def main(argv):
+    escapes = len(argv) >= 2 and argv[1] == "--escapes"
+    if escapes:
+        argv = argv[:1] + argv[2:]
     if len(argv) >= 4 and argv[1] == "--decode":
         return decode(argv[2:])
     if len(argv) >= 5 and argv[1] == "--segment-mbs":
-        compress_segmented(argv[3], argv[4], int(argv[2]))
+        compress_segmented(argv[3], argv[4], int(argv[2]), escapes)
         return 0
     if len(argv) < 3:
         print(__doc__)
@@ -157,11 +167,11 @@ def main(argv):
     if argv[1].endswith(".lhp"):
         restore_single(argv[1], argv[2])
     elif argv[2].endswith(".lhp"):
-        compress_single(argv[1], argv[2])
+        compress_single(argv[1], argv[2], escapes)
     elif ".pip" in os.path.basename(argv[1]):      # as the reference decides (h264dec.cpp:167-173)
         restore(argv[1], argv[2])
     else:
-        compress(argv[1], argv[2], argv[3] if len(argv) > 3 else None)
+        compress(argv[1], argv[2], argv[3] if len(argv) > 3 else None, escapes)
     return 0
 
 

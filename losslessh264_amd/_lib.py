@@ -97,6 +97,7 @@ _SIGS.update({
     "lh264_parser_frame_syn_offsets": (C.c_void_p, [C.c_void_p, C.c_int]),
     "lh264_parser_error": (C.c_char_p, [C.c_void_p]),
     "lh264_parser_out_of_range": (C.c_char_p, [C.c_void_p]),
+    "lh264_parser_escapes": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
 })
 CODE_JOB_DTYPE = np.dtype([("syn_syms", "<u8"), ("syn_off", "<u8"), ("ctx_syms", "<u8"), ("ctx_n_syms", "<u8"), ("n_mbs", "<i4"), ("reserved", "<i4"),
                            ("ctx_sym_off", "<u8"), ("ctx_sym_base", "<u8")])
@@ -115,8 +116,10 @@ _SIGS["lh264_parser_begin_file"] = (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t
 _SIGS["lh264_parser_feed_file_some"] = (C.c_int, [C.c_void_p, C.c_uint64])
 _SIGS["lh264_parser_drop_frames"] = (C.c_int, [C.c_void_p, C.c_int])
 _SIGS["lh264_code_last_decisions"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p])
-class CompressOpts(C.Structure):
-    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("segment_mbs", C.c_uint64)]
+COMPRESS_ESCAPES = 1
+TAG_ESC = 71
+class CompressOpts(C.Structure):       # flags: the word include/lh264.h declares as `reserved`
+    _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("segment_mbs", C.c_uint64)]
 _SIGS["lh264_compress_batch_opts"] = (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(CompressOpts), C.POINTER(C.c_void_p)])
 _SIGS["lh264_compress_batch_devices_opts"] = (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(CompressOpts), C.POINTER(C.c_void_p)])
 _SIGS["lh264_compressed_segments"] = (C.c_int, [C.c_void_p])

@@ -8,6 +8,8 @@
 //                                       stream the round trip cannot carry is stored verbatim
 //   lh264dec in.lhp out.264             restore from the container
 //   lh264dec --segment-mbs N ...               (first) streams of more than N macroblocks are coded in segments of whole pictures
+//   lh264dec --escapes ...                     (first) a stream with an mb_skip_run above 511 or 16 active references is compressed with
+//                                       the escape stream beside it (out.pip.71, or in the container) and not refused / stored verbatim
 //   lh264dec --batch out_dir a.264 b.264 ...   many streams in one lh264_compress_batch call -> out_dir/<name>.lhp
 //   lh264dec --decode [--nv12] out_dir a.264 b.264 ...   many streams in one lh264_decode_batch call -> out_dir/<name>.yuv: the
 //                                       cropped pictures as I420 (or NV12), appended by a sink run by run (the file's size bounds nothing)
@@ -87,6 +89,7 @@ static int dump_yuv (const Bytes& bs, const std::string& path) {
 }
 
 // --segment-mbs N: streams of more macroblocks are coded in segments of at most N (whole pictures); 0: the library's default
+// --escapes: LH264_COMPRESS_ESCAPES
 static lh264_compress_opts_t g_opts = {sizeof (lh264_compress_opts_t), 0, 0};
 
 static int compress_files (const std::string& src, const std::string& dst, const char* yuv) {
@@ -219,7 +222,11 @@ static int restore_single (const std::string& src, const std::string& dst) {
 }
 
 int main (int argc, char** argv) {
-  if (argc >= 3 && !strcmp (argv[1], "--segment-mbs")) { g_opts.segment_mbs = strtoull (argv[2], nullptr, 10); argv[2] = argv[0]; argv += 2; argc -= 2; }
+  for (;;) {                                    // the options that go first, in any order
+    if (argc >= 3 && !strcmp (argv[1], "--segment-mbs")) { g_opts.segment_mbs = strtoull (argv[2], nullptr, 10); argv[2] = argv[0]; argv += 2; argc -= 2; }
+    else if (argc >= 2 && !strcmp (argv[1], "--escapes")) { g_opts.reserved |= LH264_COMPRESS_ESCAPES; argv[1] = argv[0]; argv += 1; argc -= 1; }
+    else break;
+  }
   if (argc >= 4 && !strcmp (argv[1], "--batch")) {
     std::vector<std::string> srcs, dsts;
     for (int i = 3; i < argc; i++) { srcs.push_back (argv[i]); dsts.push_back (std::string (argv[2]) + "/" + base_name (argv[i]) + ".lhp"); }
@@ -234,7 +241,7 @@ int main (int argc, char** argv) {
     return decode_files (argv[first], srcs, nv12);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

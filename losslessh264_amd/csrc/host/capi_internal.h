@@ -6,7 +6,7 @@
 #include <thread>
 #include <vector>
 #include "h264_parser.h"
-struct lh264_parser { lh264host::Parser p; };
+struct lh264_parser { lh264host::Parser p; mutable std::vector<uint8_t> escapes; };      // escapes: what lh264_parser_escapes handed out last
 static inline lh264host::Parser* lh264_parser_impl (lh264_parser* h) { return h ? &h->p : nullptr; }
 
 // n independent pieces of work on `threads` host threads (0 = one per hardware thread)

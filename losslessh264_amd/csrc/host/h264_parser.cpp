@@ -1716,6 +1716,8 @@ int Parser::parse_headers (const uint8_t* nal, size_t len, HeaderInfo& o) {
 }
 const std::vector<uint8_t>& Parser::last_rbsp() const { return d_->rbsp; }
 const std::string& Parser::out_of_range() const { return d_->symbolizer.out_of_range(); }
+std::vector<uint8_t> Parser::escapes() const { return d_->symbolizer.escapes(); }
+bool Parser::escapes_carry_all() const { return d_->symbolizer.escapes_carry_all(); }
 void Parser::unescape (const uint8_t* d, size_t n, std::vector<uint8_t>& out) { Impl::unescape (d, n, out); }
 
 // ---- the recompressor's default stream ---------------------------------------------------------------------------

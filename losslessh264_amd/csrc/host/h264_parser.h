@@ -286,6 +286,11 @@ class Parser {
   // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
   // carry (Symbolizer::out_of_range: an mb_skip_run above 511, 16 active references).  Not an error of the stream: it parses and decodes
   const std::string& out_of_range() const;
+  // what puts the dropped part of those values back (stream LH264_TAG_ESC of the container, Symbolizer::escapes: a finished copy, for
+  // the pictures parsed so far; empty when nothing was out of range - or when it would not restore the stream), and whether it covers every
+  // value out_of_range() stands for (not a value of another table, nor more than 16 references, which no restorer accepts)
+  std::vector<uint8_t> escapes() const;
+  bool escapes_carry_all() const;
 
  private:
   struct Impl;

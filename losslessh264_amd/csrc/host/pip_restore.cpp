@@ -284,16 +284,28 @@ class Restorer : public Walker {
  public:
   Restorer (const uint8_t* const* tags, const size_t* tag_len, int n_tags, std::string& err) : Walker (err) {
     if (n_tags > LH264_TAG_PCM && tags[LH264_TAG_PCM]) { pcm_ = tags[LH264_TAG_PCM]; pcm_end_ = pcm_ + tag_len[LH264_TAG_PCM]; }
-    for (int t = 0; t < N_TAGS && t < n_tags; t++) if (t != LH264_TAG_PCM && tags[t]) { rd_[t].p = tags[t]; rd_[t].end = tags[t] + tag_len[t]; rd_[t].present = true; rd_[t].fill(); }
+    if (n_tags > LH264_TAG_ESC && tags[LH264_TAG_ESC]) {
+      std::string why;
+      if (pip_restore_describe_escapes (tags[LH264_TAG_ESC], tag_len[LH264_TAG_ESC], esc_, why) < 0) fail (why);
+      for (int t = 0; t < 2; t++) lh264r::escape_load (esc_cur_[t], esc_[t].data(), (uint32_t)esc_[t].size());
+    }
+    for (int t = 0; t < N_TAGS && t < n_tags; t++) if (t != LH264_TAG_PCM && t != LH264_TAG_ESC && tags[t]) { rd_[t].p = tags[t]; rd_[t].end = tags[t] + tag_len[t]; rd_[t].present = true; rd_[t].fill(); }
     build_vlc();
   }
   int run (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
-    return walk (d, n, out, [this] (const Parser::HeaderInfo& H) { return decode_slice (H); });
+    if (failed_) return -1;
+    if (walk (d, n, out, [this] (const Parser::HeaderInfo& H) { return decode_slice (H); }) < 0) return -1;
+    if (esc_cur_[0].rep || esc_cur_[1].rep) { fail ("the escape stream (LH264_TAG_ESC) has entries beyond the default stream's last symbol"); return -1; }
+    return 0;
   }
 
  private:
   BoolReader rd_[N_TAGS];
   const uint8_t* pcm_ = nullptr; const uint8_t* pcm_end_ = nullptr;     // samples of the I_PCM macroblocks still to be written
+  std::vector<lh264r::RestoreEscape> esc_[2];                            // stream LH264_TAG_ESC by table, and where each table stands in it
+  lh264r::EscapeCursor esc_cur_[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  // the part of the symbol just read that its tree drops: 0 without the tag (esc: 0 SKIPRUN, 1 NUMREF)
+  uint32_t escape (int esc) { return esc_cur_[esc].rep ? lh264r::escape_next (esc_cur_[esc], esc_[esc].data(), (uint32_t)esc_[esc].size()) : 0u; }
   DynProb test_prob_;                 // ArithmeticCodedInput::TEST_PROB: one adaptive probability shared by the raw bits of all tags
   PriorStore store_;
   // model state (as csrc/host/pip_symbols.cpp keeps it on the compress side)
@@ -1020,7 +1032,11 @@ bool Restorer::decode_slice (const Parser::HeaderInfo& H) {
     const uint32_t stop_idx = (uint32_t) (mb_in_slice < 2048 ? mb_in_slice : 2047);
     if (skip_state == -1 || cabac) {                 // CABAC: a run of 0 or 1 for every macroblock (DS:2505-2516)
       const int pr = np ? np->cached_skips / 8 + (np->cached_skips % 8 ? 1 : 0) : 0;
-      const int run = (int)tree (TAG_SKIP, LH264_TB_SKIPRUN, (uint32_t) (pr * 16 + 11));
+      int run = (int)tree (TAG_SKIP, LH264_TB_SKIPRUN, (uint32_t) (pr * 16 + 11));
+      if (const uint32_t high = escape (0)) {
+        if (high > lh264r::kEscapeHighMax) { fail ("corrupt escape stream: skip run beyond any picture"); return false; }
+        run |= (int) (high << kTreeBits[LH264_TB_SKIPRUN]);
+      }
       if (is_p && !cabac) skip_state = run; else mb_skip_run = run;
       if (cabac && run > 1) { fail ("corrupt skip flag"); return false; }
     }
@@ -1066,6 +1082,10 @@ bool Restorer::decode_slice (const Parser::HeaderInfo& H) {
       if (m.luma_qp > 51) { fail ("corrupt QP"); return false; }
     }
     m.num_ref = (int)tree (TAG_REF, LH264_TB_NUMREF, (uint32_t) ((np ? np->num_ref : 0) * 16 + mbc));
+    if (const uint32_t high = escape (1)) {
+      if (high > 1 || m.num_ref) { fail ("corrupt escape stream: more than 16 active references"); return false; }
+      m.num_ref = 16;
+    }
     int ref_bits = 0;
     while ((1 << ref_bits) < m.num_ref) ref_bits++;
     {
@@ -1272,6 +1292,35 @@ int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vect
     err = std::string ("internal: ") + e.what();
     return -1;
   }
+}
+
+int pip_restore_describe_escapes (const uint8_t* tag, size_t len, std::vector<lh264r::RestoreEscape> (&by_table)[2], std::string& err) {
+  err.clear(); by_table[0].clear(); by_table[1].clear();
+  size_t at = 0;
+  auto varint = [&] (uint64_t& v) {                  // unsigned LEB128, 64 bits at most
+    v = 0;
+    for (int shift = 0; at < len; shift += 7) {
+      const uint8_t b = tag[at++];
+      if (shift > 63 || (shift == 63 && (b & 0x7e))) return false;
+      v |= (uint64_t) (b & 127) << shift;
+      if (!(b & 128)) return true;
+    }
+    return false;
+  };
+  auto sat = [] (uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; };
+  try {
+    while (at < len) {
+      uint64_t f[4];
+      for (uint64_t& v : f) if (!varint (v)) { err = "corrupt escape stream (LH264_TAG_ESC): a truncated or too wide integer"; return -1; }
+      if (f[0] != LH264_TB_SKIPRUN && f[0] != LH264_TB_NUMREF) { err = "corrupt escape stream (LH264_TAG_ESC): unknown table " + std::to_string (f[0]); return -1; }
+      if (f[2] == 0 || f[3] == 0) { err = "corrupt escape stream (LH264_TAG_ESC): an entry with a high part or a repeat count of 0"; return -1; }
+      by_table[f[0] == LH264_TB_NUMREF ? 1 : 0].push_back (lh264r::RestoreEscape{sat (f[1]), sat (f[2]), sat (f[3])});
+    }
+  } catch (const std::exception& e) {
+    err = std::string ("internal: ") + e.what();
+    return -1;
+  }
+  return 0;
 }
 
 int pip_restore_splice (const uint8_t* main_stream, size_t main_len, const lh264r::RestoreSlice* slices, size_t n_slices, const uint8_t* bits,

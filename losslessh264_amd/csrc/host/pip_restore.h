@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-namespace lh264r { struct RestoreSlice; struct RestoreTables; struct RestoreCabacTables; }
+namespace lh264r { struct RestoreSlice; struct RestoreTables; struct RestoreCabacTables; struct RestoreEscape; }
 
 namespace lh264host {
 
@@ -33,6 +33,9 @@ int pip_restore (const uint8_t* main_stream, size_t main_len, const uint8_t* con
 // bits[slice_end[i-1] .. slice_end[i]).  Both return 0, or < 0 with a message in err.
 int pip_restore_describe (const uint8_t* main_stream, size_t main_len, std::vector<lh264r::RestoreSlice>& slices, bool& cabac, std::string& err,
                           bool keep_cabac = false);
+// pass 1 for stream LH264_TAG_ESC (include/lh264.h): its entries by table ([0] SKIPRUN, [1] NUMREF), in order; < 0 with a message for
+// a truncated or too wide varint, an unknown table, a high or repeat of 0.  The host restore reads the tag through the same call
+int pip_restore_describe_escapes (const uint8_t* tag, size_t len, std::vector<lh264r::RestoreEscape> (&by_table)[2], std::string& err);
 int pip_restore_splice (const uint8_t* main_stream, size_t main_len, const lh264r::RestoreSlice* slices, size_t n_slices, const uint8_t* bits,
                         const uint32_t* slice_end, std::vector<uint8_t>& out, std::string& err);
 // the CAVLC tables and prior sizes of the host restore, flattened for the kernel

@@ -1,6 +1,7 @@
 // pip_symbols.cpp - see pip_symbols.h.  Fresh implementation; line references are to the reference's
 // decoder/core/src/decode_slice.cpp (DS), decoder/core/src/macroblock_model.cpp (MM), decoder/core/inc/decoded_macroblock.h (DM).
 #include "pip_symbols.h"
+#include "../lh264_restore.h"
 #include <string.h>
 #include <string>
 
@@ -33,6 +34,8 @@ const char* table_name (int table) {
 struct Out {
   PoolVec<lh264_ctx_sym_t>& v;
   std::string& out_of_range;
+  EscapeLog& escapes;
+  bool& beyond_escapes;
   // a value its table's tree has no leaf for would be coded modulo 2^bits and restore as another stream: the stream is marked (the first
   // such value names the reason) and lh264_compress_batch refuses it
   void put (int kind, int table, uint32_t index, int value, int tag) {
@@ -40,6 +43,12 @@ struct Out {
       const int limit = (1 << kTreeBits[table]) - (kind == LH264_SYM_TREE ? 1 : 0);
       if ((value < 0 || value > limit) && out_of_range.empty())
         out_of_range = std::string (table_name (table)) + " " + std::to_string (value) + " is outside the container's range 0.." + std::to_string (limit);
+      // the two tables whose high part the escape stream carries; any other value out of range is lost whatever is added
+      // (both restorers refuse more than 16 references and a high part above kEscapeHighMax: such values are lost like the rest)
+      if (kind == LH264_SYM_TREE && (table == LH264_TB_SKIPRUN || table == LH264_TB_NUMREF) && value >= 0) {
+        escapes.symbol (table, (uint32_t)value);
+        if (table == LH264_TB_NUMREF ? value > 16 : (value >> kTreeBits[table]) > lh264r::kEscapeHighMax) beyond_escapes = true;
+      } else if (value < 0 || value > limit) beyond_escapes = true;
     }
     lh264_ctx_sym_t s; s.prior = LH264_PRIOR (table, index); s.value = (int16_t)value; s.kind = (uint8_t)kind; s.pad = (uint8_t)tag;
     v.push_back (s);
@@ -56,6 +65,29 @@ const uint8_t kCache30[16] = {7, 8, 13, 14, 9, 10, 15, 16, 19, 20, 25, 26, 21, 2
 const uint8_t kZ2Raster[16] = {0, 1, 4, 5, 2, 3, 6, 7, 8, 9, 12, 13, 10, 11, 14, 15};
 
 }  // namespace
+
+void EscapeLog::append (std::vector<uint8_t>& v, int table, const Run& r) {
+  const uint64_t f[4] = {(uint64_t)table, r.gap, r.high, r.repeat};
+  for (uint64_t x : f) {
+    while (x >= 128) { v.push_back ((uint8_t) (x | 128)); x >>= 7; }
+    v.push_back ((uint8_t)x);
+  }
+}
+void EscapeLog::symbol (int table, uint32_t value) {
+  const int t = table == LH264_TB_NUMREF ? 1 : 0;
+  const uint64_t high = value >> kTreeBits[table];
+  Run& r = open_[t];
+  if (r.repeat && high == r.high) { r.repeat++; return; }
+  if (r.repeat) { append (bytes_, table, r); r.repeat = 0; since_[t] = 0; }
+  if (high) { r.gap = since_[t]; r.high = high; r.repeat = 1; }
+  else since_[t]++;
+}
+std::vector<uint8_t> EscapeLog::finished() const {
+  std::vector<uint8_t> v = bytes_;
+  if (open_[0].repeat) append (v, LH264_TB_SKIPRUN, open_[0]);
+  if (open_[1].repeat) append (v, LH264_TB_NUMREF, open_[1]);
+  return v;
+}
 
 // FreqImage::updateFrame DM:119-166: the buffers flip when frame_num changes; then isSkipped / cachedSkips of the PREVIOUS
 // picture are recomputed from its coefficients (on every slice)
@@ -96,7 +128,7 @@ void Symbolizer::picture (FrameOut& f) {
     const int end = S.first_mb + S.n_mbs;
     int skip_state = -1, mb_in_slice = 0, cached_qp = 0, last_nonzero_dqp = 0;
     for (int k = S.first_mb; k < end && k < n; k++, mb_in_slice++) {
-      Out o = {flat, out_of_range_};
+      Out o = {flat, out_of_range_, escapes_, beyond_escapes_};
       start_[k] = (uint32_t)flat.size();
       struct Close { PoolVec<lh264_ctx_sym_t>& v; uint32_t& s; uint32_t& c; ~Close() { c = (uint32_t)v.size() - s; } } close_run = {flat, start_[k], cnt_[k]};
       const int x = k % w;
@@ -247,7 +279,7 @@ void Symbolizer::picture (FrameOut& f) {
     }
     // the alignment bits after the slice's stop bit go to the pad-byte tag, DS:3133-3148
     if (X.pad_bits && end - 1 < n && end - 1 >= S.first_mb && start_[end - 1] + cnt_[end - 1] == flat.size()) {
-      Out o = {flat, out_of_range_}; o.raw (X.pad_value, X.pad_bits, TAG_PADBYTE); cnt_[end - 1]++;
+      Out o = {flat, out_of_range_, escapes_, beyond_escapes_}; o.raw (X.pad_value, X.pad_bits, TAG_PADBYTE); cnt_[end - 1]++;
     }
   }
   f.syn_off.assign ((size_t)n + 1, 0);

@@ -18,6 +18,22 @@ namespace lh264host {
 // symbol (emitBitsZeroToPow2Inclusive<n>) 0 .. 2^n.  One table for the symbolizer's range guard and for both restorers
 constexpr int kTreeBits[LH264_TB_COUNT] = {4, 0, 3, 0, 0, 0, 0, 0, 0, 9, 7, 8, 4, 2, 4, 0, 0, 4};
 
+// The part of a SKIPRUN / NUMREF value its tree drops (value >> kTreeBits[table]), as stream LH264_TAG_ESC of the container carries it
+// (include/lh264.h: entries of four LEB128 varints: table, gap, high, repeat).  symbol() sees every tree symbol of the two tables in
+// coding order; a run of equal nonzero high parts is one entry
+class EscapeLog {
+ public:
+  void symbol (int table, uint32_t value);
+  // the stream so far, with the runs still open closed (SKIPRUN first, then NUMREF); empty: no value was out of range
+  std::vector<uint8_t> finished() const;
+ private:
+  struct Run { uint64_t gap = 0, high = 0, repeat = 0; };   // repeat 0: none open
+  std::vector<uint8_t> bytes_;
+  Run open_[2];
+  uint64_t since_[2] = {0, 0};          // symbols of the table behind its last entry
+  static void append (std::vector<uint8_t>& v, int table, const Run& r);
+};
+
 class Symbolizer {
  public:
   // appends the picture's symbols to f.syn_syms / f.syn_off (pictures of one stream, in decode order)
@@ -25,9 +41,16 @@ class Symbolizer {
   // empty, or the first value met that its prior table cannot carry ("mb_skip_run 687 is outside the container's range 0..511"): the
   // symbols of such a stream do not restore it
   const std::string& out_of_range() const { return out_of_range_; }
+  // whether the escape stream carries EVERY value that was out of range - a stream for which it does restores from its symbols plus
+  // that stream; not so a value of another table, more than 16 references, a run beyond any picture -, and the escape stream of the
+  // pictures so far (EscapeLog::finished); empty when it would not restore the stream
+  std::vector<uint8_t> escapes() const { return beyond_escapes_ ? std::vector<uint8_t>() : escapes_.finished(); }
+  bool escapes_carry_all() const { return !beyond_escapes_; }
 
  private:
   std::string out_of_range_;
+  EscapeLog escapes_;
+  bool beyond_escapes_ = false;
   struct Cell {                       // what the model remembers of a macroblock (DecodedMacroblock, decoded_macroblock.h:4-34)
     uint8_t initialized = 0, zeroed = 0, cbp_c = 0, cbp_l = 0, chroma_mode = 0, luma16_mode = 0;
     uint16_t cached_skips = 0;

@@ -725,6 +725,12 @@ const uint8_t* lh264_parser_pcm_samples (const lh264_parser_t* p, size_t* len) {
   if (len) *len = p->p.pcm_samples().size();
   return p->p.pcm_samples().data();
 }
+const uint8_t* lh264_parser_escapes (const lh264_parser_t* p, size_t* len) {
+  if (!p) { if (len) *len = 0; return nullptr; }
+  p->escapes = p->p.escapes();
+  if (len) *len = p->escapes.size();
+  return p->escapes.data();
+}
 int lh264_parser_frame_count (const lh264_parser_t* p) { return p ? (int)const_cast<lh264_parser_t*> (p)->p.frames().size() : 0; }
 static const lh264host::FrameOut* pf (const lh264_parser_t* p, int idx) {
   if (!p) return nullptr;

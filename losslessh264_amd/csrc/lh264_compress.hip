@@ -388,7 +388,8 @@ int lh264_compress_batch (const uint8_t* const* data, const size_t* len, int n, 
 }
 int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_compress_opts_t* opts, lh264_compressed_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && opts->struct_bytes != sizeof (lh264_compress_opts_t)) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~LH264_COMPRESS_ESCAPES))) return LH264_E_ARG;
+  const bool escapes = opts && (opts->reserved & LH264_COMPRESS_ESCAPES);      // `reserved`: the flags word
   for (int i = 0; i < n; i++) out[i] = new lh264_compressed();
   if (lh264_device_count() <= 0) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_NODEVICE; out[i]->error = "no HIP device visible"; } return LH264_E_NODEVICE; }
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
@@ -437,7 +438,7 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
     for (auto& f : fr) symbols = symbols && f->syn_off.size() == (size_t)f->mb_w * f->mb_h + 1 && (f->syn_off.back() == f->syn_syms.size());
     if (!P.error().empty()) why = P.error();
     else if (!symbols) why = "a picture with an incomplete slice";
-    else if (!P.out_of_range().empty()) why = P.out_of_range() + " (the stream would not restore)";
+    else if (!P.out_of_range().empty() && !(escapes && P.escapes_carry_all())) why = P.out_of_range() + " (the stream would not restore)";
     else if (P.damaged()) why = "a picture with macroblocks no slice covers: the reference conceals them, which is not modelled (the stream would not restore)";
     return !why.empty();
   };
@@ -503,6 +504,7 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
         lh264_compressed_t& r = *out[ls.i];
         r.main_stream = P.main_stream();
         if (!P.pcm_samples().empty()) { r.tag[LH264_TAG_PCM] = P.pcm_samples(); r.has_tag[LH264_TAG_PCM] = true; }
+        if (escapes && !P.out_of_range().empty()) { r.tag[LH264_TAG_ESC] = P.escapes(); r.has_tag[LH264_TAG_ESC] = true; }
         ls.ended = true;
       }
       group.push_back (std::move (part));
@@ -553,11 +555,14 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
         continue;
       }
       r.main_stream = P.main_stream();
-      if (!P.pcm_samples().empty()) { r.tag[LH264_TAG_PCM] = P.pcm_samples(); r.has_tag[LH264_TAG_PCM] = true; }
       r.pictures = (int)P.frames().size();
       const size_t mbs = P.held_mbs();
       std::string why;
       if (refuse (i, P.frames(), why)) { r.status = LH264_E_UNSUPPORTED; r.error = why; }
+      else {                                            // the streams of the container the coder does not write
+        if (!P.pcm_samples().empty()) { r.tag[LH264_TAG_PCM] = P.pcm_samples(); r.has_tag[LH264_TAG_PCM] = true; }
+        if (escapes && !P.out_of_range().empty()) { r.tag[LH264_TAG_ESC] = P.escapes(); r.has_tag[LH264_TAG_ESC] = true; }
+      }
       if (r.status != LH264_OK || mbs == 0) { parsers[i].reset(); continue; }
       if (in_group && in_group + mbs > kBudget) { launch (group); in_group = 0; }
       Part part; part.i = i; part.frames = std::move (P.frames());
@@ -588,7 +593,7 @@ int lh264_compress_batch_devices (const uint8_t* const* data, const size_t* len,
 }
 int lh264_compress_batch_devices_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,
                                        const lh264_compress_opts_t* opts, lh264_compressed_t** out) {
-  if (opts && opts->struct_bytes != sizeof (lh264_compress_opts_t)) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~LH264_COMPRESS_ESCAPES))) return LH264_E_ARG;
   if (!data || !len || !out || n < 0 || !devices || n_devices < 1) return LH264_E_ARG;
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   size_t total = 0;

@@ -3,6 +3,12 @@
 #pragma once
 #include <stdint.h>
 
+#ifdef __HIPCC__
+#define LH264R_HD __host__ __device__
+#else
+#define LH264R_HD
+#endif
+
 namespace lh264r {
 
 // what the model and the writers read of a slice header (Parser::HeaderInfo), in stream order
@@ -45,6 +51,25 @@ struct RestoreCabacTables {
 };
 static_assert (sizeof (RestoreCabacEnc) % 4 == 0 && sizeof (RestoreCabacTables) % 4 == 0, "the CABAC tables are copied by words");
 
+// The escape stream (include/lh264.h LH264_TAG_ESC) as pass 1 hands it to both restorers: the entries of each table in order, fixed
+// width (a varint above 32 bits saturates: no stream has that many symbols).  And the state of one table while the symbols are read:
+// `gap` symbols to go until the entry applies, then `rep` symbols that get `high`; rep 0: the table has no entry left.  cur: the
+// next entry to load.  One step per SKIPRUN / NUMREF tree symbol, the same code in the host restore and in the kernel's chain
+struct RestoreEscape { uint32_t gap, high, repeat; };
+struct EscapeCursor { uint32_t gap, rep, high, cur; };
+LH264R_HD inline void escape_load (EscapeCursor& c, const RestoreEscape* e, uint32_t n) {
+  if (c.cur < n) { c.gap = e[c.cur].gap; c.high = e[c.cur].high; c.rep = e[c.cur].repeat; c.cur++; }
+  else c.rep = 0;
+}
+LH264R_HD inline uint32_t escape_next (EscapeCursor& c, const RestoreEscape* e, uint32_t n) {      // the symbol's high part; c.rep != 0
+  if (c.gap) { c.gap--; return 0; }
+  const uint32_t h = c.high;
+  if (--c.rep == 0) escape_load (c, e, n);
+  return h;
+}
+// a restored value must fit an int: high parts above this are corrupt whatever the table
+enum { kEscapeHighMax = 0x3fffff };
+
 // status of one stream after the kernel; anything but RS_OK sends the stream to the host restore (LH264_RESTORE_PATH_FALLBACK)
 enum { RS_OK = 0, RS_CORRUPT = 1, RS_STORE_FULL = 2, RS_OUT_FULL = 3 };
 
@@ -55,6 +80,9 @@ struct RestoreJob {
   uint32_t tag_present[3];             // bit t: tags[t] exists (tag LH264_TAG_PCM: the I_PCM samples)
   uint32_t n_slices, n_max;            // slices; the largest picture in macroblocks
   const RestoreSlice* slices;
+  const RestoreEscape* esc[2];         // tag LH264_TAG_ESC by table: [0] SKIPRUN, [1] NUMREF (staged behind the tags)
+  uint32_t n_esc[2];
+  uint32_t esc_bad, pad;               // the tag is malformed: the stream ends with RS_CORRUPT and the host restore names the reason
   uint8_t* cells;                      // 2 x n_max Cell
   uint8_t* ws;                         // n_max WState (the kernel instance with the CABAC writer: its longer WState)
   int8_t* ipm;                         // n_max x 8

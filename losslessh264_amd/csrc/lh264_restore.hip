@@ -99,6 +99,7 @@ struct Shared {
   uint8_t zero[24];                     // the nnz of an absent neighbour
   uint32_t test_prob;
   int32_t status;
+  EscapeCursor esc[2];                  // where the stream stands in its escape entries: [0] SKIPRUN, [1] NUMREF
 };
 // and what the instance with the CABAC writer keeps there beside it
 struct CabacShared {
@@ -265,6 +266,8 @@ template <bool kCabac> struct Chain : EncState<kCabac> {
     return neg ? -v : v;
   }
   LH_HD unsigned tree (int tag, int table, uint32_t index) { return scan_tree (tag, T.tree_bits[table], get (table, index)); }
+  // the part of the SKIPRUN (esc 0) / NUMREF (esc 1) symbol just read that its tree drops; 0 for a stream without tag LH264_TAG_ESC
+  LH_HD uint32_t escape (int esc) { EscapeCursor& c = S.esc[esc]; return c.rep ? escape_next (c, J.esc[esc], J.n_esc[esc]) : 0u; }
 
   LH_HD void decode_coeffs (MbDec& m, int st, int mbc, const Cell* nl, const Cell* na, const Cell* np, Cell& e);
   LH_HD int pred_intra_mode (int k, int bx, int by, int w, int sid, bool cip) const;
@@ -904,7 +907,11 @@ template <bool kCabac> LH_HD void Chain<kCabac>::decode_slice (const RestoreSlic
     const uint32_t stop_idx = (uint32_t) (mb_in_slice < 2048 ? mb_in_slice : 2047);
     if (skip_state == -1 || cabac) {                    // CABAC: a run of 0 or 1 for every macroblock
       const int pr = np ? np->cached_skips / 8 + (np->cached_skips % 8 ? 1 : 0) : 0;
-      const int run = (int)tree (TAG_SKIP, LH264_TB_SKIPRUN, (uint32_t) (pr * 16 + 11));
+      int run = (int)tree (TAG_SKIP, LH264_TB_SKIPRUN, (uint32_t) (pr * 16 + 11));
+      if (const uint32_t high = escape (0)) {
+        if (high > kEscapeHighMax) { fail (RS_CORRUPT); return; }
+        run |= (int) (high << T.tree_bits[LH264_TB_SKIPRUN]);
+      }
       if (is_p && !cabac) skip_state = run; else mb_skip_run = run;
       if (cabac && run > 1) { fail (RS_CORRUPT); return; }
     }
@@ -955,6 +962,10 @@ template <bool kCabac> LH_HD void Chain<kCabac>::decode_slice (const RestoreSlic
       if (m.luma_qp > 51) { fail (RS_CORRUPT); return; }
     }
     m.num_ref = (int)tree (TAG_REF, LH264_TB_NUMREF, (uint32_t) ((np ? np->num_ref : 0) * 16 + mbc));
+    if (const uint32_t high = escape (1)) {
+      if (high > 1 || m.num_ref) { fail (RS_CORRUPT); return; }
+      m.num_ref = 16;
+    }
     int ref_bits = 0;
     while (ref_bits < 31 && (1 << ref_bits) < m.num_ref) ref_bits++;
     {
@@ -1107,13 +1118,15 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
     S.status = RS_OK;
     S.test_prob = DP_INIT;
     for (int i = 0; i < 24; i++) S.zero[i] = 0;
+    for (int t = 0; t < 2; t++) { S.esc[t] = EscapeCursor{0, 0, 0, 0}; escape_load (S.esc[t], J.esc[t], J.n_esc[t]); }
+    if (J.esc_bad) S.status = RS_CORRUPT;
   }
   if (lane < N_TAGS) {
     for (int t = lane; t < N_TAGS; t += nl) {
       Reader& r = S.rd[t];
       r.p = J.tags + J.tag_off[t]; r.end = r.p + J.tag_len[t];
       r.value = 0; r.count = -8; r.range = 255; r.pad = 0;
-      r.present = t != LH264_TAG_PCM && ((J.tag_present[t >> 5] >> (t & 31)) & 1u);
+      r.present = t != LH264_TAG_PCM && t != LH264_TAG_ESC && ((J.tag_present[t >> 5] >> (t & 31)) & 1u);
       if (r.present) rd_fill (r);
     }
   }
@@ -1184,6 +1197,8 @@ LH_HD void restore_stream (const RestoreJob& J, const RestoreTables& Tg, Shared&
     }
     RBAR();
   }
+  // entries beyond the last symbol: the tag belongs to another stream
+  if (lane == 0 && (S.esc[0].rep | S.esc[1].rep)) c.fail (RS_CORRUPT);
   if (lane == 0) { J.status[0] = S.status; J.status[1] = (int32_t)c.used; J.status[2] = (int32_t)c.pool_used; J.status[3] = (int32_t)c.pos; }
 }
 
@@ -1251,6 +1266,9 @@ struct Plan {
   int path = LH264_RESTORE_PATH_FALLBACK;
   bool cabac = false;                                   // a slice of the stream is a CABAC slice
   std::vector<RestoreSlice> slices;
+  std::vector<RestoreEscape> esc[2];                    // tag LH264_TAG_ESC by table; esc_bad: it is malformed
+  bool esc_bad = false;
+  size_t off_esc = 0;
   size_t tag_bytes = 0;
   uint32_t n_max = 0, slots = 0, pool_cap = 0, out_cap = 0;
   size_t off_slices = 0, off_tags = 0, off_hash = 0, off_work = 0, off_status = 0, off_end = 0, off_out = 0;
@@ -1334,6 +1352,8 @@ int restore_batch (lh264_restore_item_t* items, int n, const lh264_restore_opts_
     std::string err;
     if (lh264host::pip_restore_describe (it.main_stream, it.main_len, P.slices, P.cabac, err, cabac_device) < 0) return;
     if (P.cabac && !cabac_device) { P.path = LH264_RESTORE_PATH_HOST; return; }
+    if (it.n_tags > LH264_TAG_ESC && it.tags[LH264_TAG_ESC])
+      P.esc_bad = lh264host::pip_restore_describe_escapes (it.tags[LH264_TAG_ESC], it.tag_len[LH264_TAG_ESC], P.esc, err) < 0;
     for (int q = 0; q < it.n_tags && q < 72; q++) if (it.tags[q]) P.tag_bytes += it.tag_len[q];
     if (P.tag_bytes >= 0xfffff000u) return;
     size_plan (P, it);
@@ -1358,6 +1378,7 @@ int restore_batch (lh264_restore_item_t* items, int n, const lh264_restore_opts_
     Plan& P = plans[i];
     P.off_slices = off; off += al256 (sizeof (RestoreSlice) * P.slices.size());
     P.off_tags = off; off += al256 (P.tag_bytes);
+    P.off_esc = off; off += al256 (sizeof (RestoreEscape) * (P.esc[0].size() + P.esc[1].size()));
   }
   const size_t in_bytes = off;
   const size_t off_zero = off;
@@ -1410,6 +1431,12 @@ int restore_batch (lh264_restore_item_t* items, int n, const lh264_restore_opts_
       to += (uint32_t)it.tag_len[q];
     }
     J.tags = base + P.off_tags;
+    for (int t = 0, at = 0; t < 2; t++) {
+      if (!P.esc[t].empty()) memcpy (in_stage + P.off_esc + sizeof (RestoreEscape) * at, P.esc[t].data(), sizeof (RestoreEscape) * P.esc[t].size());
+      J.esc[t] = (const RestoreEscape*) (base + P.off_esc) + at; J.n_esc[t] = (uint32_t)P.esc[t].size();
+      at += (int)P.esc[t].size();
+    }
+    J.esc_bad = P.esc_bad ? 1u : 0u;
     J.n_slices = (uint32_t)P.slices.size(); J.n_max = P.n_max;
     J.slices = (const RestoreSlice*) (base + P.off_slices);
     uint8_t* w = base + P.off_work;

@@ -10,11 +10,12 @@ class ParsedFrame:
     pass
 
 
-def parse_file(data, strict=False, pcm=False):
+def parse_file(data, strict=False, pcm=False, escapes=False):
     """A whole Annex-B file fed chunk by chunk as the reference's console application does.
     -> (frames, error_text, main_stream): main_stream is the recompressor's default stream (the '.pip' file itself).
-    pcm=True: a fourth element, the samples of the stream's I_PCM macroblocks (stream LH264_TAG_PCM of the container)."""
-    return parse_stream(data, strict, _file=True, _pcm=pcm)
+    pcm=True: a fourth element, the samples of the stream's I_PCM macroblocks (stream LH264_TAG_PCM of the container).
+    escapes=True: one more element at the end, the stream's escape stream (LH264_TAG_ESC, see escapes())."""
+    return parse_stream(data, strict, _file=True, _pcm=pcm, _esc=escapes)
 
 
 def parse_batch_time(datas, threads=0, keep=True):
@@ -70,7 +71,7 @@ def _read_frame(lib, p, i):
     return f
 
 
-def parse_stream(data, strict=False, _file=False, _pcm=False):
+def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False):
     """-> (frames, error_text).  frames have the attributes ReconSession / CtxSession expect."""
     lib = L.lib()
     p = lib.lh264_parser_create()
@@ -87,10 +88,14 @@ def parse_stream(data, strict=False, _file=False, _pcm=False):
             ln = C.c_size_t(0)
             ptr = lib.lh264_parser_main_stream(p, C.byref(ln))
             main = C.string_at(ptr, ln.value) if ln.value else b""
+            out = (frames, err, main)
             if _pcm:
                 ptr = lib.lh264_parser_pcm_samples(p, C.byref(ln))
-                return frames, err, main, (C.string_at(ptr, ln.value) if ln.value else b"")
-            return frames, err, main
+                out += (C.string_at(ptr, ln.value) if ln.value else b"",)
+            if _esc:
+                ptr = lib.lh264_parser_escapes(p, C.byref(ln))
+                out += (C.string_at(ptr, ln.value) if ln.value else b"",)
+            return out
         return frames, err
     finally:
         lib.lh264_parser_destroy(p)
@@ -104,6 +109,21 @@ def out_of_range(data):
     try:
         lib.lh264_parser_feed_file(p, bytes(data), len(data))
         return lib.lh264_parser_out_of_range(p).decode()
+    finally:
+        lib.lh264_parser_destroy(p)
+
+
+def escapes(data):
+    """b'' or the escape stream of a stream that parses (lh264_parser_escapes): tag 71 of the container, the part of every mb_skip_run
+    above 511 and of 16 active references that the prior tables drop.  Empty when out_of_range(data) is, and when the stream has a value the
+    escape stream cannot carry (more than 16 references, a value of another table: such a stream stays refused).  No device is needed."""
+    lib = L.lib()
+    p = lib.lh264_parser_create()
+    try:
+        lib.lh264_parser_feed_file(p, bytes(data), len(data))
+        ln = C.c_size_t(0)
+        ptr = lib.lh264_parser_escapes(p, C.byref(ln))
+        return C.string_at(ptr, ln.value) if ln.value else b""
     finally:
         lib.lh264_parser_destroy(p)
 
