@@ -38,6 +38,10 @@ extern "C" {
 #define LH264_MB_P8x8REF0  0x0080
 #define LH264_MB_SKIP      0x0100
 #define LH264_MB_IPCM      0x0200
+/* ours, not the reference's: a macroblock no slice covered, concealed by the front end (lh264_parser_set_conceal).  The record is
+ * LH264_MB_P16x16 | LH264_MB_CONCEAL: one 16x16 prediction with mv[0] and no residual from the picture its slice entry names in
+ * ref_slot[0]; it is not filtered, and its neighbours do not filter the edges they share with it */
+#define LH264_MB_CONCEAL   0x0400
 #define LH264_MB_INTRA     (LH264_MB_I4x4 | LH264_MB_I16x16 | LH264_MB_I8x8 | LH264_MB_IPCM)
 #define LH264_MB_INTER     (LH264_MB_P16x16 | LH264_MB_P16x8 | LH264_MB_P8x16 | LH264_MB_P8x8 | LH264_MB_P8x8REF0 | LH264_MB_SKIP)
 #define LH264_SUB_8x8 1
@@ -379,6 +383,24 @@ const int16_t*       lh264_parser_frame_levels (const lh264_parser_t* p, int idx
  * coefficients - of an I_PCM macroblock its nonzero samples - come as a list, ascending:
  * (picture-relative macroblock * 384 + position) << 16 | (uint16_t) value.  What lh264_decode_batch uploads instead of 768 bytes per
  * macroblock; a kernel scatters it into planes cleared on the device */
+/* concealment of lost slices (set before the first byte is fed; LH264_CONCEAL_*, 0 = off, the default): a completed picture with
+ * macroblocks no slice covers gets their records filled - mb_type LH264_MB_P16x16 | LH264_MB_CONCEAL, the final vector in mv[], a slice
+ * entry appended to the picture's table whose ref_slot[0] names the source picture (a slot past n_refs: the picture of 128s) - the way
+ * the reference's decoder conceals them (error_concealment.cpp); lh264_parser_frame_covered still says which they were.  For the decode
+ * direction only.  LH264_E_ARG: a method that is not provided.  lh264_parser_frame_conceal: out[0] the number of concealed macroblocks,
+ * [1] the source picture's id or -1, [2] 1 when the picture is withheld from the output (the FREEZE methods), [3..4] the mean vector
+ * of the received inter partitions with ref_idx 0, [5..6] the vector before the per-macroblock clamp, [7] this picture's POC as the
+ * reference counts it (pic_order_cnt_lsb), [8] list entry 0's, [9] the source's, [10] 0 = copy, 1 = the mean, 2 = the mean scaled by
+ * the POC distances, [11] the picture's POC once it is done (what a later picture's scaling reads: 0 behind an mmco 5); set for
+ * every picture, concealed or not */
+#define LH264_CONCEAL_OFF                            0
+#define LH264_CONCEAL_SLICE_COPY                     2   /* the values of the reference's ERROR_CON_IDC (codec_app_def.h) */
+#define LH264_CONCEAL_SLICE_COPY_CROSS_IDR           4
+#define LH264_CONCEAL_SLICE_COPY_CROSS_IDR_FREEZE    5   /* ..._FREEZE_RES_CHANGE */
+#define LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR        6
+#define LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR_FREEZE 7   /* ..._FREEZE_RES_CHANGE */
+int                  lh264_parser_set_conceal (lh264_parser_t* p, int method);
+int                  lh264_parser_frame_conceal (const lh264_parser_t* p, int idx, int32_t out[12]);
 int                  lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on);
 const uint64_t*      lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count);
 const lh264_slice_t* lh264_parser_frame_slices (const lh264_parser_t* p, int idx);
@@ -556,10 +578,20 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * references the parser's DPB still holds), a pack kernel crops them into the round's output buffer, and the download runs on a
  * second HIP stream while the host threads (`threads`, 0 = all) parse and stage the next round: host and device memory follow the
  * round, not the streams' length.  group_mbs bounds the macroblocks of one round (streams wait their turn in the order given).
- * A reference slot a picture does not fill, or whose picture is not held any more, holds a picture of 128s (no concealment): what a
- * stream that has lost its references reads there is defined and the same on every run.
+ * A reference slot a picture does not fill, or whose picture is not held any more, holds a picture of 128s: what a stream that has
+ * lost its references reads there is defined and the same on every run.
+ * opts->conceal (LH264_CONCEAL_*, the reference's ERROR_CON_IDC values; 0 and the 40-byte struct of before: off): a picture with
+ * macroblocks no slice covers does not stop its stream; they are concealed as the reference's decoder does it - copied from the
+ * picture decoded before (128s where there is none, and for an IDR picture under LH264_CONCEAL_SLICE_COPY), under the MV_COPY methods
+ * moved by the mean vector of the received macroblocks - and lh264_decoded_concealed counts them per picture.  One rule differs from
+ * the reference: the edge between a received and a concealed macroblock is not filtered (the reference filters it against what its
+ * picture buffer held before).  The FREEZE methods withhold pictures until the first whole IDR picture: they are
+ * decoded and not delivered.  LH264_CONCEAL_* values the call does not provide (the FRAME_COPY pair): LH264_E_ARG.  A slice that stops
+ * parsing with an error and whole lost pictures are treated as without the option; a slice NAL unit cut short whose bits still parse
+ * as a shorter slice is a shorter slice, and the macroblocks behind it are concealed.  The stream's last picture is delivered concealed
+ * like any other (the reference's end-of-stream drain drops a damaged last picture).
  * Every out[i] is a handle to free.  A failure stays with its stream: LH264_E_UNSUPPORTED with the text of the front end for syntax it
- * does not parse; a picture with macroblocks no slice covers (no concealment), an incomplete slice or a NAL unit that does not parse
+ * does not parse; a picture with macroblocks no slice covers (unless opts->conceal), an incomplete slice or a NAL unit that does not parse
  * stops the stream THERE - the pictures in front of it are delivered and valid, the text names the picture.  A stream without a
  * picture and without an error is LH264_OK with no pictures.
  * sink: the handles keep no bytes; the sink is called with runs of consecutive pictures of one stream (pics[k].offset as above,
@@ -582,13 +614,17 @@ typedef struct lh264_decode_opts {
   uint32_t round_pictures;              /* pictures of one stream per launch at most; 0 = the default (8)       */
   uint64_t group_mbs;                   /* macroblocks of one round at most; 0 = the default (1,000,000)        */
   lh264_decode_sink_fn sink; void* user;
+  uint32_t conceal;                     /* LH264_CONCEAL_*; 0 = off.  (struct_bytes up to `user`: off)          */
 } lh264_decode_opts_t;
+#define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads,
                         const lh264_decode_opts_t* opts /* NULL = defaults */, lh264_decoded_t** out);
 int lh264_decoded_status (const lh264_decoded_t* d);
 const char* lh264_decoded_error (const lh264_decoded_t* d);
 int lh264_decoded_pictures (const lh264_decoded_t* d);
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
+/* macroblocks of delivered picture idx that were concealed (0: the picture is what the stream says; < 0: bad argument) */
+int lh264_decoded_concealed (const lh264_decoded_t* d, int idx);
 const uint8_t* lh264_decoded_bytes (const lh264_decoded_t* d, size_t* len);       /* host pointer; NULL in DEVICE_OUT and sink mode */
 const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len);   /* device pointer in DEVICE_OUT mode, else NULL  */
 /* DEVICE_OUT mode: the stream's bytes copied into the caller's device memory (cap >= their length), complete on return */

@@ -13,8 +13,11 @@
     python -m losslessh264_amd --escapes ...                (first) a stream with an mb_skip_run above 511 or 16 active references is
                                                             compressed with the escape stream, tag 71, beside it (out.pip.71, or in
                                                             the container) instead of being refused or stored verbatim
-    python -m losslessh264_amd --decode [--nv12] out_dir in.264...   decode through ONE lh264_decode_batch call: out_dir/<name>.yuv holds
-                                                            the cropped pictures as I420 (or NV12), appended by a sink run by run
+    python -m losslessh264_amd --decode [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
+                                                            out_dir/<name>.yuv holds the cropped pictures as I420 (or NV12), appended
+                                                            by a sink run by run.  METHOD: lost slices are concealed as the reference's
+                                                            decoder does (slice_copy | slice_copy_cross_idr | mv_copy |
+                                                            slice_copy_cross_idr_freeze | mv_copy_freeze) instead of ending the stream
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -139,14 +142,20 @@ def restore(src, dst):
 
 def decode(argv):
     import losslessh264_amd as lh
-    nv12 = argv[0] == "--nv12"
-    if nv12:
-        argv = argv[1:]
+    nv12, conceal = False, None
+    while argv and argv[0] in ("--nv12", "--conceal"):
+        if argv[0] == "--nv12":
+            nv12, argv = True, argv[1:]
+        else:
+            if len(argv) < 2 or argv[1] not in lh._lib.CONCEAL:
+                print("--conceal: one of " + " | ".join(lh._lib.CONCEAL))
+                return 2
+            conceal, argv = argv[1], argv[2:]
     if len(argv) < 2:
         print(__doc__)
         return 2
     ret = 0
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420"):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

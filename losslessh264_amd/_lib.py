@@ -134,7 +134,10 @@ DECODED_PIC_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("frame_num",
 DECODE_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 class DecodeOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("round_pictures", C.c_uint32),
-                ("group_mbs", C.c_uint64), ("sink", DECODE_SINK_FN), ("user", C.c_void_p)]
+                ("group_mbs", C.c_uint64), ("sink", DECODE_SINK_FN), ("user", C.c_void_p), ("conceal", C.c_uint32)]
+DECODE_OPTS_BYTES_V1 = 40          # the struct before `conceal`: still accepted, concealment off
+# LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
+CONCEAL = {"off": 0, "slice_copy": 2, "slice_copy_cross_idr": 4, "slice_copy_cross_idr_freeze": 5, "mv_copy": 6, "mv_copy_freeze": 7}
 class PackJob(C.Structure):
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("dst", C.c_void_p),
                 ("stride_y", C.c_int32), ("stride_c", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
@@ -142,13 +145,16 @@ class PackJob(C.Structure):
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
-assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 40 and C.sizeof(PackJob) == 64 and C.sizeof(RestoreOpts) == 12
+assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 48 and C.sizeof(PackJob) == 64 and C.sizeof(RestoreOpts) == 12
 _SIGS.update({
     "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodeOpts), C.POINTER(C.c_void_p)]),
     "lh264_decoded_status": (C.c_int, [C.c_void_p]),
     "lh264_decoded_error": (C.c_char_p, [C.c_void_p]),
     "lh264_decoded_pictures": (C.c_int, [C.c_void_p]),
     "lh264_decoded_picture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lh264_decoded_concealed": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_set_conceal": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_frame_conceal": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_decoded_bytes": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "lh264_decoded_bytes_dev": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "lh264_decoded_copy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -180,7 +180,16 @@ static int decode_sink (void* user, int stream, int, int, const lh264_decoded_pi
   d.bytes[stream] += len;
   return 0;
 }
-static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12) {
+// the names of `lh264dec --decode --conceal METHOD` (and of decode_batch (conceal=...) in Python)
+static int conceal_method (const char* name) {
+  static const struct { const char* n; int m; } k[] = {
+    {"off", LH264_CONCEAL_OFF}, {"slice_copy", LH264_CONCEAL_SLICE_COPY}, {"slice_copy_cross_idr", LH264_CONCEAL_SLICE_COPY_CROSS_IDR},
+    {"slice_copy_cross_idr_freeze", LH264_CONCEAL_SLICE_COPY_CROSS_IDR_FREEZE}, {"mv_copy", LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR},
+    {"mv_copy_freeze", LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR_FREEZE}};
+  for (const auto& e : k) if (!strcmp (name, e.n)) return e.m;
+  return -1;
+}
+static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
   std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
@@ -193,7 +202,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
-  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files;
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal;
   std::vector<lh264_decoded_t*> h (n, nullptr);
   const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
   for (FILE* f : files.f) fclose (f);
@@ -233,15 +242,22 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    const bool nv12 = !strcmp (argv[2], "--nv12");
-    const int first = nv12 ? 3 : 2;
-    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--nv12] out_dir in.264...\n", argv[0]); return 2; }
+    bool nv12 = false; int conceal = 0, first = 2;
+    for (;;) {
+      if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
+      else if (first + 1 < argc && !strcmp (argv[first], "--conceal")) {
+        conceal = conceal_method (argv[first + 1]);
+        if (conceal < 0) { fprintf (stderr, "--conceal: off | slice_copy | slice_copy_cross_idr | slice_copy_cross_idr_freeze | mv_copy | mv_copy_freeze\n"); return 2; }
+        first += 2;
+      } else break;
+    }
+    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
-    return decode_files (argv[first], srcs, nv12);
+    return decode_files (argv[first], srcs, nv12, conceal);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

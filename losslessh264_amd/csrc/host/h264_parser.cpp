@@ -115,6 +115,7 @@ const int kChromaNzcIdx[2][4] = {{16, 17, 20, 21}, {18, 19, 22, 23}};   // refer
 struct DpbPic {
   int frame_id = -1, frame_num = 0, frame_num_wrap = 0, long_idx = -1;
   bool is_long = false;
+  int poc = 0;              // the reference's iFramePoc: pic_order_cnt_lsb as parsed (decoder_core.cpp:2204), 0 behind an mmco 5
 };
 
 struct MbState {       // per-macroblock parse state of the current picture (neighbour context)
@@ -192,6 +193,10 @@ struct Parser::Impl {
   std::vector<uint8_t> persist_chroma, persist_l16, persist_sub;
   int persist_w = 0, persist_h = 0;
   int slice_cached_qp = 0, slice_run_before = 0;
+  // concealment of lost slices (Parser::set_conceal; the reference's error_concealment.cpp)
+  int prev_pic_id = -1, prev_pic_poc = 0;                // pPreviousDecodedPictureInDpb: the picture completed last, a reference or not
+  int ec_list0_id = -1, ec_list0_poc = 0;                // entry 0 of list 0 of the picture's last P slice (sRefPic.pRefList when concealment runs)
+  bool frozen = true; int out_w = 0, out_h = 0;          // bFreezeOutput, iLastImgWidthInPixel / iLastImgHeightInPixel
   Symbolizer symbolizer;
   int last_hdr_bits = -1; bool last_cabac = false;
   int16_t no_coef[384];                                  // where the dequantised coefficients go when nobody wants them
@@ -517,7 +522,7 @@ struct Parser::Impl {
     const int max_fn = 1 << S.log2_max_frame_num;
     if (sh.idr) {
       dpb.clear();
-      DpbPic d; d.frame_id = cur->id; d.frame_num = sh.frame_num;
+      DpbPic d; d.frame_id = cur->id; d.frame_num = sh.frame_num; d.poc = sh.poc_lsb;
       if (sh.long_term_reference) { d.is_long = true; d.long_idx = 0; }
       dpb.push_back (d);
       return;
@@ -554,6 +559,7 @@ struct Parser::Impl {
       }
     }
     DpbPic d; d.frame_id = cur->id; d.frame_num = had_mmco5 ? 0 : sh.frame_num; d.is_long = cur_long; d.long_idx = cur_lidx;
+    d.poc = had_mmco5 ? 0 : sh.poc_lsb;
     dpb.push_back (d);
     const size_t cap = (size_t)std::max (S.num_ref_frames, 1);
     while (dpb.size() > cap) {          // never exceed the DPB size the stream declared
@@ -568,18 +574,122 @@ struct Parser::Impl {
     if (!cur) return;
     if (first_sh.nal_ref_idc) { mark_reference (first_sh, *csps); cur->is_ref = true; prev_ref_frame_num = had_mmco5 ? 0 : first_sh.frame_num; }
     had_mmco5 = false;
+    const int cur_poc = first_sh.poc_lsb;
     for (const auto& d : dpb) cur->dpb_ids.push_back (d.frame_id);
+    // with concealment on, a picture is held one picture longer than its marking says: it is the next picture's concealment source
+    if (self->conceal_ && std::find (cur->dpb_ids.begin(), cur->dpb_ids.end(), cur->id) == cur->dpb_ids.end()) cur->dpb_ids.push_back (cur->id);
     {   // the row-a10 symbol lists (every slice of the picture must have been parsed to its end)
       if (cur->slice_syn.size() == cur->slices.size()) symbolizer.picture (*cur);
       else { cur->syn_off.assign ((size_t)cur->mb_w * cur->mb_h + 1, 0); cur->syn_syms.clear(); }
     }
     for (uint8_t c : cur->covered) if (!c) { self->damaged_ = true; break; }
+    if (self->conceal_) conceal_picture (cur_poc);
+    prev_pic_id = cur->id; prev_pic_poc = cur->is_ref && dpb.size() && dpb.back().frame_id == cur->id ? dpb.back().poc : cur_poc;
+    cur->poc = prev_pic_poc;
     if (coef_unsorted) { sort_coeffs(); coef_unsorted = false; }
     cur->complete = true;
     self->pictures_done_++;
     if (self->keep_frames_) self->frames_.push_back (std::move (cur));
     cur.reset();
     last_first_mb = -1;
+  }
+
+  // ImplementErrorCon (error_concealment.cpp:451-476) for the records: every macroblock no slice covered becomes one 16x16 prediction
+  // without residual from the previous decoded picture, in a slice entry of its own that is neither weighted nor filtered.  The
+  // vector is final: DoMbECMvCopy's mean of the received inter partitions of ref_idx 0 (GetAvilInfoFromCorrectMb), scaled by the POC
+  // distances where list entry 0 is not the previous picture, rounded and clamped into the output window per macroblock (:207-240).
+  // Then DecodeFrameConstruction's output freeze (decoder_core.cpp:163-210).
+  void conceal_picture (int cur_poc) {
+    const int method = self->conceal_;
+    const bool mv_copy = method == LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR || method == LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR_FREEZE;
+    const bool freeze = method == LH264_CONCEAL_SLICE_COPY_CROSS_IDR_FREEZE || method == LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR_FREEZE;
+    const int H = cur->mb_h * 16;
+    const size_t n = (size_t)cur->mb_w * cur->mb_h;
+    size_t lost = 0, first_lost = 0;
+    for (size_t k = n; k-- > 0; ) if (!cur->covered[k]) { lost++; first_lost = k; }
+    int src = prev_pic_id;
+    if (method == LH264_CONCEAL_SLICE_COPY && cur->idr) src = -1;                  // no copy across an IDR: 128s
+    int slot = -1;
+    // (a slice that stopped parsing halfway left no SliceSyn: such a picture is not concealed and is refused as without the option)
+    if (lost && !cur->slices.empty() && cur->slices.size() < 0xffff && cur->slice_syn.size() == cur->slices.size()) {
+      if (src >= 0) for (size_t q = 0; q < cur->ref_ids.size(); q++) if (cur->ref_ids[q] == src) slot = (int)q;
+      if (slot < 0 && cur->ref_ids.size() < LH264_MAX_REFS) {
+        slot = (int)cur->ref_ids.size();           // src < 0: a slot the picture does not fill, which holds the picture of 128s
+        if (src >= 0) cur->ref_ids.push_back (src);
+      }
+    }
+    if (lost && slot >= 0) {
+      // the mean vector per ref_idx (only entry 0 is used), C integer division
+      int64_t sum[2] = {0, 0}; int cnt = 0;
+      if (mv_copy) for (size_t k = 0; k < n; k++) {
+        const lh264_mb_t& m = cur->mbs[k];
+        if (!cur->covered[k] || !(m.mb_type & LH264_MB_INTER)) continue;
+        auto add = [&] (int quad, int blk) { if (m.ref_idx[quad] == 0) { sum[0] += m.mv[blk][0]; sum[1] += m.mv[blk][1]; cnt++; } };
+        if (m.mb_type == LH264_MB_SKIP || m.mb_type == LH264_MB_P16x16) add (0, 0);
+        else if (m.mb_type == LH264_MB_P16x8) { add (0, 0); add (2, 8); }
+        else if (m.mb_type == LH264_MB_P8x16) { add (0, 0); add (1, 2); }
+        else for (int i = 0; i < 4; i++) {
+          const int b = ((i >> 1) << 3) + ((i & 1) << 1);
+          switch (m.sub_type[i]) {
+          case LH264_SUB_8x8: add (i, b); break;
+          case LH264_SUB_8x4: add (i, b); add (i, b + 4); break;
+          case LH264_SUB_4x8: add (i, b); add (i, b + 1); break;
+          case LH264_SUB_4x4: add (i, b); add (i, b + 1); add (i, b + 4); add (i, b + 5); break;
+          default: break;
+          }
+        }
+      }
+      int mean[2] = {0, 0}, vec[2] = {0, 0};
+      bool use_mv = false;
+      if (cnt) { mean[0] = (int) ((int32_t)sum[0] / cnt); mean[1] = (int) ((int32_t)sum[1] / cnt); }
+      if (mv_copy && src >= 0 && !cur->idr && cnt && ec_list0_id >= 0) {
+        use_mv = true;
+        if (ec_list0_id == src) { vec[0] = (int16_t)mean[0]; vec[1] = (int16_t)mean[1]; }
+        else {
+          const int s0 = ec_list0_poc - cur_poc, s1 = prev_pic_poc - cur_poc;
+          vec[0] = s0 == 0 ? 0 : (int16_t) (mean[0] * s1 / s0);
+          vec[1] = s0 == 0 ? 0 : (int16_t) (mean[1] * s1 / s0);
+        }
+      }
+      cur->conceal_info[0] = mean[0]; cur->conceal_info[1] = mean[1]; cur->conceal_info[2] = vec[0]; cur->conceal_info[3] = vec[1];
+      cur->conceal_info[4] = cur_poc; cur->conceal_info[5] = ec_list0_poc; cur->conceal_info[6] = prev_pic_poc; cur->conceal_info[7] = use_mv ? (ec_list0_id == src ? 1 : 2) : 0;
+      cur->conceal_src = src;
+      lh264_slice_t sl; memset (&sl, 0, sizeof (sl));
+      sl.first_mb = (int32_t)first_lost; sl.n_mbs = (int32_t)lost; sl.slice_type = 0; sl.deblock_idc = 1; sl.n_refs = 1; sl.luma_dc_weight = 16;
+      for (int i = 0; i < LH264_MAX_REFS; i++) sl.ref_slot[i] = -1;
+      sl.ref_slot[0] = (int8_t)slot;
+      const uint16_t sid = (uint16_t)cur->slices.size();
+      cur->slices.push_back (sl);
+      SliceSyn ss; memset (&ss, 0, sizeof (ss));
+      cur->slice_syn.resize (cur->slices.size(), ss);
+      const int top = cur->crop_y, left = cur->crop_x, right = cur->crop_x + cur->crop_w, bottom = H - cur->crop_y;   // (the top offset twice, :218)
+      for (size_t k = 0; k < n; k++) {
+        if (cur->covered[k]) continue;
+        lh264_mb_t& m = cur->mbs[k];
+        memset (&m, 0, sizeof (m));
+        m.mb_type = LH264_MB_P16x16 | LH264_MB_CONCEAL; m.slice_id = sid;
+        int mvx = 0, mvy = 0;
+        if (use_mv) {
+          const int px = (int) (k % (size_t)cur->mb_w) * 16, py = (int) (k / (size_t)cur->mb_w) * 16;
+          int fx = (px << 2) + vec[0], fy = (py << 2) + vec[1];
+          if (fx < ((left + 2) << 2)) fx = std::max (left, (fx >> 2) << 2);
+          else if (fx > ((right - 19) << 2)) fx = std::min ((right - 17) << 2, (fx >> 2) << 2);
+          if (fy < ((top + 2) << 2)) fy = std::max (top, (fy >> 2) << 2);
+          else if (fy > ((bottom - 19) << 2)) fy = std::min ((bottom - 17) << 2, (fy >> 2) << 2);
+          mvx = (int16_t) (fx - (px << 2)); mvy = (int16_t) (fy - (py << 2));
+        }
+        for (int b = 0; b < 16; b++) { m.mv[b][0] = (int16_t)mvx; m.mv[b][1] = (int16_t)mvy; }
+      }
+      cur->concealed = (int)lost;
+    }
+    // the output freeze: nothing is handed out before the first whole IDR picture, and again from a damaged picture that changes the size
+    const bool err = lost != 0;
+    if (cur->idr && !err) frozen = false;
+    const bool res_change = out_w != cur->crop_w || out_h != cur->crop_h;
+    out_w = cur->crop_w; out_h = cur->crop_h;
+    if (!freeze) frozen = false;
+    else if (err && res_change) frozen = true;
+    cur->frozen = frozen;
   }
 
   void start_picture (const SliceHeader& sh, const Sps& S, const Pps& P) {
@@ -598,6 +708,7 @@ struct Parser::Impl {
     cur->syn.assign (n, MbSyn()); memset (cur->syn.data(), 0, n * sizeof (MbSyn));
     if (persist_w != S.mb_w || persist_h != S.mb_h) {       // the decoder re-allocates (zeroed) on a resolution change
       persist_w = S.mb_w; persist_h = S.mb_h;
+      prev_pic_id = -1;                                      // ... and forgets its previous picture
       persist_chroma.assign (n, 0); persist_l16.assign (n, 0); persist_sub.assign (n * 4, 0);
     }
     st.assign (n, MbState());
@@ -1630,6 +1741,8 @@ int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
     for (int i = 0; i < LH264_MAX_REFS; i++) sl.ref_slot[i] = -1;
     if (sh.slice_type == 0) {
       build_ref_list (sh, S, c.ref_frames);
+      ec_list0_id = c.ref_frames.empty() ? -1 : c.ref_frames[0]; ec_list0_poc = 0;
+      for (const auto& d : dpb) if (d.frame_id == ec_list0_id) ec_list0_poc = d.poc;
       for (size_t i = 0; i < c.ref_frames.size() && i < LH264_MAX_REFS; i++) {
         const int fid = c.ref_frames[i];
         if (fid < 0) continue;
@@ -1660,6 +1773,15 @@ int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
 
 Parser::Parser() : d_ (new Impl (this)) {}
 Parser::~Parser() {}
+bool Parser::conceal_method_ok (int method) {
+  return method == 0 || method == LH264_CONCEAL_SLICE_COPY || method == LH264_CONCEAL_SLICE_COPY_CROSS_IDR || method == LH264_CONCEAL_SLICE_COPY_CROSS_IDR_FREEZE ||
+         method == LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR || method == LH264_CONCEAL_SLICE_MV_COPY_CROSS_IDR_FREEZE;
+}
+bool Parser::set_conceal (int method) {
+  if (!conceal_method_ok (method)) return false;
+  conceal_ = method;
+  return true;
+}
 // the two places every entry point goes through: nothing thrown below them (allocation failures, length errors of the standard
 // containers) crosses the C ABI - the stream is reported as failed instead
 int Parser::feed_nal (const uint8_t* nal, size_t len) {

@@ -190,6 +190,13 @@ struct FrameOut {
   PoolVec<uint8_t> lev_nonzero;            // per macroblock: it has a nonzero level (FreqImage's 'zeroed' test)
   PoolVec<uint64_t> sparse;                // sparse mode instead of `levels`: (macroblock * 384 + position) << 16 | level, nonzero levels only
   PoolVec<uint64_t> sparse_coeffs;         // sparse mode instead of `coeffs`: the same entries for the nonzero dequantised coefficients, ascending
+  // Parser::set_conceal: the macroblocks no slice covered and whose records were filled (LH264_MB_CONCEAL; `covered` stays 0 for them), the id of
+  // the picture they are predicted from (-1: the picture of 128s), whether the picture is withheld from the output (the reference's
+  // bFreezeOutput), and what the vector was made of: the mean vector of ref_idx 0, the vector before the per-macroblock clamp, the POCs of
+  // this picture, of list entry 0 and of the source, and 0 = copy, 1 = the mean itself, 2 = the mean scaled by the POC distances
+  int concealed = 0, conceal_src = -1; bool frozen = false;
+  int poc = 0;                             // the picture's POC as the reference's concealment counts it once the picture is done: pic_order_cnt_lsb, 0 behind an mmco 5
+  int32_t conceal_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // The recompressor's default stream (".pip" itself, stream id 0x7fffffff): the Annex-B input minus its slice data.
@@ -283,6 +290,12 @@ class Parser {
   // a completed picture had macroblocks no slice covers (lost slices): the reference conceals them (error_concealment.cpp), which is not
   // modelled - the recompressed form of such a stream does not restore; callers that promise a round trip store it verbatim
   bool damaged() const { return damaged_; }
+  // method = LH264_CONCEAL_* (0 = off, the default: nothing changes): a completed picture with macroblocks no slice covers gets them
+  // concealed as the reference's decoder does it, see FrameOut::concealed.  Not for the compress direction: the records of a concealed
+  // picture are not the stream's.  false: a method that is not provided (the FRAME_COPY pair)
+  bool set_conceal (int method);
+  static bool conceal_method_ok (int method);
+  int conceal() const { return conceal_; }
   // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
   // carry (Symbolizer::out_of_range: an mb_skip_run above 511, 16 active references).  Not an error of the stream: it parses and decodes
   const std::string& out_of_range() const;
@@ -300,6 +313,7 @@ class Parser {
   std::string err_;
   int n_unsupported_ = 0;
   bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false, sparse_coeffs_ = false; long pictures_done_ = 0, err_pictures_ = 0; bool damaged_ = false;
+  int conceal_ = 0;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;
   const uint8_t* file_d_ = nullptr; size_t file_n_ = 0, file_pos_ = 0; int file_rc_ = 0; bool file_done_ = false, arena_paused_ = false;      // begin_file .. feed_file_some

@@ -58,6 +58,8 @@ class GpuDecoder : public ISVCDecoder {
     pics_.clear();
     for (auto* b : free_pics_) { lh264_dev_free (b->base); delete b; }
     free_pics_.clear();
+    if (grey_.base) lh264_dev_free (grey_.base);
+    grey_ = DevPic();
     if (d_chain_first_) lh264_dev_free (d_chain_first_);
     if (d_job_) lh264_dev_free (d_job_);
     if (d_mbs_) lh264_dev_free (d_mbs_);
@@ -148,7 +150,10 @@ class GpuDecoder : public ISVCDecoder {
       eos_ = * (int*)v != 0;
       return cmResultSuccess;
     case DECODER_OPTION_ERROR_CON_IDC:
+      // the one switch of concealment (the reference's console application sets it the same way; eEcActiveIdc of Initialize stays
+      // ignored): the methods the front end provides, ERROR_CON_DISABLE, or an argument error (the FRAME_COPY pair)
       if (!v) return cmInitParaError;
+      if (!parser_->set_conceal (* (int*)v)) return cmInitParaError;
       ec_idc_ = * (int*)v;
       return cmResultSuccess;
     case DECODER_OPTION_TRACE_LEVEL: if (v) trace_level_ = * (int*)v; return cmResultSuccess;
@@ -194,6 +199,20 @@ class GpuDecoder : public ISVCDecoder {
     return p.release();
   }
 
+  const DevPic* grey_pic (const DevPic& like) {
+    if (grey_.base && grey_.mb_w == like.mb_w && grey_.mb_h == like.mb_h) return &grey_;
+    if (grey_.base) lh264_dev_free (grey_.base);
+    grey_ = like;
+    grey_.base = (uint8_t*)lh264_dev_malloc (grey_.bytes);
+    const std::vector<uint8_t> v (grey_.bytes, 128);
+    if (!grey_.base || lh264_memcpy_h2d (grey_.base, v.data(), v.size(), nullptr) || lh264_stream_sync (nullptr)) {
+      if (grey_.base) lh264_dev_free (grey_.base);
+      grey_ = DevPic();
+      return nullptr;
+    }
+    return &grey_;
+  }
+
   int ensure_staging (size_t n_mbs, size_t n_slices) {
     if (n_mbs > cap_mbs_) {
       if (d_mbs_) lh264_dev_free (d_mbs_);
@@ -216,9 +235,9 @@ class GpuDecoder : public ISVCDecoder {
     const size_t n = (size_t)f.mb_w * f.mb_h;
     last_frame_num_ = f.frame_num; if (f.idr) last_idr_pic_id_ = f.idr_pic_id;
     size_t covered = 0;
-    for (size_t k = 0; k < n; k++) covered += f.covered[k] != 0;
+    for (size_t k = 0; k < n; k++) covered += f.covered[k] != 0 || (f.mbs[k].mb_type & LH264_MB_CONCEAL) != 0;
     if (covered != n || f.slices.empty()) {
-      // the reference would conceal the missing macroblocks (error_concealment.cpp); this decoder reports the loss instead
+      // without DECODER_OPTION_ERROR_CON_IDC (or where the front end could not conceal) the loss is reported and no picture comes out
       trace (2, "lh264: access unit incomplete, no picture produced");
       release_unreferenced (f, nullptr);
       return dsBitstreamError;
@@ -229,13 +248,20 @@ class GpuDecoder : public ISVCDecoder {
     lh264_frame_job_t job; memset (&job, 0, sizeof (job));
     job.mbs_dev = d_mbs_; job.coeffs_dev = d_coeffs_; job.slices_dev = d_slices_;
     job.dst.y_dev = pic->base + pic->off[0]; job.dst.u_dev = pic->base + pic->off[1]; job.dst.v_dev = pic->base + pic->off[2];
-    int state = dsErrorFree;
+    int state = f.concealed ? dsDataErrorConcealed : dsErrorFree;
+    // concealed macroblocks without a source picture read the slot behind the picture's last reference: a picture of 128s
+    // ... and so does the source's slot when the source is not held (the access unit before was refused, the option was set in
+    // mid-stream behind a non-reference picture): never the picture that is being written
+    bool src_held = false;
+    if (f.concealed && f.conceal_src >= 0) { auto it = pics_.find (f.conceal_src); src_held = it != pics_.end() && it->second.mb_w == f.mb_w && it->second.mb_h == f.mb_h; }
+    const DevPic* grey = f.concealed && !src_held ? grey_pic (*pic) : nullptr;
+    if (f.concealed && !src_held && !grey) { free_pics_.push_back (pic); return dsOutOfMemory; }
     for (size_t i = 0; i < LH264_MAX_REFS; i++) {
-      const DevPic* r = pic;
+      const DevPic* r = grey && i == f.ref_ids.size() ? grey : pic;
       if (i < f.ref_ids.size()) {
         auto it = pics_.find (f.ref_ids[i]);
         if (it != pics_.end() && it->second.mb_w == f.mb_w && it->second.mb_h == f.mb_h) r = &it->second;
-        else state |= dsRefLost;
+        else { state |= dsRefLost; if (grey && f.ref_ids[i] == f.conceal_src) r = grey; }
       }
       job.ref[i].y_dev = r->base + r->off[0]; job.ref[i].u_dev = r->base + r->off[1]; job.ref[i].v_dev = r->base + r->off[2];
     }
@@ -257,7 +283,7 @@ class GpuDecoder : public ISVCDecoder {
     dst[0] = host_out_.data() + P.off[0] + (size_t)f.crop_y * P.stride_y + f.crop_x;
     dst[1] = host_out_.data() + P.off[1] + (size_t) (f.crop_y >> 1) * P.stride_c + (f.crop_x >> 1);
     dst[2] = host_out_.data() + P.off[2] + (size_t) (f.crop_y >> 1) * P.stride_c + (f.crop_x >> 1);
-    info->iBufferStatus = 1;
+    info->iBufferStatus = f.frozen ? 0 : 1;                 // (a withheld picture was reconstructed all the same: it is a reference)
     info->uiOutYuvTimeStamp = ts;
     info->UsrData.sSystemBuffer.iFormat = (int)videoFormatI420;
     info->UsrData.sSystemBuffer.iWidth = f.crop_w; info->UsrData.sSystemBuffer.iHeight = f.crop_h;
@@ -277,7 +303,8 @@ class GpuDecoder : public ISVCDecoder {
       for (int id : f.dpb_ids) keep |= id == it->first;
       if (!keep) { free_pics_.push_back (new DevPic (it->second)); it = pics_.erase (it); } else ++it;
     }
-    if (cur && f.is_ref) { pics_[f.id] = *cur; delete cur; }
+    // (with concealment on dpb_ids names the picture itself: it may be the next picture's source, a reference or not)
+    if (cur && (f.is_ref || parser_->conceal())) { pics_[f.id] = *cur; delete cur; }
     else if (cur) free_pics_.push_back (cur);
     while (free_pics_.size() > 4) { lh264_dev_free (free_pics_.back()->base); delete free_pics_.back(); free_pics_.pop_back(); }
   }
@@ -288,6 +315,7 @@ class GpuDecoder : public ISVCDecoder {
   std::deque<Pending> pending_;
   std::map<int, DevPic> pics_;            // frame id -> reference picture resident in HBM
   std::vector<DevPic*> free_pics_;
+  DevPic grey_;                           // every sample 128: the source of concealed macroblocks that have no previous picture
   int32_t* d_chain_first_ = nullptr;
   lh264_frame_job_t* d_job_ = nullptr;
   lh264_mb_t* d_mbs_ = nullptr; int16_t* d_coeffs_ = nullptr; lh264_slice_t* d_slices_ = nullptr;

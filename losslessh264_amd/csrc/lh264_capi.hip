@@ -748,6 +748,15 @@ int lh264_parser_frame_info (const lh264_parser_t* p, int idx, lh264_frame_info_
 }
 const lh264_mb_t* lh264_parser_frame_mbs (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->mbs.data() : nullptr; }
 const int16_t* lh264_parser_frame_coeffs (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->coeffs.data() : nullptr; }
+int lh264_parser_set_conceal (lh264_parser_t* p, int method) { return p && p->p.set_conceal (method) ? LH264_OK : LH264_E_ARG; }
+int lh264_parser_frame_conceal (const lh264_parser_t* p, int idx, int32_t out[12]) {
+  const lh264host::FrameOut* f = pf (p, idx);
+  if (!f || !out) return LH264_E_ARG;
+  out[0] = f->concealed; out[1] = f->conceal_src; out[2] = f->frozen ? 1 : 0;
+  out[3] = f->conceal_info[0]; out[4] = f->conceal_info[1]; out[5] = f->conceal_info[2]; out[6] = f->conceal_info[3];
+  out[7] = f->conceal_info[4]; out[8] = f->conceal_info[5]; out[9] = f->conceal_info[6]; out[10] = f->conceal_info[7]; out[11] = f->poc;
+  return LH264_OK;
+}
 int lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_sparse_coeffs (on != 0); return LH264_OK; }
 const uint64_t* lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count) {
   auto f = pf (p, idx);

@@ -121,6 +121,7 @@ struct lh264_decoded {
   int status = LH264_OK;
   std::string error;
   std::vector<lh264_decoded_pic_t> pics;
+  std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
   ~lh264_decoded() {
@@ -220,6 +221,7 @@ struct DStream {
   std::unique_ptr<Parser> parser;
   std::deque<std::unique_ptr<FrameOut>> pending;     // parsed, not yet in a round
   long next_picture = 0;                             // the stream's pictures in rounds so far
+  long delivered = 0;                                // ... those of them that are handed out (a frozen picture is reconstructed only)
   uint64_t out_off = 0;                              // ... and their packed bytes
   size_t pic_mbs = 0;                                // macroblocks of the stream's last picture (0: none seen yet)
   Geo geo;
@@ -236,6 +238,7 @@ struct RoundChain {
   DStream* s = nullptr;
   int first_picture = 0;
   std::vector<lh264_decoded_pic_t> pics;
+  std::vector<int32_t> concealed;
   size_t at = 0, bytes = 0;                          // in the round's output buffer
 };
 struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0; bool live = false; };
@@ -243,7 +246,7 @@ struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0; bool live =
 std::string refuse_picture (const FrameOut& f) {
   const size_t n = (size_t)f.mb_w * f.mb_h;
   if (f.covered.size() != n || f.mbs.size() != n) return "an incomplete picture";
-  for (size_t k = 0; k < n; k++) if (!f.covered[k]) return "macroblocks no slice covers (the reference conceals them, which is not modelled)";
+  for (size_t k = 0; k < n; k++) if (!f.covered[k] && !(f.mbs[k].mb_type & LH264_MB_CONCEAL)) return "macroblocks no slice covers (the reference conceals them, which is not modelled)";
   if (f.slices.empty() || f.slice_syn.size() != f.slices.size()) return "an incomplete slice";
   if (f.crop_w <= 0 || f.crop_h <= 0 || (f.crop_w & 1) || (f.crop_h & 1) || f.crop_x < 0 || f.crop_y < 0 || (f.crop_x & 1) || (f.crop_y & 1) ||
       f.crop_x + f.crop_w > f.mb_w * 16 || f.crop_y + f.crop_h > f.mb_h * 16) return "a crop window outside the picture";
@@ -273,8 +276,10 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n) {
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && (opts->struct_bytes != sizeof (lh264_decode_opts_t) || opts->format > LH264_FMT_NV12 || (opts->flags & ~LH264_DECODE_DEVICE_OUT) ||
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 || (opts->flags & ~LH264_DECODE_DEVICE_OUT) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)))) return LH264_E_ARG;
+  const int conceal = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? (int)opts->conceal : 0;
+  if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
   const bool device_out = opts && (opts->flags & LH264_DECODE_DEVICE_OUT);
@@ -369,11 +374,13 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       for (RoundChain& c : rd.chains) {
         if (c.s->stopped) continue;
         lh264_decoded_t& r = *out[c.s->i];
+        if (c.pics.empty()) continue;
         if (sink (sink_user, c.s->i, c.first_picture, (int)c.pics.size(), c.pics.data(), hb + c.at, c.bytes) != 0) {
           c.s->stopped = true; r.status = LH264_E_ARG; r.error = "sink";
           continue;
         }
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
+        r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
       }
     } else {
       run_parallel ((int)rd.chains.size(), threads, [&] (int k) {
@@ -382,6 +389,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         lh264_decoded_t& r = *out[c.s->i];
         if (!device_out) r.bytes.insert (r.bytes.end(), hb + c.at, hb + c.at + c.bytes);
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
+        r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
       });
     }
     t_deliver += now_s() - t1;
@@ -407,6 +415,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s->parser.reset (new Parser());
         s->parser->set_sparse_coeffs (true);
         s->parser->set_sparse_levels (true);       // (the parser has no mode without levels: their list is the cheapest form)
+        s->parser->set_conceal (conceal);
         s->parser->begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
         active.push_back (std::move (s));
         used += avg * R; admitted++;
@@ -431,7 +440,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, sl = 0, ents = 0, bytes = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -440,7 +449,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s.geo.bytes = (lh264_pic_bytes (f0.mb_w, f0.mb_h, &s.geo.stride_y, &s.geo.stride_c, &s.geo.off[0], &s.geo.off[1], &s.geo.off[2]) + 255) & ~ (size_t)255;
       }
       RoundChain c;
-      c.s = &s; c.first_picture = (int)s.next_picture; c.at = rd.out_bytes; c.bytes = bytes;
+      c.s = &s; c.first_picture = (int)s.delivered; c.at = rd.out_bytes; c.bytes = bytes;
       place.push_back ({n_mbs, n_sl, n_sp, n_jobs});
       n_mbs += m; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       rd.out_bytes += (bytes + 15) & ~ (size_t)15;
@@ -515,6 +524,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         jb.flags = f.is_ref ? 0 : LH264_JOB_NO_EXPAND;
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
+        if (f.frozen) { mo += nm; so += f.slices.size(); j++; continue; }      // withheld: a reference like any other, but no window to pack (crop_h 0)
         pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
         pj.dst = d_out + at;
         pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
@@ -523,6 +533,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         lh264_decoded_pic_t dp;
         dp.width = f.crop_w; dp.height = f.crop_h; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
         rc.pics.push_back (dp);
+        rc.concealed.push_back (f.concealed);
         at += bytes; off += bytes;
         mo += nm; so += f.slices.size(); j++;
       }
@@ -535,6 +546,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
       for (Slot& sl : s.pool) if (sl.pic_id >= 0 && std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end()) sl.pic_id = -1;
       s.next_picture += (long)s.sel.size();
+      s.delivered += (long)rd.chains[c].pics.size();
       s.out_off += rd.chains[c].bytes;
       s.sel.clear();                                  // the pictures' records are staged: their memory goes back
     }
@@ -554,6 +566,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         // the pictures stay on the device: every stream's run goes behind what its handle holds (the buffer grows by doubling)
         for (RoundChain& c : rd.chains) {
           lh264_decoded_t& r = *out[c.s->i];
+          if (!c.bytes) continue;                   // (every picture of the chain withheld)
           if (r.dev_len + c.bytes > r.dev_cap) {
             const size_t cap = std::max<size_t> (4 * (r.dev_len + c.bytes), (size_t)1 << 16);
             uint8_t* p = nullptr;
@@ -568,7 +581,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       }
       ok = ok && hipEventRecord (A.e_run[rb], st) == hipSuccess;
       if (ok && !device_out) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
-                                  hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess &&
+                                  (!rd.out_bytes || hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess) &&
                                   hipEventRecord (A.e_down[rb], A.s_down) == hipSuccess;
       if (!ok) { const char* le = lh264_last_error(); fail_device (std::string ("launching the device stage failed") + (le && *le ? std::string (": ") + le : std::string())); for (RoundChain& c : rd.chains) c.s->stopped = true; }
       else rd.live = true;
@@ -617,6 +630,10 @@ int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap)
   if (!d || !dst_dev || cap < d->dev_len) return LH264_E_ARG;
   if (d->dev_len && hipMemcpy (dst_dev, d->dev, d->dev_len, hipMemcpyDeviceToDevice) != hipSuccess) return LH264_E_HIP;
   return LH264_OK;
+}
+int lh264_decoded_concealed (const lh264_decoded_t* d, int idx) {
+  if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->concealed.size() != d->pics.size()) return LH264_E_ARG;
+  return d->concealed[idx];
 }
 void lh264_decoded_free (lh264_decoded_t* d) { delete d; }
 int lh264_decode_arena_bytes (size_t* device, size_t* pinned) {

@@ -1225,6 +1225,10 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
   const int idc = sl.deblock_idc();
   const bool filt = covered && !(F.flags & LH264_JOB_NO_DEBLOCK) && idc != 1 && (stype == 0 || stype == 2);
   bool left_av = mbx > 0, top_av = mby > 0;
+  if (filt) {                       // an edge towards a concealed macroblock is not filtered: it takes no part in the filter
+    if (lm.mb_type() & LH264_MB_CONCEAL) left_av = false;
+    if (tm.mb_type() & LH264_MB_CONCEAL) top_av = false;
+  }
   if (filt && idc == 2) {           // DeblockingAvailableNoInterlayer deblocking.cpp:354-369
     if (left_av) left_av = lm.slice_id() == sid;
     if (top_av) top_av = tm.slice_id() == sid;

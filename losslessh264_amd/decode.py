@@ -44,6 +44,10 @@ class DecodedBatch:
             out.append((int(r["width"]), int(r["height"]), int(r["frame_num"]), int(r["idr"]), int(r["offset"]), int(r["bytes"])))
         return out
 
+    def concealed(self, i):
+        """per delivered picture of stream i: the number of its macroblocks that were concealed (all 0 without conceal=)"""
+        return [self._lib.lh264_decoded_concealed(self._h[i], k) for k in range(self._lib.lh264_decoded_pictures(self._h[i]))]
+
     def data(self, i):
         """the packed pictures of stream i as bytes (empty with device_out=True or a sink)"""
         ln = C.c_size_t(0)
@@ -85,15 +89,21 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
     DecodedBatch.pictures, data a bytes object); the handles then keep no bytes.  round_pictures / group_mbs: the cuts of the work
-    (None = the library's defaults); the bytes do not depend on them."""
+    (None = the library's defaults); the bytes do not depend on them.
+    conceal: None / "off" (a picture with macroblocks no slice covers stops its stream) or how such macroblocks are concealed, as the
+    reference's decoder does under the ERROR_CON_IDC of that name: "slice_copy" | "slice_copy_cross_idr" | "mv_copy" (slice MV copy
+    across IDR) | "slice_copy_cross_idr_freeze" | "mv_copy_freeze" (the FREEZE_RES_CHANGE variants: pictures are withheld until the
+    first whole IDR picture).  DecodedBatch.concealed(i) counts the concealed macroblocks per picture."""
     lib = L.lib()
     if fmt not in _FORMATS:
         raise ValueError("fmt must be 'i420' or 'nv12'")
+    if conceal is not None and conceal not in L.CONCEAL:
+        raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
     n = len(datas)
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
@@ -104,6 +114,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     opts.flags = L.DECODE_DEVICE_OUT if device_out else 0
     opts.round_pictures = int(round_pictures or 0)
     opts.group_mbs = int(group_mbs or 0)
+    opts.conceal = L.CONCEAL[conceal or "off"]
     cb = None
     if sink is not None:
         def _cb(user, stream, first, count, pics, data, ln):
@@ -133,7 +144,7 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420"):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None):
     """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
     pictures, bytes)]"""
     datas = [open(p, "rb").read() for p in paths]
@@ -147,7 +158,7 @@ def decode_to_files(paths, out_dir, fmt="i420"):
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal)
     finally:
         for f in files:
             f.close()

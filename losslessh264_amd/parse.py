@@ -10,12 +10,15 @@ class ParsedFrame:
     pass
 
 
-def parse_file(data, strict=False, pcm=False, escapes=False):
+def parse_file(data, strict=False, pcm=False, escapes=False, conceal=None):
     """A whole Annex-B file fed chunk by chunk as the reference's console application does.
     -> (frames, error_text, main_stream): main_stream is the recompressor's default stream (the '.pip' file itself).
     pcm=True: a fourth element, the samples of the stream's I_PCM macroblocks (stream LH264_TAG_PCM of the container).
-    escapes=True: one more element at the end, the stream's escape stream (LH264_TAG_ESC, see escapes())."""
-    return parse_stream(data, strict, _file=True, _pcm=pcm, _esc=escapes)
+    escapes=True: one more element at the end, the stream's escape stream (LH264_TAG_ESC, see escapes()).
+    conceal: a name of decode_batch's conceal= (lh264_parser_set_conceal): macroblocks no slice covers get concealment records, and
+    every frame says how many (concealed), from which picture (conceal_src, -1: 128s), whether it is withheld (frozen) and what the
+    vector was made of (conceal_info, see lh264_parser_frame_conceal).  For the decode direction only."""
+    return parse_stream(data, strict, _file=True, _pcm=pcm, _esc=escapes, _conceal=conceal)
 
 
 def parse_batch_time(datas, threads=0, keep=True):
@@ -68,14 +71,21 @@ def _read_frame(lib, p, i):
     ptr = lib.lh264_parser_frame_syn_symbols(p, i, C.byref(cnt))
     f.syn_syms = arr(ptr, cnt.value * 8, L.CTX_SYM_DTYPE) if cnt.value else np.zeros(0, L.CTX_SYM_DTYPE)
     f.syn_off = arr(lib.lh264_parser_frame_syn_offsets(p, i), (n + 1) * 4, "<u4")
+    ci = np.zeros(12, dtype="<i4")
+    L.check(lib.lh264_parser_frame_conceal(p, i, ci.ctypes.data_as(C.c_void_p)))
+    f.concealed, f.conceal_src, f.frozen, f.conceal_info, f.poc = int(ci[0]), int(ci[1]), bool(ci[2]), ci, int(ci[11])
     return f
 
 
-def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False):
+def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False, _conceal=None):
     """-> (frames, error_text).  frames have the attributes ReconSession / CtxSession expect."""
     lib = L.lib()
     p = lib.lh264_parser_create()
     try:
+        if _conceal is not None:
+            if _conceal not in L.CONCEAL:
+                raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
+            L.check(lib.lh264_parser_set_conceal(p, L.CONCEAL[_conceal]))
         if _file:
             rc = lib.lh264_parser_feed_file(p, bytes(data), len(data))
         else:
