@@ -29,31 +29,31 @@ def sha(b):
     return hashlib.sha1(bytes(b)).hexdigest()
 
 
-def data(name):
-    return open(os.path.join(EDGE_DIR, name + ".264"), "rb").read()
+def data(name, directory=EDGE_DIR):
+    return open(os.path.join(directory, name + ".264"), "rb").read()
 
 
 _made = {}
 
 
-def made():
+def made(script="make_edge_streams"):
     """{name: (bytes, the writer's counters)} from the generator script, run once"""
-    if not _made:
-        spec = importlib.util.spec_from_file_location("make_edge_streams", os.path.join(golden_io.GOLDEN_DIR, "make_edge_streams.py"))
+    if script not in _made:
+        spec = importlib.util.spec_from_file_location(script, os.path.join(golden_io.GOLDEN_DIR, script + ".py"))
         m = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(m)
-        _made.update(m.build())
-    return _made
+        _made[script] = m.build()
+    return _made[script]
 
 
 _parsed = {}
 
 
-def parsed(name):
-    """(frames, error text, default stream, I_PCM samples) of the host front end, once per stream"""
+def parsed(name, directory=EDGE_DIR):
+    """(frames, error text, default stream, I_PCM samples) of the host front end, once per stream (names are unique over directories)"""
     if name not in _parsed:
         import losslessh264_amd as lh
-        _parsed[name] = lh.parse_file(data(name), pcm=True)
+        _parsed[name] = lh.parse_file(data(name, directory), pcm=True)
     return _parsed[name]
 
 
@@ -78,10 +78,10 @@ def merged_symbols(frames):
 _compressed = {}
 
 
-def cpu_compress(name):
+def cpu_compress(name, directory=EDGE_DIR):
     """-> (default stream, {tag: bytes}) without a device: what lh264_compress_batch computes with its kernels"""
     if name not in _compressed:
-        frames, err, main, pcm = parsed(name)
+        frames, err, main, pcm = parsed(name, directory)
         assert err == "", (name, err)
         syms = merged_symbols(frames)
         L = O.lib()
@@ -118,10 +118,11 @@ def oracle_i420(frames):
     return b"".join(out)
 
 
-def same_as_reference_files(name, main, tags):
-    """the files equal the reference's recorded ones (our additional I_PCM stream and the tags of FILES_DIFFER aside, which must differ)"""
-    ref = REF[name]["files"]
+def same_as_reference_files(name, main, tags, record=None, files_differ=None):
+    """the files equal the reference's recorded ones (our additional I_PCM stream and the tags of FILES_DIFFER aside, which must differ);
+    record, files_differ: those of another set of streams"""
+    ref = (record or REF)[name]["files"]
     ours = {t: b for t, b in tags.items() if t != TAG_PCM and b}
     differ = {t for t in ours if str(t) in ref and sha(ours[t]) != ref[str(t)][1]}
     return set(str(t) for t in ours) == set(k for k in ref if k != "main") and sha(main) == ref["main"][1] and \
-        differ == FILES_DIFFER.get(name, set())
+        differ == (FILES_DIFFER if files_differ is None else files_differ).get(name, set())

@@ -14,6 +14,7 @@ import glob
 import hashlib
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -262,15 +263,16 @@ def sha1(b):
     return hashlib.sha1(b).hexdigest()
 
 
-def reference_verdict(name, data, tmp, pictures, mbs):
+def reference_verdict(name, data, tmp, pictures, mbs, messages=False):
+    """messages: keep what the restore said last when it did not end well (an assertion's text, without its source path)"""
     cli = os.path.join(ROOT, "oracle", "_ref", "h264dec")
     wd = os.path.join(tmp, name); os.makedirs(wd)
     src = os.path.join(wd, "in.264")
     open(src, "wb").write(data)
 
-    def run(*args):
+    def run(*args, log=None):
         try:
-            return subprocess.call([cli] + list(args), cwd=wd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+            return subprocess.call([cli] + list(args), cwd=wd, stdout=subprocess.DEVNULL, stderr=open(log, "wb") if log else subprocess.DEVNULL, timeout=900)
         except subprocess.TimeoutExpired:
             return -999
     rec = {"bytes": len(data), "sha1": sha1(data)}
@@ -288,9 +290,14 @@ def reference_verdict(name, data, tmp, pictures, mbs):
     for q in glob.glob(p + ".*"):
         b = open(q, "rb").read(); files[q.rsplit(".", 1)[1]] = [len(b), sha1(b)]
     rec["files"] = files
-    rec["restore_rc"] = run(p, os.path.join(wd, "back.264"))
+    rec["restore_rc"] = run(p, os.path.join(wd, "back.264"), log=os.path.join(wd, "restore.log") if messages else None)
     back = os.path.join(wd, "back.264")
     rec["reference_roundtrip"] = bool(os.path.exists(back) and open(back, "rb").read() == data)
+    if messages:
+        rec["restore_bytes"] = os.path.getsize(back) if os.path.exists(back) else 0
+        said = [ln for ln in open(os.path.join(wd, "restore.log"), errors="replace").read().splitlines() if ln.strip()]
+        last = said[-1] if said and rec["restore_rc"] != 0 else ""
+        rec["restore_message"] = re.sub(r"0x[0-9a-f]+", "0x..", re.sub(r"\S*/([\w.]+:\d+)", r"\1", re.sub(r"^\S*h264dec: ", "", last)))[:300]
     return rec
 
 

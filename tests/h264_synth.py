@@ -6,7 +6,8 @@ tables (coeff_token, total_zeros, run_before, coded_block_pattern) are read from
 
 The subset: SPS (profile 66 or 100, frame macroblocks only, POC type 2), PPS (CAVLC, deblocking control present), I and P slice
 headers (first_mb, num_ref_idx_active_override, sliding-window marking, no reordering), macroblocks P_Skip (as runs), P_L0_16x16,
-I16x16 with DC prediction, I_PCM; residual_block_cavlc in full.  Pure Python and deterministic.
+I16x16 with DC prediction, I_PCM; residual_block_cavlc in full.  Pure Python and deterministic.  tests/h264_synth_cabac.py builds
+on it: a slice may name another PPS ("pps") and carry cabac_init_idc ("init_idc"); _pps() writes further parameter sets.
 
 The writer counts what it wrote (Synth.count), so that a test can assert that a stream reaches the edge it is named after:
   skip_runs            every mb_skip_run written, in order
@@ -165,10 +166,10 @@ class Synth:
         b.trailing()
         self._nal(3, 7, b)
 
-    def _pps(self):
+    def _pps(self, pps_id=0, cabac=0, t8=0):
         b = Bits()
-        b.ue(0); b.ue(0)
-        b.u(1, 0)                                                # CAVLC
+        b.ue(pps_id); b.ue(0)
+        b.u(1, cabac)                                            # entropy_coding_mode_flag: CAVLC unless a subclass asks
         b.u(1, 0)                                                # bottom_field_pic_order_in_frame_present
         b.ue(0)                                                  # one slice group
         b.ue(0); b.ue(0)                                         # num_ref_idx default 1 / 1
@@ -177,7 +178,7 @@ class Synth:
         b.u(1, 1)                                                # deblocking_filter_control_present
         b.u(1, 0); b.u(1, 0)                                     # constrained_intra_pred, redundant_pic_cnt_present
         if self.profile == 100:
-            b.u(1, 0); b.u(1, 0); b.se(0)                        # transform_8x8_mode, no scaling matrices, second chroma offset
+            b.u(1, t8); b.u(1, 0); b.se(0)                       # transform_8x8_mode, no scaling matrices, second chroma offset
         b.trailing()
         self._nal(3, 8, b)
 
@@ -194,12 +195,11 @@ class Synth:
         self.frame_num = (self.frame_num + 1) % (1 << self.l2fn)
         self.count["pictures"] += 1
 
-    def _slice(self, si, s, idr):
-        C = self.count
+    def _header(self, b, s, idr):
+        """slice_header (7.3.3) up to and including the deblocking fields -> (num_ref_idx_l0_active, SliceQPY)"""
         is_p = s["type"] == "P"
-        b = Bits()
         b.u(8, 0)                                                # the NAL header's place, so that bit phases are those of the NAL unit
-        b.ue(s["first_mb"]); b.ue(5 if is_p else 7); b.ue(0)
+        b.ue(s["first_mb"]); b.ue(5 if is_p else 7); b.ue(s.get("pps", 0))
         b.u(self.l2fn, self.frame_num)
         if idr:
             b.ue(0)
@@ -215,12 +215,21 @@ class Synth:
             b.u(1, 0); b.u(1, 0)
         else:
             b.u(1, 0)                                            # sliding window
+        if is_p and s.get("init_idc") is not None:
+            b.ue(s["init_idc"])                                  # cabac_init_idc (slices of a CABAC PPS only)
         qp = s["qp"]
         b.se(qp - self.pic_init_qp)
         dis, al, be = s.get("deblock", (0, 0, 0))
         b.ue(dis)
         if dis != 1:
             b.se(al); b.se(be)
+        return num_ref, qp
+
+    def _slice(self, si, s, idr):
+        C = self.count
+        is_p = s["type"] == "P"
+        b = Bits()
+        num_ref, qp = self._header(b, s, idr)
         k, run = s["first_mb"], 0
         for kind, m in s["mbs"]:
             if kind == "skip":
@@ -239,8 +248,7 @@ class Synth:
                     b.u(1, 0)
                 for c in m:
                     b.u(8, c)
-                self.tc[k] = [16] * 24
-                qp = 0
+                self.tc[k] = [16] * 24                           # (no mb_qp_delta: QPY,PRED of the next macroblock stays, 7.4.5)
             elif kind == "p16":
                 assert is_p
                 b.ue(0)
