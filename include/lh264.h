@@ -598,12 +598,25 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * bytes = the first picture's first byte), in order within a stream, never from two threads at once, bytes valid for the call only;
  * a non-zero return stops that stream (LH264_E_ARG, text "sink").
  * The bytes do not depend on threads, round_pictures, group_mbs, the sink or on which other streams share the batch.
- * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a format out of range, sink together with
- * LH264_DECODE_DEVICE_OUT, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
+ * Digests (LH264_DECODE_SHA1_*): the SHA-1 of every delivered picture's bytes, and / or of all delivered pictures of the stream one
+ * behind the other - for I420 the number the reference's decoder test keeps per stream (test/api/decoder_test.cpp) - computed on the
+ * device from the round's packed buffer (sha1_spans_kernel), in every output mode.  A withheld picture has no index and no digest, a
+ * concealed picture is hashed as delivered, a stream that stops at picture k has the digests of the pictures in front of it and a
+ * stream digest over exactly their bytes, a stream without pictures the SHA-1 of the empty message.  With LH264_DECODE_NO_PICTURES
+ * nothing is downloaded or kept: lh264_decoded_picture still describes every picture, lh264_decoded_bytes / _bytes_dev give NULL and
+ * length 0.  The digests do not depend on threads, round_pictures, group_mbs, the output mode or the batch either.
+ * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a format out of range, a flag bit that is not
+ * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
+ * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
  * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
 #define LH264_FMT_I420 0
 #define LH264_FMT_NV12 1
 #define LH264_DECODE_DEVICE_OUT 1u   /* the pictures stay in device memory owned by the handle */
+/* (bits 2u and 16u are not defined and stay LH264_E_ARG, as every other bit: callers and tests of the library before the digests
+ * rely on 2u being refused) */
+#define LH264_DECODE_SHA1_PICTURES 4u /* a digest per delivered picture, of the bytes the call delivers (I420 or NV12 as asked) */
+#define LH264_DECODE_SHA1_STREAM 8u   /* one digest of all delivered pictures of the stream in order: the reference's table for I420 */
+#define LH264_DECODE_NO_PICTURES 32u  /* digests only: nothing is downloaded or kept */
 typedef struct lh264_decoded lh264_decoded_t;
 typedef struct lh264_decoded_pic { int32_t width, height, frame_num, idr; uint64_t offset, bytes; } lh264_decoded_pic_t;
 typedef int (*lh264_decode_sink_fn) (void* user, int stream, int first_picture, int n_pictures,
@@ -630,6 +643,10 @@ const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len); 
 /* DEVICE_OUT mode: the stream's bytes copied into the caller's device memory (cap >= their length), complete on return */
 int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap);
 void lh264_decoded_free (lh264_decoded_t* d);
+/* the 20 bytes of a digest the call was asked for.  LH264_E_ARG: a bad index, or a digest that was not asked for; a stream that
+ * carries LH264_E_HIP gives that status */
+int lh264_decoded_picture_sha1 (const lh264_decoded_t* d, int idx, uint8_t out[20]);
+int lh264_decoded_stream_sha1 (const lh264_decoded_t* d, uint8_t out[20]);
 int lh264_decode_arena_bytes (size_t* device, size_t* pinned);
 void lh264_decode_release (void);
 /* milliseconds of the last lh264_decode_batch call in this process: ms[0] the call, ms[1] parsing and picking the rounds' pictures
@@ -645,6 +662,11 @@ typedef struct lh264_pack_job {
   int32_t stride_y, stride_c, crop_x, crop_y, crop_w, crop_h, format, reserved;
 } lh264_pack_job_t;
 int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
+/* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
+ * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
+ * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message
+ * without a span is the empty message.  out: 20 bytes per message */
+int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out);
 
 #define LH264_OK            0
 #define LH264_E_NODEVICE   -1

@@ -18,6 +18,9 @@
                                                             by a sink run by run.  METHOD: lost slices are concealed as the reference's
                                                             decoder does (slice_copy | slice_copy_cross_idr | mv_copy |
                                                             slice_copy_cross_idr_freeze | mv_copy_freeze) instead of ending the stream
+    python -m losslessh264_amd --decode --sha1 [--nv12] [--conceal METHOD] out_dir in.264...   digests only, no .yuv: out_dir/<name>.sha1
+                                                            holds a line `index width height frame_num idr hex` per picture and a last
+                                                            line `stream hex`, the SHA-1 of all pictures in order (computed on the device)
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -142,10 +145,12 @@ def restore(src, dst):
 
 def decode(argv):
     import losslessh264_amd as lh
-    nv12, conceal = False, None
-    while argv and argv[0] in ("--nv12", "--conceal"):
+    nv12, conceal, sha1 = False, None, False
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1"):
         if argv[0] == "--nv12":
             nv12, argv = True, argv[1:]
+        elif argv[0] == "--sha1":
+            sha1, argv = True, argv[1:]
         else:
             if len(argv) < 2 or argv[1] not in lh._lib.CONCEAL:
                 print("--conceal: one of " + " | ".join(lh._lib.CONCEAL))
@@ -155,6 +160,11 @@ def decode(argv):
         print(__doc__)
         return 2
     ret = 0
+    if sha1:
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal):
+            print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
+            ret = ret or (1 if status else 0)
+        return ret
     for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)

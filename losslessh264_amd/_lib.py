@@ -128,7 +128,7 @@ _SIGS["lh264_compress_arena_bytes"] = (C.c_int, [C.POINTER(C.c_size_t), C.POINTE
 _SIGS["lh264_code_carry_decisions"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
 # ---- the decode direction behind one call
 FMT_I420, FMT_NV12 = 0, 1
-DECODE_DEVICE_OUT = 1
+DECODE_DEVICE_OUT, DECODE_SHA1_PICTURES, DECODE_SHA1_STREAM, DECODE_NO_PICTURES = 1, 4, 8, 32
 E_NODEVICE, E_ARG, E_HIP, E_UNSUPPORTED = -1, -2, -3, -4
 DECODED_PIC_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("frame_num", "<i4"), ("idr", "<i4"), ("offset", "<u8"), ("bytes", "<u8")])
 DECODE_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -163,6 +163,9 @@ _SIGS.update({
     "lh264_decode_release": (None, []),
     "lh264_decode_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "lh264_debug_pack_cpu": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_decoded_picture_sha1": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lh264_decoded_stream_sha1": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lh264_debug_sha1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "lh264_parser_set_sparse_coeffs": (C.c_int, [C.c_void_p, C.c_int]),
     "lh264_parser_frame_sparse_coeffs": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
 })

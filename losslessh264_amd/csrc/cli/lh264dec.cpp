@@ -13,6 +13,8 @@
 //   lh264dec --batch out_dir a.264 b.264 ...   many streams in one lh264_compress_batch call -> out_dir/<name>.lhp
 //   lh264dec --decode [--nv12] out_dir a.264 b.264 ...   many streams in one lh264_decode_batch call -> out_dir/<name>.yuv: the
 //                                       cropped pictures as I420 (or NV12), appended by a sink run by run (the file's size bounds nothing)
+//   lh264dec --decode --sha1 [--nv12] out_dir a.264 ...   digests only, no .yuv: out_dir/<name>.sha1 with a line `index width height
+//                                       frame_num idr hex` per picture and a last line `stream hex`, the SHA-1 of all of them in order
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
 #include <stdio.h>
@@ -217,6 +219,42 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   return ret;
 }
 
+// --decode --sha1: one digests-only lh264_decode_batch; no picture leaves the device
+static std::string hex20 (const uint8_t* d) { char b[41]; for (int k = 0; k < 20; k++) snprintf (b + 2 * k, 3, "%02x", d[k]); return std::string (b, 40); }
+static int decode_sha1_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal) {
+  const int n = (int)srcs.size();
+  std::vector<Bytes> in (n);
+  std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
+  for (int i = 0; i < n; i++) { if (!load (srcs[i], in[i])) { perror (srcs[i].c_str()); return 2; } d[i] = in[i].data(); l[i] = in[i].size(); }
+  lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal;
+  o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
+  std::vector<lh264_decoded_t*> h (n, nullptr);
+  const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
+  if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
+  int ret = 0;
+  for (int i = 0; i < n; i++) {
+    const int st = lh264_decoded_status (h[i]);
+    const std::string dst = out_dir + "/" + base_name (srcs[i]) + ".sha1";
+    FILE* f = fopen (dst.c_str(), "w");
+    if (!f) { perror (dst.c_str()); ret = 2; lh264_decoded_free (h[i]); continue; }
+    uint8_t dig[20];
+    const int np = lh264_decoded_pictures (h[i]);
+    for (int k = 0; k < np; k++) {
+      lh264_decoded_pic_t p;
+      if (lh264_decoded_picture (h[i], k, &p) != LH264_OK || lh264_decoded_picture_sha1 (h[i], k, dig) != LH264_OK) { ret = 1; break; }
+      fprintf (f, "%d %d %d %d %d %s\n", k, p.width, p.height, p.frame_num, p.idr, hex20 (dig).c_str());
+    }
+    std::string total;
+    if (lh264_decoded_stream_sha1 (h[i], dig) == LH264_OK) { total = hex20 (dig); fprintf (f, "stream %s\n", total.c_str()); } else ret = 1;
+    fclose (f);
+    printf ("%s -> %s: %d pictures, stream %s%s%s\n", srcs[i].c_str(), dst.c_str(), np, total.c_str(), st == LH264_OK ? "" : "  [stopped: ", st == LH264_OK ? "" : (std::string (lh264_decoded_error (h[i])) + "]").c_str());
+    if (st != LH264_OK) ret = 1;
+    lh264_decoded_free (h[i]);
+  }
+  return ret;
+}
+
 static int restore_single (const std::string& src, const std::string& dst) {
   Bytes f;
   if (!load (src, f)) { perror (src.c_str()); return 2; }
@@ -242,22 +280,23 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    bool nv12 = false; int conceal = 0, first = 2;
+    bool nv12 = false, sha1 = false; int conceal = 0, first = 2;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
+      else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
       else if (first + 1 < argc && !strcmp (argv[first], "--conceal")) {
         conceal = conceal_method (argv[first + 1]);
         if (conceal < 0) { fprintf (stderr, "--conceal: off | slice_copy | slice_copy_cross_idr | slice_copy_cross_idr_freeze | mv_copy | mv_copy_freeze\n"); return 2; }
         first += 2;
       } else break;
     }
-    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
-    return decode_files (argv[first], srcs, nv12, conceal);
+    return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal) : decode_files (argv[first], srcs, nv12, conceal);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

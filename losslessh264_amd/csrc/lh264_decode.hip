@@ -21,6 +21,7 @@
 #include "host/h264_parser.h"
 #include "host/capi_internal.h"
 #include "host/device_mem.h"
+#include "lh264_sha1.h"
 
 // ---- the pack step: crop + I420 / NV12, host and device from one source ------------------------------------------------------------
 // A picture is cut into bands of 16 luma rows (and the 8 chroma rows that belong to them); a band's rows are cut into PIECES: the
@@ -117,6 +118,15 @@ __global__ void __launch_bounds__ (256) decode_pack_kernel (const lh264_pack_job
   lh264pack::pack_band (j, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
+// ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
+// One lane per span job, 64 jobs per wave (a message is serial; the width comes from the batch).  The host orders a launch's jobs by
+// descending length, so the lanes of a wave end near one another.  No LDS, no wave waits for another; every bound is the job's.
+__global__ void __launch_bounds__ (64) sha1_spans_kernel (const lh264_sha1_job_t* __restrict__ jobs, int n) {
+  const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (i >= n) return;
+  lh264sha1::run_job (jobs[i]);
+}
+
 struct lh264_decoded {
   int status = LH264_OK;
   std::string error;
@@ -124,6 +134,11 @@ struct lh264_decoded {
   std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
+  uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
+  std::vector<uint8_t> pic_sha;                 // 20 bytes per delivered picture
+  lh264_sha1_state_t stream_state;              // the stream's message behind the last round delivered
+  uint8_t stream_sha[20];
+  lh264_decoded() { lh264sha1::init (&stream_state); memset (stream_sha, 0, 20); }
   ~lh264_decoded() {
     if (!dev) return;
     int cur = 0;
@@ -181,6 +196,10 @@ struct PicCache {
 struct Arena {
   DevBuf d_mbs, d_coef, d_sparse, d_sl, d_jobs, d_first, d_pack, d_out[2];
   PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
+  // digests: the span jobs, a round's results (20 bytes per picture, then a copy of every chain's stream record), the records of the
+  // picture messages (scratch), and one record per stream of the batch that lives as long as the call
+  DevBuf d_sjobs, d_dig, d_rec, d_state;
+  PinBuf h_sjobs[2], h_dig[2];
   PicCache pics;
   hipStream_t s_run = nullptr, s_down = nullptr;
   hipEvent_t e_run[2] = {nullptr, nullptr}, e_down[2] = {nullptr, nullptr};
@@ -199,12 +218,12 @@ struct Arena {
   }
   size_t device_bytes() const {
     size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
-    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack}) n += b->cap;
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state}) n += b->cap;
     return n;
   }
   size_t pinned_bytes() const {
     size_t n = 0;
-    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap;
+    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap;
     return n;
   }
 };
@@ -229,6 +248,7 @@ struct DStream {
   std::vector<Slot> pool;
   // set by select(): the stream ends behind the pictures selected
   bool ending = false; int end_code = LH264_OK; std::string end_text;
+  bool sha_started = false;                          // the stream's digest record on the device holds its message so far
   bool stopped = false;                              // the sink refused, or the device stage failed: nothing more is delivered
   std::vector<std::unique_ptr<FrameOut>> sel;        // the pictures of the round in preparation
 };
@@ -240,8 +260,9 @@ struct RoundChain {
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed;
   size_t at = 0, bytes = 0;                          // in the round's output buffer
+  size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
 };
-struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0; bool live = false; };
+struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0, dig_states_at = 0; bool live = false; };
 
 std::string refuse_picture (const FrameOut& f) {
   const size_t n = (size_t)f.mb_w * f.mb_h;
@@ -274,15 +295,70 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n) {
   return LH264_OK;
 }
 
+int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
+  if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
+  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
+  uint64_t end = 0;
+  size_t steps = 1;
+  for (int k = 0; k < n_spans; k++) {
+    const uint64_t m = spans[3 * k], off = spans[3 * k + 1], ln = spans[3 * k + 2];
+    if (m >= (uint64_t)n_messages || off + ln < off) return LH264_E_ARG;
+    of[m].push_back ({off, ln});
+    end = std::max (end, off + ln);
+    steps = std::max (steps, of[m].size());
+  }
+  if (!n_messages) return LH264_OK;
+  if (on_device && lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  std::vector<lh264_sha1_state_t> h_state ((size_t)n_messages);
+  uint8_t* d_bytes = nullptr; lh264_sha1_state_t* d_state = nullptr; uint8_t* d_dig = nullptr; lh264_sha1_job_t* d_jobs = nullptr;
+  bool ok = true;
+  if (on_device) {
+    ok = hipMalloc ((void**)&d_bytes, end + 16) == hipSuccess && hipMalloc ((void**)&d_state, (size_t)n_messages * sizeof (lh264_sha1_state_t)) == hipSuccess &&
+         hipMalloc ((void**)&d_dig, (size_t)n_messages * 20) == hipSuccess && hipMalloc ((void**)&d_jobs, (size_t)n_messages * sizeof (lh264_sha1_job_t)) == hipSuccess &&
+         (!end || hipMemcpy (d_bytes, bytes, end, hipMemcpyHostToDevice) == hipSuccess);
+  }
+  // step k: the k-th span of every message that has one (a message without spans is the empty message, ended in step 0)
+  std::vector<lh264_sha1_job_t> jobs;
+  for (size_t k = 0; k < steps && ok; k++) {
+    jobs.clear();
+    for (int m = 0; m < n_messages; m++) {
+      const size_t ns = of[m].size();
+      if (k >= ns && !(k == 0 && ns == 0)) continue;
+      lh264_sha1_job_t j;
+      j.src = (on_device ? d_bytes : bytes) + (ns ? of[m][k].first : 0); j.len = ns ? of[m][k].second : 0;
+      j.state = on_device ? d_state + m : &h_state[m];
+      j.out = (on_device ? d_dig : out) + (size_t)m * 20;
+      j.flags = (k == 0 ? LH264_SHA1_FRESH : 0) | (k + 1 >= ns ? LH264_SHA1_FINAL : 0); j.reserved = 0;
+      if (!(j.flags & LH264_SHA1_FINAL)) j.out = nullptr;
+      jobs.push_back (j);
+    }
+    std::stable_sort (jobs.begin(), jobs.end(), [] (const lh264_sha1_job_t& a, const lh264_sha1_job_t& b) { return a.len > b.len; });
+    if (!on_device) { for (const lh264_sha1_job_t& j : jobs) lh264sha1::run_job (j); continue; }
+    if (jobs.empty()) continue;
+    ok = hipMemcpy (d_jobs, jobs.data(), jobs.size() * sizeof (lh264_sha1_job_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) { hipLaunchKernelGGL (sha1_spans_kernel, dim3 ((unsigned) ((jobs.size() + 63) / 64)), dim3 (64), 0, 0, d_jobs, (int)jobs.size()); ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess; }
+  }
+  if (on_device) {
+    ok = ok && hipMemcpy (out, d_dig, (size_t)n_messages * 20, hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree (d_bytes); hipFree (d_state); hipFree (d_dig); hipFree (d_jobs);
+  }
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 || (opts->flags & ~LH264_DECODE_DEVICE_OUT) ||
-               (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)))) return LH264_E_ARG;
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
+               (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
+               (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
+               ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
   const int conceal = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? (int)opts->conceal : 0;
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
   const bool device_out = opts && (opts->flags & LH264_DECODE_DEVICE_OUT);
+  const bool no_pictures = opts && (opts->flags & LH264_DECODE_NO_PICTURES);          // digests only: nothing is downloaded or kept
+  const bool sha_pics = opts && (opts->flags & LH264_DECODE_SHA1_PICTURES), sha_stream = opts && (opts->flags & LH264_DECODE_SHA1_STREAM);
+  const bool sha = sha_pics || sha_stream;
   const lh264_decode_sink_fn sink = opts ? opts->sink : nullptr;
   void* const sink_user = opts ? opts->user : nullptr;
   const size_t R = opts && opts->round_pictures ? opts->round_pictures : kDefaultRoundPictures;
@@ -291,7 +367,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   if (threads < 1) threads = 1;
   int device = 0;
   if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
-  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; }
+  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sha = opts ? opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM) : 0; }
   auto arena_lock = g_arena.lock (device);
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
@@ -362,7 +438,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     if (!rd.live) return;
     rd.live = false;
     const double t0 = now_s();
-    if (!device_failed && hipEventSynchronize (device_out ? A.e_run[b] : A.e_down[b]) != hipSuccess) fail_device ("the device stage failed");
+    if (!device_failed && hipEventSynchronize (device_out || no_pictures ? A.e_run[b] : A.e_down[b]) != hipSuccess) fail_device ("the device stage failed");
     const double t1 = now_s();
     t_wait += t1 - t0;
     if (device_failed) {
@@ -370,8 +446,16 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       return;
     }
     const uint8_t* hb = A.h_out[b].as<uint8_t>();
+    // the round's digests came down on the run stream, in front of the event: the pictures' 20 bytes, and the stream's record as this
+    // round leaves it (a stream's digest covers the rounds that were delivered, whatever is on the device behind them)
+    const uint8_t* hd = A.h_dig[b].as<uint8_t>();
+    auto take_digests = [&] (RoundChain& c, lh264_decoded_t& r, int k) {
+      if (sha_pics) r.pic_sha.insert (r.pic_sha.end(), hd + c.dig0 * 20, hd + (c.dig0 + c.pics.size()) * 20);
+      if (sha_stream) memcpy (&r.stream_state, hd + rd.dig_states_at + (size_t)k * sizeof (lh264_sha1_state_t), sizeof (lh264_sha1_state_t));
+    };
     if (sink) {
-      for (RoundChain& c : rd.chains) {
+      for (size_t k = 0; k < rd.chains.size(); k++) {
+        RoundChain& c = rd.chains[k];
         if (c.s->stopped) continue;
         lh264_decoded_t& r = *out[c.s->i];
         if (c.pics.empty()) continue;
@@ -381,15 +465,17 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         }
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
+        if (sha) take_digests (c, r, (int)k);
       }
     } else {
       run_parallel ((int)rd.chains.size(), threads, [&] (int k) {
         RoundChain& c = rd.chains[k];
         if (c.s->stopped) return;
         lh264_decoded_t& r = *out[c.s->i];
-        if (!device_out) r.bytes.insert (r.bytes.end(), hb + c.at, hb + c.at + c.bytes);
+        if (!device_out && !no_pictures) r.bytes.insert (r.bytes.end(), hb + c.at, hb + c.at + c.bytes);
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
+        if (sha) take_digests (c, r, k);
       });
     }
     t_deliver += now_s() - t1;
@@ -433,14 +519,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     rd.chains.clear(); rd.out_bytes = 0;
     struct Place { size_t mb0, sl0, sp0, job0; };
     std::vector<Place> place;
-    size_t n_mbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0;
+    size_t n_mbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0;
     int max_w = 1, max_h = 1, max_bands = 1;
     bool alloc_ok = true;
     for (auto& sp : active) {
       DStream& s = *sp;
       if (s.sel.empty()) continue;
-      size_t m = 0, sl = 0, ents = 0, bytes = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; }
+      size_t m = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -449,7 +535,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s.geo.bytes = (lh264_pic_bytes (f0.mb_w, f0.mb_h, &s.geo.stride_y, &s.geo.stride_c, &s.geo.off[0], &s.geo.off[1], &s.geo.off[2]) + 255) & ~ (size_t)255;
       }
       RoundChain c;
-      c.s = &s; c.first_picture = (int)s.delivered; c.at = rd.out_bytes; c.bytes = bytes;
+      c.s = &s; c.first_picture = (int)s.delivered; c.at = rd.out_bytes; c.bytes = bytes; c.n_out = shown; c.dig0 = n_out;
+      n_out += shown;
       place.push_back ({n_mbs, n_sl, n_sp, n_jobs});
       n_mbs += m; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       rd.out_bytes += (bytes + 15) & ~ (size_t)15;
@@ -464,9 +551,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     const int n_chains = (int)rd.chains.size();
     alloc_ok = A.d_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_mbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_chains + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
-               A.d_out[rb].alloc (rd.out_bytes) && (device_out || A.h_out[rb].alloc (rd.out_bytes)) &&
+               A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
                A.h_mbs[rb].alloc (n_mbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_chains + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
+    const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
+    rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
+    const size_t dig_bytes = rd.dig_states_at + (size_t)n_chains * sizeof (lh264_sha1_state_t);
+    if (sha) alloc_ok = alloc_ok && A.d_sjobs.alloc (n_sjobs * sizeof (lh264_sha1_job_t)) && A.h_sjobs[rb].alloc (n_sjobs * sizeof (lh264_sha1_job_t)) && A.d_dig.alloc (dig_bytes) &&
+                          A.h_dig[rb].alloc (dig_bytes) && A.d_rec.alloc (n_out * sizeof (lh264_sha1_state_t)) && A.d_state.alloc ((size_t)n * sizeof (lh264_sha1_state_t));
     // picture slots (serial: the cache is shared).  A picture takes a slot that was free when the round began; a slot becomes free
     // behind the round when its picture is in no DPB any more - the round's pictures are all packed by then
     std::vector<std::vector<int>> slot_of (n_chains);
@@ -539,6 +631,25 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       }
     });
     h_first[n_chains] = (int32_t)n_jobs;
+    if (sha) {
+      // the span jobs: a picture is a message of its own (its record is scratch), a chain's bytes are the next span of its stream's
+      // message, whose record stays on the device from round to round; a copy of it comes down with the round
+      lh264_sha1_job_t* sj = A.h_sjobs[rb].as<lh264_sha1_job_t>();
+      size_t q = 0;
+      for (int c = 0; c < n_chains; c++) {
+        RoundChain& rc = rd.chains[c];
+        size_t at = rc.at;
+        if (sha_pics) for (size_t k = 0; k < rc.pics.size(); k++) {
+          sj[q++] = {d_out + at, rc.pics[k].bytes, A.d_rec.as<lh264_sha1_state_t>() + rc.dig0 + k, A.d_dig.as<uint8_t>() + (rc.dig0 + k) * 20, LH264_SHA1_FRESH | LH264_SHA1_FINAL, 0};
+          at += rc.pics[k].bytes;
+        }
+        if (sha_stream) {
+          sj[q++] = {d_out + rc.at, rc.bytes, A.d_state.as<lh264_sha1_state_t>() + rc.s->i, A.d_dig.as<uint8_t>() + rd.dig_states_at + (size_t)c * sizeof (lh264_sha1_state_t), rc.s->sha_started ? 0u : (uint32_t)LH264_SHA1_FRESH, 0};
+          rc.s->sha_started = true;
+        }
+      }
+      std::stable_sort (sj, sj + q, [] (const lh264_sha1_job_t& a, const lh264_sha1_job_t& b) { return a.len > b.len; });
+    }
     for (int c = 0; c < n_chains; c++) {
       DStream& s = *rd.chains[c].s;
       for (auto& f : s.sel) max_bands = std::max (max_bands, (f->crop_h + lh264pack::kBandRows - 1) / lh264pack::kBandRows);
@@ -562,6 +673,11 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
       if (ok) { hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>()); ok = hipGetLastError() == hipSuccess; }
+      if (ok && sha) {
+        ok = up (A.d_sjobs, A.h_sjobs[rb].p, n_sjobs * sizeof (lh264_sha1_job_t));
+        if (ok && n_sjobs) { hipLaunchKernelGGL (sha1_spans_kernel, dim3 ((unsigned) ((n_sjobs + 63) / 64)), dim3 (64), 0, st, A.d_sjobs.as<lh264_sha1_job_t>(), (int)n_sjobs); ok = hipGetLastError() == hipSuccess; }
+        ok = ok && hipMemcpyAsync (A.h_dig[rb].p, A.d_dig.p, dig_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+      }
       if (ok && device_out) {
         // the pictures stay on the device: every stream's run goes behind what its handle holds (the buffer grows by doubling)
         for (RoundChain& c : rd.chains) {
@@ -580,7 +696,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         }
       }
       ok = ok && hipEventRecord (A.e_run[rb], st) == hipSuccess;
-      if (ok && !device_out) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
+      if (ok && !device_out && !no_pictures) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
                                   (!rd.out_bytes || hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess) &&
                                   hipEventRecord (A.e_down[rb], A.s_down) == hipSuccess;
       if (!ok) { const char* le = lh264_last_error(); fail_device (std::string ("launching the device stage failed") + (le && *le ? std::string (": ") + le : std::string())); for (RoundChain& c : rd.chains) c.s->stopped = true; }
@@ -597,6 +713,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   hipStreamSynchronize (A.s_down);
   for (auto& s : active) finish (*s);
   active.clear(); retired.clear();
+  if (sha_stream) for (int i = 0; i < n; i++) { lh264_sha1_state_t fin = out[i]->stream_state; lh264sha1::finish (&fin, out[i]->stream_sha); }
   // (streams that were complete before a failure of the device stage keep their result; the others carry the error)
   if (device_failed) for (int i = next_stream; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = device_error; }
   g_timing[0] = (now_s() - t_call) * 1e3; g_timing[1] = t_parse * 1e3; g_timing[2] = t_stage * 1e3; g_timing[3] = t_enqueue * 1e3; g_timing[4] = t_wait * 1e3; g_timing[5] = t_deliver * 1e3;
@@ -629,6 +746,20 @@ const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len) {
 int lh264_decoded_copy_dev (const lh264_decoded_t* d, void* dst_dev, size_t cap) {
   if (!d || !dst_dev || cap < d->dev_len) return LH264_E_ARG;
   if (d->dev_len && hipMemcpy (dst_dev, d->dev, d->dev_len, hipMemcpyDeviceToDevice) != hipSuccess) return LH264_E_HIP;
+  return LH264_OK;
+}
+int lh264_decoded_picture_sha1 (const lh264_decoded_t* d, int idx, uint8_t out[20]) {
+  if (!d || !out) return LH264_E_ARG;
+  if (d->status == LH264_E_HIP) return d->status;
+  if (!(d->sha & LH264_DECODE_SHA1_PICTURES) || idx < 0 || (size_t)idx >= d->pics.size() || d->pic_sha.size() != d->pics.size() * 20) return LH264_E_ARG;
+  memcpy (out, &d->pic_sha[(size_t)idx * 20], 20);
+  return LH264_OK;
+}
+int lh264_decoded_stream_sha1 (const lh264_decoded_t* d, uint8_t out[20]) {
+  if (!d || !out) return LH264_E_ARG;
+  if (d->status == LH264_E_HIP) return d->status;
+  if (!(d->sha & LH264_DECODE_SHA1_STREAM)) return LH264_E_ARG;
+  memcpy (out, d->stream_sha, 20);
   return LH264_OK;
 }
 int lh264_decoded_concealed (const lh264_decoded_t* d, int idx) {

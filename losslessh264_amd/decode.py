@@ -8,6 +8,7 @@ import numpy as np
 from . import _lib as L
 
 _FORMATS = {"i420": L.FMT_I420, "nv12": L.FMT_NV12}
+_SHA1 = {None: 0, "pictures": L.DECODE_SHA1_PICTURES, "stream": L.DECODE_SHA1_STREAM, "both": L.DECODE_SHA1_PICTURES | L.DECODE_SHA1_STREAM}
 
 
 class _DevSpan:
@@ -48,8 +49,23 @@ class DecodedBatch:
         """per delivered picture of stream i: the number of its macroblocks that were concealed (all 0 without conceal=)"""
         return [self._lib.lh264_decoded_concealed(self._h[i], k) for k in range(self._lib.lh264_decoded_pictures(self._h[i]))]
 
+    def picture_sha1(self, i):
+        """sha1="pictures" | "both": the SHA-1 of every delivered picture of stream i, as delivered (20-byte bytes objects)"""
+        out = []
+        buf = (C.c_uint8 * 20)()
+        for k in range(self._lib.lh264_decoded_pictures(self._h[i])):
+            L.check(self._lib.lh264_decoded_picture_sha1(self._h[i], k, buf))
+            out.append(bytes(buf))
+        return out
+
+    def stream_sha1(self, i):
+        """sha1="stream" | "both": the SHA-1 of all delivered pictures of stream i, one behind the other (20 bytes)"""
+        buf = (C.c_uint8 * 20)()
+        L.check(self._lib.lh264_decoded_stream_sha1(self._h[i], buf))
+        return bytes(buf)
+
     def data(self, i):
-        """the packed pictures of stream i as bytes (empty with device_out=True or a sink)"""
+        """the packed pictures of stream i as bytes (empty with device_out=True, a sink or pictures=False)"""
         ln = C.c_size_t(0)
         ptr = self._lib.lh264_decoded_bytes(self._h[i], C.byref(ln))
         return C.string_at(ptr, ln.value) if ptr and ln.value else b""
@@ -89,7 +105,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -98,12 +114,19 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     conceal: None / "off" (a picture with macroblocks no slice covers stops its stream) or how such macroblocks are concealed, as the
     reference's decoder does under the ERROR_CON_IDC of that name: "slice_copy" | "slice_copy_cross_idr" | "mv_copy" (slice MV copy
     across IDR) | "slice_copy_cross_idr_freeze" | "mv_copy_freeze" (the FREEZE_RES_CHANGE variants: pictures are withheld until the
-    first whole IDR picture).  DecodedBatch.concealed(i) counts the concealed macroblocks per picture."""
+    first whole IDR picture).  DecodedBatch.concealed(i) counts the concealed macroblocks per picture.
+    sha1: None | "pictures" | "stream" | "both": SHA-1 digests computed on the device, of every delivered picture
+    (DecodedBatch.picture_sha1) and / or of all delivered pictures of a stream in order (stream_sha1: for "i420" the number the
+    reference's decoder test keeps per stream).  pictures=False (with sha1): digests only, no picture leaves the device."""
     lib = L.lib()
     if fmt not in _FORMATS:
         raise ValueError("fmt must be 'i420' or 'nv12'")
     if conceal is not None and conceal not in L.CONCEAL:
         raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
+    if sha1 not in _SHA1:
+        raise ValueError("sha1 must be None, 'pictures', 'stream' or 'both'")
+    if not pictures and (sha1 is None or device_out or sink is not None):
+        raise ValueError("pictures=False needs sha1= and neither device_out nor a sink")
     n = len(datas)
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
@@ -111,7 +134,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     opts = L.DecodeOpts()
     opts.struct_bytes = C.sizeof(L.DecodeOpts)
     opts.format = _FORMATS[fmt]
-    opts.flags = L.DECODE_DEVICE_OUT if device_out else 0
+    opts.flags = (L.DECODE_DEVICE_OUT if device_out else 0) | _SHA1[sha1] | (0 if pictures else L.DECODE_NO_PICTURES)
     opts.round_pictures = int(round_pictures or 0)
     opts.group_mbs = int(group_mbs or 0)
     opts.conceal = L.CONCEAL[conceal or "off"]
@@ -164,4 +187,29 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None):
             f.close()
     res = [(names[i], b.status(i), b.error(i), len(b.pictures(i)), total[i]) for i in range(len(paths))]
     b.free()
+    return res
+
+
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None):
+    """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]"""
+    datas = [open(p, "rb").read() for p in paths]
+    os.makedirs(out_dir, exist_ok=True)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False)
+    res = []
+    try:
+        for i, p in enumerate(paths):
+            name = os.path.join(out_dir, os.path.basename(p) + ".sha1")
+            st = b.status(i)
+            pics = b.pictures(i) if st != L.E_HIP else []
+            digs = b.picture_sha1(i) if pics else []
+            total = b.stream_sha1(i).hex() if st != L.E_HIP else ""
+            with open(name, "w") as f:
+                for k, (w, h, fn, idr, _off, _n) in enumerate(pics):
+                    f.write("%d %d %d %d %d %s\n" % (k, w, h, fn, idr, digs[k].hex()))
+                if st != L.E_HIP:
+                    f.write("stream %s\n" % total)
+            res.append((name, st, b.error(i), len(pics), total))
+    finally:
+        b.free()
     return res
