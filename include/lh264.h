@@ -110,7 +110,14 @@ typedef struct lh264_slice {
   int16_t  luma_offset[LH264_MAX_REFS];
   int16_t  chroma_weight[LH264_MAX_REFS][2];
   int16_t  chroma_offset[LH264_MAX_REFS][2];
-  int8_t   ref_slot[LH264_MAX_REFS]; /* ref_idx -> index into lh264_frame_job_t.ref (sRefPic.pRefList[LIST_0]) */
+  int8_t   ref_slot[LH264_MAX_REFS]; /* ref_idx -> index into lh264_frame_job_t.ref (sRefPic.pRefList[LIST_0]); -1: no picture,
+                                   the partition then predicts from list entry 0 (rec_mb.cpp:229-233).  RULE: an inter macroblock
+                                   whose slice has ref_slot[0] < 0, or whose job has no ref[0], is defined only where ref[0] of the job
+                                   is a picture of 128s that nothing writes - the reference reads a null picture there, the oracle
+                                   predicts nothing and keeps its fresh picture's 128, the kernel reads job reference 0.  The front
+                                   end emits such pictures only in front of a stream's first IDR picture (the IDR was lost);
+                                   lh264_decode_batch supplies the 128s, every other caller must not hand such a record to the
+                                   device (ReconSession refuses it) */
   uint8_t  luma_dc_weight;      /* Intra-Y 4x4 scaling-list entry [0] (16 = flat): feeds kiQMul of
                                    WelsLumaDcDequantIdct, decode_slice.cpp:272                      */
   uint8_t  reserved[7];
@@ -667,6 +674,11 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message
  * without a span is the empty message.  out: 20 bytes per message */
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out);
+/* the launch geometry lh264_recon_chains / lh264_recon_frames would choose for pictures of at most max_mb_w x max_mb_h macroblocks:
+ * waves per workgroup (one per macroblock row in flight, at most 8, halved until the LDS line buffers fit; LH264_WAVES is honoured as
+ * in a launch) and the dynamic LDS bytes.  Read-only, needs no device.  LH264_E_UNSUPPORTED with the launch's own text when one wave
+ * does not fit (the outputs are still written: 1 wave and the bytes it would need); LH264_E_ARG: a dimension <= 0 */
+int lh264_debug_recon_geometry (int max_mb_w, int max_mb_h, int* waves, size_t* lds_bytes);
 
 #define LH264_OK            0
 #define LH264_E_NODEVICE   -1

@@ -201,6 +201,13 @@ def pic_geometry(mb_w, mb_h):
     total = lib().lh264_pic_bytes(mb_w, mb_h, C.byref(sy), C.byref(sc), C.byref(oy), C.byref(ou), C.byref(ov))
     return sy.value, sc.value, oy.value, ou.value, ov.value, total
 
+def recon_geometry(max_mb_w, max_mb_h):
+    """-> (status, waves, LDS bytes) of the reconstruct launch for pictures of at most this size (needs no device)"""
+    nw, lds = C.c_int(), C.c_size_t()
+    rc = lib().lh264_debug_recon_geometry(max_mb_w, max_mb_h, C.byref(nw), C.byref(lds))
+    return rc, nw.value, lds.value
+
+
 # ---- context-index (row a8) ----------------------------------------------------------------------------------
 # row a10 syntax record (lh264_mbsyn_t, byte-packed)
 MBSYN_DTYPE = np.dtype([
@@ -232,4 +239,5 @@ _SIGS["lh264_debug_restore_cpu_opts"] = (C.c_int, [C.c_void_p, C.c_int, C.c_void
 _SIGS["lh264_debug_dp_update"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
 _SIGS["lh264_restore_release"] = (None, [])
 _SIGS["lh264_restore_last_timing"] = (C.c_int, [C.POINTER(C.c_double)])
+_SIGS["lh264_debug_recon_geometry"] = (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)])
 EXPORTS = sorted(_SIGS)

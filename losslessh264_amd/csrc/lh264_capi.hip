@@ -171,6 +171,9 @@ static int pick_waves (int max_mb_w, int max_mb_h, int slot_bytes, size_t* lds_o
   }
 }
 
+static int recon_slot_bytes (int max_mb_w) { return 128 * max_mb_w + 96; }
+static const char* const kTooWide = "picture too wide for the LDS line buffers";
+
 // per device: what the reconstruct launches keep between calls
 namespace {
 struct ReconDev {
@@ -187,10 +190,10 @@ static int launch_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chai
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
   if (!jobs_dev || !chain_first_dev || n_chains < 0 || max_mb_w <= 0 || max_mb_h <= 0) return fail (LH264_E_ARG, "bad argument");
   if (n_chains == 0) return LH264_OK;
-  const int slot_bytes = 128 * max_mb_w + 96;
+  const int slot_bytes = recon_slot_bytes (max_mb_w);
   size_t lds = 0;
   const int nw = pick_waves (max_mb_w, max_mb_h, slot_bytes, &lds);
-  if (lds > 160 * 1024) return fail (LH264_E_UNSUPPORTED, "picture too wide for the LDS line buffers");
+  if (lds > 160 * 1024) return fail (LH264_E_UNSUPPORTED, kTooWide);
   const auto raise_lds_limit = [] (ReconDev& R) {
     if (!R.attr_set) {
       HIPCHK (hipFuncSetAttribute ((const void*)lh264::recon_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -212,6 +215,17 @@ static int launch_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chai
 int lh264_recon_chains (const lh264_frame_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains,
                         int max_mb_w, int max_mb_h, void* stream) {
   return launch_chains (jobs_dev, chain_first_dev, n_chains, max_mb_w, max_mb_h, (hipStream_t)stream);
+}
+
+// what launch_chains would launch with: no device is looked at
+int lh264_debug_recon_geometry (int max_mb_w, int max_mb_h, int* waves, size_t* lds_bytes) {
+  if (max_mb_w <= 0 || max_mb_h <= 0) return fail (LH264_E_ARG, "bad argument");
+  size_t lds = 0;
+  const int nw = pick_waves (max_mb_w, max_mb_h, recon_slot_bytes (max_mb_w), &lds);
+  if (waves) *waves = nw;
+  if (lds_bytes) *lds_bytes = lds;
+  if (lds > 160 * 1024) return fail (LH264_E_UNSUPPORTED, kTooWide);
+  return LH264_OK;
 }
 
 int lh264_recon_frames (const lh264_frame_job_t* jobs_dev, int n_jobs, int max_mb_w, int max_mb_h, void* stream) {

@@ -23,6 +23,13 @@ class ReconSession:
     """
 
     def __init__(self, streams, device=0, flags=0, replicate=1, share_records=True, ring=0):
+        # the rule beside ref_slot in include/lh264.h: the kernel would read job reference 0, which this session does not fill
+        for st in streams:
+            for f in st:
+                inter = (np.asarray(f.mbs["mb_type"]) & 0x1F8) != 0
+                if inter.any() and (len(f.ref_ids) == 0 or (np.asarray(f.slices["ref_slot"])[f.mbs["slice_id"][inter], 0] < 0).any()):
+                    raise ValueError("losslessh264_amd: picture %d holds inter macroblocks without reference 0 (ref_slot[0] < 0 or no "
+                                     "reference picture): not defined outside decode_batch" % f.id)
         torch = _torch()
         self.torch = torch
         self.lib = L.lib()

@@ -24,6 +24,7 @@ void orc_deblock_luma_eq4 (uint8_t* pix, int xstride, int ystride, int alpha, in
 void orc_deblock_chroma_lt4 (uint8_t* pix, int xstride, int ystride, int alpha, int beta, const int8_t* tc);
 void orc_deblock_chroma_eq4 (uint8_t* pix, int xstride, int ystride, int alpha, int beta);
 int  orc_luma_dc_qmul (int qp, int weight);
+void orc_weight_pred (uint8_t* y, uint8_t* u, uint8_t* v, int stride_y, int stride_c, int w, int h, const lh264_slice_t* s, int ref_idx);
 
 /* a picture in host memory, same layout as lh264_pic_t (plane pointers at pixel (0,0), padded) */
 typedef struct orc_pic {

@@ -15,10 +15,14 @@
 #include "expand_pic.h"
 #include "mc.h"
 #include "deblocking.h"
+#include "rec_mb.h"
 #include "../include/lh264.h"   /* our record layout (input of the shim) */
 #include <vector>
 
 using namespace WelsDec;
+namespace WelsDec {
+void WeightPrediction (PDqLayer, sMCRefMember*, int32_t, int32_t, int32_t);   // rec_mb.cpp:276, in no header
+}
 
 extern "C" {
 
@@ -29,6 +33,17 @@ void refk_luma_dc_dequant_idct (int16_t* blk, int qp) {
   // the function only reads bUseScalingList / pDequant_coeff4x4 of the context (decode_slice.cpp:272)
   static SWelsDecoderContext* ctx = (SWelsDecoderContext*)calloc (1, sizeof (SWelsDecoderContext));
   ctx->bUseScalingList = false;
+  WelsLumaDcDequantIdct (blk, qp, ctx);
+}
+
+// the same with a scaling list: the context's table row as the reference fills it (decode_slice.cpp:1258-1263: the list's entry times
+// g_kuiDequantCoeff, stored as uint16_t, for QP 0..50 - row 51 is never written), of which the function reads entry [0] >> 4
+void refk_luma_dc_dequant_idct_weighted (int16_t* blk, int qp, int weight) {
+  static SWelsDecoderContext* ctx = (SWelsDecoderContext*)calloc (1, sizeof (SWelsDecoderContext));
+  for (int q = 0; q < 51; q++)
+    for (int x = 0; x < 16; x++) ctx->pDequant_coeff_buffer4x4[0][q][x] = weight * g_kuiDequantCoeff[q][x & 0x07];
+  ctx->pDequant_coeff4x4[0] = ctx->pDequant_coeff_buffer4x4[0];
+  ctx->bUseScalingList = true;
   WelsLumaDcDequantIdct (blk, qp, ctx);
 }
 
@@ -138,6 +153,20 @@ void refk_deblock_picture (const lh264_mb_t* mbs, const lh264_slice_t* slices, i
     WelsDeblockingMb (&L, &F, DeblockingAvailableNoInterlayer (&L, sl.deblock_idc));
   }
   free (t8);
+}
+
+// WeightPrediction (rec_mb.cpp:276-341; not declared in a header) on one partition's prediction, list entry 0 of a table of our own
+void refk_weight_prediction (uint8_t* y, uint8_t* u, uint8_t* v, int stride_y, int stride_c, int w, int h, int luma_denom, int chroma_denom,
+                             int luma_weight, int luma_offset, const int* chroma_weight, const int* chroma_offset) {
+  SDqLayer L; memset (&L, 0, sizeof (L));
+  SPredWeightTabSyn T; memset (&T, 0, sizeof (T));
+  T.uiLumaLog2WeightDenom = luma_denom; T.uiChromaLog2WeightDenom = chroma_denom;
+  T.sPredList[0].iLumaWeight[0] = luma_weight; T.sPredList[0].iLumaOffset[0] = luma_offset;
+  for (int k = 0; k < 2; k++) { T.sPredList[0].iChromaWeight[0][k] = chroma_weight[k]; T.sPredList[0].iChromaOffset[0][k] = chroma_offset[k]; }
+  L.pPredWeightTable = &T;
+  sMCRefMember M; memset (&M, 0, sizeof (M));
+  M.pDstY = y; M.pDstU = u; M.pDstV = v; M.iDstLineLuma = stride_y; M.iDstLineChroma = stride_c;
+  WeightPrediction (&L, &M, 0, w, h);
 }
 
 }  // extern "C"

@@ -215,12 +215,96 @@ def _expand(orc, ref, h):
         _agree(h, a.buf, b.buf if ref else None)
 
 
+def _luma_dc_scaling_list(orc, ref, h):
+    """WelsLumaDcDequantIdct with a scaling list (decode_slice.cpp:272: kiQMul = pDequant_coeff4x4[0][qp][0] >> 4), QP 0..50, weights
+    1..255, amplitudes up to the bound that keeps f * kiQMul inside int32.  The reference keeps weight * dequant as uint16_t
+    (decoder_context.h:446-448), so kiQMul is ((weight * dq) & 0xffff) >> 4: the oracle's transform is run with that factor, and
+    orc_luma_dc_qmul must give it wherever the product fits 16 bits.  -> the number of inputs whose product does not fit.
+    (Row 51 of the table is never written, decode_slice.cpp:1260: QP 51 is left out.)"""
+    rng = np.random.default_rng(21)
+    norm = [10, 11, 13, 14, 16, 18]
+    had = [(1, 1, 1, 1), (1, 1, -1, -1), (1, -1, -1, 1), (1, -1, 1, -1)]
+    blk_x, blk_y = [0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3], [0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3]
+    n_trunc = 0
+    for it in range(1530):
+        qp = it % 51
+        weight = [1, 6, 15, 17, 64, 255][(it // 51) % 6] if it % 2 else int(rng.integers(1, 256))
+        dq = norm[qp % 6] << (qp // 6)
+        qmul = ((weight * dq) & 0xffff) >> 4
+        if weight * dq < 65536:
+            assert orc.orc_luma_dc_qmul(qp, weight) == qmul, (qp, weight)
+        else:
+            n_trunc += 1
+        amp = min(32767, ((1 << 31) - 3) // (16 * max(qmul, 1)))
+        blk = rng.integers(-amp, amp + 1, 384).astype(np.int16)
+        if it % 5 == 0:                  # the sign patterns that put 16 * amp into one output
+            for zb in range(16):
+                blk[zb * 16] = amp * had[it % 4][blk_x[zb]] * had[(it // 4) % 4][blk_y[zb]] * (-1 if it & 16 else 1)
+        a, b = blk.copy(), blk.copy()
+        orc.orc_luma_dc_dequant_idct(_p(a), qmul)
+        if ref:
+            ref.refk_luma_dc_dequant_idct_weighted(_p(b), qp, weight)
+        _agree(h, a, b if ref else None, (qp, weight, amp))
+    return n_trunc
+
+
+def _weight_prediction(orc, ref, h):
+    """WeightPrediction (rec_mb.cpp:276-341) at the ends of its syntax: denominators 0, 1, 7, weights and offsets -128, -1, 0, 1, 127 and
+    random ones, every partition size; the chroma quirk (only the top-left quarter is weighted) included"""
+    from refdump import SLICE_DTYPE
+    rng = np.random.default_rng(22)
+    sizes = [(16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8), (4, 4)]
+    ext = [-128, -1, 0, 1, 127]
+    for it in range(1260):
+        w, hh = sizes[it % 7]
+        ld, cd = ([0, 1, 7][(it // 7) % 3], [0, 1, 7][(it // 21) % 3]) if it % 4 else (int(rng.integers(0, 8)), int(rng.integers(0, 8)))
+        v = [int(rng.choice(ext)) if rng.random() < 0.6 else int(rng.integers(-128, 128)) for _ in range(6)]
+        sl = np.zeros(1, dtype=SLICE_DTYPE)
+        sl["weighted_pred"], sl["luma_log2_denom"], sl["chroma_log2_denom"] = 1, ld, cd
+        sl["luma_weight"][0, 3], sl["luma_offset"][0, 3] = v[0], v[1]
+        sl["chroma_weight"][0, 3], sl["chroma_offset"][0, 3] = v[2:4], v[4:6]
+        planes = [rng.integers(0, 256, (16, 32)).astype(np.uint8), rng.integers(0, 256, (8, 16)).astype(np.uint8), rng.integers(0, 256, (8, 16)).astype(np.uint8)]
+        if it % 6 == 0:
+            planes = [np.where(rng.random(q.shape) < 0.5, 0, 255).astype(np.uint8) for q in planes]
+        a, b = [q.copy() for q in planes], [q.copy() for q in planes]
+        orc.orc_weight_pred(_p(a[0]), _p(a[1]), _p(a[2]), 32, 16, w, hh, _p(sl), 3)
+        if ref:
+            ref.refk_weight_prediction(_p(b[0]), _p(b[1]), _p(b[2]), 32, 16, w, hh, ld, cd, v[0], v[1], (C.c_int * 2)(*v[2:4]), (C.c_int * 2)(*v[4:6]))
+        for q in range(3):
+            _agree(h, a[q], b[q] if ref else None, (w, hh, ld, cd, v, q))
+
+
+def _bs_thresholds(orc, ref, h):
+    """the boundary-strength cases of tests/recon_directed.py (vectors 3 and 4 apart across every edge, reference indices, the
+    8x8-transform remaps, P16x16, SKIP) through the reference's macroblock drivers: the unfiltered picture of each case, filtered by both"""
+    import recon_directed as D
+    for c in D.bs_thresholds():
+        pics = {}
+        for f in c.frames:
+            refs = [pics[r] for r in f.ref_ids]
+            pics[f.id] = O.HostPic(f.mb_w, f.mb_h)
+            O.recon_frame(f.mbs, f.coeffs, f.slices, pics[f.id], refs, 0)
+        a = O.HostPic(f.mb_w, f.mb_h)
+        O.recon_frame(f.mbs, f.coeffs, f.slices, a, refs, O.NO_DEBLOCK | O.NO_EXPAND)
+        b = O.HostPic(f.mb_w, f.mb_h)
+        b.buf[:] = a.buf
+        mbs = np.ascontiguousarray(f.mbs); sl = np.ascontiguousarray(f.slices)
+        sa = a.struct()
+        orc.orc_deblock_slice(_p(mbs), _p(sl), 0, C.byref(sa), f.mb_w, f.mb_h)
+        if ref:
+            sb = b.struct()
+            ref.refk_deblock_picture(_p(mbs), _p(sl), f.mb_w, f.mb_h, C.c_void_p(sb.y), C.c_void_p(sb.u), C.c_void_p(sb.v), sb.stride_y, sb.stride_c)
+        for p in range(3):
+            _agree(h, a.plane(p), b.plane(p) if ref else None, (c.name, p))
+
+
 INTRA_PRED = [("pred4x4", 14, 4), ("pred16x16", 7, 16), ("predc8x8", 7, 8)]
 # digest name -> (case, its arguments): what tests/golden/make_golden_ref_kernels.py runs against the reference
 CASES = {"idct4x4": (_idct4x4, ()), "idct8x8": (_idct8x8, ()), "dc_transforms": (_dc_transforms, ()),
          **{"intra_pred[%s]" % k[0]: (_intra_pred, k) for k in INTRA_PRED}, "intra_pred8x8l": (_intra_pred8x8l, ()), "mc": (_mc, ()),
          "deblock_edge_filters": (_deblock_edge_filters, ()), "deblock_macroblock_drivers": (_deblock_macroblock_drivers, ()),
-         "expand": (_expand, ())}
+         "expand": (_expand, ()),
+         "luma_dc_scaling_list": (_luma_dc_scaling_list, ()), "weight_prediction": (_weight_prediction, ()), "bs_thresholds": (_bs_thresholds, ())}
 
 
 # ---- the tests ------------------------------------------------------------------------------------------------------------------------
@@ -264,3 +348,16 @@ def test_deblock_macroblock_drivers():
 
 def test_expand():
     _check("expand", _expand)
+
+
+def test_luma_dc_scaling_list():
+    n_trunc = _check("luma_dc_scaling_list", _luma_dc_scaling_list)
+    assert n_trunc > 100        # products beyond 16 bits take part (see the case)
+
+
+def test_weight_prediction():
+    _check("weight_prediction", _weight_prediction)
+
+
+def test_bs_thresholds():
+    _check("bs_thresholds", _bs_thresholds)

@@ -155,8 +155,9 @@ def test_big_geometries_match_oracle():
 @pytest.mark.parametrize("name", ["syn720p_allI_4slices_8f.264", "syn1080p_IP_8f.264", "tibby.264"])
 def test_bench_streams_match_oracle(name):
     """the streams bench.py runs (--config 2 / 3: the 8-picture 720p and 1080p streams; BASELINE.json configs[0]: tibby.264), all
-    pictures: host front end -> HIP reconstruct, every padded plane of every picture against the oracle.  68 macroblock rows on 8
-    waves over eight 1080p pictures: the cross-picture wait_prefix path of recon_chain_kernel beyond the first two pictures."""
+    pictures: host front end -> HIP reconstruct, every padded plane of every picture against the oracle.  68 macroblock rows on 4
+    waves over eight 1080p pictures (the line buffers of 8 waves do not fit 120 macroblocks of width; the 720p pictures run on 8): the
+    cross-picture wait_prefix path of recon_chain_kernel beyond the first two pictures."""
     import os
     import losslessh264_amd as lh
     frames, err = lh.parse_stream(open(os.path.join(golden_io.GOLDEN_DIR, "streams", name), "rb").read())
