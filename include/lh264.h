@@ -229,12 +229,15 @@ enum { LH264_TB_MBTYPE = 0, LH264_TB_MVD, LH264_TB_MODE8, LH264_TB_LDC, LH264_TB
  * nnz images: 24 bytes per macroblock = per-4x4 nonzero counts (DecodedMacroblock::countSubblockNonzeros) of the
  * reference's FreqImage entry of that position: a skipped macroblock inherits the PAST entry
  * (decode_slice.cpp:3104-3108).  The host decides which earlier frame is PAST (frame_num flips, resolution
- * changes: decoded_macroblock.h:119-123, decode_slice.cpp:3032-3046) by pointing nnz_past_dev at its image. */
+ * changes: decoded_macroblock.h:119-123, decode_slice.cpp:3032-3046) by pointing nnz_past_dev at its image.
+ * A macroblock no slice covers (mb_type 0: a lost slice) is not written by the reference at all: its entry stays what the picture that
+ * last occupied the SAME FreqImage buffer left there (KEEP).  The struct has no field for that image: lh264_ctx_index_chains gives such
+ * a macroblock the PAST entry, lh264_ctx_index_chains_keep takes the KEEP images beside the jobs. */
 typedef struct lh264_ctx_job {
   const lh264_mb_t*    mbs_dev;       /* mb_w*mb_h records                                       */
   const int16_t*       levels_dev;    /* mb_w*mb_h*384                                           */
   const lh264_slice_t* slices_dev;
-  const uint8_t*       nnz_past_dev;  /* mb_w*mb_h*24 or NULL (no PAST)                          */
+  const uint8_t*       nnz_past_dev;  /* mb_w*mb_h*24 or NULL (no PAST); KEEP: lh264_ctx_index_chains_keep */
   uint8_t*             nnz_cur_dev;   /* mb_w*mb_h*24, written by pass 1, read by pass 2 and later frames */
   lh264_ctx_sym_t*     syms_dev;      /* the symbols, emission order.  FIXED layout (sym_off_dev == NULL): mb_w*mb_h*LH264_CTX_MAX_SYMS slots,
                                          macroblock k at k*LH264_CTX_MAX_SYMS, first n_syms[k] valid.  COMPACT layout: see below       */
@@ -254,6 +257,17 @@ typedef struct lh264_ctx_job {
  * later one).  Pass 1 (nnz images) runs one workgroup per chain, pass 2 (symbols) one wave per macroblock. */
 int lh264_ctx_index_chains (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains,
                             int n_jobs, int max_mbs_per_frame, void* hip_stream);
+/* The same for pictures with lost slices.  A macroblock whose record has mb_type 0 (no slice covers it) has no symbols; the two
+ * calls above give it the PAST entry, like a skipped one.  The reference's FreqImage does not: a cell that no slice writes keeps what
+ * the last picture in the SAME buffer left there.  keep_dev: a device array of n_jobs pointers, keep_dev[j] = the nnz image (mb_w*mb_h*24
+ * bytes) of the picture that last occupied the buffer picture j goes to - the picture before when frame_num did not change, else the
+ * one two flips back -, an earlier job of the same chain or a buffer the caller carried; NULL = no KEEP (the stream's first pictures,
+ * after a change of size): zeros.  Macroblocks of type 0 take their entry from there, skipped ones from PAST as ever.  keep_dev ==
+ * NULL: exactly the calls above. */
+int lh264_ctx_index_chains_keep (const lh264_ctx_job_t* jobs_dev, const uint8_t* const* keep_dev, const int32_t* chain_first_dev, int n_chains,
+                                 int n_jobs, int max_mbs_per_frame, void* hip_stream);
+int lh264_ctx_count_chains_keep (const lh264_ctx_job_t* jobs_dev, const uint8_t* const* keep_dev, const int32_t* chain_first_dev, int n_chains,
+                                 int n_jobs, int max_mbs_per_frame, unsigned long long* total_dev, void* hip_stream);
 /* COMPACT layout, first half: pass 1 and the count alone - fills n_syms_dev, sym_off_dev and *sym_base_dev of every job and
  * *total_dev = the symbols of all jobs (what the pool must hold).  lh264_ctx_index_chains repeats this on its own: the call exists so
  * that the caller can size the pool. */
@@ -434,6 +448,16 @@ const char*          lh264_parser_error (const lh264_parser_t* p);
 /* "" or why lh264_compress_batch refuses the stream although it parses: the first syntax value met so far that the container's prior
  * tables cannot carry ("mb_skip_run 687 is outside the container's range 0..511"); such a stream is stored verbatim */
 const char*          lh264_parser_out_of_range (const lh264_parser_t* p);
+/* LH264_COMPRESS_TOLERANT for a parser: to be called before the first byte is fed (LH264_E_ARG afterwards).  The default stream then
+ * keeps the payload of every NAL unit that is not handed to the model as a slice. */
+int                  lh264_parser_set_tolerant (lh264_parser_t* p, int on);
+/* "" or a text naming the first NAL unit met so far whose bytes the default stream does not keep with the flag off (its place in the
+ * file, counted from 0, its type and the byte offset of its header byte): the stream needs LH264_COMPRESS_TOLERANT to restore.  The
+ * same text whether the flag is on or off.  No device is needed. */
+const char*          lh264_parser_not_kept (const lh264_parser_t* p);
+/* "" or a text naming the first NAL unit that the default stream cannot carry even with the flag (see LH264_COMPRESS_TOLERANT): why
+ * lh264_compress_batch_opts refuses the stream under the flag */
+const char*          lh264_parser_not_carried (const lh264_parser_t* p);
 /* what carries those values all the same: the escape stream of the pictures parsed so far (stream LH264_TAG_ESC of the container, see
  * lh264_pip_restore for the format), runs still open closed; *len = 0 when no value was out of range, and also when one was that the
  * escape stream cannot carry (17 or more active references, a value of another table): such a stream stays refused.  A finished copy at any time -
@@ -502,8 +526,23 @@ int lh264_compress_batch_devices (const uint8_t* const* data, const size_t* len,
  * LH264_COMPRESS_ESCAPES - a stream that lh264_parser_out_of_range names, and nothing else stands against, is compressed and
  * gets the escape stream lh264_parser_escapes as tag LH264_TAG_ESC (every other tag and the default stream are what they are without
  * the flag's guard: the reference's own files); without the flag it is refused as ever.  Streams inside the range are not touched by
- * the flag.  An unknown flag: LH264_E_ARG. */
+ * the flag.  An unknown flag: LH264_E_ARG.
+ * LH264_COMPRESS_TOLERANT - streams with NAL units the format drops and pictures with lost slices are compressed.
+ *  (a) KEPT: with the flag the default stream keeps the payload (the unescaped bytes behind the header byte, without the trailing zero
+ *  bytes) of EVERY NAL unit that is not handed to the model as a slice - types 2-4 and 9-31, and a PPS in front of the first SPS -, as
+ *  it always did for types 6, 7 and 8; without the flag it keeps the header byte of those and drops the rest, as the reference does
+ *  (lh264_parser_not_kept tells beforehand), and the call returns LH264_OK for a stream that does not restore.  The restorers write
+ *  the payload back with the code they have for SEI.  What cannot be carried is refused under the flag, LH264_E_UNSUPPORTED with a
+ *  text that names the unit (lh264_parser_not_carried): a unit of type 1 or 5 that is not handed to the model (it arrives before its
+ *  parameter sets, or is a redundant picture), a unit with the forbidden bit set; a slice whose header does not parse (an unknown PPS)
+ *  or whose data stops parsing halfway is refused with the parser's text, as without the flag.  B, SP and SI slices, FMO and
+ *  interlace stay refused; trailing zero bytes behind a CABAC slice stay as they are.
+ *  (b) LOST SLICES: a picture with macroblocks no slice covers no longer refuses the stream: such a macroblock has no symbols, and
+ *  its entry of the nnz image is the KEEP entry (see lh264_ctx_index_chains_keep), which is what the restorers hold there.
+ * Without the flag nothing changes; a stream without such units and with whole pictures gets the same bytes with it as without -
+ * except one that changes its picture size, where PAST and KEEP start from nothing under the flag as they do in the restorers. */
 #define LH264_COMPRESS_ESCAPES 1u
+#define LH264_COMPRESS_TOLERANT 2u
 typedef struct lh264_compress_opts { uint32_t struct_bytes; uint32_t reserved; uint64_t segment_mbs; } lh264_compress_opts_t;
 int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_compress_opts_t* opts, lh264_compressed_t** out);
 int lh264_compress_batch_devices_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,

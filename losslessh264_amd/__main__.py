@@ -13,6 +13,10 @@
     python -m losslessh264_amd --escapes ...                (first) a stream with an mb_skip_run above 511 or 16 active references is
                                                             compressed with the escape stream, tag 71, beside it (out.pip.71, or in
                                                             the container) instead of being refused or stored verbatim
+    python -m losslessh264_amd --tolerant ...               (first) through lh264_compress_batch_opts with LH264_COMPRESS_TOLERANT: NAL
+                                                            units the format drops (delimiters, filler, ...) are kept, pictures with
+                                                            lost slices are compressed; out.lhp is still restored and compared
+                                                            before it is written, with the verbatim fallback behind it
     python -m losslessh264_amd --decode [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
                                                             out_dir/<name>.yuv holds the cropped pictures as I420 (or NV12), appended
                                                             by a sink run by run.  METHOD: lost slices are concealed as the reference's
@@ -32,32 +36,39 @@ import sys
 import numpy as np
 
 
-def compress_single(src, dst, escapes=False):
+def compress_single(src, dst, escapes=False, tolerant=False):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
     blob = None
     why = ""
     try:
-        frames, err, main, pcm, esc = lh.parse_file(data, pcm=True, escapes=True)
-        if err:
-            why = err
-        elif frames:
-            ctx = lh.CtxSession([frames])
-            ctx.run()
-            coder = lh.CoderSession(ctx, hash_cap=1 << 18, out_cap=max(1 << 16, 2 * len(data)))
-            coder.run()
-            ctx.synchronize()
-            tags = coder.tags(0)
-            if pcm:
-                tags[70] = pcm          # LH264_TAG_PCM: the samples of the I_PCM macroblocks travel as they are
-            if escapes and esc:
-                tags[71] = esc          # LH264_TAG_ESC (--escapes): what the SKIPRUN / NUMREF trees drop of a value above their range
+        # the streams of the container: through the library's whole compress call under --tolerant (the flag lives there), else through
+        # the sessions
+        main = tags = None
+        if tolerant:
+            (main, tags, err), = lh.compress_batch([data], escapes=escapes, tolerant=True)
+            if err:
+                main, why = None, err
+        else:
+            frames, err, main, pcm, esc = lh.parse_file(data, pcm=True, escapes=True)
+            if err or not frames:
+                main, why = None, err or "no picture"
+            else:
+                ctx = lh.CtxSession([frames])
+                ctx.run()
+                coder = lh.CoderSession(ctx, hash_cap=1 << 18, out_cap=max(1 << 16, 2 * len(data)))
+                coder.run()
+                ctx.synchronize()
+                tags = coder.tags(0)
+                if pcm:
+                    tags[70] = pcm          # LH264_TAG_PCM: the samples of the I_PCM macroblocks travel as they are
+                if escapes and esc:
+                    tags[71] = esc          # LH264_TAG_ESC (--escapes): what the SKIPRUN / NUMREF trees drop of a value above their range
+        if main is not None:
             if lh.restore(main, tags) == data:
                 blob = lh.pack(main, tags)
             else:
                 why = "the restored stream differs"
-        else:
-            why = "no picture"
     except RuntimeError as e:
         why = str(e)
     if blob is None or len(blob) >= len(data) + 32:
@@ -76,10 +87,10 @@ def restore_single(src, dst):
     print("%s -> %s: %d bytes" % (src, dst, len(out)))
 
 
-def compress_segmented(src, dst, segment_mbs, escapes=False):
+def compress_segmented(src, dst, segment_mbs, escapes=False, tolerant=False):
     import losslessh264_amd as lh
     data = open(src, "rb").read()
-    b = lh.compress_batch_handles([data], segment_mbs=segment_mbs, escapes=escapes)
+    b = lh.compress_batch_handles([data], segment_mbs=segment_mbs, escapes=escapes, tolerant=tolerant)
     main, tags, err = b.result(0)
     segs = b.segments(0)
     b.free()
@@ -172,13 +183,14 @@ def decode(argv):
 
 
 def main(argv):
-    escapes = len(argv) >= 2 and argv[1] == "--escapes"
-    if escapes:
+    escapes = tolerant = False
+    while len(argv) >= 2 and argv[1] in ("--escapes", "--tolerant"):      # the options that go first, in any order
+        escapes, tolerant = escapes or argv[1] == "--escapes", tolerant or argv[1] == "--tolerant"
         argv = argv[:1] + argv[2:]
     if len(argv) >= 4 and argv[1] == "--decode":
         return decode(argv[2:])
     if len(argv) >= 5 and argv[1] == "--segment-mbs":
-        compress_segmented(argv[3], argv[4], int(argv[2]), escapes)
+        compress_segmented(argv[3], argv[4], int(argv[2]), escapes, tolerant)
         return 0
     if len(argv) < 3:
         print(__doc__)
@@ -186,9 +198,13 @@ def main(argv):
     if argv[1].endswith(".lhp"):
         restore_single(argv[1], argv[2])
     elif argv[2].endswith(".lhp"):
-        compress_single(argv[1], argv[2], escapes)
+        compress_single(argv[1], argv[2], escapes, tolerant)
     elif ".pip" in os.path.basename(argv[1]):      # as the reference decides (h264dec.cpp:167-173)
         restore(argv[1], argv[2])
+    elif tolerant:                                 # (the library's whole compress call: 0 = no cut below its default)
+        if len(argv) > 3:
+            raise SystemExit("--tolerant writes no YUV dump through this command line (lh264dec --tolerant does)")
+        compress_segmented(argv[1], argv[2], 0, escapes, True)
     else:
         compress(argv[1], argv[2], argv[3] if len(argv) > 3 else None, escapes)
     return 0

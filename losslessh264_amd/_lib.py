@@ -97,6 +97,9 @@ _SIGS.update({
     "lh264_parser_frame_syn_offsets": (C.c_void_p, [C.c_void_p, C.c_int]),
     "lh264_parser_error": (C.c_char_p, [C.c_void_p]),
     "lh264_parser_out_of_range": (C.c_char_p, [C.c_void_p]),
+    "lh264_parser_set_tolerant": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_not_kept": (C.c_char_p, [C.c_void_p]),
+    "lh264_parser_not_carried": (C.c_char_p, [C.c_void_p]),
     "lh264_parser_escapes": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
 })
 CODE_JOB_DTYPE = np.dtype([("syn_syms", "<u8"), ("syn_off", "<u8"), ("ctx_syms", "<u8"), ("ctx_n_syms", "<u8"), ("n_mbs", "<i4"), ("reserved", "<i4"),
@@ -117,6 +120,7 @@ _SIGS["lh264_parser_feed_file_some"] = (C.c_int, [C.c_void_p, C.c_uint64])
 _SIGS["lh264_parser_drop_frames"] = (C.c_int, [C.c_void_p, C.c_int])
 _SIGS["lh264_code_last_decisions"] = (C.c_int, [C.c_int, C.c_int, C.c_void_p])
 COMPRESS_ESCAPES = 1
+COMPRESS_TOLERANT = 2
 TAG_ESC = 71
 class CompressOpts(C.Structure):       # flags: the word include/lh264.h declares as `reserved`
     _fields_ = [("struct_bytes", C.c_uint32), ("flags", C.c_uint32), ("segment_mbs", C.c_uint64)]
@@ -223,6 +227,8 @@ CTX_JOB_DTYPE = np.dtype([("mbs", "<u8"), ("levels", "<u8"), ("slices", "<u8"), 
                           ("sym_off", "<u8"), ("sym_base", "<u8"), ("syms_cap", "<u8")])
 CTX_MAX_SYMS = 432
 assert CTX_SYM_DTYPE.itemsize == 8 and CTX_JOB_DTYPE.itemsize == 88
+_SIGS["lh264_ctx_index_chains_keep"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p])
+_SIGS["lh264_ctx_count_chains_keep"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
 _SIGS["lh264_ctx_index_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p])
 _SIGS["lh264_ctx_count_chains"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
 CODE_JOB_DTYPE = np.dtype([("syn_syms", "<u8"), ("syn_off", "<u8"), ("ctx_syms", "<u8"), ("ctx_n_syms", "<u8"), ("n_mbs", "<i4"), ("reserved", "<i4"),

@@ -10,6 +10,8 @@
 //   lh264dec --segment-mbs N ...               (first) streams of more than N macroblocks are coded in segments of whole pictures
 //   lh264dec --escapes ...                     (first) a stream with an mb_skip_run above 511 or 16 active references is compressed with
 //                                       the escape stream beside it (out.pip.71, or in the container) and not refused / stored verbatim
+//   lh264dec --tolerant ...                    (first) LH264_COMPRESS_TOLERANT: NAL units the format drops (delimiters, filler, ...) are kept and pictures
+//                                       with lost slices are compressed; the container modes still restore, compare and fall back to verbatim
 //   lh264dec --batch out_dir a.264 b.264 ...   many streams in one lh264_compress_batch call -> out_dir/<name>.lhp
 //   lh264dec --decode [--nv12] out_dir a.264 b.264 ...   many streams in one lh264_decode_batch call -> out_dir/<name>.yuv: the
 //                                       cropped pictures as I420 (or NV12), appended by a sink run by run (the file's size bounds nothing)
@@ -91,7 +93,7 @@ static int dump_yuv (const Bytes& bs, const std::string& path) {
 }
 
 // --segment-mbs N: streams of more macroblocks are coded in segments of at most N (whole pictures); 0: the library's default
-// --escapes: LH264_COMPRESS_ESCAPES
+// --escapes: LH264_COMPRESS_ESCAPES; --tolerant: LH264_COMPRESS_TOLERANT
 static lh264_compress_opts_t g_opts = {sizeof (lh264_compress_opts_t), 0, 0};
 
 static int compress_files (const std::string& src, const std::string& dst, const char* yuv) {
@@ -272,6 +274,7 @@ int main (int argc, char** argv) {
   for (;;) {                                    // the options that go first, in any order
     if (argc >= 3 && !strcmp (argv[1], "--segment-mbs")) { g_opts.segment_mbs = strtoull (argv[2], nullptr, 10); argv[2] = argv[0]; argv += 2; argc -= 2; }
     else if (argc >= 2 && !strcmp (argv[1], "--escapes")) { g_opts.reserved |= LH264_COMPRESS_ESCAPES; argv[1] = argv[0]; argv += 1; argc -= 1; }
+    else if (argc >= 2 && !strcmp (argv[1], "--tolerant")) { g_opts.reserved |= LH264_COMPRESS_TOLERANT; argv[1] = argv[0]; argv += 1; argc -= 1; }
     else break;
   }
   if (argc >= 4 && !strcmp (argv[1], "--batch")) {
@@ -296,7 +299,7 @@ int main (int argc, char** argv) {
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal) : decode_files (argv[first], srcs, nv12, conceal);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

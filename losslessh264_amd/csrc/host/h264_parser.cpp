@@ -1878,7 +1878,7 @@ int Parser::feed_file (const uint8_t* d, size_t n) {
   feed_file_some ((size_t)-1);
   return file_rc_;
 }
-void Parser::begin_file (const uint8_t* d, size_t n) { file_d_ = d; file_n_ = n; file_pos_ = 0; file_rc_ = 0; file_done_ = false; }
+void Parser::begin_file (const uint8_t* d, size_t n) { file_d_ = d; file_n_ = n; file_pos_ = 0; file_rc_ = 0; file_done_ = false; nal_index_ = 0; }
 size_t Parser::held_mbs() const {
   size_t m = 0;
   for (auto& f : frames_) m += (size_t)f->mb_w * f->mb_h;
@@ -1917,21 +1917,41 @@ bool Parser::feed_file_some (size_t want_mbs) {
     size_t tz = 0;
     while (tz < nal.size() && nal[nal.size() - 1 - tz] == 0) tz++;
     bool slice_ok = false;
+    // (for not_kept / not_carried: the unit's place in the file, its type, where its header byte stands)
+    auto name_nal = [&] () { return "NAL unit " + std::to_string (nal_index_) + " (nal_unit_type " + std::to_string (nal.empty() ? 0 : nal[0] & 31) + ", header byte at offset " + std::to_string ((size_t) (c - d) + off) + ")"; };
     if (!nal.empty() && !(nal[0] & 0x80)) {
       const int type = nal[0] & 31;
       main_.append_byte (nal[0]);
       const bool have_sps = !d_->sps.empty(), have_pps = !d_->pps.empty();
-      if (type == 6 || type == 7 || (type == 8 && have_sps)) {
-        if (nal.size() > 1 + tz) main_.append_bytes (nal.data() + 1, nal.size() - 1 - tz);
+      const bool slice_type = type == 1 || type == 5, payload = nal.size() > 1 + tz;
+      const bool kept = type == 6 || type == 7 || (type == 8 && have_sps);
+      if (kept || (tolerant_ && !slice_type)) {
+        if (payload) main_.append_bytes (nal.data() + 1, nal.size() - 1 - tz);
       }
+      if (!kept && !slice_type && payload && not_kept_.empty())
+        not_kept_ = name_nal() + ": the default stream keeps its header byte and drops " + std::to_string (nal.size() - 1 - tz) + " payload bytes";
       if ((type == 1 || type == 5 || type == 7 || type == 8) && (type == 7 || have_sps) && (type == 7 || type == 8 || have_pps)) {
         size_t end = len;
         while (end > off && c[end - 1] == 0) end--;
         d_->last_hdr_bits = -1;
         if (end > off && feed_nal (c + off, end - off) < 0) rc = -1;
         slice_ok = (type == 1 || type == 5) && d_->last_hdr_bits >= 0;
+      } else if (slice_type) {
+        const std::string why = name_nal() + ": a slice in front of its parameter sets is not handed to the model";
+        if (not_kept_.empty()) not_kept_ = why + ", the default stream drops its payload";
+        if (not_carried_.empty()) not_carried_ = why + " and cannot be carried (the stream would not restore)";
       }
+      if (slice_type && !slice_ok && rc == 0 && err_.empty()) {       // (a redundant picture; a slice that failed has the parser's text)
+        const std::string why = name_nal() + ": a slice that is not handed to the model";
+        if (not_kept_.empty()) not_kept_ = why + ", the default stream drops its payload";
+        if (not_carried_.empty()) not_carried_ = why + " cannot be carried (the stream would not restore)";
+      }
+    } else if (!nal.empty()) {
+      const std::string why = name_nal() + ": the forbidden_zero_bit is set";
+      if (not_kept_.empty()) not_kept_ = why + ", the default stream drops the unit";
+      if (not_carried_.empty()) not_carried_ = why + ", the unit cannot be carried (the stream would not restore)";
     }
+    nal_index_++;
     for (size_t q = 0; q < tz; q++) main_.append_byte (0);
     if (slice_ok) {
       for (int b = 0; b < d_->last_hdr_bits; b++) main_.emit_bit ((d_->rbsp[(size_t)b >> 3] >> (7 - (b & 7))) & 1);

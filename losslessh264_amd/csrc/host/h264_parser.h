@@ -304,6 +304,15 @@ class Parser {
   // value out_of_range() stands for (not a value of another table, nor more than 16 references, which no restorer accepts)
   std::vector<uint8_t> escapes() const;
   bool escapes_carry_all() const;
+  // LH264_COMPRESS_TOLERANT (before the first byte of a file is fed; false afterwards): the default stream keeps the payload of every
+  // NAL unit that is not handed to the model as a slice, not of types 6, 7 and 8 alone
+  bool set_tolerant (bool on) { if (file_d_ || !main_.buffer.empty()) return false; tolerant_ = on; return true; }
+  bool tolerant() const { return tolerant_; }
+  // empty, or a text naming the first NAL unit of the file whose bytes the default stream does not keep with the flag off
+  const std::string& not_kept() const { return not_kept_; }
+  // empty, or a text naming the first NAL unit the default stream cannot carry even with the flag: a unit of type 1 or 5 that was not
+  // handed to the model as a slice, a unit with the forbidden bit set
+  const std::string& not_carried() const { return not_carried_; }
 
  private:
   struct Impl;
@@ -314,6 +323,7 @@ class Parser {
   int n_unsupported_ = 0;
   bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false, sparse_coeffs_ = false; long pictures_done_ = 0, err_pictures_ = 0; bool damaged_ = false;
   int conceal_ = 0;
+  bool tolerant_ = false; long nal_index_ = 0; std::string not_kept_, not_carried_;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;
   const uint8_t* file_d_ = nullptr; size_t file_n_ = 0, file_pos_ = 0; int file_rc_ = 0; bool file_done_ = false, arena_paused_ = false;      // begin_file .. feed_file_some

@@ -19,7 +19,7 @@
 namespace lh264 {
 __global__ void recon_chain_kernel (const lh264_frame_job_t* jobs, const int32_t* chain_first, int n_chains, int line_bytes);
 __global__ void ctx_nnz_kernel (const lh264_ctx_job_t* jobs, int n_jobs, int blocks_per_job);
-__global__ void ctx_inherit_chain_kernel (const lh264_ctx_job_t* jobs, const int32_t* chain_first, int n_chains);
+__global__ void ctx_inherit_chain_kernel (const lh264_ctx_job_t* jobs, const uint8_t* const* keep, const int32_t* chain_first, int n_chains);
 __global__ void ctx_symbols_kernel (const lh264_ctx_job_t* jobs, int n_jobs, int blocks_per_job);
 __global__ void ctx_offsets_kernel (const lh264_ctx_job_t* jobs, int n_jobs, unsigned long long* job_total);
 __global__ void ctx_bases_kernel (int n_jobs, unsigned long long* job_total, unsigned long long* total);
@@ -253,7 +253,7 @@ namespace {
 struct CtxWs { DevBuf totals; };
 PerDevice<CtxWs>& g_ctx_ws = *new PerDevice<CtxWs>;
 }
-static int ctx_passes (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains, int n_jobs, int max_mbs_per_frame,
+static int ctx_passes (const lh264_ctx_job_t* jobs_dev, const uint8_t* const* keep_dev, const int32_t* chain_first_dev, int n_chains, int n_jobs, int max_mbs_per_frame,
                        unsigned long long* total_dev, bool symbols, hipStream_t st) {
   if (lh264_device_count() <= 0) return fail (LH264_E_NODEVICE, "no HIP device visible");
   if (!jobs_dev || !chain_first_dev || n_chains < 0 || n_jobs < 0 || max_mbs_per_frame <= 0) return fail (LH264_E_ARG, "bad argument");
@@ -266,7 +266,7 @@ static int ctx_passes (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_fir
   const int bpj = (max_mbs_per_frame + 3) / 4;
   hipLaunchKernelGGL (lh264::ctx_nnz_kernel, dim3 ((unsigned)n_jobs * bpj), dim3 (256), 0, st, jobs_dev, n_jobs, bpj);
   HIPCHK (hipGetLastError());
-  hipLaunchKernelGGL (lh264::ctx_inherit_chain_kernel, dim3 (n_chains), dim3 (256), 0, st, jobs_dev, chain_first_dev, n_chains);
+  hipLaunchKernelGGL (lh264::ctx_inherit_chain_kernel, dim3 (n_chains), dim3 (256), 0, st, jobs_dev, keep_dev, chain_first_dev, n_chains);
   HIPCHK (hipGetLastError());
   // the compact layout: where every macroblock's symbols go (pictures in the fixed layout count as empty)
   hipLaunchKernelGGL (lh264::ctx_offsets_kernel, dim3 (n_jobs), dim3 (256), 0, st, jobs_dev, n_jobs, W.totals.as<unsigned long long>());
@@ -283,12 +283,21 @@ static int ctx_passes (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_fir
 }
 int lh264_ctx_index_chains (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains,
                             int n_jobs, int max_mbs_per_frame, void* stream) {
-  return ctx_passes (jobs_dev, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, nullptr, true, (hipStream_t)stream);
+  return ctx_passes (jobs_dev, nullptr, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, nullptr, true, (hipStream_t)stream);
+}
+int lh264_ctx_index_chains_keep (const lh264_ctx_job_t* jobs_dev, const uint8_t* const* keep_dev, const int32_t* chain_first_dev, int n_chains,
+                                 int n_jobs, int max_mbs_per_frame, void* stream) {
+  return ctx_passes (jobs_dev, keep_dev, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, nullptr, true, (hipStream_t)stream);
 }
 int lh264_ctx_count_chains (const lh264_ctx_job_t* jobs_dev, const int32_t* chain_first_dev, int n_chains,
                             int n_jobs, int max_mbs_per_frame, unsigned long long* total_dev, void* stream) {
   if (!total_dev) return fail (LH264_E_ARG, "bad argument");
-  return ctx_passes (jobs_dev, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, total_dev, false, (hipStream_t)stream);
+  return ctx_passes (jobs_dev, nullptr, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, total_dev, false, (hipStream_t)stream);
+}
+int lh264_ctx_count_chains_keep (const lh264_ctx_job_t* jobs_dev, const uint8_t* const* keep_dev, const int32_t* chain_first_dev, int n_chains,
+                                 int n_jobs, int max_mbs_per_frame, unsigned long long* total_dev, void* stream) {
+  if (!total_dev) return fail (LH264_E_ARG, "bad argument");
+  return ctx_passes (jobs_dev, keep_dev, chain_first_dev, n_chains, n_jobs, max_mbs_per_frame, total_dev, false, (hipStream_t)stream);
 }
 
 // Work memory of the coder stages, kept between calls and grown on demand: one set per device.  The lock only serialises the host
@@ -791,6 +800,9 @@ const lh264_ctx_sym_t* lh264_parser_frame_syn_symbols (const lh264_parser_t* p, 
 const uint32_t* lh264_parser_frame_syn_offsets (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? f->syn_off.data() : nullptr; }
 const char* lh264_parser_error (const lh264_parser_t* p) { return p ? const_cast<lh264_parser_t*> (p)->p.error().c_str() : ""; }
 const char* lh264_parser_out_of_range (const lh264_parser_t* p) { return p ? p->p.out_of_range().c_str() : ""; }
+int lh264_parser_set_tolerant (lh264_parser_t* p, int on) { return p && p->p.set_tolerant (on != 0) ? LH264_OK : LH264_E_ARG; }
+const char* lh264_parser_not_kept (const lh264_parser_t* p) { return p ? p->p.not_kept().c_str() : ""; }
+const char* lh264_parser_not_carried (const lh264_parser_t* p) { return p ? p->p.not_carried().c_str() : ""; }
 
 #ifdef LH264_CODER_DEBUG
 void lh264_debug_read_rs_stamps (unsigned long long* out16, int reset) { lh264::read_rs_stamps (out16, reset != 0); }

@@ -73,12 +73,13 @@ bool trace_on() { static const bool t = lh264host::trace_on ("LH264_TRACE_COMPRE
 
 struct Arena {
   DevBuf d_mbs, d_lev, d_sl, d_nnz, d_syms, d_nsyms, d_symoff, d_symbase, d_cj, d_first, d_syn, d_off, d_kj, d_st, d_keys, d_cells, d_out, d_len, d_items, d_packed;
+  DevBuf d_keep;                                // LH264_COMPRESS_TOLERANT: the KEEP image of every picture (lh264_ctx_index_chains_keep)
   PinBuf h_mbs, h_sparse, h_sl, h_syn, h_off, h_packed;
   DevBuf d_sparse;
   DevBuf d_rebase;
   DevBuf d_carry, d_flags;                      // groups with a segment of a long stream: the carry blocks' addresses, the streams' flags
   size_t device_bytes() const {
-    size_t n = d_sparse.cap + d_carry.cap + d_flags.cap + d_rebase.cap;
+    size_t n = d_sparse.cap + d_carry.cap + d_flags.cap + d_rebase.cap + d_keep.cap;
     for (const DevBuf* b : {&d_mbs, &d_lev, &d_sl, &d_nnz, &d_syms, &d_nsyms, &d_symoff, &d_symbase, &d_cj, &d_first, &d_syn, &d_off, &d_kj, &d_st, &d_keys, &d_cells, &d_out, &d_len, &d_items, &d_packed}) n += b->cap;
     return n;
   }
@@ -94,6 +95,7 @@ struct LongStream {
   uint32_t hash_cap = 0, out_cap = 0;
   DevBuf carry, outb, lens, nnz[2];
   int cur = 0, last_fn = 0; long slot[2] = {-1, -1};          // past_policy, continued: the pictures (counted over the stream) in the two buffers
+  int pol_w = 0, pol_h = 0;                     // ... and the size of the last picture (tolerant: a change of size empties both buffers)
   long pics_done = 0;                           // pictures handed to the coder so far
   size_t seg_mbs = 0;                           // the segment size of the call (sizes the output buffers)
   size_t max_pics = (size_t)-1;                 // a segment over one of the coder's counters is sent again with half the pictures
@@ -115,7 +117,7 @@ struct Part {
   bool again = false;                           // out: status 8 with more than one picture - nothing was coded, the pictures go back
   // left by the staging of compress_group for where its results are read: the PAST policy behind the part's last picture (a long
   // stream takes it over once the segment is coded) and the first macroblock of every picture in the group's buffers
-  int cur = 0, last_fn = 0; long slot[2] = {-1, -1};
+  int cur = 0, last_fn = 0; long slot[2] = {-1, -1}; int pol_w = 0, pol_h = 0;
   std::vector<size_t> mb_at;
 };
 
@@ -123,11 +125,17 @@ struct Part {
 // frame_num changes; -1 = none
 // For a segment of a long stream the walk starts where the segment before left it: pictures count from the stream's first one, base = the
 // segment's first; past[i] < base: that picture's image is in the stream's buffer past_buf[i].
-void past_policy (const std::vector<std::unique_ptr<lh264host::FrameOut>>& fr, std::vector<long>& past, std::vector<int>& past_buf, long base, int& cur, int& last_fn, long slot[2]) {
-  past.resize (fr.size()); past_buf.resize (fr.size());
+// keep[i]: the picture that last occupied the buffer picture i goes to, slot[cur] before the picture is entered - the picture before when
+// frame_num did not change, else the one two flips back; a cell no slice of picture i writes holds that picture's entry (KEEP), in the
+// stream's buffer 1 - past_buf[i] when keep[i] < base.  size: {w, h} of the picture before, continued like the rest; given (tolerant), a
+// change of size empties both buffers as the restorers do (decode_slice.cpp:3035-3046) - PAST and KEEP of one size never meet a picture
+// of another
+void past_policy (const std::vector<std::unique_ptr<lh264host::FrameOut>>& fr, std::vector<long>& past, std::vector<int>& past_buf, std::vector<long>& keep, long base, int& cur, int& last_fn, long slot[2], int* size) {
+  past.resize (fr.size()); past_buf.resize (fr.size()); keep.resize (fr.size());
   for (size_t i = 0; i < fr.size(); i++) {
     if (fr[i]->frame_num != last_fn) { cur ^= 1; last_fn = fr[i]->frame_num; }
-    past[i] = slot[1 - cur]; past_buf[i] = 1 - cur;
+    if (size && (size[0] != fr[i]->mb_w || size[1] != fr[i]->mb_h)) { slot[0] = slot[1] = -1; size[0] = fr[i]->mb_w; size[1] = fr[i]->mb_h; }
+    past[i] = slot[1 - cur]; past_buf[i] = 1 - cur; keep[i] = slot[cur];
     slot[cur] = base + (long)i;
   }
 }
@@ -138,7 +146,7 @@ void fail_all (lh264_compressed_t** out, std::vector<Part>& parts, int code, con
 
 // one sub-batch: whole streams and segments of long ones, all parsed without error.  A group without a segment is coded by
 // lh264_code_chains as ever; with one, by lh264_code_chains_resume, the whole streams as FIRST | LAST beside the segments.
-void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh264_compressed_t** out, int threads) {
+void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh264_compressed_t** out, int threads, bool tolerant) {
   using lh264host::FrameOut;
   const int n_chains = (int)parts.size();
   std::vector<int> idx (n_chains);
@@ -163,6 +171,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   std::vector<lh264_ctx_job_t> h_cj (n_jobs);
   std::vector<lh264_code_job_t> h_kj (n_jobs);
   std::vector<int32_t> h_first (n_chains + 1);
+  std::vector<const uint8_t*> h_keep (tolerant ? n_jobs : 0);
   std::vector<lh264_code_stream_t> h_st (n_chains);
   std::vector<uint32_t> hash_cap (n_chains), out_cap (n_chains);
   std::vector<size_t> key0 (n_chains + 1, 0), out0 (n_chains + 1, 0);
@@ -207,7 +216,8 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
                   A.d_len.alloc ((size_t)n_chains * (LH264_N_TAG_SLOTS + 1) * 4) && A.d_len.zero ((size_t)n_chains * (LH264_N_TAG_SLOTS + 1) * 4, nullptr) &&
                   A.h_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.h_sparse.alloc (n_sparse * 8) && A.h_sl.alloc (n_slices * sizeof (lh264_slice_t)) &&
                   A.h_syn.alloc (n_syn * sizeof (lh264_ctx_sym_t)) && A.h_off.alloc (n_off * 4) &&
-                  (!resumable || (A.d_carry.alloc (n_chains * sizeof (void*)) && A.d_flags.alloc (n_chains * 4)));
+                  (!resumable || (A.d_carry.alloc (n_chains * sizeof (void*)) && A.d_flags.alloc (n_chains * 4))) &&
+                  (!tolerant || A.d_keep.alloc (n_jobs * sizeof (void*)));
   if (!ok) { fail_all (out, parts, LH264_E_HIP, "device allocation failed"); return; }
   const double t_b = now_s();
   lh264_mb_t* h_mbs = A.h_mbs.as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse.as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl.as<lh264_slice_t>();
@@ -218,14 +228,16 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     LongStream* ls = parts[c].ls;
     size_t mo = mb0[c], so = sl0[c], yo = sy0[c], oo = of0[c], j = jb0[c], po = sp0[c];
     h_first[c] = (int32_t)j;
-    std::vector<long> past; std::vector<int> past_buf;
+    std::vector<long> past, keep; std::vector<int> past_buf;
     Part& pt = parts[c];
     const long base = ls ? ls->pics_done : 0;
     // (a segment that has to be sent again must find the stream's policy as it was: the walk works on a copy in the part, which the
     // stream takes over when the segment was coded)
-    pt.cur = 0; pt.last_fn = 0; pt.slot[0] = pt.slot[1] = -1;
-    if (ls) { pt.cur = ls->cur; pt.last_fn = ls->last_fn; pt.slot[0] = ls->slot[0]; pt.slot[1] = ls->slot[1]; }
-    past_policy (fr, past, past_buf, base, pt.cur, pt.last_fn, pt.slot);
+    pt.cur = 0; pt.last_fn = 0; pt.slot[0] = pt.slot[1] = -1; pt.pol_w = pt.pol_h = 0;
+    if (ls) { pt.cur = ls->cur; pt.last_fn = ls->last_fn; pt.slot[0] = ls->slot[0]; pt.slot[1] = ls->slot[1]; pt.pol_w = ls->pol_w; pt.pol_h = ls->pol_h; }
+    int pol_size[2] = {pt.pol_w, pt.pol_h};
+    past_policy (fr, past, past_buf, keep, base, pt.cur, pt.last_fn, pt.slot, tolerant ? pol_size : nullptr);
+    pt.pol_w = pol_size[0]; pt.pol_h = pol_size[1];
     std::vector<size_t>& mb_at = pt.mb_at;
     mb_at.resize (fr.size());
     for (size_t i = 0; i < fr.size(); i++) {
@@ -241,6 +253,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
       cj.mbs_dev = A.d_mbs.as<lh264_mb_t>() + mo; cj.levels_dev = A.d_lev.as<int16_t>() + mo * 384; cj.slices_dev = A.d_sl.as<lh264_slice_t>() + so;
       cj.nnz_cur_dev = A.d_nnz.as<uint8_t>() + mo * 24;
       cj.nnz_past_dev = past[i] < 0 ? nullptr : past[i] < base ? ls->nnz[past_buf[i]].as<uint8_t>() : A.d_nnz.as<uint8_t>() + mb_at[past[i] - base] * 24;
+      if (tolerant) h_keep[j] = keep[i] < 0 ? nullptr : keep[i] < base ? ls->nnz[1 - past_buf[i]].as<uint8_t>() : A.d_nnz.as<uint8_t>() + mb_at[keep[i] - base] * 24;
       // (the compact layout: the pool's address and size are set once the count pass has said how many symbols there are)
       cj.syms_dev = nullptr; cj.syms_cap = 0; cj.n_syms_dev = A.d_nsyms.as<uint16_t>() + mo;
       cj.sym_off_dev = A.d_symoff.as<uint32_t>() + mo; cj.sym_base_dev = A.d_symbase.as<uint64_t>() + j;
@@ -267,7 +280,8 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   if (!(up (A.d_mbs, h_mbs, n_mbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sparse * 8) && up (A.d_sl, h_sl, n_slices * sizeof (lh264_slice_t)) &&
         up (A.d_syn, h_syn, n_syn * sizeof (lh264_ctx_sym_t)) && up (A.d_off, h_off, n_off * 4) && up (A.d_cj, h_cj.data(), n_jobs * sizeof (lh264_ctx_job_t)) &&
         up (A.d_kj, h_kj.data(), n_jobs * sizeof (lh264_code_job_t)) && up (A.d_first, h_first.data(), (n_chains + 1) * 4) && up (A.d_st, h_st.data(), n_chains * sizeof (lh264_code_stream_t)) &&
-        (!resumable || (up (A.d_carry, h_carry.data(), n_chains * sizeof (void*)) && up (A.d_flags, h_flags.data(), n_chains * 4))))) {
+        (!resumable || (up (A.d_carry, h_carry.data(), n_chains * sizeof (void*)) && up (A.d_flags, h_flags.data(), n_chains * 4))) &&
+        (!tolerant || up (A.d_keep, h_keep.data(), n_jobs * sizeof (void*))))) {
     fail_all (out, parts, LH264_E_HIP, "upload failed"); return;
   }
   if (n_sparse) lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sparse, A.d_lev.as<int16_t>(), nullptr);
@@ -276,7 +290,9 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
   // the symbol pool: the count pass says how many symbols the group's pictures have (8 bytes each; the fixed layout took 3,456 bytes per
   // macroblock), then the job tables get the pool's address
   unsigned long long n_syms_total = 0;
-  int rc = n_jobs == 0 ? LH264_OK : lh264_ctx_count_chains (A.d_cj.as<lh264_ctx_job_t>(), A.d_first.as<int32_t>(), n_chains, (int)n_jobs, max_mbs, A.d_symbase.as<unsigned long long>() + n_jobs + 1, nullptr);
+  // (tolerant: a macroblock no slice covers takes its nnz entry from the KEEP image; otherwise the calls are the ones without KEEP)
+  const uint8_t* const* d_keep = tolerant ? A.d_keep.as<const uint8_t*>() : nullptr;
+  int rc = n_jobs == 0 ? LH264_OK : lh264_ctx_count_chains_keep (A.d_cj.as<lh264_ctx_job_t>(), d_keep, A.d_first.as<int32_t>(), n_chains, (int)n_jobs, max_mbs, A.d_symbase.as<unsigned long long>() + n_jobs + 1, nullptr);
   if (rc == LH264_OK && n_jobs && hipMemcpy (&n_syms_total, A.d_symbase.as<unsigned long long>() + n_jobs + 1, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = LH264_E_HIP;
   if (rc == LH264_OK && !A.d_syms.alloc ((size_t)n_syms_total * sizeof (lh264_ctx_sym_t))) rc = LH264_E_HIP;
   if (rc == LH264_OK) {
@@ -284,7 +300,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     if (hipMemcpy (A.d_cj.p, h_cj.data(), n_jobs * sizeof (lh264_ctx_job_t), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy (A.d_kj.p, h_kj.data(), n_jobs * sizeof (lh264_code_job_t), hipMemcpyHostToDevice) != hipSuccess) rc = LH264_E_HIP;
   }
-  if (rc == LH264_OK && n_jobs) rc = lh264_ctx_index_chains (A.d_cj.as<lh264_ctx_job_t>(), A.d_first.as<int32_t>(), n_chains, (int)n_jobs, max_mbs, nullptr);
+  if (rc == LH264_OK && n_jobs) rc = lh264_ctx_index_chains_keep (A.d_cj.as<lh264_ctx_job_t>(), d_keep, A.d_first.as<int32_t>(), n_chains, (int)n_jobs, max_mbs, nullptr);
   if (rc == LH264_OK && !resumable) rc = lh264_code_chains (A.d_kj.as<lh264_code_job_t>(), A.d_first.as<int32_t>(), A.d_st.as<lh264_code_stream_t>(), n_chains, (int)n_jobs, (long long)n_mbs, max_mbs, nullptr);
   if (rc == LH264_OK && resumable) rc = lh264_code_chains_resume (A.d_kj.as<lh264_code_job_t>(), A.d_first.as<int32_t>(), A.d_st.as<lh264_code_stream_t>(), A.d_carry.as<void*>(), A.d_flags.as<uint32_t>(),
                                                                   n_chains, (int)n_jobs, (long long)n_mbs, max_mbs, nullptr);
@@ -322,7 +338,7 @@ void compress_group (Arena& A, std::vector<Part>& parts, const size_t* len, lh26
     if (ls && L[LH264_N_TAG_SLOTS] == 0) {
       // the stream's PAST policy moves on, and the images its two buffers name now are kept for the segments to come
       const long base = ls->pics_done;
-      ls->cur = parts[c].cur; ls->last_fn = parts[c].last_fn; ls->slot[0] = parts[c].slot[0]; ls->slot[1] = parts[c].slot[1];
+      ls->cur = parts[c].cur; ls->last_fn = parts[c].last_fn; ls->slot[0] = parts[c].slot[0]; ls->slot[1] = parts[c].slot[1]; ls->pol_w = parts[c].pol_w; ls->pol_h = parts[c].pol_h;
       ls->pics_done += (long)parts[c].frames.size();
       if (!(parts[c].flags & LH264_CODE_SEG_LAST)) {
         const std::vector<size_t>& at = parts[c].mb_at;
@@ -388,8 +404,9 @@ int lh264_compress_batch (const uint8_t* const* data, const size_t* len, int n, 
 }
 int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_compress_opts_t* opts, lh264_compressed_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~LH264_COMPRESS_ESCAPES))) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~ (LH264_COMPRESS_ESCAPES | LH264_COMPRESS_TOLERANT)))) return LH264_E_ARG;
   const bool escapes = opts && (opts->reserved & LH264_COMPRESS_ESCAPES);      // `reserved`: the flags word
+  const bool tolerant = opts && (opts->reserved & LH264_COMPRESS_TOLERANT);
   for (int i = 0; i < n; i++) out[i] = new lh264_compressed();
   if (lh264_device_count() <= 0) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_NODEVICE; out[i]->error = "no HIP device visible"; } return LH264_E_NODEVICE; }
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
@@ -439,7 +456,8 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
     if (!P.error().empty()) why = P.error();
     else if (!symbols) why = "a picture with an incomplete slice";
     else if (!P.out_of_range().empty() && !(escapes && P.escapes_carry_all())) why = P.out_of_range() + " (the stream would not restore)";
-    else if (P.damaged()) why = "a picture with macroblocks no slice covers: the reference conceals them, which is not modelled (the stream would not restore)";
+    else if (tolerant && !P.not_carried().empty()) why = P.not_carried();
+    else if (P.damaged() && !tolerant) why = "a picture with macroblocks no slice covers: the reference conceals them, which is not modelled (the stream would not restore)";
     return !why.empty();
   };
   // the pictures a long stream's parser has completed go to the stream's queue; false: the stream is refused
@@ -521,7 +539,7 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
     device_thread = std::thread ([&, device] () {
       hipSetDevice (device);
       if (!getenv ("LH264_COMPRESS_PARSE_ONLY"))          // diagnostic: the host side alone
-        compress_group (arena, running, len, out, std::max (1, threads / 2));
+        compress_group (arena, running, len, out, std::max (1, threads / 2), tolerant);
     });
   };
   std::vector<Part> group;
@@ -535,6 +553,7 @@ int lh264_compress_batch_opts (const uint8_t* const* data, const size_t* len, in
       parsers[i]->set_want_coeffs (false);
       parsers[i]->set_sparse_levels (true);
       parsers[i]->set_stream_arena (true);
+      parsers[i]->set_tolerant (tolerant);
       parsers[i]->begin_file (data[i], data[i] ? len[i] : 0);
       parsers[i]->feed_file_some (kSegment);            // (a stream of up to kSegment macroblocks is parsed whole)
     });
@@ -593,7 +612,7 @@ int lh264_compress_batch_devices (const uint8_t* const* data, const size_t* len,
 }
 int lh264_compress_batch_devices_opts (const uint8_t* const* data, const size_t* len, int n, int threads, const int* devices, int n_devices,
                                        const lh264_compress_opts_t* opts, lh264_compressed_t** out) {
-  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~LH264_COMPRESS_ESCAPES))) return LH264_E_ARG;
+  if (opts && (opts->struct_bytes != sizeof (lh264_compress_opts_t) || (opts->reserved & ~ (LH264_COMPRESS_ESCAPES | LH264_COMPRESS_TOLERANT)))) return LH264_E_ARG;
   if (!data || !len || !out || n < 0 || !devices || n_devices < 1) return LH264_E_ARG;
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   size_t total = 0;

@@ -4,7 +4,8 @@
 //         levels coalesced (lane = 4 coefficients of one 4x4 row), counts nonzeros per 4x4 block across the lane quad
 //         and writes the 24-byte entry of the "nnz image".
 // Pass 1b ctx_inherit_chain_kernel : one workgroup per stream, frames in order: a skipped macroblock inherits the
-//         PAST entry (FreqImage semantics, decode_slice.cpp:3104-3108) - 24 bytes per skipped macroblock.
+//         PAST entry (FreqImage semantics, decode_slice.cpp:3104-3108) - 24 bytes per skipped macroblock; a macroblock
+//         no slice covers keeps the entry of the picture that held its buffer before (KEEP), where the caller names it.
 // Pass 2  ctx_symbols_kernel   : one wave per macroblock, all frames of all streams at once (context INDICES do not
 //         depend on the adaptive state).  Levels are staged in LDS; one lane per 4x4 block (or per 8x8 block) pulls its
 //         levels into registers in scan order (static zig-zag offsets), finds the last nonzero one with a bit mask,
@@ -126,23 +127,29 @@ ctx_nnz_kernel (const lh264_ctx_job_t* __restrict__ jobs, int n_jobs, int blocks
 }
 
 // ---- pass 1b: a skipped macroblock inherits the PAST entry (FreqImage semantics, decode_slice.cpp:3104-3108).  The only
-// step that is sequential over the frames of a stream; it moves 24 bytes per skipped macroblock. -------------------------
+// step that is sequential over the frames of a stream; it moves 24 bytes per skipped macroblock.
+// keep != NULL (lh264_ctx_index_chains_keep, pictures with lost slices): a macroblock no slice covers (mb_type 0) is not written by the
+// reference at all - its cell holds what the last picture in the same FreqImage buffer left there, the KEEP image keep[job] (an
+// earlier job of this chain, fenced like PAST, or a buffer of the caller's; NULL: a fresh cell, zeros).  Without the array such a
+// macroblock inherits PAST like a skipped one, as before. -------------------------
 __global__ void __launch_bounds__ (256)
-ctx_inherit_chain_kernel (const lh264_ctx_job_t* __restrict__ jobs, const int32_t* __restrict__ chain_first, int n_chains) {
+ctx_inherit_chain_kernel (const lh264_ctx_job_t* __restrict__ jobs, const uint8_t* const* __restrict__ keep, const int32_t* __restrict__ chain_first, int n_chains) {
   const int chain = blockIdx.x;
   if (chain >= n_chains) return;
   for (int ji = chain_first[chain]; ji < chain_first[chain + 1]; ji++) {
     const lh264_ctx_job_t* J = jobs + ji;
     const GLB lh264_mb_t* mbs = glb<const lh264_mb_t> (J->mbs_dev);
-    const GLB uint8_t* past = glb<const uint8_t> (J->nnz_past_dev);
+    const uint8_t* past_p = J->nnz_past_dev;
+    const uint8_t* keep_p = keep ? keep[ji] : past_p;
     GLB uint8_t* cur = glb<uint8_t> (J->nnz_cur_dev);
     const int n = J->mb_w * J->mb_h;
     for (int k = threadIdx.x; k < n; k += blockDim.x) {
       const int type = mbs[k].mb_type;
       if (type == LH264_MB_SKIP || type == 0) {
         GLB uint32_t* d = (GLB uint32_t*) (cur + (size_t)k * 24);
-        if (J->nnz_past_dev) {
-          const GLB uint32_t* sp = (const GLB uint32_t*) (past + (size_t)k * 24);
+        const uint8_t* from = type == 0 ? keep_p : past_p;
+        if (from) {
+          const GLB uint32_t* sp = (const GLB uint32_t*) (glb<const uint8_t> (from) + (size_t)k * 24);
           const uint32_t v0 = sp[0], v1 = sp[1], v2 = sp[2], v3 = sp[3], v4 = sp[4], v5 = sp[5];
           d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4; d[5] = v5;
         } else { d[0] = d[1] = d[2] = d[3] = d[4] = d[5] = 0u; }

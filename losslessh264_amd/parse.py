@@ -10,15 +10,16 @@ class ParsedFrame:
     pass
 
 
-def parse_file(data, strict=False, pcm=False, escapes=False, conceal=None):
+def parse_file(data, strict=False, pcm=False, escapes=False, conceal=None, tolerant=False):
     """A whole Annex-B file fed chunk by chunk as the reference's console application does.
     -> (frames, error_text, main_stream): main_stream is the recompressor's default stream (the '.pip' file itself).
     pcm=True: a fourth element, the samples of the stream's I_PCM macroblocks (stream LH264_TAG_PCM of the container).
     escapes=True: one more element at the end, the stream's escape stream (LH264_TAG_ESC, see escapes()).
     conceal: a name of decode_batch's conceal= (lh264_parser_set_conceal): macroblocks no slice covers get concealment records, and
     every frame says how many (concealed), from which picture (conceal_src, -1: 128s), whether it is withheld (frozen) and what the
-    vector was made of (conceal_info, see lh264_parser_frame_conceal).  For the decode direction only."""
-    return parse_stream(data, strict, _file=True, _pcm=pcm, _esc=escapes, _conceal=conceal)
+    vector was made of (conceal_info, see lh264_parser_frame_conceal).  For the decode direction only.
+    tolerant=True: lh264_parser_set_tolerant - the default stream keeps the payload of every NAL unit that is no slice (not_kept())."""
+    return parse_stream(data, strict, _file=True, _pcm=pcm, _esc=escapes, _conceal=conceal, _tolerant=tolerant)
 
 
 def parse_batch_time(datas, threads=0, keep=True):
@@ -77,7 +78,7 @@ def _read_frame(lib, p, i):
     return f
 
 
-def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False, _conceal=None):
+def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False, _conceal=None, _tolerant=False):
     """-> (frames, error_text).  frames have the attributes ReconSession / CtxSession expect."""
     lib = L.lib()
     p = lib.lh264_parser_create()
@@ -86,6 +87,8 @@ def parse_stream(data, strict=False, _file=False, _pcm=False, _esc=False, _conce
             if _conceal not in L.CONCEAL:
                 raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
             L.check(lib.lh264_parser_set_conceal(p, L.CONCEAL[_conceal]))
+        if _tolerant:
+            L.check(lib.lh264_parser_set_tolerant(p, 1))
         if _file:
             rc = lib.lh264_parser_feed_file(p, bytes(data), len(data))
         else:
@@ -121,6 +124,30 @@ def out_of_range(data):
         return lib.lh264_parser_out_of_range(p).decode()
     finally:
         lib.lh264_parser_destroy(p)
+
+
+def _file_text(data, query, tolerant=False):
+    lib = L.lib()
+    p = lib.lh264_parser_create()
+    try:
+        if tolerant:
+            L.check(lib.lh264_parser_set_tolerant(p, 1))
+        lib.lh264_parser_feed_file(p, bytes(data), len(data))
+        return getattr(lib, query)(p).decode()
+    finally:
+        lib.lh264_parser_destroy(p)
+
+
+def not_kept(data):
+    """'' or a text naming the first NAL unit whose bytes the default stream does not keep without tolerant=True (lh264_parser_not_kept):
+    compress_batch answers LH264_OK for such a stream and the result does not restore; with tolerant=True it does.  No device is needed."""
+    return _file_text(data, "lh264_parser_not_kept")
+
+
+def not_carried(data):
+    """'' or a text naming the first NAL unit that the default stream cannot carry even with tolerant=True (lh264_parser_not_carried): a
+    slice in front of its parameter sets, a unit with the forbidden bit set.  compress_batch(tolerant=True) refuses the stream with it."""
+    return _file_text(data, "lh264_parser_not_carried", True)
 
 
 def escapes(data):

@@ -229,11 +229,12 @@ class CompressedBatch:
             pass
 
 
-def compress_batch_handles(datas, threads=0, devices=None, segment_mbs=None, escapes=False):
+def compress_batch_handles(datas, threads=0, devices=None, segment_mbs=None, escapes=False, tolerant=False):
     """lh264_compress_batch_opts / lh264_compress_batch_devices_opts -> CompressedBatch (call .free() when done).  segment_mbs: streams of
     more macroblocks are coded in segments of at most that many (whole pictures); None: the library's default.  escapes: a stream with
     an mb_skip_run above 511 or 16 active references is compressed and gets the escape stream, tag 71 (LH264_COMPRESS_ESCAPES), instead
-    of being refused"""
+    of being refused.  tolerant: LH264_COMPRESS_TOLERANT - the default stream keeps the payload of every NAL unit that is no slice (see
+    not_kept()), and a picture with macroblocks no slice covers is compressed instead of refusing the stream"""
     import time
     lib = L.lib()
     n = len(datas)
@@ -241,7 +242,7 @@ def compress_batch_handles(datas, threads=0, devices=None, segment_mbs=None, esc
     lens = (C.c_size_t * n)(*[len(d) for d in datas])
     outs = (C.c_void_p * n)()
     t0 = time.perf_counter()
-    opts = L.CompressOpts(C.sizeof(L.CompressOpts), L.COMPRESS_ESCAPES if escapes else 0, int(segment_mbs or 0))
+    opts = L.CompressOpts(C.sizeof(L.CompressOpts), (L.COMPRESS_ESCAPES if escapes else 0) | (L.COMPRESS_TOLERANT if tolerant else 0), int(segment_mbs or 0))
     if devices:
         devs = (C.c_int * len(devices))(*devices)
         rc = lib.lh264_compress_batch_devices_opts(ptrs, lens, n, threads, devs, len(devices), C.byref(opts), outs)
@@ -252,11 +253,11 @@ def compress_batch_handles(datas, threads=0, devices=None, segment_mbs=None, esc
     return CompressedBatch(outs, n, dt)
 
 
-def compress_batch(datas, threads=0, devices=None, segment_mbs=None, escapes=False):
+def compress_batch(datas, threads=0, devices=None, segment_mbs=None, escapes=False, tolerant=False):
     """the whole compress direction behind one C call (lh264_compress_batch): list of Annex-B byte strings ->
     list of (main bytes, {tag: bytes}, error text or None).  devices: list of device indices to shard the batch over
-    (lh264_compress_batch_devices); default: the current device.  segment_mbs, escapes: see compress_batch_handles"""
-    b = compress_batch_handles(datas, threads, devices, segment_mbs, escapes)
+    (lh264_compress_batch_devices); default: the current device.  segment_mbs, escapes, tolerant: see compress_batch_handles"""
+    b = compress_batch_handles(datas, threads, devices, segment_mbs, escapes, tolerant)
     res = [b.result(i) for i in range(b.n)]
     b.free()
     return res
