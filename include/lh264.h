@@ -423,6 +423,21 @@ const int16_t*       lh264_parser_frame_levels (const lh264_parser_t* p, int idx
 int                  lh264_parser_set_conceal (lh264_parser_t* p, int method);
 int                  lh264_parser_frame_conceal (const lh264_parser_t* p, int idx, int32_t out[12]);
 int                  lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on);
+/* deferred slice data (set before the first byte is fed; off by default, and then nothing changes): the header of a CAVLC slice is walked -
+ * picture boundaries, reference lists, marking, the entry in the slice table - and its macroblock layer is not parsed; the slice is kept
+ * with its picture (payload, where slice_data() begins, a copy of its header and parameter sets).  Records, coefficients, `covered`,
+ * n_mbs and the slice syntax of such a slice stay empty until lh264_parser_parse_deferred runs the host macroblock layer over it - to be
+ * called for the slices 0 .. lh264_parser_frame_deferred - 1 of a completed picture in order; 1: parsed, 0: the slice failed (then
+ * lh264_parser_error / _error_pictures / _file_status say what the undeferred parser says); out (may be NULL): the slice's index in
+ * the picture's slice table and the bit position at which the macroblock layer stopped.  CABAC slices are parsed on the spot.
+ * For the decode direction: symbol lists, I_PCM samples and concealment are not kept up for deferred pictures.
+ * lh264_parser_error_pictures: how many pictures were complete when lh264_parser_error was raised; lh264_parser_file_status: what
+ * lh264_parser_feed_file returned, or would return now */
+int                  lh264_parser_set_defer_slice_data (lh264_parser_t* p, int on);
+int                  lh264_parser_frame_deferred (const lh264_parser_t* p, int idx);
+int                  lh264_parser_parse_deferred (lh264_parser_t* p, int idx, int slice, int32_t out[2]);
+long long            lh264_parser_error_pictures (const lh264_parser_t* p);
+int                  lh264_parser_file_status (const lh264_parser_t* p);
 const uint64_t*      lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count);
 const lh264_slice_t* lh264_parser_frame_slices (const lh264_parser_t* p, int idx);
 const uint8_t*       lh264_parser_frame_covered (const lh264_parser_t* p, int idx);
@@ -651,7 +666,15 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * stream digest over exactly their bytes, a stream without pictures the SHA-1 of the empty message.  With LH264_DECODE_NO_PICTURES
  * nothing is downloaded or kept: lh264_decoded_picture still describes every picture, lh264_decoded_bytes / _bytes_dev give NULL and
  * length 0.  The digests do not depend on threads, round_pictures, group_mbs, the output mode or the batch either.
- * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a format out of range, a flag bit that is not
+ * opts->parse = LH264_PARSE_DEVICE (opt-in; struct_bytes 40 and 48 mean host): the host walks headers only (NAL split, unescape, SPS / PPS /
+ * slice header, reference lists, marking, picture boundaries) and per round the payloads of the CAVLC slices and one task per slice go
+ * to the device instead of records and coefficient lists; slice_parse_kernel writes the records and dequantised coefficients where
+ * recon_chain_kernel reads them, and its 12 bytes per slice come down before the round's pictures are picked: from them the host fills
+ * in n_mbs and coverage and applies the same rules as ever.  Per stream: host from the start with opts->conceal; host for a picture
+ * with CABAC slices and for good behind the first of them; a round in which a slice of the stream gets a status (syntax the host fails
+ * on, a slice that runs into the next one) is parsed again by the host parser, and the stream stays with it.  Pictures, statuses, texts,
+ * digests and the stop-there position do not depend on parse.  lh264_decoded_parse_path tells the route.
+ * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a format out of range, a flag bit that is not
  * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
  * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
  * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
@@ -674,11 +697,27 @@ typedef struct lh264_decode_opts {
   uint64_t group_mbs;                   /* macroblocks of one round at most; 0 = the default (1,000,000)        */
   lh264_decode_sink_fn sink; void* user;
   uint32_t conceal;                     /* LH264_CONCEAL_*; 0 = off.  (struct_bytes up to `user`: off)          */
+  uint32_t reserved0;                   /* (the tail padding of the 48-byte struct: callers of it left it undefined, it is not read) */
+  uint32_t parse;                       /* LH264_PARSE_*; 0 = host.  (struct_bytes 40 and 48: host)             */
+  uint32_t reserved1;
 } lh264_decode_opts_t;
 #define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
+#define LH264_DECODE_OPTS_BYTES_V2 48u  /* the struct before `parse` was added: still accepted                   */
+#define LH264_PARSE_HOST   0u           /* the host front end parses slice data (the default)                    */
+#define LH264_PARSE_DEVICE 1u           /* CAVLC slice data is parsed by slice_parse_kernel, one wave per slice  */
+#define LH264_PARSE_PATH_HOST     0
+#define LH264_PARSE_PATH_DEVICE   1
+#define LH264_PARSE_PATH_FALLBACK 2
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads,
                         const lh264_decode_opts_t* opts /* NULL = defaults */, lh264_decoded_t** out);
 int lh264_decoded_status (const lh264_decoded_t* d);
+/* how the stream's slice data was parsed: LH264_PARSE_PATH_HOST (none of it on the device), _DEVICE (CAVLC slices by the kernel; CABAC
+ * pictures and what follows the first of them by the host), _FALLBACK (a slice of some round got a status from the kernel: that round's
+ * slices were parsed again by the host and the stream stayed there) */
+int lh264_decoded_parse_path (const lh264_decoded_t* d);
+/* ... and how many of the stream's slices slice_parse_kernel parsed (a round that fell back, and what the host parsed behind a CABAC
+ * picture, do not count; a picture that waited for another round counts once per round it was parsed in) */
+long long lh264_decoded_device_slices (const lh264_decoded_t* d);
 const char* lh264_decoded_error (const lh264_decoded_t* d);
 int lh264_decoded_pictures (const lh264_decoded_t* d);
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
@@ -699,6 +738,9 @@ void lh264_decode_release (void);
  * (host threads), ms[2] staging, ms[3] enqueueing the device stage, ms[4] the main thread's wait for the device (the download
  * included), ms[5] delivery (copies into the handles, or the sink).  LH264_TRACE_DECODE=1 prints the same to stderr. */
 int lh264_decode_last_timing (double* ms);
+/* parse = LH264_PARSE_DEVICE: of ms[1] above, out[0] the milliseconds of the device parse stage (filling tasks, upload, slice_parse_kernel,
+ * the wait for its results) and out[1] the number of slices it parsed, in the last call (0, 0 under LH264_PARSE_HOST) */
+int lh264_decode_last_parse_timing (double* out);
 /* one picture to crop and pack (decode_pack_kernel): the planes' pixel (0,0) in a padded picture, the window, where the packed
  * picture begins.  crop_x/y/w/h are even.  lh264_debug_pack_cpu steps the kernel's code over HOST memory: a check of the crop / format
  * arithmetic where no device is present; not a decode path */
@@ -713,6 +755,27 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message
  * without a span is the empty message.  out: 20 bytes per message */
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out);
+/* The CAVLC macroblock layer apart from the header walk (csrc/lh264_slice.h, slice_parse_kernel): one Annex-B stream goes through the
+ * deferred parser (lh264_parser_set_defer_slice_data), then every deferred slice through the one piece of code that parses slice data
+ * for the device - stepped on `threads` host threads (on_device = 0, needs no device) or run by slice_parse_kernel, one wave per slice
+ * (on_device != 0; LH264_E_NODEVICE without one).  The handle gives per picture what that code wrote: the records, the dense
+ * coefficient plane (768 bytes per macroblock), the slice table with n_mbs, and per slice 4 x int32 {1 = the slice was deferred, status,
+ * n_mbs, the bit position behind the last macroblock}; status 0 = parsed as the host front end parses it, 1 = syntax the host front end
+ * fails on, 2 = the slice would run into the next slice's first macroblock (nothing at or beyond it is written), 3 = an inconsistent
+ * task.  Every buffer the code reads or writes lies in one arena with 64 guard bytes behind it; lh264_slice_dump_guards_ok: 1 when all
+ * of them are intact after the run.  tweak (may be NULL): {picture, slice, limit_mb} replaces the limit of one slice - the macroblock
+ * at which it must stop - for tests of the overrun status.  lh264_slice_dump_error: the header walk's error text.  Not a decode path */
+typedef struct lh264_slice_dump lh264_slice_dump_t;
+int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int threads, const int32_t* tweak, lh264_slice_dump_t** out);
+int lh264_slice_dump_pictures (const lh264_slice_dump_t* d);
+int lh264_slice_dump_picture (const lh264_slice_dump_t* d, int idx, int32_t info[4] /* mb_w, mb_h, slices, deferred slices */);
+const lh264_mb_t* lh264_slice_dump_mbs (const lh264_slice_dump_t* d, int idx);
+const int16_t* lh264_slice_dump_coeffs (const lh264_slice_dump_t* d, int idx);
+const lh264_slice_t* lh264_slice_dump_slices (const lh264_slice_dump_t* d, int idx);
+const int32_t* lh264_slice_dump_results (const lh264_slice_dump_t* d, int idx);
+int lh264_slice_dump_guards_ok (const lh264_slice_dump_t* d);
+const char* lh264_slice_dump_error (const lh264_slice_dump_t* d);
+void lh264_slice_dump_free (lh264_slice_dump_t* d);
 /* the launch geometry lh264_recon_chains / lh264_recon_frames would choose for pictures of at most max_mb_w x max_mb_h macroblocks:
  * waves per workgroup (one per macroblock row in flight, at most 8, halved until the LDS line buffers fit; LH264_WAVES is honoured as
  * in a launch) and the dynamic LDS bytes.  Read-only, needs no device.  LH264_E_UNSUPPORTED with the launch's own text when one wave

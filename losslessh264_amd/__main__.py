@@ -17,7 +17,7 @@
                                                             units the format drops (delimiters, filler, ...) are kept, pictures with
                                                             lost slices are compressed; out.lhp is still restored and compared
                                                             before it is written, with the verbatim fallback behind it
-    python -m losslessh264_amd --decode [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
+    python -m losslessh264_amd --decode [--device-parse] [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
                                                             out_dir/<name>.yuv holds the cropped pictures as I420 (or NV12), appended
                                                             by a sink run by run.  METHOD: lost slices are concealed as the reference's
                                                             decoder does (slice_copy | slice_copy_cross_idr | mv_copy |
@@ -156,8 +156,11 @@ def restore(src, dst):
 
 def decode(argv):
     import losslessh264_amd as lh
-    nv12, conceal, sha1 = False, None, False
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1"):
+    nv12, conceal, sha1, parse = False, None, False, "host"
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse"):
+        if argv[0] == "--device-parse":
+            parse, argv = "device", argv[1:]
+            continue
         if argv[0] == "--nv12":
             nv12, argv = True, argv[1:]
         elif argv[0] == "--sha1":
@@ -172,11 +175,11 @@ def decode(argv):
         return 2
     ret = 0
     if sha1:
-        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal):
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

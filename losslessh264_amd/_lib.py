@@ -140,6 +140,12 @@ class DecodeOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("round_pictures", C.c_uint32),
                 ("group_mbs", C.c_uint64), ("sink", DECODE_SINK_FN), ("user", C.c_void_p), ("conceal", C.c_uint32)]
 DECODE_OPTS_BYTES_V1 = 40          # the struct before `conceal`: still accepted, concealment off
+class DecodeOptsV3(C.Structure):   # the struct as it is now: `parse` behind what was the 48-byte struct's tail padding
+    _fields_ = DecodeOpts._fields_ + [("reserved0", C.c_uint32), ("parse", C.c_uint32), ("reserved1", C.c_uint32)]
+DECODE_OPTS_BYTES_V2 = 48          # the struct before `parse` (DecodeOpts): still accepted, the host parses
+PARSE = {"host": 0, "device": 1}
+PARSE_PATH = {0: "host", 1: "device", 2: "fallback"}
+assert C.sizeof(DecodeOptsV3) == 56
 # LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
 CONCEAL = {"off": 0, "slice_copy": 2, "slice_copy_cross_idr": 4, "slice_copy_cross_idr_freeze": 5, "mv_copy": 6, "mv_copy_freeze": 7}
 class PackJob(C.Structure):
@@ -151,7 +157,10 @@ class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
 assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 48 and C.sizeof(PackJob) == 64 and C.sizeof(RestoreOpts) == 12
 _SIGS.update({
-    "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodeOpts), C.POINTER(C.c_void_p)]),
+    "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_parse_path": (C.c_int, [C.c_void_p]),
+    "lh264_decoded_device_slices": (C.c_longlong, [C.c_void_p]),
+    "lh264_decode_last_parse_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "lh264_decoded_status": (C.c_int, [C.c_void_p]),
     "lh264_decoded_error": (C.c_char_p, [C.c_void_p]),
     "lh264_decoded_pictures": (C.c_int, [C.c_void_p]),
@@ -172,6 +181,25 @@ _SIGS.update({
     "lh264_debug_sha1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "lh264_parser_set_sparse_coeffs": (C.c_int, [C.c_void_p, C.c_int]),
     "lh264_parser_frame_sparse_coeffs": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
+})
+# ---- CAVLC slice data apart from the header walk (csrc/lh264_slice.h)
+SLICE_OK, SLICE_SYNTAX, SLICE_OVERRUN, SLICE_BAD_TASK = 0, 1, 2, 3
+_SIGS.update({
+    "lh264_parser_set_defer_slice_data": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_frame_deferred": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_parse_deferred": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lh264_parser_error_pictures": (C.c_longlong, [C.c_void_p]),
+    "lh264_parser_file_status": (C.c_int, [C.c_void_p]),
+    "lh264_debug_slice_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_slice_dump_pictures": (C.c_int, [C.c_void_p]),
+    "lh264_slice_dump_picture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lh264_slice_dump_mbs": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lh264_slice_dump_coeffs": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lh264_slice_dump_slices": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lh264_slice_dump_results": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lh264_slice_dump_guards_ok": (C.c_int, [C.c_void_p]),
+    "lh264_slice_dump_error": (C.c_char_p, [C.c_void_p]),
+    "lh264_slice_dump_free": (None, [C.c_void_p]),
 })
 EXPORTS = sorted(_SIGS)
 

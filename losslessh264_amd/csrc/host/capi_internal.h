@@ -22,6 +22,32 @@ template <typename F> static void run_parallel (int n, int threads, F&& fn) {
   for (auto& t : pool) t.join();
 }
 
+// One CAVLC slice whose macroblock layer is parsed apart from its header (lh264_slice.h: on the device by slice_parse_kernel, on the
+// host by the same code).  The pointers are the walker's own: device addresses for the kernel, host addresses for the CPU form.
+namespace lh264host {
+struct SliceTask {
+  const uint8_t* rbsp;              // the slice NAL's unescaped payload ...
+  uint32_t rbsp_bytes, data_bit;    // ... its length, and the bit at which slice_data() begins
+  int32_t first_mb, limit_mb;       // the slice may write macroblocks [first_mb, limit_mb): limit_mb is the next slice's first_mb, or mb_w * mb_h
+  int32_t mb_w, mb_h;
+  int32_t slice_index;              // in its picture's lh264_slice_t table (the records' slice_id)
+  int32_t slice_qp;
+  uint8_t slice_type, num_ref_idx_l0, transform_8x8, constrained_intra_pred, use_sl;
+  int8_t chroma_qp_offset[2];
+  uint8_t reserved;
+  const uint8_t* scaling;           // use_sl: the PPS's resolved lists, 6 x 16 then 2 x 64 entries in raster order
+  lh264_mb_t* mbs;                  // the picture's records, 16-byte aligned
+  int16_t* coeffs;                  // the picture's coefficient plane, cleared by the caller
+  lh264_slice_t* slice;             // the slice's table entry: n_mbs is written (may be null: the result carries it too)
+  int8_t* line;                     // 4 * mb_w bytes of scratch; the kernel needs it only for pictures wider than its LDS line
+};
+static_assert (sizeof (SliceTask) == 88, "SliceTask is fixed-width: the host fills what the kernel reads");
+struct SliceResult { int32_t status, n_mbs, stop_bit; };
+// lh264_slice.hip: n tasks in device memory through slice_parse_kernel, enqueued on `stream`; force_fail: -1, or the task that is to
+// report a status unwalked
+bool launch_slice_parse (const SliceTask* tasks_dev, SliceResult* results_dev, int n, void* stream, int force_fail);
+}
+
 // n entries of (index << 16 | 16-bit value) in device memory written into the dense planes (lh264_capi.hip: expand_sparse_kernel, one
 // thread per entry, enqueued on `stream`); n > 0.  The caller asks hipGetLastError() if it wants to know
 namespace lh264host { void expand_sparse (const uint64_t* ents_dev, size_t n, int16_t* dense_dev, void* stream); }

@@ -2,6 +2,7 @@
 // (intra mode and motion vector prediction), 9.2 (CAVLC).  Frame (progressive) pictures, I and P slices, one slice
 // group -- the subset the reference decoder itself supports.
 #include "h264_parser.h"
+#include "../lh264_slice.h"
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -110,7 +111,6 @@ inline int z2x (int z) { return (z & 1) | ((z >> 2) & 1) << 1; }
 inline int z2y (int z) { return ((z >> 1) & 1) | ((z >> 3) & 1) << 1; }
 inline int xy2z (int x, int y) { return (x & 1) | ((y & 1) << 1) | ((x >> 1) << 2) | ((y >> 1) << 3); }
 inline bool zidx_before (int x, int y, int z) { return xy2z (x, y) < z; }
-const int kChromaNzcIdx[2][4] = {{16, 17, 20, 21}, {18, 19, 22, 23}};   // reference nzc layout (common_tables.cpp:39-47)
 
 struct DpbPic {
   int frame_id = -1, frame_num = 0, frame_num_wrap = 0, long_idx = -1;
@@ -248,7 +248,15 @@ struct Parser::Impl {
   explicit Impl (Parser* s) : self (s) {}
 
   // ---- helpers -------------------------------------------------------------------------------------------------
-  void fail (const std::string& m) { if (self->err_.empty()) { self->err_ = m; self->err_pictures_ = self->pictures_done_; } }
+  long nal_seq = 0, err_seq = 0;                        // NAL units handled so far; the one that raised error()
+  const DeferredSlice* deferred_now = nullptr;           // parse_deferred is running over this slice
+  void fail (const std::string& m) {
+    if (!self->err_.empty()) return;
+    self->err_ = m;
+    self->err_pictures_ = deferred_now ? deferred_now->pictures_before : self->pictures_done_;
+    err_seq = deferred_now ? deferred_now->seq : nal_seq;
+  }
+  bool parse_deferred (FrameOut& f, size_t slice);
 
   static void unescape (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
     out.clear(); out.reserve (n);
@@ -582,8 +590,8 @@ struct Parser::Impl {
       if (cur->slice_syn.size() == cur->slices.size()) symbolizer.picture (*cur);
       else { cur->syn_off.assign ((size_t)cur->mb_w * cur->mb_h + 1, 0); cur->syn_syms.clear(); }
     }
-    for (uint8_t c : cur->covered) if (!c) { self->damaged_ = true; break; }
-    if (self->conceal_) conceal_picture (cur_poc);
+    if (cur->deferred.empty()) for (uint8_t c : cur->covered) if (!c) { self->damaged_ = true; break; }
+    if (self->conceal_ && cur->deferred.empty()) conceal_picture (cur_poc);
     prev_pic_id = cur->id; prev_pic_poc = cur->is_ref && dpb.size() && dpb.back().frame_id == cur->id ? dpb.back().poc : cur_poc;
     cur->poc = prev_pic_poc;
     if (coef_unsorted) { sort_coeffs(); coef_unsorted = false; }
@@ -1714,6 +1722,7 @@ bool Parser::Impl::parse_slice_data_cabac (BitReader& br, SliceCtx& c) {
 }
 
 int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
+  nal_seq++;
   if (len < 1) return 0;
   const int type = nal[0] & 31, ref_idc = (nal[0] >> 5) & 3;
   if (type == 7 || type == 8 || type == 1 || type == 5) {
@@ -1762,6 +1771,13 @@ int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
     cur->slices.push_back (sl);
     if (sh.first_mb < 0 || (uint32_t)sh.first_mb >= (uint32_t) (S.mb_w * S.mb_h)) { fail ("first_mb_in_slice out of range"); return -1; }
     last_hdr_bits = (int)br.pos; last_cabac = P.cabac;
+    if (self->defer_ && !P.cabac) {
+      cur->deferred.emplace_back();
+      DeferredSlice& d = cur->deferred.back();
+      d.rbsp = rbsp; d.data_bit = br.pos; d.sid = c.sid; d.sh = sh; d.pps = P; d.sps_scaling = S.scaling_matrix_present;
+      d.seq = nal_seq; d.pictures_before = self->pictures_done_;
+      return 0;
+    }
     // (a slice that fails is not modelled: the I_PCM samples it appended so far would shift every later macroblock's in the PCM stream)
     const size_t pcm_mark = self->pcm_.size();
     if (P.cabac ? !parse_slice_data_cabac (br, c) : !parse_slice_data_cavlc (br, c)) { self->pcm_.resize (pcm_mark); return -1; }
@@ -1769,6 +1785,58 @@ int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
   }
   if (type == 10 || type == 11) finish_picture();
   return 0;
+}
+
+// The host macroblock layer over a slice that was deferred: the picture becomes the picture in progress for the length of the call, with
+// neighbour state of its own (availability is "same slice": nothing of another slice is ever read) and the recompressor's per-position
+// arrays set aside.
+bool Parser::Impl::parse_deferred (FrameOut& f, size_t slice) {
+  if (slice >= f.deferred.size()) return false;
+  DeferredSlice& d = f.deferred[slice];
+  if (d.resolved) return d.ok;
+  const size_t n = (size_t)f.mb_w * f.mb_h;
+  struct Swap {
+    Impl* I; std::unique_ptr<FrameOut> cur; std::vector<MbState> st; std::vector<uint8_t> rbsp, pc, pl, ps; int pw, ph, cq, rb; bool unsorted;
+    std::string err; long err_pictures, err_seq;
+    Swap (Impl* i, FrameOut& f, size_t n, DeferredSlice& d) : I (i), pw (i->persist_w), ph (i->persist_h), cq (i->slice_cached_qp), rb (i->slice_run_before), unsorted (i->coef_unsorted) {
+      cur = std::move (I->cur); I->cur.reset (&f);
+      st.swap (I->st); I->st.assign (n, MbState());
+      rbsp.swap (I->rbsp); I->rbsp.swap (d.rbsp);
+      pc.swap (I->persist_chroma); pl.swap (I->persist_l16); ps.swap (I->persist_sub);
+      I->persist_chroma.assign (n, 0); I->persist_l16.assign (n, 0); I->persist_sub.assign (n * 4, 0);
+      I->coef_unsorted = false;
+      err.swap (I->self->err_); err_pictures = I->self->err_pictures_; err_seq = I->err_seq;
+      I->deferred_now = &d;
+    }
+    ~Swap() {
+      DeferredSlice& d = const_cast<DeferredSlice&> (*I->deferred_now);
+      I->deferred_now = nullptr;
+      // the error that stands is the one of the earlier NAL unit
+      if (I->self->err_.empty() || (!err.empty() && err_seq < d.seq)) { I->self->err_.swap (err); I->self->err_pictures_ = err_pictures; I->err_seq = err_seq; }
+      I->coef_unsorted = unsorted;
+      I->persist_chroma.swap (pc); I->persist_l16.swap (pl); I->persist_sub.swap (ps);
+      I->persist_w = pw; I->persist_h = ph; I->slice_cached_qp = cq; I->slice_run_before = rb;
+      d.rbsp.swap (I->rbsp); I->rbsp.swap (rbsp);
+      I->st.swap (st);
+      I->cur.release(); I->cur = std::move (cur);
+    }
+  } swap (this, f, n, d);
+  Sps S; S.scaling_matrix_present = d.sps_scaling; S.mb_w = f.mb_w; S.mb_h = f.mb_h;
+  SliceCtx c; c.S = &S; c.P = &d.pps; c.sh = &d.sh; c.sid = d.sid;
+  BitReader br; br.init (rbsp.data(), rbsp.size()); br.pos = d.data_bit;
+  const size_t pcm_mark = self->pcm_.size();
+  d.resolved = true;
+  // (an exception is caught here, while the slice is still the one in hand: its error lands at the slice's place in the stream)
+  try { d.ok = parse_slice_data_cavlc (br, c); }
+  catch (const std::exception& e) { fail (std::string ("internal: ") + e.what()); d.ok = false; }
+  d.stop_bit = br.pos;
+  if (!d.ok) { self->pcm_.resize (pcm_mark); self->file_rc_ = -1; }
+  if (coef_unsorted) sort_coeffs();
+  return d.ok;
+}
+bool Parser::parse_deferred (FrameOut& f, size_t slice) {
+  try { return d_->parse_deferred (f, slice); }
+  catch (const std::exception& e) { d_->fail (std::string ("internal: ") + e.what()); return false; }
 }
 
 Parser::Parser() : d_ (new Impl (this)) {}

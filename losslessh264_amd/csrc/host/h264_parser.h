@@ -172,6 +172,20 @@ template <typename T> struct PoolAlloc {
 };
 template <typename T> using PoolVec = std::vector<T, PoolAlloc<T>>;
 
+// Parser::set_defer_slice_data: a CAVLC slice whose header was walked and whose macroblock layer was not.  Everything that layer reads
+// is held here by value (a later PPS with the same id does not change it): the unescaped payload, where slice_data() begins, the
+// header, the picture parameter set and the one fact of the sequence parameter set that counts.  seq / pictures_before place the
+// slice in the stream for the error it may still raise.
+struct DeferredSlice {
+  std::vector<uint8_t> rbsp;
+  size_t data_bit = 0;
+  int sid = 0;                             // index in FrameOut::slices
+  SliceHeader sh; Pps pps; bool sps_scaling = false;
+  long seq = 0, pictures_before = 0;
+  bool resolved = false, ok = false;       // parse_deferred ran, and what it returned
+  size_t stop_bit = 0;                     // ... and where its bit reader stood then
+};
+
 // one parsed picture: exactly what lh264_recon_chains / lh264_ctx_index_chains consume
 struct FrameOut {
   int id = 0, mb_w = 0, mb_h = 0, frame_num = 0, crop_w = 0, crop_h = 0, crop_x = 0, crop_y = 0;
@@ -197,6 +211,7 @@ struct FrameOut {
   int concealed = 0, conceal_src = -1; bool frozen = false;
   int poc = 0;                             // the picture's POC as the reference's concealment counts it once the picture is done: pic_order_cnt_lsb, 0 behind an mmco 5
   int32_t conceal_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<DeferredSlice> deferred;     // Parser::set_defer_slice_data: the picture's CAVLC slices, in stream order
 };
 
 // The recompressor's default stream (".pip" itself, stream id 0x7fffffff): the Annex-B input minus its slice data.
@@ -294,6 +309,16 @@ class Parser {
   // concealed as the reference's decoder does it, see FrameOut::concealed.  Not for the compress direction: the records of a concealed
   // picture are not the stream's.  false: a method that is not provided (the FRAME_COPY pair)
   bool set_conceal (int method);
+  // on: the macroblock layer of a CAVLC slice is not parsed.  handle_nal does all it does up to the slice's entry in FrameOut::slices and
+  // the first_mb range check, then keeps a DeferredSlice with the picture; records, coefficients, `covered`, n_mbs and slice_syn of that
+  // slice stay as start_picture left them until somebody fills them in (lh264_slice.h on the device or the host) or parse_deferred does.
+  // CABAC slices are parsed on the spot.  For the decode direction: the symbol lists, the I_PCM sample stream, damaged() and
+  // concealment are not maintained for deferred pictures.  Off (the default): nothing changes
+  void set_defer_slice_data (bool on) { defer_ = on; }
+  // the host macroblock layer over deferred slice `slice` of a picture this parser completed (the slices of a picture in order): records,
+  // covered, n_mbs, slice_syn as the undeferred parser leaves them; on failure error() / error_pictures() as it would have set them
+  // (a deferred slice lies in front of whatever failed after it).  false: the slice failed, or there is no such slice
+  bool parse_deferred (FrameOut& f, size_t slice);
   static bool conceal_method_ok (int method);
   int conceal() const { return conceal_; }
   // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
@@ -323,6 +348,7 @@ class Parser {
   int n_unsupported_ = 0;
   bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false, sparse_coeffs_ = false; long pictures_done_ = 0, err_pictures_ = 0; bool damaged_ = false;
   int conceal_ = 0;
+  bool defer_ = false;
   bool tolerant_ = false; long nal_index_ = 0; std::string not_kept_, not_carried_;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;

@@ -780,6 +780,17 @@ int lh264_parser_frame_conceal (const lh264_parser_t* p, int idx, int32_t out[12
   out[7] = f->conceal_info[4]; out[8] = f->conceal_info[5]; out[9] = f->conceal_info[6]; out[10] = f->conceal_info[7]; out[11] = f->poc;
   return LH264_OK;
 }
+int lh264_parser_set_defer_slice_data (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_defer_slice_data (on != 0); return LH264_OK; }
+int lh264_parser_frame_deferred (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? (int)f->deferred.size() : 0; }
+int lh264_parser_parse_deferred (lh264_parser_t* p, int idx, int slice, int32_t out[2]) {
+  if (!p || idx < 0 || (size_t)idx >= p->p.frames().size() || slice < 0 || (size_t)slice >= p->p.frames()[(size_t)idx]->deferred.size()) return LH264_E_ARG;
+  lh264host::FrameOut& f = *p->p.frames()[(size_t)idx];
+  const bool ok = p->p.parse_deferred (f, (size_t)slice);
+  if (out) { out[0] = f.deferred[(size_t)slice].sid; out[1] = (int32_t)f.deferred[(size_t)slice].stop_bit; }
+  return ok ? 1 : 0;
+}
+long long lh264_parser_error_pictures (const lh264_parser_t* p) { return p ? (long long)p->p.error_pictures() : 0; }
+int lh264_parser_file_status (const lh264_parser_t* p) { return p ? p->p.file_status() : LH264_E_ARG; }
 int lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_sparse_coeffs (on != 0); return LH264_OK; }
 const uint64_t* lh264_parser_frame_sparse_coeffs (const lh264_parser_t* p, int idx, size_t* count) {
   auto f = pf (p, idx);

@@ -22,6 +22,7 @@
 #include "host/capi_internal.h"
 #include "host/device_mem.h"
 #include "lh264_sha1.h"
+#include "lh264_slice.h"
 
 // ---- the pack step: crop + I420 / NV12, host and device from one source ------------------------------------------------------------
 // A picture is cut into bands of 16 luma rows (and the 8 chroma rows that belong to them); a band's rows are cut into PIECES: the
@@ -132,6 +133,8 @@ struct lh264_decoded {
   std::string error;
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
+  int parse_path = LH264_PARSE_PATH_HOST;
+  long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
   uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
@@ -200,6 +203,10 @@ struct Arena {
   // picture messages (scratch), and one record per stream of the batch that lives as long as the call
   DevBuf d_sjobs, d_dig, d_rec, d_state;
   PinBuf h_sjobs[2], h_dig[2];
+  // parse = LH264_PARSE_DEVICE: the round's slice payloads (+ scaling lists, + lines of wide pictures), tasks and results; the records and
+  // coefficient planes slice_parse_kernel writes and recon_chain_kernel reads
+  DevBuf d_pbytes, d_ptasks, d_pres, d_pmbs, d_pcoef;
+  PinBuf h_pbytes, h_ptasks, h_pres;
   PicCache pics;
   hipStream_t s_run = nullptr, s_down = nullptr;
   hipEvent_t e_run[2] = {nullptr, nullptr}, e_down[2] = {nullptr, nullptr};
@@ -218,11 +225,11 @@ struct Arena {
   }
   size_t device_bytes() const {
     size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
-    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state}) n += b->cap;
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef}) n += b->cap;
     return n;
   }
   size_t pinned_bytes() const {
-    size_t n = 0;
+    size_t n = h_pbytes.cap + h_ptasks.cap + h_pres.cap;
     for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap;
     return n;
   }
@@ -251,6 +258,11 @@ struct DStream {
   bool sha_started = false;                          // the stream's digest record on the device holds its message so far
   bool stopped = false;                              // the sink refused, or the device stage failed: nothing more is delivered
   std::vector<std::unique_ptr<FrameOut>> sel;        // the pictures of the round in preparation
+  // parse = LH264_PARSE_DEVICE: the stream's CAVLC slices go to slice_parse_kernel (until a CABAC picture or a fallback ends that), and
+  // where in the parse arena the records / the slice table of the pictures parsed there in this round lie
+  bool dev_route = false;
+  struct DevAt { size_t mb; };
+  std::map<const FrameOut*, DevAt> dev_at;
 };
 
 // one chain of a round that is on the device: what its delivery needs
@@ -276,6 +288,7 @@ std::string refuse_picture (const FrameOut& f) {
 
 lh264host::PerDevice<Arena> g_arena;      // one decode call at a time per device
 double g_timing[6] = {0, 0, 0, 0, 0, 0};
+double g_parse_timing[2] = {0, 0};      // of g_timing[1]: the device parse stage (tasks, upload, slice_parse_kernel, results), and its slices
 
 const uint32_t kDefaultRoundPictures = 8;
 const uint64_t kDefaultGroupMbs = 1000000;
@@ -347,11 +360,13 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
                ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
-  const int conceal = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? (int)opts->conceal : 0;
+  const int conceal = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V2 ? (int)opts->conceal : 0;
+  const uint32_t parse = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? opts->parse : LH264_PARSE_HOST;
+  if (parse != LH264_PARSE_HOST && parse != LH264_PARSE_DEVICE) return LH264_E_ARG;
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -372,7 +387,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
   const double t_call = now_s();
-  double t_parse = 0, t_stage = 0, t_enqueue = 0, t_wait = 0, t_deliver = 0;
+  double t_parse = 0, t_stage = 0, t_enqueue = 0, t_wait = 0, t_deliver = 0, t_dev_parse = 0, n_dev_slices = 0;
 
   std::vector<std::unique_ptr<DStream>> active;
   std::vector<std::unique_ptr<DStream>> retired;   // streams that are through (a round on the device still names them)
@@ -382,6 +397,9 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   int rb = 0;                                       // the buffers the next round takes
   bool device_failed = false;
   std::string device_error;
+  const bool parse_dev = parse == LH264_PARSE_DEVICE && conceal == 0;      // (concealment builds records on the host)
+  // LH264_SLICE_PARSE_FAIL=k (tests): task k of the call's first parse launch reports a status unwalked, which forces the fallback
+  int force_fail = parse_dev && getenv ("LH264_SLICE_PARSE_FAIL") ? atoi (getenv ("LH264_SLICE_PARSE_FAIL")) : -1;
 
   auto release_pool = [&] (DStream& s) {
     for (Slot& sl : s.pool) A.pics.put (s.geo.bytes, sl.base);
@@ -396,16 +414,17 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   };
 
   // host threads: parse until the stream has a round's pictures (or ends), then pick the round's pictures
-  auto fill_and_select = [&] (DStream& s) {
+  // tentative (a stream on the device route): the round's candidates, before their slice data is parsed - nothing is refused yet
+  auto fill_and_select = [&] (DStream& s, bool fill, bool tentative) {
     Parser& P = *s.parser;
-    while (s.pending.size() < R && !P.file_finished()) {
+    while (fill && s.pending.size() < R && !P.file_finished()) {
       const size_t want = s.pic_mbs ? (R - s.pending.size()) * s.pic_mbs - 1 : 0;
       P.feed_file_some (want);
       for (auto& f : P.frames()) { s.pic_mbs = (size_t)f->mb_w * f->mb_h; s.pending.push_back (std::move (f)); }
       P.frames().clear();
     }
     s.ending = false; s.end_code = LH264_OK; s.end_text.clear();
-    const bool has_err = !P.error().empty();
+    const bool has_err = !tentative && !P.error().empty();
     const long limit = has_err ? P.error_pictures() : 0x7fffffffffffffffl;
     while (s.sel.size() < R) {
       const long idx = s.next_picture + (long)s.sel.size();
@@ -415,7 +434,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         break;
       }
       FrameOut& f = *s.pending.front();
-      const std::string why = refuse_picture (f);
+      const std::string why = tentative ? std::string() : refuse_picture (f);
       if (!why.empty()) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + why; break; }
       // a change of resolution ends the round: the next one starts with a new pool
       if (!s.sel.empty() && (f.mb_w != s.sel[0]->mb_w || f.mb_h != s.sel[0]->mb_h)) break;
@@ -502,6 +521,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s->parser->set_sparse_coeffs (true);
         s->parser->set_sparse_levels (true);       // (the parser has no mode without levels: their list is the cheapest form)
         s->parser->set_conceal (conceal);
+        s->dev_route = parse_dev;
+        s->parser->set_defer_slice_data (parse_dev);
         s->parser->begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
         active.push_back (std::move (s));
         used += avg * R; admitted++;
@@ -509,7 +530,125 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     }
     if (active.empty()) break;
     const double t_a = now_s();
-    run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k]); });
+    run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k], true, parse_dev); });
+    if (parse_dev) {
+      // ---- the round's CAVLC slice data on the device: payloads and tasks up, slice_parse_kernel, 12 bytes per slice down; then the
+      // round's pictures are picked as ever.  On the run stream, behind the round before (whose kernels still read the parse arena),
+      // and waited for: the results decide what the round holds
+      const double t_p0 = now_s();
+      struct TRef { DStream* s; FrameOut* f; size_t def, bytes_at; };
+      std::vector<TRef> refs;
+      size_t pm = 0, pb = 0;
+      for (auto& sp : active) {
+        DStream& s = *sp;
+        s.dev_at.clear();
+        for (auto& fp : s.sel) {
+          FrameOut& f = *fp;
+          if (f.deferred.empty()) {
+            // a picture of CABAC slices (parsed on the spot): the stream stays with the host parser from here on
+            if (!f.slices.empty() && s.dev_route) { s.dev_route = false; s.parser->set_defer_slice_data (false); }
+            continue;
+          }
+          if (!s.dev_route) continue;
+          s.dev_at[&f] = {pm};
+          pm += (size_t)f.mb_w * f.mb_h;
+          for (size_t d = 0; d < f.deferred.size(); d++) refs.push_back ({&s, &f, d, 0});
+        }
+      }
+      std::stable_sort (refs.begin(), refs.end(), [] (const TRef& a, const TRef& b) { return a.f->deferred[a.def].rbsp.size() > b.f->deferred[b.def].rbsp.size(); });
+      for (TRef& r : refs) {
+        r.bytes_at = pb;
+        pb += ((r.f->deferred[r.def].rbsp.size() + 15) & ~ (size_t)15) + 224 + (r.f->mb_w > lh264slice::kLdsLineMbs ? (((size_t)r.f->mb_w * 4 + 15) & ~ (size_t)15) : 0);
+      }
+      const size_t nt = refs.size();
+      bool ok = true;
+      if (nt) {
+        ok = A.d_pbytes.alloc (pb) && A.h_pbytes.alloc (pb) && A.d_ptasks.alloc (nt * sizeof (lh264host::SliceTask)) && A.h_ptasks.alloc (nt * sizeof (lh264host::SliceTask)) &&
+             A.d_pres.alloc (nt * sizeof (lh264host::SliceResult)) && A.h_pres.alloc (nt * sizeof (lh264host::SliceResult)) &&
+             A.d_pmbs.alloc (pm * sizeof (lh264_mb_t)) && A.d_pcoef.alloc (pm * 768);
+        if (ok) {
+          uint8_t* hb = A.h_pbytes.as<uint8_t>(); uint8_t* db = A.d_pbytes.as<uint8_t>();
+          lh264host::SliceTask* ht = A.h_ptasks.as<lh264host::SliceTask>();
+          run_parallel ((int)nt, threads, [&] (int j) {
+            const TRef& r = refs[(size_t)j];
+            const FrameOut& f = *r.f;
+            const lh264host::DeferredSlice& ds = f.deferred[r.def];
+            const DStream::DevAt at = r.s->dev_at.at (r.f);
+            const int n = f.mb_w * f.mb_h;
+            const size_t sc_at = r.bytes_at + ((ds.rbsp.size() + 15) & ~ (size_t)15);
+            if (!ds.rbsp.empty()) memcpy (hb + r.bytes_at, ds.rbsp.data(), ds.rbsp.size());
+            memcpy (hb + sc_at, ds.pps.sl4, 96); memcpy (hb + sc_at + 96, ds.pps.sl8, 128);
+            lh264host::SliceTask& t = ht[j];
+            memset (&t, 0, sizeof (t));
+            t.rbsp = db + r.bytes_at; t.rbsp_bytes = (uint32_t)ds.rbsp.size(); t.data_bit = (uint32_t)ds.data_bit;
+            t.first_mb = ds.sh.first_mb;
+            t.limit_mb = (size_t)ds.sid + 1 < f.slices.size() ? std::min (n, f.slices[(size_t)ds.sid + 1].first_mb) : n;
+            t.mb_w = f.mb_w; t.mb_h = f.mb_h; t.slice_index = ds.sid; t.slice_qp = ds.sh.slice_qp;
+            t.slice_type = (uint8_t)ds.sh.slice_type; t.num_ref_idx_l0 = (uint8_t)ds.sh.num_ref_idx_l0;
+            t.transform_8x8 = ds.pps.transform_8x8; t.constrained_intra_pred = ds.pps.constrained_intra_pred;
+            t.use_sl = ds.sps_scaling || ds.pps.scaling_matrix_present;
+            t.chroma_qp_offset[0] = (int8_t)ds.pps.chroma_qp_offset[0]; t.chroma_qp_offset[1] = (int8_t)ds.pps.chroma_qp_offset[1];
+            t.scaling = db + sc_at;
+            t.mbs = A.d_pmbs.as<lh264_mb_t>() + at.mb; t.coeffs = A.d_pcoef.as<int16_t>() + at.mb * 384;
+            t.slice = nullptr;                                  // (the host fills n_mbs in from the result; the table is staged as ever)
+            t.line = f.mb_w > lh264slice::kLdsLineMbs ? (int8_t*) (db + sc_at + 224) : nullptr;
+          });
+          hipStream_t st = A.s_run;
+          ok = hipMemcpyAsync (A.d_pbytes.p, hb, pb, hipMemcpyHostToDevice, st) == hipSuccess &&
+               hipMemcpyAsync (A.d_ptasks.p, ht, nt * sizeof (lh264host::SliceTask), hipMemcpyHostToDevice, st) == hipSuccess &&
+               hipMemsetAsync (A.d_pmbs.p, 0, pm * sizeof (lh264_mb_t), st) == hipSuccess && hipMemsetAsync (A.d_pcoef.p, 0, pm * 768, st) == hipSuccess &&
+               lh264host::launch_slice_parse (A.d_ptasks.as<lh264host::SliceTask>(), A.d_pres.as<lh264host::SliceResult>(), (int)nt, st, force_fail) &&
+               hipMemcpyAsync (A.h_pres.p, A.d_pres.p, nt * sizeof (lh264host::SliceResult), hipMemcpyDeviceToHost, st) == hipSuccess &&
+               hipStreamSynchronize (st) == hipSuccess;
+          force_fail = -1;
+        }
+        if (!ok) {
+          fail_device ("the slice parse stage failed");
+          for (auto& s : active) { s->dev_at.clear(); unselect (*s); }
+          deliver (rounds[rb ^ 1], rb ^ 1);
+          continue;
+        }
+      }
+      if (ok && nt) {
+        const lh264host::SliceResult* res = A.h_pres.as<lh264host::SliceResult>();
+        // a status anywhere in a stream's round: the whole round of that stream goes back to the host parser, and the stream stays there
+        for (size_t j = 0; j < nt; j++) if (res[j].status != lh264slice::SLICE_OK && refs[j].s->dev_route) {
+          DStream& s = *refs[j].s;
+          s.dev_route = false; s.parser->set_defer_slice_data (false); s.dev_at.clear();
+          out[s.i]->parse_path = LH264_PARSE_PATH_FALLBACK;
+        }
+        for (size_t j = 0; j < nt; j++) {
+          const TRef& r = refs[j];
+          if (!r.s->dev_route) continue;
+          FrameOut& f = *r.f;
+          const lh264host::DeferredSlice& ds = f.deferred[r.def];
+          if (out[r.s->i]->parse_path == LH264_PARSE_PATH_HOST) out[r.s->i]->parse_path = LH264_PARSE_PATH_DEVICE;
+          out[r.s->i]->device_slices++;
+          // what parse_slice_data_cavlc leaves with the picture: n_mbs, coverage, the slice's syntax entry
+          f.slices[(size_t)ds.sid].n_mbs = res[j].n_mbs;
+          for (int k = 0; k < res[j].n_mbs; k++) f.covered[(size_t) (ds.sh.first_mb + k)] = 1;
+          lh264host::SliceSyn ss;
+          const size_t stop = (size_t)res[j].stop_bit;
+          ss.pad_bits = 7 - (int) (stop & 7);
+          ss.pad_value = (ss.pad_bits && (stop >> 3) < ds.rbsp.size()) ? (ds.rbsp[stop >> 3] & ((1 << ss.pad_bits) - 1)) : 0;
+          ss.transform8x8_pps = ds.pps.transform_8x8 ? 1 : 0;
+          ss.flags = ds.pps.constrained_intra_pred ? 2 : 0;
+          if (f.slice_syn.size() <= (size_t)ds.sid) f.slice_syn.resize ((size_t)ds.sid + 1);
+          f.slice_syn[(size_t)ds.sid] = ss;
+        }
+      }
+      t_dev_parse += now_s() - t_p0; n_dev_slices += (double)nt;
+      // whatever was deferred and did not stay on the device is parsed by the host parser now (a fallback, the pictures behind a CABAC
+      // picture); then the round's pictures are picked with everything known
+      run_parallel ((int)active.size(), threads, [&] (int k) {
+        DStream& s = *active[k];
+        auto resolve = [&] (FrameOut& f) { if (!s.dev_at.count (&f)) for (size_t d = 0; d < f.deferred.size(); d++) s.parser->parse_deferred (f, d); };
+        for (auto& f : s.sel) resolve (*f);
+        if (!s.dev_route) for (auto& f : s.pending) resolve (*f);
+        unselect (s);
+        fill_and_select (s, false, false);
+      });
+    }
     const double t_b = now_s();
     t_parse += t_b - t_a;
 
@@ -519,14 +658,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     rd.chains.clear(); rd.out_bytes = 0;
     struct Place { size_t mb0, sl0, sp0, job0; };
     std::vector<Place> place;
-    size_t n_mbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0;
+    size_t n_mbs = 0, n_hmbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0;      // n_hmbs: the macroblocks whose records the host stages (not those in the parse arena)
     int max_w = 1, max_h = 1, max_bands = 1;
     bool alloc_ok = true;
     for (auto& sp : active) {
       DStream& s = *sp;
       if (s.sel.empty()) continue;
-      size_t m = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; shown++; } }
+      size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -537,8 +676,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       RoundChain c;
       c.s = &s; c.first_picture = (int)s.delivered; c.at = rd.out_bytes; c.bytes = bytes; c.n_out = shown; c.dig0 = n_out;
       n_out += shown;
-      place.push_back ({n_mbs, n_sl, n_sp, n_jobs});
-      n_mbs += m; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
+      place.push_back ({n_hmbs, n_sl, n_sp, n_jobs});
+      n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       rd.out_bytes += (bytes + 15) & ~ (size_t)15;
       max_w = std::max (max_w, f0.mb_w); max_h = std::max (max_h, f0.mb_h);
       rd.chains.push_back (std::move (c));
@@ -549,10 +688,10 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       continue;
     }
     const int n_chains = (int)rd.chains.size();
-    alloc_ok = A.d_mbs.alloc (n_mbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_mbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
+    alloc_ok = A.d_mbs.alloc (n_hmbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_hmbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_chains + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
-               A.h_mbs[rb].alloc (n_mbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
+               A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_chains + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
     const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
     rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
@@ -593,14 +732,17 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       for (size_t q = 0; q < s.sel.size(); q++) {
         FrameOut& f = *s.sel[q];
         const size_t nm = (size_t)f.mb_w * f.mb_h;
-        memcpy (&h_mbs[mo], f.mbs.data(), nm * sizeof (lh264_mb_t));
+        const auto dev_it = s.dev_at.find (&f);                  // the picture's records and coefficients lie in the parse arena
+        const bool on_dev = dev_it != s.dev_at.end();
+        if (!on_dev) memcpy (&h_mbs[mo], f.mbs.data(), nm * sizeof (lh264_mb_t));
         memcpy (&h_sl[so], f.slices.data(), f.slices.size() * sizeof (lh264_slice_t));
         { const uint64_t add = (uint64_t) (mo * 384) << 16; const size_t ns = f.sparse_coeffs.size(); for (size_t e = 0; e < ns; e++) h_sparse[po + e] = f.sparse_coeffs[e] + add; po += ns; }
         const Slot& me = s.pool[slot_of[c][q]];
         auto pic_at = [&] (const uint8_t* base) { lh264_pic_t p; p.y_dev = (uint8_t*)base + s.geo.off[0]; p.u_dev = (uint8_t*)base + s.geo.off[1]; p.v_dev = (uint8_t*)base + s.geo.off[2]; return p; };
         lh264_frame_job_t& jb = h_jobs[j];
         memset (&jb, 0, sizeof (jb));
-        jb.mbs_dev = A.d_mbs.as<lh264_mb_t>() + mo; jb.coeffs_dev = A.d_coef.as<int16_t>() + mo * 384; jb.slices_dev = A.d_sl.as<lh264_slice_t>() + so;
+        jb.mbs_dev = on_dev ? A.d_pmbs.as<lh264_mb_t>() + dev_it->second.mb : A.d_mbs.as<lh264_mb_t>() + mo;
+        jb.coeffs_dev = on_dev ? A.d_pcoef.as<int16_t>() + dev_it->second.mb * 384 : A.d_coef.as<int16_t>() + mo * 384; jb.slices_dev = A.d_sl.as<lh264_slice_t>() + so;
         jb.dst = pic_at (me.base);
         for (size_t k = 0; k < LH264_MAX_REFS; k++) {
           // A slot the picture does not fill, or whose picture is not held, points at the 128 picture.  recon_chain_kernel reads job slot
@@ -616,7 +758,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         jb.flags = f.is_ref ? 0 : LH264_JOB_NO_EXPAND;
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
-        if (f.frozen) { mo += nm; so += f.slices.size(); j++; continue; }      // withheld: a reference like any other, but no window to pack (crop_h 0)
+        if (f.frozen) { if (!on_dev) mo += nm; so += f.slices.size(); j++; continue; }      // withheld: a reference like any other, but no window to pack (crop_h 0)
         pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
         pj.dst = d_out + at;
         pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
@@ -627,7 +769,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         rc.pics.push_back (dp);
         rc.concealed.push_back (f.concealed);
         at += bytes; off += bytes;
-        mo += nm; so += f.slices.size(); j++;
+        if (!on_dev) mo += nm;
+        so += f.slices.size(); j++;
       }
     });
     h_first[n_chains] = (int32_t)n_jobs;
@@ -667,9 +810,9 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     {
       hipStream_t st = A.s_run;
       auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
-      bool ok = up (A.d_mbs, h_mbs, n_mbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
+      bool ok = up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
                 up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_chains + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
-                hipMemsetAsync (A.d_coef.p, 0, n_mbs * 768, st) == hipSuccess;
+                (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
       if (ok) { hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>()); ok = hipGetLastError() == hipSuccess; }
@@ -717,6 +860,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   // (streams that were complete before a failure of the device stage keep their result; the others carry the error)
   if (device_failed) for (int i = next_stream; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = device_error; }
   g_timing[0] = (now_s() - t_call) * 1e3; g_timing[1] = t_parse * 1e3; g_timing[2] = t_stage * 1e3; g_timing[3] = t_enqueue * 1e3; g_timing[4] = t_wait * 1e3; g_timing[5] = t_deliver * 1e3;
+  g_parse_timing[0] = t_dev_parse * 1e3; g_parse_timing[1] = n_dev_slices;
   if (trace_on()) fprintf (stderr, "[lh264 decode] %d streams: %.3f s (parse %.3f, staging %.3f, enqueue %.3f, waiting for the device %.3f, delivery %.3f); arena %.1f MB device, %.1f MB pinned\n",
                            n, g_timing[0] / 1e3, t_parse, t_stage, t_enqueue, t_wait, t_deliver, A.device_bytes() / 1e6, A.pinned_bytes() / 1e6);
   return LH264_OK;
@@ -727,7 +871,14 @@ int lh264_decode_last_timing (double* ms) {
   for (int k = 0; k < 6; k++) ms[k] = g_timing[k];
   return LH264_OK;
 }
+int lh264_decode_last_parse_timing (double* out) {
+  if (!out) return LH264_E_ARG;
+  out[0] = g_parse_timing[0]; out[1] = g_parse_timing[1];
+  return LH264_OK;
+}
 int lh264_decoded_status (const lh264_decoded_t* d) { return d ? d->status : LH264_E_ARG; }
+int lh264_decoded_parse_path (const lh264_decoded_t* d) { return d ? d->parse_path : LH264_E_ARG; }
+long long lh264_decoded_device_slices (const lh264_decoded_t* d) { return d ? (long long)d->device_slices : 0; }
 const char* lh264_decoded_error (const lh264_decoded_t* d) { return d ? d->error.c_str() : ""; }
 int lh264_decoded_pictures (const lh264_decoded_t* d) { return d ? (int)d->pics.size() : 0; }
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* o) {

@@ -31,6 +31,15 @@ class DecodedBatch:
     def status(self, i):
         return self._lib.lh264_decoded_status(self._h[i])
 
+    def parse_path(self, i):
+        """how stream i's slice data was parsed: "host" | "device" | "fallback" (decode_batch (parse="device"): a slice got a status from
+        the kernel, its round was parsed again by the host parser and the stream stayed there)"""
+        return L.PARSE_PATH[self._lib.lh264_decoded_parse_path(self._h[i])]
+
+    def device_slices(self, i):
+        """how many slices of stream i slice_parse_kernel parsed (0 on the host route)"""
+        return int(self._lib.lh264_decoded_device_slices(self._h[i]))
+
     def error(self, i):
         return self._lib.lh264_decoded_error(self._h[i]).decode()
 
@@ -105,7 +114,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host"):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -117,7 +126,9 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     first whole IDR picture).  DecodedBatch.concealed(i) counts the concealed macroblocks per picture.
     sha1: None | "pictures" | "stream" | "both": SHA-1 digests computed on the device, of every delivered picture
     (DecodedBatch.picture_sha1) and / or of all delivered pictures of a stream in order (stream_sha1: for "i420" the number the
-    reference's decoder test keeps per stream).  pictures=False (with sha1): digests only, no picture leaves the device."""
+    reference's decoder test keeps per stream).  pictures=False (with sha1): digests only, no picture leaves the device.
+    parse: "host" (the default) | "device": CAVLC slice data is parsed on the device by slice_parse_kernel, one wave per slice; the host
+    walks headers only.  The bytes are the same; DecodedBatch.parse_path(i) tells the route each stream took."""
     lib = L.lib()
     if fmt not in _FORMATS:
         raise ValueError("fmt must be 'i420' or 'nv12'")
@@ -125,14 +136,17 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
     if sha1 not in _SHA1:
         raise ValueError("sha1 must be None, 'pictures', 'stream' or 'both'")
+    if parse not in L.PARSE:
+        raise ValueError("parse must be 'host' or 'device'")
     if not pictures and (sha1 is None or device_out or sink is not None):
         raise ValueError("pictures=False needs sha1= and neither device_out nor a sink")
     n = len(datas)
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
     lens = (C.c_size_t * n)(*[len(d) for d in keep])
-    opts = L.DecodeOpts()
-    opts.struct_bytes = C.sizeof(L.DecodeOpts)
+    opts = L.DecodeOptsV3()
+    opts.struct_bytes = C.sizeof(L.DecodeOptsV3)
+    opts.parse = L.PARSE[parse]
     opts.format = _FORMATS[fmt]
     opts.flags = (L.DECODE_DEVICE_OUT if device_out else 0) | _SHA1[sha1] | (0 if pictures else L.DECODE_NO_PICTURES)
     opts.round_pictures = int(round_pictures or 0)
@@ -167,7 +181,7 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
     """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
     pictures, bytes)]"""
     datas = [open(p, "rb").read() for p in paths]
@@ -181,7 +195,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None):
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse)
     finally:
         for f in files:
             f.close()
@@ -190,12 +204,12 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None):
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
     per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse)
     res = []
     try:
         for i, p in enumerate(paths):

@@ -3,7 +3,7 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
@@ -31,6 +31,10 @@ def main(argv):
         modes = argv[argv.index("--modes") + 1].split(",")
         args.remove(argv[argv.index("--modes") + 1])
     fmt = "nv12" if "--nv12" in argv else "i420"
+    parse = "host"
+    if "--parse" in argv:
+        parse = argv[argv.index("--parse") + 1]
+        args.remove(parse)
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
     data = open(path, "rb").read()
@@ -42,12 +46,15 @@ def main(argv):
         for r in range(runs):
             t0 = time.perf_counter()
             if mode == "digests":
-                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False)
+                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse)
             else:
-                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device")
+                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse)
             dt = time.perf_counter() - t0
             ms = (C.c_double * 6)()
             lib.lh264_decode_last_timing(ms)
+            pt = (C.c_double * 2)()
+            lib.lh264_decode_last_parse_timing(pt)
+            route = {} if parse == "host" else {"parse": parse, "routes": sorted(set(b.parse_path(i) for i in range(streams))), "device_parse_ms": round(pt[0], 1), "device_parse_slices": int(pt[1])}
             pics = sum(len(b.pictures(i)) for i in (0, streams - 1)) // 2 * streams
             bad = [i for i in range(streams) if b.status(i) != 0]
             extra = {"stream_sha1": b.stream_sha1(0).hex(), "same_digests": len(set(b.stream_sha1(i) for i in range(streams))) == 1} if mode == "digests" else {}
@@ -58,7 +65,7 @@ def main(argv):
                                   output_MB=round(out_bytes / 1e6, 1), failed=len(bad),
                                   ms={"call": round(ms[0], 1), "parse": round(ms[1], 1), "staging": round(ms[2], 1), "enqueue": round(ms[3], 1),
                                       "wait_device": round(ms[4], 1), "delivery": round(ms[5], 1)},
-                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **extra)), flush=True)
+                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **extra, **route)), flush=True)
     for r in range(runs if "parse" in modes else 0):
         dt, pics = lh.parse_batch_time(datas, threads=0, keep=False)
         print(json.dumps(dict(base, what="parse_batch_discard", run=r, seconds=round(dt, 4), MBps=round(mb / dt, 1), pictures_per_s=round(pics / dt))), flush=True)
