@@ -639,87 +639,99 @@ __device__ __forceinline__ Row12 align12 (v4u d, int sh) {
 // The 6-tap filter (1,-5,20,20,-5,1) on bytes without unpacking them one by one.
 // Horizontal: the six samples of an output are consecutive bytes - two signed 4x8-bit dot products (v_dot4c_i32_i8) on the row
 // with 128 subtracted from every sample (the taps sum to 32, so 4096 goes back in).  Vertical: the same byte position of six
-// rows - the rows are split into two 2x16-bit words each (even / odd bytes) and the filter runs on 16-bit pairs (v_pk_*); the
-// sums stay within int16 (|sum| <= 10,710).
+// rows - two adjacent columns of a row are picked into one 2x16-bit word (v_perm_b32) and the filter runs on 16-bit pairs
+// (v_pk_*); the sums stay within int16 (|sum| <= 10,710).
 typedef short s16x2 __attribute__ ((ext_vector_type (2)));
 __device__ __forceinline__ s16x2 as_s2 (uint32_t v) { return __builtin_bit_cast (s16x2, v); }
 __device__ __forceinline__ uint32_t as_u (s16x2 v) { return __builtin_bit_cast (uint32_t, v); }
-// horizontal taps at outputs 0..3 of a row (output i = samples i..i+5)
-__device__ __forceinline__ void htap4 (const Row12 R, int out[4]) {
+// horizontal taps at outputs 0..3 of a row (output i = samples i..i+5), each with `bias` added
+__device__ __forceinline__ void htap4 (const Row12 R, int bias, int out[4]) {
   const uint32_t s0 = R.w0 ^ 0x80808080u, s1 = R.w1 ^ 0x80808080u, s2 = R.w2 ^ 0x80808080u;
   const int ca = 0x1414FB01, cb = 0x000001FB;       // bytes (1, -5, 20, 20) and (-5, 1, 0, 0)
-  out[0] = __builtin_amdgcn_sdot4 ((int)s0, ca, __builtin_amdgcn_sdot4 ((int)s1, cb, 4096, false), false);
+  out[0] = __builtin_amdgcn_sdot4 ((int)s0, ca, __builtin_amdgcn_sdot4 ((int)s1, cb, 4096 + bias, false), false);
 #pragma unroll
   for (int i = 1; i < 4; i++)
     out[i] = __builtin_amdgcn_sdot4 ((int)__builtin_amdgcn_alignbyte (s1, s0, i), ca,
-                                     __builtin_amdgcn_sdot4 ((int)__builtin_amdgcn_alignbyte (s2, s1, i), cb, 4096, false), false);
+                                     __builtin_amdgcn_sdot4 ((int)__builtin_amdgcn_alignbyte (s2, s1, i), cb, 4096 + bias, false), false);
 }
-// vertical taps of the byte positions of one word of six rows: even bytes (0, 2) in e, odd bytes (1, 3) in o, as 16-bit pairs
-__device__ __forceinline__ void vtap_word (uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t r4, uint32_t r5, s16x2& e, s16x2& o) {
-  const uint32_t M = 0x00ff00ffu;
+// bytes a, a + 1 (compile-time) of the eight bytes hi:lo as a 16-bit pair (v_perm_b32: selector 0x0c gives a zero byte)
+#define PAIR16(hi, lo, a) __builtin_amdgcn_perm ((hi), (lo), 0x0c000c00u | (uint32_t) ((a) + 1) << 16 | (uint32_t) (a))
+// vertical taps of two adjacent columns of six rows (p_k = the two samples of row k as a 16-bit pair), on 16-bit pairs (v_pk_*)
+__device__ __forceinline__ s16x2 vtap_pair (uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t p4, uint32_t p5) {
   const s16x2 k20 = {20, 20}, k5 = {5, 5};
-  e = (as_s2 (r2 & M) + as_s2 (r3 & M)) * k20 + (as_s2 (r0 & M) + as_s2 (r5 & M)) - (as_s2 (r1 & M) + as_s2 (r4 & M)) * k5;
-  o = (as_s2 ((r2 >> 8) & M) + as_s2 ((r3 >> 8) & M)) * k20 + (as_s2 ((r0 >> 8) & M) + as_s2 ((r5 >> 8) & M)) - (as_s2 ((r1 >> 8) & M) + as_s2 ((r4 >> 8) & M)) * k5;
+  return (as_s2 (p2) + as_s2 (p3)) * k20 + (as_s2 (p0) + as_s2 (p5)) - (as_s2 (p1) + as_s2 (p4)) * k5;
 }
+#define VTAP_PAIR(R, hi, lo, a) vtap_pair (PAIR16 (R[0].hi, R[0].lo, a), PAIR16 (R[1].hi, R[1].lo, a), PAIR16 (R[2].hi, R[2].lo, a), \
+                                           PAIR16 (R[3].hi, R[3].lo, a), PAIR16 (R[4].hi, R[4].lo, a), PAIR16 (R[5].hi, R[5].lo, a))
+// clip_u8 (v >> 5) of both halves of a pair (the rounding 16 already added): bytes 0 and 2 of the result, bytes 1 and 3 zero
+__device__ __forceinline__ uint32_t shr5_clip_pair (s16x2 v) {
+  const s16x2 z = {0, 0}, m = {255, 255};
+  return as_u (__builtin_elementwise_min (__builtin_elementwise_max (v >> 5, z), m));
+}
+// bytes 0 and 2 of lo, then bytes 0 and 2 of hi: two clipped pairs -> four samples
+__device__ __forceinline__ uint32_t pack_pairs (uint32_t hi, uint32_t lo) { return __builtin_amdgcn_perm (hi, lo, 0x06040200u); }
 
-// one 4x1 luma strip from the fetched rows: R[k] holds samples -2..9 of row k-2 relative to the strip's first sample
-// (McLuma_c / McHorVer* common/src/mc.cpp:142-380).  With fy == 0 only R[2] is defined.
-__device__ __forceinline__ void mc_luma_rows (const Row12 R[6], int fx, int fy, int out[4]) {
-  if ((fx | fy) == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = RB (R[2], i + 2);
-    return;
-  }
-  if (fy == 0) {                      // a, b, c : one row
+// one 4x1 luma strip from the fetched rows, as four bytes: R[k] holds samples -2..9 of row k-2 relative to the strip's first
+// sample (McLuma_c / McHorVer* common/src/mc.cpp:142-380).  With any_fy false (no strip of the wave has a vertical fraction) only
+// R[2] is defined.
+// By STAGES, not by fraction classes: the strips of a wave differ in their fractions (a macroblock of several partitions), and a
+// branch per class makes the wave pay the sum of its classes.  Each stage is computed by all lanes together behind one wave-uniform
+// test and skipped when no lane needs it:
+//   H  fx != 0            the horizontal half samples of row 2 (row 3 where fy == 3): positions a b c and the b / s term of e g p r f q
+//   V  fy != 0            vertical sums (int16, as the reference keeps them) of columns 2..5: d h n, the h / m term of e p i
+//   X  both fractions     columns 6, 7: the m term of g r k
+//   J  both, one of them 2: columns 0, 1, 8 and the four horizontal taps over the nine sums: j and the j term of f q i k
+// Every position is (A + B + 1) >> 1 of two of those four-byte terms (A == B: the term itself), so the stages only select A and B
+// per lane and one v_lerp_u8 finishes the strip.
+__device__ __forceinline__ uint32_t mc_luma_rows (const Row12 R[6], int fx, int fy, bool any_fy) {
+  const uint32_t G = __builtin_amdgcn_alignbyte (R[2].w1, R[2].w0, 2);      // the integer samples
+  uint32_t A = G, B = G;
+  if (__ballot (fx != 0)) {                         // ---- H
+    Row12 H = R[2];
+    if (fy == 3) H = R[3];
     int t[4];
-    htap4 (R[2], t);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int b = clip_u8 ((t[i] + 16) >> 5);
-      out[i] = fx == 2 ? b : (b + (fx == 1 ? RB (R[2], i + 2) : RB (R[2], i + 3)) + 1) >> 1;
+    htap4 (H, 16, t);
+    const s16x2 t01 = {(short)t[0], (short)t[1]}, t23 = {(short)t[2], (short)t[3]};      // |sum + 16| <= 10,726
+    const uint32_t HH = pack_pairs (shr5_clip_pair (t23), shr5_clip_pair (t01));
+    A = fx != 0 ? HH : A;
+    B = fx == 2 ? HH : fx == 3 ? __builtin_amdgcn_alignbyte (R[2].w1, R[2].w0, 3) : B;
+  }
+  if (any_fy) {                                     // ---- V
+    const s16x2 k16 = {16, 16};
+    const s16x2 P = VTAP_PAIR (R, w1, w0, 2), Q = VTAP_PAIR (R, w1, w0, 4);       // columns 2, 3 and 4, 5
+    const uint32_t VV0 = pack_pairs (shr5_clip_pair (Q + k16), shr5_clip_pair (P + k16));
+    uint32_t VVx = VV0;
+    const bool both = fx != 0 && fy != 0;
+    if (__ballot (both)) {                          // ---- X
+      const s16x2 E = VTAP_PAIR (R, w2, w1, 2);     // columns 6, 7
+      VVx = fx == 3 ? __builtin_amdgcn_alignbyte (shr5_clip_pair (E + k16), VV0, 1) : VV0;
+      const bool isj = both && (fx == 2 || fy == 2);
+      if (__ballot (isj)) {                         // ---- J
+        const s16x2 Z = VTAP_PAIR (R, w1, w0, 0);   // columns 0, 1
+        const uint32_t M = 0xffu;
+        const s16x2 W = vtap_pair (R[0].w2 & M, R[1].w2 & M, R[2].w2 & M, R[3].w2 & M, R[4].w2 & M, R[5].w2 & M);       // column 8
+        // the horizontal taps over the nine sums, in int32 as the reference has them
+        const int vs[9] = {Z.x, Z.y, P.x, P.y, Q.x, Q.y, E.x, E.y, W.x};
+        const int j0 = tap6 (vs[0], vs[1], vs[2], vs[3], vs[4], vs[5]) + 512, j1 = tap6 (vs[1], vs[2], vs[3], vs[4], vs[5], vs[6]) + 512;
+        const int j2 = tap6 (vs[2], vs[3], vs[4], vs[5], vs[6], vs[7]) + 512, j3 = tap6 (vs[3], vs[4], vs[5], vs[6], vs[7], vs[8]) + 512;
+        // clipped as 16-bit pairs like the other terms (-300 < j >> 10 < 600).  Not as clip_u8 (j0 >> 10) | clip_u8 (j1 >> 10) << 8:
+        // hipcc turns that into v_ashr_pk_u8_i32 and ORs bytes 2, 3 into its result register, whose upper half the instruction was seen to
+        // leave as it was (stale on an MI355X: wrong samples 2 and 3)
+        const s16x2 z = {0, 0}, m = {255, 255};
+        const s16x2 j01 = {(short) (j0 >> 10), (short) (j1 >> 10)}, j23 = {(short) (j2 >> 10), (short) (j3 >> 10)};
+        const uint32_t J = pack_pairs (as_u (__builtin_elementwise_min (__builtin_elementwise_max (j23, z), m)),
+                                       as_u (__builtin_elementwise_min (__builtin_elementwise_max (j01, z), m)));
+        A = isj ? J : A;
+        B = (fx == 2 && fy == 2) ? J : B;
+      }
     }
-    return;
+    // fx == 0: d h n = the vertical half sample with G (row 2), itself, or row 3; both fractions: fx == 2 keeps what H / J chose (the
+    // horizontal half sample, or j), odd fx takes the vertical half sample of column fx >> 1
+    const uint32_t Bv = fx == 0 ? (fy == 2 ? VV0 : fy == 3 ? __builtin_amdgcn_alignbyte (R[3].w1, R[3].w0, 2) : G) : (fx == 2 ? B : VVx);
+    B = fy != 0 ? Bv : B;
+    A = (fy != 0 && fx == 0) ? VV0 : A;
   }
-  if (fx == 0) {                      // d, h, n : six rows, samples 0..3 = bytes 2..5
-    s16x2 e, o;
-    vtap_word (__builtin_amdgcn_alignbyte (R[0].w1, R[0].w0, 2), __builtin_amdgcn_alignbyte (R[1].w1, R[1].w0, 2), __builtin_amdgcn_alignbyte (R[2].w1, R[2].w0, 2),
-               __builtin_amdgcn_alignbyte (R[3].w1, R[3].w0, 2), __builtin_amdgcn_alignbyte (R[4].w1, R[4].w0, 2), __builtin_amdgcn_alignbyte (R[5].w1, R[5].w0, 2), e, o);
-    const int t[4] = {e.x, o.x, e.y, o.y};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int h = clip_u8 ((t[i] + 16) >> 5);
-      out[i] = fy == 2 ? h : (h + (fy == 1 ? RB (R[2], i + 2) : RB (R[3], i + 2)) + 1) >> 1;
-    }
-    return;
-  }
-  // both fractions: vertical 6-tap sums of the 9 columns -2..6 (int16, as the reference keeps them)
-  int vs[9];
-  {
-    s16x2 e0, o0, e1, o1, e2, o2;
-    vtap_word (R[0].w0, R[1].w0, R[2].w0, R[3].w0, R[4].w0, R[5].w0, e0, o0);
-    vtap_word (R[0].w1, R[1].w1, R[2].w1, R[3].w1, R[4].w1, R[5].w1, e1, o1);
-    vtap_word (R[0].w2, R[1].w2, R[2].w2, R[3].w2, R[4].w2, R[5].w2, e2, o2);
-    vs[0] = e0.x; vs[1] = o0.x; vs[2] = e0.y; vs[3] = o0.y; vs[4] = e1.x; vs[5] = o1.x; vs[6] = e1.y; vs[7] = o1.y; vs[8] = e2.x;
-  }
-  int hh[4];                          // horizontal half-sample of window row 2 (fy==1,2) or 3 (fy==3)
-  Row12 H = R[2];
-  if (fy == 3) H = R[3];
-  htap4 (H, hh);
-#pragma unroll
-  for (int i = 0; i < 4; i++) hh[i] = clip_u8 ((hh[i] + 16) >> 5);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int c = i + 2;
-    const int vv0 = clip_u8 ((vs[c] + 16) >> 5), vv1 = clip_u8 ((vs[c + 1] + 16) >> 5);
-    int v;
-    if (fx == 2 || fy == 2) {
-      const int j = clip_u8 ((tap6 (vs[c - 2], vs[c - 1], vs[c], vs[c + 1], vs[c + 2], vs[c + 3]) + 512) >> 10);
-      if (fx == 2 && fy == 2) v = j;
-      else if (fx == 2) v = (j + hh[i] + 1) >> 1;          // f, q
-      else v = (j + (fx == 1 ? vv0 : vv1) + 1) >> 1;       // i, k
-    } else v = (hh[i] + (fx == 1 ? vv0 : vv1) + 1) >> 1;   // e, g, p, r
-    out[i] = v;
-  }
+  return __builtin_amdgcn_lerp (A, B, 0x01010101u);   // per byte (A + B + 1) >> 1
 }
 
 // two horizontally adjacent chroma samples sharing one motion vector (a 4x4 luma block = 2x2 chroma); a / b = the
@@ -817,7 +829,8 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
     if (any_fy) {
       lrow[0] = * (const GLB v4u*) (q - 2 * F.sy); lrow[1] = * (const GLB v4u*) (q - F.sy);
       lrow[3] = * (const GLB v4u*) (q + F.sy); lrow[4] = * (const GLB v4u*) (q + 2 * F.sy); lrow[5] = * (const GLB v4u*) (q + 3 * F.sy);
-    } else lrow[0] = lrow[1] = lrow[3] = lrow[4] = lrow[5] = (v4u) (0u);     // never read (every strip has fy == 0)
+    }                                               // else they stay undefined and are never used: every strip has fy == 0, and 20
+                                                    // moves of zeros in front of the branch would be paid by every macroblock
 #endif
   }
   // chroma: lane l and lane l + 32 share the 4-sample strip of lane l < 32; half h = l >> 5 takes the pair at columns
@@ -841,20 +854,26 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
   }
   // ---- luma ------------------------------------------------------------------------------------------------------
   int pr[4], res[4];
+  uint32_t lpk;
   {
     Row12 R[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) R[k] = align12 (lrow[k], lsh);
-    mc_luma_rows (R, lfx, lfy, pr);
+    lpk = mc_luma_rows (R, lfx, lfy, any_fy);
+  }
+  if (__ballot (wp || has_res)) {                   // (wave-uniform) otherwise the strip is final as it is
+#pragma unroll
+    for (int i = 0; i < 4; i++) pr[i] = BYTE (lpk, i);
     if (wp) {
       const int ri = (linfo >> 16) & 15, ld = sl.luma_denom(), wt = sl.luma_weight (ri), of = sl.luma_offset (ri);
 #pragma unroll
       for (int i = 0; i < 4; i++) pr[i] = clip_u8 (ld >= 1 ? ((pr[i] * wt + (1 << (ld - 1))) >> ld) + of : pr[i] * wt + of);
     }
+    res[0] = res[1] = res[2] = res[3] = 0;
+    if (has_res) load_res4 (L.R, lane, res);
+    lpk = pack_add4 (pr, res);
   }
-  res[0] = res[1] = res[2] = res[3] = 0;
-  if (has_res) load_res4 (L.R, lane, res);
-  * (LDS uint32_t*)&L.T[tY (ly, lx0)] = pack_add4 (pr, res);
+  * (LDS uint32_t*)&L.T[tY (ly, lx0)] = lpk;
   // ---- chroma pair: plane cp, row cy, cols cx, cx+1 --------------------------------------------------------------
   {
     int cpr[2];
@@ -883,46 +902,59 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
 // ------------------------------------------------------------------------------------------------
 // deblocking (deblocking.cpp / deblocking_common.cpp)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int bs_mv (RecView a, int ia, RecView b, int ib) {
-  const int dx = abs (a.mvx (ia) - b.mvx (ib)), dy = abs (a.mvy (ia) - b.mvy (ib));
-  return (a.ref4 (ia) != b.ref4 (ib)) || dx >= 4 || dy >= 4;   // MB_BS_MV deblocking.cpp:58-63: reference INDICES
-}
+// Boundary strengths from the blocks, not from the edges: DeblockingBsMarginalMBAvcbase deblocking.cpp:273-352,
+// DeblockingBSInsideMB* :160-271, WelsDeblockingMb :815-862.  The strength of segment `seg` of edge `e` in direction dir (0: vertical
+// edges) is a function of two 4x4 blocks: q = (e, seg) for dir 0, (seg, e) for dir 1, and p, the block to its left / above it - inside
+// the macroblock, or in the left / upper neighbour for e == 0.  A lane holds q's data once (BsBlk), gets p's from the lane 4 below it
+// (one DPP row shift serves both directions) or from the neighbour's record, and decides in straight-line code (bs_decide).
 
-// boundary strength of segment `seg` of edge `e` in direction dir (0: vertical edges, 1: horizontal);
-// DeblockingBsMarginalMBAvcbase deblocking.cpp:273-352, DeblockingBSInsideMB* :160-271, WelsDeblockingMb :815-862
-__device__ __forceinline__ int compute_bs (RecView m, RecView nb, bool have_nb, int dir, int e, int seg, bool intra) {
-  const int t8 = m.flags() & LH264_MBF_T8x8;
-  const int mtype = m.mb_type();
-  if (e == 0) {
-    if (!have_nb) return 0;
-    if (intra || (nb.mb_type() & LH264_MB_INTRA)) return 4;
-    const int t8n = nb.flags() & LH264_MBF_T8x8;
-    const int bc = dir == 0 ? seg * 4 : seg;
-    const int bn = dir == 0 ? seg * 4 + 3 : 12 + seg;
-    int nzc_c = m.nzc (bc), nzc_n = nb.nzc (bn);
-    if (t8) nzc_c = m.nz8 (((bc >> 3) << 3) + ((bc & 3) >> 1) * 2);
-    if (t8n) nzc_n = nb.nz8 (((bn >> 3) << 3) + ((bn & 3) >> 1) * 2);
-    if (nzc_c | nzc_n) return 2;
-    int mc_ = bc, mn_ = bn;
-    if (t8) mc_ = dir == 0 ? (seg >> 1) * 8 : (seg >> 1) * 2;
-    if (t8n) mn_ = dir == 0 ? (seg >> 1) * 8 + 2 : 8 + (seg >> 1) * 2;
-    return bs_mv (m, mc_, nb, mn_);
+// what a strength needs of the 4x4 block (bx, by) of a staged record.  Under the 8x8 transform a block stands for its 8x8 block: the
+// counts of all four blocks, the vector of the first one (deblocking.cpp:273-352).  nr: bits 0..7 ref_idx, bits 8.. nonzero if a count is
+struct BsBlk { uint32_t mv; int nr; };
+// ANY8 false: no 8x8 transform on either side of any edge of this macroblock (known per wave) - byte reads, nothing to remap
+template <bool ANY8> __device__ __forceinline__ BsBlk bs_block (RecView r, int bx, int by, bool t8) {
+  const int ri = (by & 2) + (bx >> 1);
+  BsBlk o;
+  if (!ANY8) {
+    const int b = by * 4 + bx;
+    o.mv = * (const LDS uint32_t*) (r.p + 60 + 4 * b);
+    o.nr = r.p[32 + ri] | r.p[36 + b] << 8;
+    return o;
   }
-  if (intra) return 3;
-  if (mtype == LH264_MB_SKIP) return 0;
-  if (t8 && e != 2) return 0;
-  const bool mv_too = mtype != LH264_MB_P16x16;
-  if (t8) {
-    const int r = seg >> 1;
-    int a, b;
-    if (dir == 0) { a = r * 8; b = r * 8 + 2; } else { a = r * 2; b = 8 + r * 2; }
-    if (m.nz8 (a) | m.nz8 (b)) return 2;
-    return mv_too ? bs_mv (m, b, m, a) : 0;
-  }
-  const int a = dir == 0 ? seg * 4 + e - 1 : (e - 1) * 4 + seg;
-  const int b = dir == 0 ? seg * 4 + e : e * 4 + seg;
-  if (m.nzc (a) | m.nzc (b)) return 2;
-  return mv_too ? bs_mv (m, b, m, a) : 0;
+  const LDS uint32_t* w = (const LDS uint32_t*)r.p;          // dword 8: ref_idx[4], 9..12: nzc rows, 15..30: mv[16]
+  const uint32_t n0 = w[9 + (by & 2)], n1 = w[10 + (by & 2)];
+  const uint32_t nw = t8 ? (n0 | n1) : (by & 1) ? n1 : n0;
+  const uint32_t nz = (nw >> (t8 ? 16 * (bx >> 1) : 8 * bx)) & (t8 ? 0xffffu : 0xffu);
+  o.mv = w[15 + (t8 ? (by & 2) * 4 + (bx & 2) : by * 4 + bx)];
+  o.nr = (int) ((w[8] >> (8 * ri)) & 0xffu) | (nz ? 0x100 : 0);
+  return o;
+}
+// edge0: a macroblock edge (p lies in the neighbour: have_nb, nb_intra); intra / skip / mv_too / t8: of the current macroblock.
+// Reference INDICES are compared, not pictures (MB_BS_MV deblocking.cpp:58-63); inside P16x16 no vectors are compared, SKIP has no
+// inner edges, edges 1 and 3 do not exist under the 8x8 transform (deblocking.cpp:836-849).
+__device__ __forceinline__ int bs_decide (BsBlk q, BsBlk p, bool edge0, int e, bool have_nb, bool nb_intra, bool intra, bool skip, bool mv_too, bool t8) {
+  const int dx = sext16 ((int)q.mv) - sext16 ((int)p.mv), dy = ((int)q.mv >> 16) - ((int)p.mv >> 16);
+  const bool mv = (((q.nr ^ p.nr) & 0xff) != 0) || (uint32_t) (dx + 3) > 6u || (uint32_t) (dy + 3) > 6u;      // |d| >= 4
+  const int core = ((q.nr | p.nr) & 0xff00) ? 2 : (mv && (edge0 || mv_too)) ? 1 : 0;
+  const int inner = intra ? 3 : skip ? 0 : core;
+  const int outer = !have_nb ? 0 : (intra || nb_intra) ? 4 : core;
+  return (t8 && (e & 1)) ? 0 : edge0 ? outer : inner;
+}
+// the strength of lane < 32 = (dir, edge, segment), the layout of L.bs
+template <bool ANY8> __device__ __forceinline__ int bs_lane (RecView m, RecView lm, RecView tm, bool left_av, bool top_av, int mtype, int ltype, int ttype,
+                                                            bool mintra, bool t8, bool lt8, bool tt8, int lane) {
+  const int dir = lane >> 4, e = (lane >> 2) & 3, seg = lane & 3;
+  const BsBlk q = bs_block<ANY8> (m, dir ? seg : e, dir ? e : seg, t8);
+  // the block before the edge: lanes 0..15 hold the blocks column by column, lanes 16..31 row by row, so it is 4 lanes down in both
+  BsBlk p;
+  p.mv = (uint32_t)__builtin_amdgcn_update_dpp (0, (int)q.mv, 0x114, 0xf, 0xf, true);      // row_shr:4
+  p.nr = __builtin_amdgcn_update_dpp (0, q.nr, 0x114, 0xf, 0xf, true);
+  const RecView nb = {dir ? tm.p : lm.p};
+  const BsBlk n = bs_block<ANY8> (nb, dir ? seg : 3, dir ? 3 : seg, dir ? tt8 : lt8);
+  const bool edge0 = e == 0;
+  if (edge0) p = n;
+  return bs_decide (q, p, edge0, e, dir ? top_av : left_av, ((dir ? ttype : ltype) & LH264_MB_INTRA) != 0, mintra, mtype == LH264_MB_SKIP,
+                    mtype != LH264_MB_P16x16, t8);
 }
 
 // Filter one line across one edge, samples in registers.  Luma: DeblockLumaLt4_c / DeblockLumaEq4_c
@@ -971,10 +1003,11 @@ __device__ LH264_PHASE void deblock_phase (LDS WaveLds& L, const LDS WgLds& G, R
   const bool mintra = (mtype == LH264_MB_I4x4 || mtype == LH264_MB_I8x8 || mtype == LH264_MB_I16x16 || mtype == LH264_MB_IPCM);
   int my_bs = 0;
   if (lane < 32) {
-    const int dir = lane >> 4, e = (lane >> 2) & 3, seg = lane & 3;
-    // with the 8x8 transform the luma edges 1 and 3 do not exist (deblocking.cpp:836-849; chroma never uses them)
-    const bool t8 = (m.flags() & LH264_MBF_T8x8) != 0;
-    my_bs = (t8 && (e & 1)) ? 0 : compute_bs (m, dir == 0 ? lm : tm, dir == 0 ? left_av : top_av, dir, e, seg, mintra);
+    const bool t8 = (uni (m.flags()) & LH264_MBF_T8x8) != 0;
+    const int ltype = uni (lm.mb_type()), ttype = uni (tm.mb_type());
+    const bool lt8 = (uni (lm.flags()) & LH264_MBF_T8x8) != 0, tt8 = (uni (tm.flags()) & LH264_MBF_T8x8) != 0;
+    if (t8 || lt8 || tt8) my_bs = bs_lane<true> (m, lm, tm, left_av, top_av, mtype, ltype, ttype, mintra, t8, lt8, tt8, lane);
+    else my_bs = bs_lane<false> (m, lm, tm, left_av, top_av, mtype, ltype, ttype, mintra, false, false, false, lane);
     L.bs[lane] = (uint8_t)my_bs;
   }
   // which of the 2 x 4 edges have any strength at all: one scalar mask (bit 16 dir + 4 edge + segment), so that an edge nobody
