@@ -429,12 +429,18 @@ int                  lh264_parser_set_sparse_coeffs (lh264_parser_t* p, int on);
  * n_mbs and the slice syntax of such a slice stay empty until lh264_parser_parse_deferred runs the host macroblock layer over it - to be
  * called for the slices 0 .. lh264_parser_frame_deferred - 1 of a completed picture in order; 1: parsed, 0: the slice failed (then
  * lh264_parser_error / _error_pictures / _file_status say what the undeferred parser says); out (may be NULL): the slice's index in
- * the picture's slice table and the bit position at which the macroblock layer stopped.  CABAC slices are parsed on the spot.
+ * the picture's slice table and the bit position at which the macroblock layer stopped.  CABAC slices are parsed on the spot, unless
+ * lh264_parser_set_defer_cabac is on as well: then they are deferred like the CAVLC ones (lh264_parser_frame_deferred counts both,
+ * lh264_parser_frame_deferred_cabac tells 1 for a CABAC slice, 0 for a CAVLC one, LH264_E_ARG for no slice), lh264_parser_parse_deferred
+ * runs the host's CABAC layer over them and the position it reports is the arithmetic decoder's: the number of the next bit it would
+ * take in.  lh264_parser_set_defer_cabac on its own does nothing; lh264_parser_set_defer_slice_data keeps its meaning whatever its value.
  * For the decode direction: symbol lists, I_PCM samples and concealment are not kept up for deferred pictures.
  * lh264_parser_error_pictures: how many pictures were complete when lh264_parser_error was raised; lh264_parser_file_status: what
  * lh264_parser_feed_file returned, or would return now */
 int                  lh264_parser_set_defer_slice_data (lh264_parser_t* p, int on);
+int                  lh264_parser_set_defer_cabac (lh264_parser_t* p, int on);
 int                  lh264_parser_frame_deferred (const lh264_parser_t* p, int idx);
+int                  lh264_parser_frame_deferred_cabac (const lh264_parser_t* p, int idx, int slice);
 int                  lh264_parser_parse_deferred (lh264_parser_t* p, int idx, int slice, int32_t out[2]);
 long long            lh264_parser_error_pictures (const lh264_parser_t* p);
 int                  lh264_parser_file_status (const lh264_parser_t* p);
@@ -674,7 +680,12 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * with CABAC slices and for good behind the first of them; a round in which a slice of the stream gets a status (syntax the host fails
  * on, a slice that runs into the next one) is parsed again by the host parser, and the stream stays with it.  Pictures, statuses, texts,
  * digests and the stop-there position do not depend on parse.  lh264_decoded_parse_path tells the route.
- * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a format out of range, a flag bit that is not
+ * opts->parse_flags = LH264_PARSE_FLAG_CABAC together with LH264_PARSE_DEVICE (struct_bytes 40 and 48: not read): CABAC slices become
+ * tasks as well, in the same parse arena and with the same 12 bytes per slice coming down; slice_parse_cabac_kernel walks them, on the
+ * same stream and ahead of the same synchronisation as slice_parse_kernel.  The stream then stays on the device route through CABAC
+ * pictures; conceal and a status from either kernel send it to the host parser as before.  Without the flag nothing changes.
+ * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a parse_flags bit that is not defined or
+ * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, a format out of range, a flag bit that is not
  * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
  * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
  * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
@@ -699,12 +710,13 @@ typedef struct lh264_decode_opts {
   uint32_t conceal;                     /* LH264_CONCEAL_*; 0 = off.  (struct_bytes up to `user`: off)          */
   uint32_t reserved0;                   /* (the tail padding of the 48-byte struct: callers of it left it undefined, it is not read) */
   uint32_t parse;                       /* LH264_PARSE_*; 0 = host.  (struct_bytes 40 and 48: host)             */
-  uint32_t reserved1;
+  uint32_t parse_flags;                 /* LH264_PARSE_FLAG_*; 0 = none.  (struct_bytes 40 and 48: not read)   */
 } lh264_decode_opts_t;
 #define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
 #define LH264_DECODE_OPTS_BYTES_V2 48u  /* the struct before `parse` was added: still accepted                   */
 #define LH264_PARSE_HOST   0u           /* the host front end parses slice data (the default)                    */
 #define LH264_PARSE_DEVICE 1u           /* CAVLC slice data is parsed by slice_parse_kernel, one wave per slice  */
+#define LH264_PARSE_FLAG_CABAC 1u       /* with LH264_PARSE_DEVICE: CABAC slice data too, by slice_parse_cabac_kernel */
 #define LH264_PARSE_PATH_HOST     0
 #define LH264_PARSE_PATH_DEVICE   1
 #define LH264_PARSE_PATH_FALLBACK 2
@@ -712,12 +724,15 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
                         const lh264_decode_opts_t* opts /* NULL = defaults */, lh264_decoded_t** out);
 int lh264_decoded_status (const lh264_decoded_t* d);
 /* how the stream's slice data was parsed: LH264_PARSE_PATH_HOST (none of it on the device), _DEVICE (CAVLC slices by the kernel; CABAC
- * pictures and what follows the first of them by the host), _FALLBACK (a slice of some round got a status from the kernel: that round's
- * slices were parsed again by the host and the stream stayed there) */
+ * pictures and what follows the first of them by the host - with LH264_PARSE_FLAG_CABAC the slices of both entropy modes by the
+ * kernels), _FALLBACK (a slice of some round got a status from a kernel: that round's slices were parsed again by the host and the
+ * stream stayed there) */
 int lh264_decoded_parse_path (const lh264_decoded_t* d);
 /* ... and how many of the stream's slices slice_parse_kernel parsed (a round that fell back, and what the host parsed behind a CABAC
  * picture, do not count; a picture that waited for another round counts once per round it was parsed in) */
 long long lh264_decoded_device_slices (const lh264_decoded_t* d);
+/* ... and how many of those were CABAC slices, parsed by slice_parse_cabac_kernel (0 without LH264_PARSE_FLAG_CABAC) */
+long long lh264_decoded_device_cabac_slices (const lh264_decoded_t* d);
 const char* lh264_decoded_error (const lh264_decoded_t* d);
 int lh264_decoded_pictures (const lh264_decoded_t* d);
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
@@ -738,8 +753,8 @@ void lh264_decode_release (void);
  * (host threads), ms[2] staging, ms[3] enqueueing the device stage, ms[4] the main thread's wait for the device (the download
  * included), ms[5] delivery (copies into the handles, or the sink).  LH264_TRACE_DECODE=1 prints the same to stderr. */
 int lh264_decode_last_timing (double* ms);
-/* parse = LH264_PARSE_DEVICE: of ms[1] above, out[0] the milliseconds of the device parse stage (filling tasks, upload, slice_parse_kernel,
- * the wait for its results) and out[1] the number of slices it parsed, in the last call (0, 0 under LH264_PARSE_HOST) */
+/* parse = LH264_PARSE_DEVICE: of ms[1] above, out[0] the milliseconds of the device parse stage (filling tasks, upload, slice_parse_kernel and
+ * - with LH264_PARSE_FLAG_CABAC - slice_parse_cabac_kernel, the wait for their results) and out[1] the number of slices it parsed, in the last call (0, 0 under LH264_PARSE_HOST) */
 int lh264_decode_last_parse_timing (double* out);
 /* one picture to crop and pack (decode_pack_kernel): the planes' pixel (0,0) in a padded picture, the window, where the packed
  * picture begins.  crop_x/y/w/h are even.  lh264_debug_pack_cpu steps the kernel's code over HOST memory: a check of the crop / format
@@ -764,9 +779,17 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
  * fails on, 2 = the slice would run into the next slice's first macroblock (nothing at or beyond it is written), 3 = an inconsistent
  * task.  Every buffer the code reads or writes lies in one arena with 64 guard bytes behind it; lh264_slice_dump_guards_ok: 1 when all
  * of them are intact after the run.  tweak (may be NULL): {picture, slice, limit_mb} replaces the limit of one slice - the macroblock
- * at which it must stop - for tests of the overrun status.  lh264_slice_dump_error: the header walk's error text.  Not a decode path */
+ * at which it must stop - for tests of the overrun status.  lh264_slice_dump_error: the header walk's error text.  Not a decode path.
+ * lh264_debug_slice_parse_opts is the same call with flags: LH264_SLICE_PARSE_ON_DEVICE for on_device, and LH264_SLICE_PARSE_CABAC, with
+ * which CABAC slices are deferred too (lh264_parser_set_defer_cabac) and walked by csrc/lh264_slice_cabac.h, on the host threads or by
+ * slice_parse_cabac_kernel; the bit position of such a slice is the arithmetic decoder's.  Without that flag a CABAC stream defers
+ * nothing, as with lh264_debug_slice_parse, which forwards here.  Its tweak has a fourth entry: >= 0 replaces the byte of the slice's
+ * task that names the entropy mode and cabac_init_idc (0 = CAVLC, 0x80 | idc = CABAC), for tests of the inconsistent-task status */
 typedef struct lh264_slice_dump lh264_slice_dump_t;
+#define LH264_SLICE_PARSE_ON_DEVICE 1u
+#define LH264_SLICE_PARSE_CABAC     2u
 int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int threads, const int32_t* tweak, lh264_slice_dump_t** out);
+int lh264_debug_slice_parse_opts (const uint8_t* data, size_t len, uint32_t flags, int threads, const int32_t* tweak /* [4] */, lh264_slice_dump_t** out);
 int lh264_slice_dump_pictures (const lh264_slice_dump_t* d);
 int lh264_slice_dump_picture (const lh264_slice_dump_t* d, int idx, int32_t info[4] /* mb_w, mb_h, slices, deferred slices */);
 const lh264_mb_t* lh264_slice_dump_mbs (const lh264_slice_dump_t* d, int idx);

@@ -17,7 +17,7 @@
                                                             units the format drops (delimiters, filler, ...) are kept, pictures with
                                                             lost slices are compressed; out.lhp is still restored and compared
                                                             before it is written, with the verbatim fallback behind it
-    python -m losslessh264_amd --decode [--device-parse] [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
+    python -m losslessh264_amd --decode [--device-parse | --device-parse-cabac] [--nv12] [--conceal METHOD] out_dir in.264...   decode through ONE lh264_decode_batch call:
                                                             out_dir/<name>.yuv holds the cropped pictures as I420 (or NV12), appended
                                                             by a sink run by run.  METHOD: lost slices are concealed as the reference's
                                                             decoder does (slice_copy | slice_copy_cross_idr | mv_copy |
@@ -157,9 +157,9 @@ def restore(src, dst):
 def decode(argv):
     import losslessh264_amd as lh
     nv12, conceal, sha1, parse = False, None, False, "host"
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse"):
-        if argv[0] == "--device-parse":
-            parse, argv = "device", argv[1:]
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac"):
+        if argv[0] in ("--device-parse", "--device-parse-cabac"):
+            parse, argv = ("device" if argv[0] == "--device-parse" else "device+cabac"), argv[1:]
             continue
         if argv[0] == "--nv12":
             nv12, argv = True, argv[1:]

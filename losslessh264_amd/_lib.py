@@ -141,9 +141,13 @@ class DecodeOpts(C.Structure):
                 ("group_mbs", C.c_uint64), ("sink", DECODE_SINK_FN), ("user", C.c_void_p), ("conceal", C.c_uint32)]
 DECODE_OPTS_BYTES_V1 = 40          # the struct before `conceal`: still accepted, concealment off
 class DecodeOptsV3(C.Structure):   # the struct as it is now: `parse` behind what was the 48-byte struct's tail padding
-    _fields_ = DecodeOpts._fields_ + [("reserved0", C.c_uint32), ("parse", C.c_uint32), ("reserved1", C.c_uint32)]
+    _fields_ = DecodeOpts._fields_ + [("reserved0", C.c_uint32), ("parse", C.c_uint32), ("parse_flags", C.c_uint32)]
 DECODE_OPTS_BYTES_V2 = 48          # the struct before `parse` (DecodeOpts): still accepted, the host parses
 PARSE = {"host": 0, "device": 1}
+PARSE_FLAG_CABAC = 1
+# decode_batch (parse=...): the strings of PARSE, and "device+cabac" = LH264_PARSE_DEVICE with LH264_PARSE_FLAG_CABAC
+PARSE_MODES = {"host": (0, 0), "device": (1, 0), "device+cabac": (1, PARSE_FLAG_CABAC)}
+SLICE_PARSE_ON_DEVICE, SLICE_PARSE_CABAC = 1, 2
 PARSE_PATH = {0: "host", 1: "device", 2: "fallback"}
 assert C.sizeof(DecodeOptsV3) == 56
 # LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
@@ -160,6 +164,7 @@ _SIGS.update({
     "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decoded_parse_path": (C.c_int, [C.c_void_p]),
     "lh264_decoded_device_slices": (C.c_longlong, [C.c_void_p]),
+    "lh264_decoded_device_cabac_slices": (C.c_longlong, [C.c_void_p]),
     "lh264_decode_last_parse_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "lh264_decoded_status": (C.c_int, [C.c_void_p]),
     "lh264_decoded_error": (C.c_char_p, [C.c_void_p]),
@@ -187,10 +192,13 @@ SLICE_OK, SLICE_SYNTAX, SLICE_OVERRUN, SLICE_BAD_TASK = 0, 1, 2, 3
 _SIGS.update({
     "lh264_parser_set_defer_slice_data": (C.c_int, [C.c_void_p, C.c_int]),
     "lh264_parser_frame_deferred": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_set_defer_cabac": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_parser_frame_deferred_cabac": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lh264_parser_parse_deferred": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lh264_parser_error_pictures": (C.c_longlong, [C.c_void_p]),
     "lh264_parser_file_status": (C.c_int, [C.c_void_p]),
     "lh264_debug_slice_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_debug_slice_parse_opts": (C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_slice_dump_pictures": (C.c_int, [C.c_void_p]),
     "lh264_slice_dump_picture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_slice_dump_mbs": (C.c_void_p, [C.c_void_p, C.c_int]),

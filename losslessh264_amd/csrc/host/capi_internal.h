@@ -22,8 +22,8 @@ template <typename F> static void run_parallel (int n, int threads, F&& fn) {
   for (auto& t : pool) t.join();
 }
 
-// One CAVLC slice whose macroblock layer is parsed apart from its header (lh264_slice.h: on the device by slice_parse_kernel, on the
-// host by the same code).  The pointers are the walker's own: device addresses for the kernel, host addresses for the CPU form.
+// One slice whose macroblock layer is parsed apart from its header (CAVLC: lh264_slice.h, on the device by slice_parse_kernel; CABAC:
+// lh264_slice_cabac.h, by slice_parse_cabac_kernel; on the host by the same code).  The pointers are the walker's own: device addresses for the kernel, host addresses for the CPU form.
 namespace lh264host {
 struct SliceTask {
   const uint8_t* rbsp;              // the slice NAL's unescaped payload ...
@@ -34,18 +34,21 @@ struct SliceTask {
   int32_t slice_qp;
   uint8_t slice_type, num_ref_idx_l0, transform_8x8, constrained_intra_pred, use_sl;
   int8_t chroma_qp_offset[2];
-  uint8_t reserved;
+  uint8_t reserved;                 // 0: CAVLC.  CABAC: lh264slice::kTaskCabac | cabac_init_idc.  Checked by task_ok since the CABAC walk
+                                    // exists: a CAVLC task with any other value here is SLICE_BAD_TASK (the byte used to be ignored)
   const uint8_t* scaling;           // use_sl: the PPS's resolved lists, 6 x 16 then 2 x 64 entries in raster order
   lh264_mb_t* mbs;                  // the picture's records, 16-byte aligned
   int16_t* coeffs;                  // the picture's coefficient plane, cleared by the caller
   lh264_slice_t* slice;             // the slice's table entry: n_mbs is written (may be null: the result carries it too)
-  int8_t* line;                     // 4 * mb_w bytes of scratch; the kernel needs it only for pictures wider than its LDS line
+  int8_t* line;                     // 4 * mb_w bytes of scratch (CABAC: lh264slice::kCabacLineBytes * mb_w); the kernels need it only for pictures wider than their LDS line
 };
 static_assert (sizeof (SliceTask) == 88, "SliceTask is fixed-width: the host fills what the kernel reads");
 struct SliceResult { int32_t status, n_mbs, stop_bit; };
 // lh264_slice.hip: n tasks in device memory through slice_parse_kernel, enqueued on `stream`; force_fail: -1, or the task that is to
 // report a status unwalked
 bool launch_slice_parse (const SliceTask* tasks_dev, SliceResult* results_dev, int n, void* stream, int force_fail);
+// ... and n CABAC tasks through slice_parse_cabac_kernel
+bool launch_slice_parse_cabac (const SliceTask* tasks_dev, SliceResult* results_dev, int n, void* stream, int force_fail);
 }
 
 // n entries of (index << 16 | 16-bit value) in device memory written into the dense planes (lh264_capi.hip: expand_sparse_kernel, one

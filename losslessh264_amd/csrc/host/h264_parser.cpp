@@ -11,6 +11,7 @@
 #include <functional>
 #include "pip_symbols.h"
 #include "h264_cabac_tables.h"
+#include "h264_cabac_ctx_tables.h"
 #include <string.h>
 #include <algorithm>
 #include "h264_tables.h"
@@ -257,6 +258,7 @@ struct Parser::Impl {
     err_seq = deferred_now ? deferred_now->seq : nal_seq;
   }
   bool parse_deferred (FrameOut& f, size_t slice);
+  size_t cabac_stop = 0;                                 // Cabac::pos where the CABAC slice parsed last ended or failed
 
   static void unescape (const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
     out.clear(); out.reserve (n);
@@ -1258,14 +1260,13 @@ bool Parser::Impl::parse_slice_data_cavlc (BitReader& br, SliceCtx& c) {
 }
 
 // ---- CABAC macroblock layer (7.3.5 with the binarisations and context selection of 9.3.2 / 9.3.3) ------------------------
-namespace {
+// (declared in h264_cabac_ctx_tables.h: lh264_slice_cabac.h copies them into its table record)
 // ctxIdxInc of significant_coeff_flag (frame coded) and last_significant_coeff_flag for 8x8 blocks, Table 9-43
 const uint8_t kSig8x8[63] = {0, 1, 2, 3, 4, 5, 5, 4, 4, 3, 3, 4, 4, 4, 5, 5, 4, 4, 4, 4, 3, 3, 6, 7, 7, 7, 8, 9, 10, 9, 8, 7, 7, 6, 11, 12, 13, 11, 6, 7, 8, 9,
                              14, 10, 9, 8, 6, 11, 12, 13, 11, 6, 9, 14, 10, 9, 11, 12, 13, 11, 14, 10, 12};
 const uint8_t kLast8x8[63] = {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 3,
                               4, 4, 4, 4, 4, 4, 4, 4, 5, 5, 5, 5, 6, 6, 6, 6, 7, 7, 7, 7, 8, 8, 8};
-const int kCatCbf[5] = {0, 4, 8, 12, 16}, kCatMap[5] = {0, 15, 29, 44, 47}, kCatAbs[5] = {0, 10, 20, 30, 39};
-}  // namespace
+const uint8_t kCatCbf[5] = {0, 4, 8, 12, 16}, kCatMap[5] = {0, 15, 29, 44, 47}, kCatAbs[5] = {0, 10, 20, 30, 39};
 
 // one residual block (7.3.5.3.3): returns the number of nonzero coefficients, levels in scan order in lv[0..maxc-1]
 int Parser::Impl::cabac_residual (Cabac& cb, int k, int sid, int cat, int blk, int plane, bool cur_intra, int* lv, int maxc) {
@@ -1469,7 +1470,7 @@ bool Parser::Impl::parse_mb_cabac (Cabac& cb, SliceCtx& c, int k, int& qp_prev, 
         }
         const int pred = dcpred ? 2 : std::min (modeA, modeB);
         int mode = pred;
-        if (!cb.decode (68)) { const int rem = cb.decode (69) | cb.decode (69) << 1 | cb.decode (69) << 2; mode = rem < pred ? rem : rem + 1; }
+        if (!cb.decode (68)) { int rem = cb.decode (69); rem |= cb.decode (69) << 1; rem |= cb.decode (69) << 2; mode = rem < pred ? rem : rem + 1; }      // (one bin per statement: their order is the stream's)
         const int n = t8 ? 2 : 1;
         y.pred_mode[i] = (int8_t)mode;
         for (int yy = 0; yy < n; yy++) for (int x = 0; x < n; x++) { s.ipm[(by + yy) * 4 + bx + x] = (int8_t)mode; raw_modes[(by + yy) * 4 + bx + x] = mode; }
@@ -1691,6 +1692,7 @@ bool Parser::Impl::parse_slice_data_cabac (BitReader& br, SliceCtx& c) {
   const int n = cur->mb_w * cur->mb_h;
   while (!br.byte_aligned()) br.u1();                   // cabac_alignment_one_bit
   Cabac cb;
+  struct Stop { Impl* I; Cabac& cb; ~Stop() { I->cabac_stop = cb.pos; } } stop = {this, cb};      // DeferredSlice::stop_bit, however the slice ends
   cb.init_contexts (c.sh->slice_type == 2 ? 0 : 1 + c.sh->cabac_init_idc, c.sh->slice_qp);
   cb.start (rbsp.data(), rbsp.size(), br.pos);
   int k = c.sh->first_mb, qp_prev = c.sh->slice_qp, count = 0, last_dqp = 0;
@@ -1771,10 +1773,10 @@ int Parser::Impl::handle_nal (const uint8_t* nal, size_t len) {
     cur->slices.push_back (sl);
     if (sh.first_mb < 0 || (uint32_t)sh.first_mb >= (uint32_t) (S.mb_w * S.mb_h)) { fail ("first_mb_in_slice out of range"); return -1; }
     last_hdr_bits = (int)br.pos; last_cabac = P.cabac;
-    if (self->defer_ && !P.cabac) {
+    if (self->defer_ && (!P.cabac || self->defer_cabac_)) {
       cur->deferred.emplace_back();
       DeferredSlice& d = cur->deferred.back();
-      d.rbsp = rbsp; d.data_bit = br.pos; d.sid = c.sid; d.sh = sh; d.pps = P; d.sps_scaling = S.scaling_matrix_present;
+      d.rbsp = rbsp; d.data_bit = br.pos; d.sid = c.sid; d.sh = sh; d.pps = P; d.sps_scaling = S.scaling_matrix_present; d.cabac = P.cabac != 0;
       d.seq = nal_seq; d.pictures_before = self->pictures_done_;
       return 0;
     }
@@ -1827,9 +1829,10 @@ bool Parser::Impl::parse_deferred (FrameOut& f, size_t slice) {
   const size_t pcm_mark = self->pcm_.size();
   d.resolved = true;
   // (an exception is caught here, while the slice is still the one in hand: its error lands at the slice's place in the stream)
-  try { d.ok = parse_slice_data_cavlc (br, c); }
+  cabac_stop = 0;
+  try { d.ok = d.cabac ? parse_slice_data_cabac (br, c) : parse_slice_data_cavlc (br, c); }
   catch (const std::exception& e) { fail (std::string ("internal: ") + e.what()); d.ok = false; }
-  d.stop_bit = br.pos;
+  d.stop_bit = d.cabac ? cabac_stop : br.pos;
   if (!d.ok) { self->pcm_.resize (pcm_mark); self->file_rc_ = -1; }
   if (coef_unsorted) sort_coeffs();
   return d.ok;

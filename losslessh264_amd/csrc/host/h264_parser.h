@@ -172,7 +172,8 @@ template <typename T> struct PoolAlloc {
 };
 template <typename T> using PoolVec = std::vector<T, PoolAlloc<T>>;
 
-// Parser::set_defer_slice_data: a CAVLC slice whose header was walked and whose macroblock layer was not.  Everything that layer reads
+// Parser::set_defer_slice_data: a CAVLC slice (with set_defer_cabac: a slice of either entropy mode) whose header was walked and whose
+// macroblock layer was not.  Everything that layer reads
 // is held here by value (a later PPS with the same id does not change it): the unescaped payload, where slice_data() begins, the
 // header, the picture parameter set and the one fact of the sequence parameter set that counts.  seq / pictures_before place the
 // slice in the stream for the error it may still raise.
@@ -183,7 +184,12 @@ struct DeferredSlice {
   SliceHeader sh; Pps pps; bool sps_scaling = false;
   long seq = 0, pictures_before = 0;
   bool resolved = false, ok = false;       // parse_deferred ran, and what it returned
-  size_t stop_bit = 0;                     // ... and where its bit reader stood then
+  bool cabac = false;                      // the slice's PPS has entropy_coding_mode_flag set
+  // ... and where its reader stood then.  CAVLC: the bit reader's position, which is the rbsp stop bit of a slice that parsed.  CABAC:
+  // Cabac::pos, the number of the next bit the arithmetic decoder would take in - 9 bits behind the (aligned) start of slice_data() once
+  // the engine is initialised, again 9 bits behind the last sample of an I_PCM macroblock, and beyond the payload's end by as many
+  // zero bits as the decoder was fed (at most 65: that is where it gives up).  lh264_slice_cabac.h reports the same number
+  size_t stop_bit = 0;
 };
 
 // one parsed picture: exactly what lh264_recon_chains / lh264_ctx_index_chains consume
@@ -211,7 +217,7 @@ struct FrameOut {
   int concealed = 0, conceal_src = -1; bool frozen = false;
   int poc = 0;                             // the picture's POC as the reference's concealment counts it once the picture is done: pic_order_cnt_lsb, 0 behind an mmco 5
   int32_t conceal_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<DeferredSlice> deferred;     // Parser::set_defer_slice_data: the picture's CAVLC slices, in stream order
+  std::vector<DeferredSlice> deferred;     // Parser::set_defer_slice_data: the picture's deferred slices, in stream order
 };
 
 // The recompressor's default stream (".pip" itself, stream id 0x7fffffff): the Annex-B input minus its slice data.
@@ -315,6 +321,9 @@ class Parser {
   // CABAC slices are parsed on the spot.  For the decode direction: the symbol lists, the I_PCM sample stream, damaged() and
   // concealment are not maintained for deferred pictures.  Off (the default): nothing changes
   void set_defer_slice_data (bool on) { defer_ = on; }
+  // on, together with set_defer_slice_data: CABAC slices are deferred too, each marked DeferredSlice::cabac, and parse_deferred runs the
+  // host's CABAC macroblock layer over them.  On its own it does nothing.  Off (the default): CABAC slices are parsed on the spot
+  void set_defer_cabac (bool on) { defer_cabac_ = on; }
   // the host macroblock layer over deferred slice `slice` of a picture this parser completed (the slices of a picture in order): records,
   // covered, n_mbs, slice_syn as the undeferred parser leaves them; on failure error() / error_pictures() as it would have set them
   // (a deferred slice lies in front of whatever failed after it).  false: the slice failed, or there is no such slice
@@ -348,7 +357,7 @@ class Parser {
   int n_unsupported_ = 0;
   bool keep_frames_ = true, want_coeffs_ = true, lazy_levels_ = false, sparse_levels_ = false, sparse_coeffs_ = false; long pictures_done_ = 0, err_pictures_ = 0; bool damaged_ = false;
   int conceal_ = 0;
-  bool defer_ = false;
+  bool defer_ = false, defer_cabac_ = false;
   bool tolerant_ = false; long nal_index_ = 0; std::string not_kept_, not_carried_;
   MainStreamWriter main_;
   std::vector<uint8_t> pcm_;

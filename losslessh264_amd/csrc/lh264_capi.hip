@@ -781,6 +781,11 @@ int lh264_parser_frame_conceal (const lh264_parser_t* p, int idx, int32_t out[12
   return LH264_OK;
 }
 int lh264_parser_set_defer_slice_data (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_defer_slice_data (on != 0); return LH264_OK; }
+int lh264_parser_set_defer_cabac (lh264_parser_t* p, int on) { if (!p) return LH264_E_ARG; p->p.set_defer_cabac (on != 0); return LH264_OK; }
+int lh264_parser_frame_deferred_cabac (const lh264_parser_t* p, int idx, int slice) {
+  auto f = pf (p, idx);
+  return f && slice >= 0 && (size_t)slice < f->deferred.size() ? (f->deferred[(size_t)slice].cabac ? 1 : 0) : LH264_E_ARG;
+}
 int lh264_parser_frame_deferred (const lh264_parser_t* p, int idx) { auto f = pf (p, idx); return f ? (int)f->deferred.size() : 0; }
 int lh264_parser_parse_deferred (lh264_parser_t* p, int idx, int slice, int32_t out[2]) {
   if (!p || idx < 0 || (size_t)idx >= p->p.frames().size() || slice < 0 || (size_t)slice >= p->p.frames()[(size_t)idx]->deferred.size()) return LH264_E_ARG;

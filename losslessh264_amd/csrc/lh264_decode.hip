@@ -22,7 +22,7 @@
 #include "host/capi_internal.h"
 #include "host/device_mem.h"
 #include "lh264_sha1.h"
-#include "lh264_slice.h"
+#include "lh264_slice_cabac.h"
 
 // ---- the pack step: crop + I420 / NV12, host and device from one source ------------------------------------------------------------
 // A picture is cut into bands of 16 luma rows (and the 8 chroma rows that belong to them); a band's rows are cut into PIECES: the
@@ -134,6 +134,7 @@ struct lh264_decoded {
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
   int parse_path = LH264_PARSE_PATH_HOST;
+  long device_cabac_slices = 0;                 // ... of them CABAC slices (slice_parse_cabac_kernel)
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
@@ -367,6 +368,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   const int conceal = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V2 ? (int)opts->conceal : 0;
   const uint32_t parse = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? opts->parse : LH264_PARSE_HOST;
   if (parse != LH264_PARSE_HOST && parse != LH264_PARSE_DEVICE) return LH264_E_ARG;
+  const uint32_t parse_flags = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? opts->parse_flags : 0;
+  if ((parse_flags & ~LH264_PARSE_FLAG_CABAC) || (parse_flags && parse != LH264_PARSE_DEVICE)) return LH264_E_ARG;
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -400,6 +403,10 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   const bool parse_dev = parse == LH264_PARSE_DEVICE && conceal == 0;      // (concealment builds records on the host)
   // LH264_SLICE_PARSE_FAIL=k (tests): task k of the call's first parse launch reports a status unwalked, which forces the fallback
   int force_fail = parse_dev && getenv ("LH264_SLICE_PARSE_FAIL") ? atoi (getenv ("LH264_SLICE_PARSE_FAIL")) : -1;
+  // LH264_PARSE_FLAG_CABAC: CABAC slices are deferred and become tasks too; LH264_SLICE_PARSE_FAIL_CABAC=k: the same for task k of the
+  // call's first CABAC launch
+  const bool parse_cabac = parse_dev && (parse_flags & LH264_PARSE_FLAG_CABAC);
+  int force_fail_cabac = parse_cabac && getenv ("LH264_SLICE_PARSE_FAIL_CABAC") ? atoi (getenv ("LH264_SLICE_PARSE_FAIL_CABAC")) : -1;
 
   auto release_pool = [&] (DStream& s) {
     for (Slot& sl : s.pool) A.pics.put (s.geo.bytes, sl.base);
@@ -434,10 +441,11 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         break;
       }
       FrameOut& f = *s.pending.front();
+      // a change of resolution ends the round: the next one starts with a new pool.  (Asked first: on the device route the tentative
+      // pass stopped here too, so the picture's slice data is not parsed yet and there is nothing to refuse it by)
+      if (!s.sel.empty() && (f.mb_w != s.sel[0]->mb_w || f.mb_h != s.sel[0]->mb_h)) break;
       const std::string why = tentative ? std::string() : refuse_picture (f);
       if (!why.empty()) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + why; break; }
-      // a change of resolution ends the round: the next one starts with a new pool
-      if (!s.sel.empty() && (f.mb_w != s.sel[0]->mb_w || f.mb_h != s.sel[0]->mb_h)) break;
       s.sel.push_back (std::move (s.pending.front())); s.pending.pop_front();
     }
   };
@@ -523,6 +531,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s->parser->set_conceal (conceal);
         s->dev_route = parse_dev;
         s->parser->set_defer_slice_data (parse_dev);
+        s->parser->set_defer_cabac (parse_cabac);
         s->parser->begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
         active.push_back (std::move (s));
         used += avg * R; admitted++;
@@ -556,9 +565,12 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         }
       }
       std::stable_sort (refs.begin(), refs.end(), [] (const TRef& a, const TRef& b) { return a.f->deferred[a.def].rbsp.size() > b.f->deferred[b.def].rbsp.size(); });
+      // (the CAVLC tasks in front of the CABAC ones, longest first within each: one launch per kernel)
+      const size_t n_cavlc = (size_t) (std::stable_partition (refs.begin(), refs.end(), [] (const TRef& a) { return !a.f->deferred[a.def].cabac; }) - refs.begin());
+      auto line_bytes = [] (const TRef& r) { return (size_t)r.f->mb_w * (r.f->deferred[r.def].cabac ? (size_t)lh264slice::kCabacLineBytes : 4); };
       for (TRef& r : refs) {
         r.bytes_at = pb;
-        pb += ((r.f->deferred[r.def].rbsp.size() + 15) & ~ (size_t)15) + 224 + (r.f->mb_w > lh264slice::kLdsLineMbs ? (((size_t)r.f->mb_w * 4 + 15) & ~ (size_t)15) : 0);
+        pb += ((r.f->deferred[r.def].rbsp.size() + 15) & ~ (size_t)15) + 224 + (r.f->mb_w > lh264slice::kLdsLineMbs ? ((line_bytes (r) + 15) & ~ (size_t)15) : 0);
       }
       const size_t nt = refs.size();
       bool ok = true;
@@ -588,6 +600,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
             t.transform_8x8 = ds.pps.transform_8x8; t.constrained_intra_pred = ds.pps.constrained_intra_pred;
             t.use_sl = ds.sps_scaling || ds.pps.scaling_matrix_present;
             t.chroma_qp_offset[0] = (int8_t)ds.pps.chroma_qp_offset[0]; t.chroma_qp_offset[1] = (int8_t)ds.pps.chroma_qp_offset[1];
+            if (ds.cabac) t.reserved = (uint8_t) (lh264slice::kTaskCabac | (ds.sh.cabac_init_idc & 3));
             t.scaling = db + sc_at;
             t.mbs = A.d_pmbs.as<lh264_mb_t>() + at.mb; t.coeffs = A.d_pcoef.as<int16_t>() + at.mb * 384;
             t.slice = nullptr;                                  // (the host fills n_mbs in from the result; the table is staged as ever)
@@ -597,10 +610,12 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
           ok = hipMemcpyAsync (A.d_pbytes.p, hb, pb, hipMemcpyHostToDevice, st) == hipSuccess &&
                hipMemcpyAsync (A.d_ptasks.p, ht, nt * sizeof (lh264host::SliceTask), hipMemcpyHostToDevice, st) == hipSuccess &&
                hipMemsetAsync (A.d_pmbs.p, 0, pm * sizeof (lh264_mb_t), st) == hipSuccess && hipMemsetAsync (A.d_pcoef.p, 0, pm * 768, st) == hipSuccess &&
-               lh264host::launch_slice_parse (A.d_ptasks.as<lh264host::SliceTask>(), A.d_pres.as<lh264host::SliceResult>(), (int)nt, st, force_fail) &&
+               lh264host::launch_slice_parse (A.d_ptasks.as<lh264host::SliceTask>(), A.d_pres.as<lh264host::SliceResult>(), (int)n_cavlc, st, force_fail) &&
+               lh264host::launch_slice_parse_cabac (A.d_ptasks.as<lh264host::SliceTask>() + n_cavlc, A.d_pres.as<lh264host::SliceResult>() + n_cavlc, (int) (nt - n_cavlc), st, force_fail_cabac) &&
                hipMemcpyAsync (A.h_pres.p, A.d_pres.p, nt * sizeof (lh264host::SliceResult), hipMemcpyDeviceToHost, st) == hipSuccess &&
                hipStreamSynchronize (st) == hipSuccess;
-          force_fail = -1;
+          if (n_cavlc) force_fail = -1;
+          if (nt > n_cavlc) force_fail_cabac = -1;
         }
         if (!ok) {
           fail_device ("the slice parse stage failed");
@@ -624,7 +639,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
           const lh264host::DeferredSlice& ds = f.deferred[r.def];
           if (out[r.s->i]->parse_path == LH264_PARSE_PATH_HOST) out[r.s->i]->parse_path = LH264_PARSE_PATH_DEVICE;
           out[r.s->i]->device_slices++;
-          // what parse_slice_data_cavlc leaves with the picture: n_mbs, coverage, the slice's syntax entry
+          if (ds.cabac) out[r.s->i]->device_cabac_slices++;
+          // what parse_slice_data_cavlc / _cabac leaves with the picture: n_mbs, coverage, the slice's syntax entry
           f.slices[(size_t)ds.sid].n_mbs = res[j].n_mbs;
           for (int k = 0; k < res[j].n_mbs; k++) f.covered[(size_t) (ds.sh.first_mb + k)] = 1;
           lh264host::SliceSyn ss;
@@ -633,6 +649,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
           ss.pad_value = (ss.pad_bits && (stop >> 3) < ds.rbsp.size()) ? (ds.rbsp[stop >> 3] & ((1 << ss.pad_bits) - 1)) : 0;
           ss.transform8x8_pps = ds.pps.transform_8x8 ? 1 : 0;
           ss.flags = ds.pps.constrained_intra_pred ? 2 : 0;
+          if (ds.cabac) { ss.pad_bits = 7; ss.pad_value = ds.rbsp.empty() ? 0 : ds.rbsp.back() & 0x7f; ss.flags |= 1; }
           if (f.slice_syn.size() <= (size_t)ds.sid) f.slice_syn.resize ((size_t)ds.sid + 1);
           f.slice_syn[(size_t)ds.sid] = ss;
         }
@@ -879,6 +896,7 @@ int lh264_decode_last_parse_timing (double* out) {
 int lh264_decoded_status (const lh264_decoded_t* d) { return d ? d->status : LH264_E_ARG; }
 int lh264_decoded_parse_path (const lh264_decoded_t* d) { return d ? d->parse_path : LH264_E_ARG; }
 long long lh264_decoded_device_slices (const lh264_decoded_t* d) { return d ? (long long)d->device_slices : 0; }
+long long lh264_decoded_device_cabac_slices (const lh264_decoded_t* d) { return d ? (long long)d->device_cabac_slices : 0; }
 const char* lh264_decoded_error (const lh264_decoded_t* d) { return d ? d->error.c_str() : ""; }
 int lh264_decoded_pictures (const lh264_decoded_t* d) { return d ? (int)d->pics.size() : 0; }
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* o) {

@@ -185,7 +185,147 @@ LH264S_HD inline int residual_block (const Tables& T, Bits& br, int nC, int max_
 }
 
 // ---- the walk over one slice --------------------------------------------------------------------------------------------------------
-struct Walk {
+// What the walk of either entropy mode does with a macroblock once its syntax elements are known: availability, dequantisation, motion
+// vector prediction, the final intra modes, the record's way out.  The walk D (Walk here, CabacWalk in lh264_slice_cabac.h) holds the
+// data - T (its table record, with chroma_qp, norm4 and norm8 under these names), t, m, w, first, k - and derives from WalkOps<D>: one
+// definition for both, and neither walk's layout depends on the other's.
+template <typename D> struct WalkOps {
+  LH264S_HD D& self() { return *static_cast<D*> (this); }
+  LH264S_HD const D& self() const { return *static_cast<const D*> (this); }
+  LH264S_HD bool avail (int kk) const { const D& S = self(); return kk >= S.first && kk < S.k; }
+  LH264S_HD bool intra_nb_avail (int kk) const { const D& S = self(); return avail (kk) && (!S.t->constrained_intra_pred || (S.t->mbs[kk].mb_type & LH264_MB_INTRA)); }
+  // dequantisation as the host front end does it (flat, or with the PPS's resolved lists: 6 x 16 then 2 x 64 entries, raster)
+  LH264S_HD int dq4 (int list, int qp, int j, int level) const {
+    const D& S = self();
+    const int x = j & 3, y = j >> 2;
+    const int cls = ((x & 1) == 0 && (y & 1) == 0) ? 0 : ((x & 1) && (y & 1)) ? 1 : 2;
+    const int d = S.T->norm4[qp % 6][cls] << (qp / 6);
+    return S.t->use_sl ? (level * (S.t->scaling[list * 16 + j] * d)) >> 4 : level * d;
+  }
+  LH264S_HD static int cls8 (int x, int y) {
+    if ((x & 3) == 0 && (y & 3) == 0) return 0;
+    if ((x & 1) && (y & 1)) return 1;
+    if ((x & 3) == 2 && (y & 3) == 2) return 2;
+    if (((x & 3) == 0 && (y & 1)) || ((x & 1) && (y & 3) == 0)) return 3;
+    if (((x & 3) == 0 && (y & 3) == 2) || ((x & 3) == 2 && (y & 3) == 0)) return 4;
+    return 5;
+  }
+  LH264S_HD int dq8 (int list8, int qp, int j, int level) const {
+    const D& S = self();
+    const int d = (S.t->use_sl ? S.t->scaling[96 + list8 * 64 + j] : 16) * S.T->norm8[qp % 6][cls8 (j & 7, j >> 3)];
+    return qp >= 36 ? (level * d) * (1 << (qp / 6 - 6)) : (level * d + (1 << (5 - qp / 6))) >> (6 - qp / 6);
+  }
+  LH264S_HD void set_qp (int qp) {
+    D& S = self();
+    S.m->qp_y = (uint8_t)qp;
+    for (int p = 0; p < 2; p++) S.m->qp_c[p] = S.T->chroma_qp[imin (51, imax (0, qp + S.t->chroma_qp_offset[p]))];
+  }
+  LH264S_HD void put (int16_t* coef, int at, int v) const { if ((unsigned)at < 384u) coef[at] = (int16_t)v; }
+
+  // median motion vector prediction (8.4.1.3); motion and references of other macroblocks come from their records
+  struct Nb { bool avail; int ref, mvx, mvy; };
+  LH264S_HD Nb nb_block (int bx, int by, uint32_t filled) const {
+    const D& S = self();
+    int kk = S.k, x = bx, y = by;
+    if (x < 0) { kk = (kk % S.w) ? kk - 1 : -1; x += 4; } else if (x > 3) { kk = ((kk % S.w) + 1 < S.w) ? kk + 1 : -1; x -= 4; }
+    if (kk >= 0 && y < 0) { kk = kk >= S.w ? kk - S.w : -1; y += 4; }
+    Nb r = {false, -1, 0, 0};
+    if (kk < 0) return r;
+    if (kk == S.k) {
+      if (bx < 0 || bx > 3 || by < 0) return r;
+      if (!((filled >> (y * 4 + x)) & 1)) return r;
+    } else if (!avail (kk)) return r;
+    r.avail = true;
+    const lh264_mb_t* s = kk == S.k ? S.m : &S.t->mbs[kk];
+    r.ref = s->ref_idx[(y >> 1) * 2 + (x >> 1)];
+    r.mvx = s->mv[y * 4 + x][0]; r.mvy = s->mv[y * 4 + x][1];
+    return r;
+  }
+  LH264S_HD static int median3 (int a, int b, int c) { return imax (imin (a, b), imin (imax (a, b), c)); }
+  LH264S_HD void predict_mv (uint32_t filled, int bx, int by, int bw, int ref, int shape, int& px, int& py) const {
+    Nb A = nb_block (bx - 1, by, filled), B = nb_block (bx, by - 1, filled), C = nb_block (bx + bw, by - 1, filled);
+    if (!C.avail) C = nb_block (bx - 1, by - 1, filled);
+    if (shape == 1 && B.avail && B.ref == ref) { px = B.mvx; py = B.mvy; return; }
+    if (shape == 2 && A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; return; }
+    if (shape == 3 && A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; return; }
+    if (shape == 4 && C.avail && C.ref == ref) { px = C.mvx; py = C.mvy; return; }
+    if (!B.avail && !C.avail && A.avail) { px = A.mvx; py = A.mvy; return; }
+    const int cnt = (A.avail && A.ref == ref) + (B.avail && B.ref == ref) + (C.avail && C.ref == ref);
+    if (cnt == 1) {
+      if (A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; }
+      else if (B.avail && B.ref == ref) { px = B.mvx; py = B.mvy; }
+      else { px = C.mvx; py = C.mvy; }
+      return;
+    }
+    px = median3 (A.avail ? A.mvx : 0, B.avail ? B.mvx : 0, C.avail ? C.mvx : 0);
+    py = median3 (A.avail ? A.mvy : 0, B.avail ? B.mvy : 0, C.avail ? C.mvy : 0);
+  }
+  LH264S_HD void fill_part (int bx, int by, int bw, int bh, int mvx, int mvy, uint32_t& filled) {
+    D& S = self();
+    for (int y = by; y < by + bh; y++) for (int x = bx; x < bx + bw; x++) {
+        S.m->mv[y * 4 + x][0] = (int16_t)mvx; S.m->mv[y * 4 + x][1] = (int16_t)mvy;
+        filled |= 1u << (y * 4 + x);
+      }
+  }
+
+  // parsed (standard-numbered) intra modes -> the availability-resolved final modes of the record
+  LH264S_HD static int dcmap (bool l, bool t_, int dc, int dcl, int dct, int dc128) { return l && t_ ? dc : l ? dcl : t_ ? dct : dc128; }
+  LH264S_HD void finalize_intra_modes (const int* raw, bool is8, int i16mode, int chroma_mode) {
+    D& S = self();
+    const bool L = (S.k % S.w) && intra_nb_avail (S.k - 1);
+    const bool Tp = S.k >= S.w && intra_nb_avail (S.k - S.w);
+    const bool TL = (S.k % S.w) && S.k >= S.w && intra_nb_avail (S.k - S.w - 1);
+    const bool TR = S.k >= S.w && ((S.k % S.w) + 1 < S.w) && intra_nb_avail (S.k - S.w + 1);
+    S.m->intra_avail = (uint8_t) ((Tp ? LH264_AVAIL_T : 0) | (TL ? LH264_AVAIL_TL : 0) | (L ? LH264_AVAIL_L : 0) | (TR ? LH264_AVAIL_TR : 0));
+    if (raw) {
+      if (!is8) {
+        for (int z = 0; z < 16; z++) {
+          const int bx = z2x (z), by = z2y (z);
+          const bool l = bx > 0 || L, tt = by > 0 || Tp;
+          bool tr;
+          if (by == 0) tr = bx < 3 ? Tp : TR;
+          else tr = bx < 3 && xy2z (bx + 1, by - 1) < z;
+          int mode = raw[by * 4 + bx];
+          if (mode == 2) mode = dcmap (l, tt, LH264_I4_DC, LH264_I4_DC_L, LH264_I4_DC_T, LH264_I4_DC_128);
+          else if (mode == 3 && !tr) mode = LH264_I4_DDL_TOP;
+          else if (mode == 7 && !tr) mode = LH264_I4_VL_TOP;
+          S.m->intra_mode[by * 4 + bx] = (int8_t)mode;
+        }
+      } else {
+        for (int i8 = 0; i8 < 4; i8++) {
+          const int bx = i8 & 1, by = i8 >> 1;
+          const bool l = bx > 0 || L, tt = by > 0 || Tp;
+          const bool tr = i8 == 0 ? Tp : i8 == 1 ? TR : i8 == 2;
+          int mode = raw[by * 8 + bx * 2];
+          if (mode == 2) mode = dcmap (l, tt, LH264_I4_DC, LH264_I4_DC_L, LH264_I4_DC_T, LH264_I4_DC_128);
+          else if (mode == 3 && !tr) mode = LH264_I4_DDL_TOP;
+          else if (mode == 7 && !tr) mode = LH264_I4_VL_TOP;
+          for (int j = 0; j < 4; j++) S.m->intra_mode[(by * 2 + (j >> 1)) * 4 + bx * 2 + (j & 1)] = (int8_t)mode;
+        }
+      }
+    } else if (i16mode >= 0) {
+      int mode = i16mode;
+      if (mode == 2) mode = dcmap (L, Tp, LH264_I16_DC, LH264_I16_DC_L, LH264_I16_DC_T, LH264_I16_DC_128);
+      S.m->intra_mode[0] = (int8_t)mode;
+    }
+    if (chroma_mode >= 0) {
+      int mode = chroma_mode;
+      if (mode == 0) mode = dcmap (L, Tp, LH264_C_DC, LH264_C_DC_L, LH264_C_DC_T, LH264_C_DC_128);
+      S.m->chroma_mode = (int8_t)mode;
+    }
+  }
+
+  // the macroblock in hand is done: its record goes where recon_chain_kernel reads it (16 bytes at a time; both sides are 16-byte
+  // aligned)
+  LH264S_HD void store_record() {
+    D& S = self();
+    const uint4_like* s = (const uint4_like*)S.m; uint4_like* d = (uint4_like*)&S.t->mbs[S.k];
+    for (int i = 0; i < 8; i++) d[i] = s[i];
+  }
+  struct alignas (16) uint4_like { uint32_t x, y, z, w; };
+};
+
+struct Walk : WalkOps<Walk> {
   const Tables* T; const SliceTask* t; Bits br;
   lh264_mb_t* m;            // the record in hand (the caller's scratch: LDS on the device); copied to t->mbs[k] when the macroblock is done
   int8_t* line;             // raw intra modes of the bottom row of the macroblock parsed last in every column, 4 per column
@@ -193,8 +333,6 @@ struct Walk {
   int8_t ipm[16];           // ... of the macroblock in hand, raster (2 where it is not I_NxN)
   int w, n, first, k;
 
-  LH264S_HD bool avail (int kk) const { return kk >= first && kk < k; }
-  LH264S_HD bool intra_nb_avail (int kk) const { return avail (kk) && (!t->constrained_intra_pred || (t->mbs[kk].mb_type & LH264_MB_INTRA)); }
   LH264S_HD int nz_luma (int bx, int by, bool& a) const {
     int kk = k;
     if (bx < 0) { kk = (k % w) ? k - 1 : -1; bx = 3; }
@@ -220,129 +358,11 @@ struct Walk {
   }
   LH264S_HD int luma_nC (int bx, int by) const { bool aA, aB; const int nA = nz_luma (bx - 1, by, aA), nB = nz_luma (bx, by - 1, aB); return nC_of (nA, aA, nB, aB); }
 
-  // dequantisation as the host front end does it (flat, or with the PPS's resolved lists: 6 x 16 then 2 x 64 entries, raster)
-  LH264S_HD int dq4 (int list, int qp, int j, int level) const {
-    const int x = j & 3, y = j >> 2;
-    const int cls = ((x & 1) == 0 && (y & 1) == 0) ? 0 : ((x & 1) && (y & 1)) ? 1 : 2;
-    const int d = T->norm4[qp % 6][cls] << (qp / 6);
-    return t->use_sl ? (level * (t->scaling[list * 16 + j] * d)) >> 4 : level * d;
-  }
-  LH264S_HD static int cls8 (int x, int y) {
-    if ((x & 3) == 0 && (y & 3) == 0) return 0;
-    if ((x & 1) && (y & 1)) return 1;
-    if ((x & 3) == 2 && (y & 3) == 2) return 2;
-    if (((x & 3) == 0 && (y & 1)) || ((x & 1) && (y & 3) == 0)) return 3;
-    if (((x & 3) == 0 && (y & 3) == 2) || ((x & 3) == 2 && (y & 3) == 0)) return 4;
-    return 5;
-  }
-  LH264S_HD int dq8 (int list8, int qp, int j, int level) const {
-    const int d = (t->use_sl ? t->scaling[96 + list8 * 64 + j] : 16) * T->norm8[qp % 6][cls8 (j & 7, j >> 3)];
-    return qp >= 36 ? (level * d) * (1 << (qp / 6 - 6)) : (level * d + (1 << (5 - qp / 6))) >> (6 - qp / 6);
-  }
-  LH264S_HD void set_qp (int qp) {
-    m->qp_y = (uint8_t)qp;
-    for (int p = 0; p < 2; p++) m->qp_c[p] = T->chroma_qp[imin (51, imax (0, qp + t->chroma_qp_offset[p]))];
-  }
-  LH264S_HD void put (int16_t* coef, int at, int v) const { if ((unsigned)at < 384u) coef[at] = (int16_t)v; }
-
-  // median motion vector prediction (8.4.1.3); motion and references of other macroblocks come from their records
-  struct Nb { bool avail; int ref, mvx, mvy; };
-  LH264S_HD Nb nb_block (int bx, int by, uint32_t filled) const {
-    int kk = k, x = bx, y = by;
-    if (x < 0) { kk = (kk % w) ? kk - 1 : -1; x += 4; } else if (x > 3) { kk = ((kk % w) + 1 < w) ? kk + 1 : -1; x -= 4; }
-    if (kk >= 0 && y < 0) { kk = kk >= w ? kk - w : -1; y += 4; }
-    Nb r = {false, -1, 0, 0};
-    if (kk < 0) return r;
-    if (kk == k) {
-      if (bx < 0 || bx > 3 || by < 0) return r;
-      if (!((filled >> (y * 4 + x)) & 1)) return r;
-    } else if (!avail (kk)) return r;
-    r.avail = true;
-    const lh264_mb_t* s = kk == k ? m : &t->mbs[kk];
-    r.ref = s->ref_idx[(y >> 1) * 2 + (x >> 1)];
-    r.mvx = s->mv[y * 4 + x][0]; r.mvy = s->mv[y * 4 + x][1];
-    return r;
-  }
-  LH264S_HD static int median3 (int a, int b, int c) { return imax (imin (a, b), imin (imax (a, b), c)); }
-  LH264S_HD void predict_mv (uint32_t filled, int bx, int by, int bw, int ref, int shape, int& px, int& py) const {
-    Nb A = nb_block (bx - 1, by, filled), B = nb_block (bx, by - 1, filled), C = nb_block (bx + bw, by - 1, filled);
-    if (!C.avail) C = nb_block (bx - 1, by - 1, filled);
-    if (shape == 1 && B.avail && B.ref == ref) { px = B.mvx; py = B.mvy; return; }
-    if (shape == 2 && A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; return; }
-    if (shape == 3 && A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; return; }
-    if (shape == 4 && C.avail && C.ref == ref) { px = C.mvx; py = C.mvy; return; }
-    if (!B.avail && !C.avail && A.avail) { px = A.mvx; py = A.mvy; return; }
-    const int cnt = (A.avail && A.ref == ref) + (B.avail && B.ref == ref) + (C.avail && C.ref == ref);
-    if (cnt == 1) {
-      if (A.avail && A.ref == ref) { px = A.mvx; py = A.mvy; }
-      else if (B.avail && B.ref == ref) { px = B.mvx; py = B.mvy; }
-      else { px = C.mvx; py = C.mvy; }
-      return;
-    }
-    px = median3 (A.avail ? A.mvx : 0, B.avail ? B.mvx : 0, C.avail ? C.mvx : 0);
-    py = median3 (A.avail ? A.mvy : 0, B.avail ? B.mvy : 0, C.avail ? C.mvy : 0);
-  }
-  LH264S_HD void fill_part (int bx, int by, int bw, int bh, int mvx, int mvy, uint32_t& filled) {
-    for (int y = by; y < by + bh; y++) for (int x = bx; x < bx + bw; x++) {
-        m->mv[y * 4 + x][0] = (int16_t)mvx; m->mv[y * 4 + x][1] = (int16_t)mvy;
-        filled |= 1u << (y * 4 + x);
-      }
-  }
-
-  // parsed (standard-numbered) intra modes -> the availability-resolved final modes of the record
-  LH264S_HD static int dcmap (bool l, bool t_, int dc, int dcl, int dct, int dc128) { return l && t_ ? dc : l ? dcl : t_ ? dct : dc128; }
-  LH264S_HD void finalize_intra_modes (const int* raw, bool is8, int i16mode, int chroma_mode) {
-    const bool L = (k % w) && intra_nb_avail (k - 1);
-    const bool Tp = k >= w && intra_nb_avail (k - w);
-    const bool TL = (k % w) && k >= w && intra_nb_avail (k - w - 1);
-    const bool TR = k >= w && ((k % w) + 1 < w) && intra_nb_avail (k - w + 1);
-    m->intra_avail = (uint8_t) ((Tp ? LH264_AVAIL_T : 0) | (TL ? LH264_AVAIL_TL : 0) | (L ? LH264_AVAIL_L : 0) | (TR ? LH264_AVAIL_TR : 0));
-    if (raw) {
-      if (!is8) {
-        for (int z = 0; z < 16; z++) {
-          const int bx = z2x (z), by = z2y (z);
-          const bool l = bx > 0 || L, tt = by > 0 || Tp;
-          bool tr;
-          if (by == 0) tr = bx < 3 ? Tp : TR;
-          else tr = bx < 3 && xy2z (bx + 1, by - 1) < z;
-          int mode = raw[by * 4 + bx];
-          if (mode == 2) mode = dcmap (l, tt, LH264_I4_DC, LH264_I4_DC_L, LH264_I4_DC_T, LH264_I4_DC_128);
-          else if (mode == 3 && !tr) mode = LH264_I4_DDL_TOP;
-          else if (mode == 7 && !tr) mode = LH264_I4_VL_TOP;
-          m->intra_mode[by * 4 + bx] = (int8_t)mode;
-        }
-      } else {
-        for (int i8 = 0; i8 < 4; i8++) {
-          const int bx = i8 & 1, by = i8 >> 1;
-          const bool l = bx > 0 || L, tt = by > 0 || Tp;
-          const bool tr = i8 == 0 ? Tp : i8 == 1 ? TR : i8 == 2;
-          int mode = raw[by * 8 + bx * 2];
-          if (mode == 2) mode = dcmap (l, tt, LH264_I4_DC, LH264_I4_DC_L, LH264_I4_DC_T, LH264_I4_DC_128);
-          else if (mode == 3 && !tr) mode = LH264_I4_DDL_TOP;
-          else if (mode == 7 && !tr) mode = LH264_I4_VL_TOP;
-          for (int j = 0; j < 4; j++) m->intra_mode[(by * 2 + (j >> 1)) * 4 + bx * 2 + (j & 1)] = (int8_t)mode;
-        }
-      }
-    } else if (i16mode >= 0) {
-      int mode = i16mode;
-      if (mode == 2) mode = dcmap (L, Tp, LH264_I16_DC, LH264_I16_DC_L, LH264_I16_DC_T, LH264_I16_DC_128);
-      m->intra_mode[0] = (int8_t)mode;
-    }
-    if (chroma_mode >= 0) {
-      int mode = chroma_mode;
-      if (mode == 0) mode = dcmap (L, Tp, LH264_C_DC, LH264_C_DC_L, LH264_C_DC_T, LH264_C_DC_128);
-      m->chroma_mode = (int8_t)mode;
-    }
-  }
-
-  // the macroblock in hand is done: its record goes where recon_chain_kernel reads it (16 bytes at a time; both sides are 16-byte
-  // aligned), its intra modes become the neighbours' context
+  // ... and its intra modes become the neighbours' context
   LH264S_HD void done() {
-    const uint4_like* s = (const uint4_like*)m; uint4_like* d = (uint4_like*)&t->mbs[k];
-    for (int i = 0; i < 8; i++) d[i] = s[i];
+    store_record();
     for (int i = 0; i < 4; i++) { line[(k % w) * 4 + i] = ipm[12 + i]; left[i] = ipm[i * 4 + 3]; }
   }
-  struct alignas (16) uint4_like { uint32_t x, y, z, w; };
 
   // one macroblock (7.3.5); false where the host's parse_mb_cavlc returns false
   LH264S_HD bool parse_mb (int& qp_prev, bool is_skip) {
@@ -520,9 +540,12 @@ struct Walk {
 };
 
 enum { SLICE_OK = 0, SLICE_SYNTAX = 1, SLICE_OVERRUN = 2, SLICE_BAD_TASK = 3 };
+// SliceTask::reserved: 0 for a CAVLC task; for a CABAC task (lh264_slice_cabac.h) bit 7 and cabac_init_idc, 0..2, in bits 0..1
+enum { kTaskCabac = 0x80, kTaskCabacIdcMask = 0x03 };
+LH264S_HD inline bool task_is_cabac (const SliceTask& t) { return (t.reserved & kTaskCabac) != 0; }
 
 // what the walk takes on trust from the host: checked before anything is read or written
-LH264S_HD inline bool task_ok (const SliceTask& t) {
+LH264S_HD inline bool task_ok (const SliceTask& t, bool cabac = false) {
   if (!t.rbsp || !t.mbs || !t.coeffs || (t.use_sl && !t.scaling)) return false;      // (slice may be null: n_mbs is in the result too)
   if (t.mb_w <= 0 || t.mb_h <= 0 || t.mb_w > 4096 || t.mb_h > 4096) return false;
   const int n = t.mb_w * t.mb_h;
@@ -532,6 +555,7 @@ LH264S_HD inline bool task_ok (const SliceTask& t) {
   if (t.slice_qp < -1024 || t.slice_qp > 1024 || t.chroma_qp_offset[0] < -12 || t.chroma_qp_offset[0] > 12 || t.chroma_qp_offset[1] < -12 || t.chroma_qp_offset[1] > 12) return false;
   if (((uintptr_t)t.mbs & 15) || ((uintptr_t)t.coeffs & 1) || ((uintptr_t)t.slice & 3)) return false;
   if (t.mb_w > kLdsLineMbs && !t.line) return false;
+  if (cabac ? (t.reserved < kTaskCabac || t.reserved > (kTaskCabac | 2)) : t.reserved != 0) return false;      // the entropy mode is the walk's, cabac_init_idc is defined
   return true;
 }
 

@@ -1,6 +1,7 @@
-// lh264_slice.hip - slice_parse_kernel: the CAVLC macroblock layer of lh264_slice.h on the device, one wave64 per slice, and
-// lh264_debug_slice_parse, which runs one stream's deferred slices through that code on the host or through the kernel and hands back
-// what it wrote, with guard bytes behind every buffer.  DESIGN.md section 4.4.
+// lh264_slice.hip - slice_parse_kernel and slice_parse_cabac_kernel: the CAVLC macroblock layer of lh264_slice.h and the CABAC one of
+// lh264_slice_cabac.h on the device, one wave64 per slice, and lh264_debug_slice_parse_opts, which runs one stream's deferred slices
+// through that code on the host or through the kernels and hands back what it wrote, with guard bytes behind every buffer.  DESIGN.md
+// section 4.4.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -15,6 +16,7 @@
 #include "host/capi_internal.h"
 #include "host/device_mem.h"
 #include "lh264_slice.h"
+#include "lh264_slice_cabac.h"
 
 using lh264host::SliceResult;
 using lh264host::SliceTask;
@@ -50,11 +52,73 @@ __global__ void __launch_bounds__ (64) slice_parse_kernel (const SliceTask* __re
   results[i] = lh264slice::parse_slice (T, t, &rec, t.mb_w > lh264slice::kLdsLineMbs ? t.line : line);
 }
 
+// The CABAC form, a kernel of its own (slice_parse_kernel's registers, scratch and LDS stay what they are).  One wave per task again:
+// the lanes copy the table record and the payload as above and initialise the slice's 460 context bytes from its column of the
+// (m, n) table (`init`, [460][4][2], read once from global memory); lane 0 walks the slice with the record in hand, the context bytes
+// and (for pictures up to kLdsLineMbs macroblocks wide) the line in LDS.
+__global__ void __launch_bounds__ (64) slice_parse_cabac_kernel (const SliceTask* __restrict__ tasks, SliceResult* __restrict__ results, int n,
+                                                                 const lh264slice::CabacTables* __restrict__ tables, const int8_t* __restrict__ init, int force_fail) {
+  __shared__ lh264slice::CabacTables T;
+  __shared__ alignas (16) lh264_mb_t rec;
+  __shared__ alignas (16) uint8_t line[lh264slice::kLdsLineMbs * lh264slice::kCabacLineBytes];
+  __shared__ uint8_t payload[kLdsRbspBytes];
+  __shared__ uint8_t state[lh264slice::kCabacContexts];
+  const int i = (int)blockIdx.x;
+  if (i >= n) return;
+  SliceTask t = tasks[i];
+  if (i == force_fail || !lh264slice::cabac_task_ok (t)) {
+    if (threadIdx.x == 0) { SliceResult r = {i == force_fail ? lh264slice::SLICE_SYNTAX : lh264slice::SLICE_BAD_TASK, 0, 0}; results[i] = r; }
+    return;
+  }
+  const bool staged = t.rbsp_bytes <= (uint32_t)kLdsRbspBytes;
+  if (staged) for (uint32_t q = threadIdx.x; q < t.rbsp_bytes; q += 64) payload[q] = t.rbsp[q];
+  {
+    const uint4* s = (const uint4*)tables; uint4* d = (uint4*)&T;
+    for (int q = (int)threadIdx.x; q < (int) (sizeof (lh264slice::CabacTables) / 16); q += 64) d[q] = s[q];
+  }
+  {
+    const int col = lh264slice::cabac_init_column (t);      // 0..3: task_ok has checked cabac_init_idc
+    for (int q = (int)threadIdx.x; q < lh264slice::kCabacContexts; q += 64) state[q] = lh264slice::cabac_init_state (init[(q * 4 + col) * 2], init[(q * 4 + col) * 2 + 1], t.slice_qp);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (staged) t.rbsp = payload;
+  results[i] = lh264slice::parse_slice_cabac (T, t, &rec, t.mb_w > lh264slice::kLdsLineMbs ? (uint8_t*)t.line : line, state);
+}
+
 namespace lh264host {
 
 namespace {
 struct TablesDev { DevBuf buf; bool up = false; };
-PerDevice<TablesDev> g_tables;
+PerDevice<TablesDev> g_tables, g_cabac_tables;
+const size_t kCabacInitAt = (sizeof (lh264slice::CabacTables) + 15) & ~ (size_t)15;      // the (m, n) table lies behind the record
+}
+
+const lh264slice::CabacTables& slice_cabac_tables_host() {
+  static const lh264slice::CabacTables* t = [] { lh264slice::CabacTables* p = new lh264slice::CabacTables(); lh264slice::fill_cabac_tables (*p); return p; }();
+  return *t;
+}
+
+// the same for CABAC tasks through slice_parse_cabac_kernel
+bool launch_slice_parse_cabac (const SliceTask* tasks_dev, SliceResult* results_dev, int n, void* stream, int force_fail) {
+  if (n <= 0) return true;
+  int device = 0;
+  if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= kMaxDevices) return false;
+  const uint8_t* td = nullptr;
+  {
+    auto ref = g_cabac_tables.lock (device);
+    TablesDev& t = ref.get();
+    if (!t.up) {
+      static_assert (sizeof (kCabacInit) == lh264slice::kCabacContexts * 8, "kCabacInit");
+      if (!t.buf.alloc (kCabacInitAt + sizeof (kCabacInit)) || hipMemcpy (t.buf.p, &slice_cabac_tables_host(), sizeof (lh264slice::CabacTables), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy ((uint8_t*)t.buf.p + kCabacInitAt, kCabacInit, sizeof (kCabacInit), hipMemcpyHostToDevice) != hipSuccess) return false;
+      t.up = true;
+    }
+    td = t.buf.as<uint8_t>();
+  }
+  hipLaunchKernelGGL (slice_parse_cabac_kernel, dim3 ((unsigned)n), dim3 (64), 0, (hipStream_t)stream, tasks_dev, results_dev, n,
+                      (const lh264slice::CabacTables*)td, (const int8_t*) (td + kCabacInitAt), force_fail);
+  return hipGetLastError() == hipSuccess;
 }
 
 const lh264slice::Tables& slice_tables_host() {
@@ -104,12 +168,19 @@ const uint8_t kGuardByte = 0xA5;
 extern "C" {
 
 int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int threads, const int32_t* tweak, lh264_slice_dump_t** out) {
-  if (!out || (!data && len)) return LH264_E_ARG;
+  int32_t tw[4] = {tweak ? tweak[0] : -1, tweak ? tweak[1] : -1, tweak ? tweak[2] : 0, -1};
+  return lh264_debug_slice_parse_opts (data, len, on_device ? LH264_SLICE_PARSE_ON_DEVICE : 0, threads, tweak ? tw : nullptr, out);
+}
+
+int lh264_debug_slice_parse_opts (const uint8_t* data, size_t len, uint32_t flags, int threads, const int32_t* tweak, lh264_slice_dump_t** out) {
+  if (!out || (!data && len) || (flags & ~ (uint32_t) (LH264_SLICE_PARSE_ON_DEVICE | LH264_SLICE_PARSE_CABAC))) return LH264_E_ARG;
   *out = nullptr;
+  const bool on_device = (flags & LH264_SLICE_PARSE_ON_DEVICE) != 0;
   if (on_device && lh264_device_count() <= 0) return LH264_E_NODEVICE;
   using namespace lh264host;
   Parser P;
   P.set_defer_slice_data (true);
+  P.set_defer_cabac ((flags & LH264_SLICE_PARSE_CABAC) != 0);
   P.set_sparse_levels (true);
   P.feed_file (data, len);
   std::unique_ptr<lh264_slice_dump> D (new lh264_slice_dump());
@@ -129,7 +200,7 @@ int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int
     pc.results.assign (f.slices.size() * 4, 0);
     for (size_t d = 0; d < f.deferred.size(); d++) {
       const DeferredSlice& ds = f.deferred[d];
-      jobs.push_back ({p, d, take (ds.rbsp.size()), take (224), take ((size_t)f.mb_w * 4)});
+      jobs.push_back ({p, d, take (ds.rbsp.size()), take (224), take ((size_t)f.mb_w * (ds.cabac ? (size_t)lh264slice::kCabacLineBytes : 4))});
     }
     D->pics.push_back (std::move (pc));
   }
@@ -142,8 +213,9 @@ int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int
   uint8_t* dev = nullptr;
   if (on_device && hipMalloc ((void**)&dev, at ? at : 64) != hipSuccess) return LH264_E_HIP;
   uint8_t* const B = on_device ? dev : A;               // the base the tasks' pointers are made from
-  // longest first, as the restore kernel takes its streams
+  // longest first, as the restore kernel takes its streams; the CAVLC tasks in front of the CABAC ones: one launch each
   std::stable_sort (jobs.begin(), jobs.end(), [&] (const Job& a, const Job& b) { return frames[a.pic]->deferred[a.def].rbsp.size() > frames[b.pic]->deferred[b.def].rbsp.size(); });
+  const size_t n_cavlc = (size_t) (std::stable_partition (jobs.begin(), jobs.end(), [&] (const Job& a) { return !frames[a.pic]->deferred[a.def].cabac; }) - jobs.begin());
   SliceTask* tasks = (SliceTask*) (A + tasks_at);
   for (size_t p = 0; p < frames.size(); p++) {
     FrameOut& f = *frames[p];
@@ -166,7 +238,8 @@ int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int
     t.rbsp = B + jb.rbsp; t.rbsp_bytes = (uint32_t)ds.rbsp.size(); t.data_bit = (uint32_t)ds.data_bit;
     t.first_mb = ds.sh.first_mb;
     t.limit_mb = (size_t)ds.sid + 1 < f.slices.size() ? std::min (n, f.slices[(size_t)ds.sid + 1].first_mb) : n;
-    if (tweak && tweak[0] == (int32_t)jb.pic && tweak[1] == ds.sid) t.limit_mb = tweak[2];
+    if (ds.cabac) t.reserved = (uint8_t) (lh264slice::kTaskCabac | (ds.sh.cabac_init_idc & 3));
+    if (tweak && tweak[0] == (int32_t)jb.pic && tweak[1] == ds.sid) { t.limit_mb = tweak[2]; if (tweak[3] >= 0) t.reserved = (uint8_t)tweak[3]; }
     t.mb_w = f.mb_w; t.mb_h = f.mb_h; t.slice_index = ds.sid; t.slice_qp = ds.sh.slice_qp;
     t.slice_type = (uint8_t)ds.sh.slice_type; t.num_ref_idx_l0 = (uint8_t)ds.sh.num_ref_idx_l0;
     t.transform_8x8 = ds.pps.transform_8x8; t.constrained_intra_pred = ds.pps.constrained_intra_pred;
@@ -182,13 +255,18 @@ int lh264_debug_slice_parse (const uint8_t* data, size_t len, int on_device, int
   if (!on_device) {
     // slices of one picture may run side by side: no two of them write one record
     const lh264slice::Tables& T = slice_tables_host();
+    const lh264slice::CabacTables& TC = slice_cabac_tables_host();
     run_parallel ((int)jobs.size(), threads, [&] (int j) {
       alignas (16) lh264_mb_t rec;
-      results[j] = lh264slice::parse_slice (T, tasks[j], &rec, tasks[j].line);
+      if ((size_t)j < n_cavlc) { results[j] = lh264slice::parse_slice (T, tasks[j], &rec, tasks[j].line); return; }
+      uint8_t state[lh264slice::kCabacContexts];
+      lh264slice::cabac_init_states (tasks[j], state);
+      results[j] = lh264slice::parse_slice_cabac (TC, tasks[j], &rec, (uint8_t*)tasks[j].line, state);
     });
   } else {
     bool ok = hipMemcpy (dev, A, at, hipMemcpyHostToDevice) == hipSuccess &&
-              launch_slice_parse ((const SliceTask*) (dev + tasks_at), (SliceResult*) (dev + results_at), (int)jobs.size(), nullptr, -1) &&
+              launch_slice_parse ((const SliceTask*) (dev + tasks_at), (SliceResult*) (dev + results_at), (int)n_cavlc, nullptr, -1) &&
+              launch_slice_parse_cabac ((const SliceTask*) (dev + tasks_at) + n_cavlc, (SliceResult*) (dev + results_at) + n_cavlc, (int) (jobs.size() - n_cavlc), nullptr, -1) &&
               hipStreamSynchronize (nullptr) == hipSuccess && hipMemcpy (A, dev, at, hipMemcpyDeviceToHost) == hipSuccess;
     hipFree (dev);
     if (!ok) rc = LH264_E_HIP;

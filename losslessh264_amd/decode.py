@@ -40,6 +40,10 @@ class DecodedBatch:
         """how many slices of stream i slice_parse_kernel parsed (0 on the host route)"""
         return int(self._lib.lh264_decoded_device_slices(self._h[i]))
 
+    def device_cabac_slices(self, i):
+        """... and how many of them were CABAC slices, parsed by slice_parse_cabac_kernel (parse="device+cabac")"""
+        return int(self._lib.lh264_decoded_device_cabac_slices(self._h[i]))
+
     def error(self, i):
         return self._lib.lh264_decoded_error(self._h[i]).decode()
 
@@ -128,7 +132,8 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     (DecodedBatch.picture_sha1) and / or of all delivered pictures of a stream in order (stream_sha1: for "i420" the number the
     reference's decoder test keeps per stream).  pictures=False (with sha1): digests only, no picture leaves the device.
     parse: "host" (the default) | "device": CAVLC slice data is parsed on the device by slice_parse_kernel, one wave per slice; the host
-    walks headers only.  The bytes are the same; DecodedBatch.parse_path(i) tells the route each stream took."""
+    walks headers only.  "device+cabac": CABAC slice data as well, by slice_parse_cabac_kernel, so that a stream stays on the device route
+    through its CABAC pictures.  The bytes are the same; DecodedBatch.parse_path(i) tells the route each stream took."""
     lib = L.lib()
     if fmt not in _FORMATS:
         raise ValueError("fmt must be 'i420' or 'nv12'")
@@ -136,8 +141,8 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise ValueError("conceal must be one of %s" % ", ".join(sorted(L.CONCEAL)))
     if sha1 not in _SHA1:
         raise ValueError("sha1 must be None, 'pictures', 'stream' or 'both'")
-    if parse not in L.PARSE:
-        raise ValueError("parse must be 'host' or 'device'")
+    if parse not in L.PARSE_MODES:
+        raise ValueError("parse must be 'host', 'device' or 'device+cabac'")
     if not pictures and (sha1 is None or device_out or sink is not None):
         raise ValueError("pictures=False needs sha1= and neither device_out nor a sink")
     n = len(datas)
@@ -146,7 +151,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     lens = (C.c_size_t * n)(*[len(d) for d in keep])
     opts = L.DecodeOptsV3()
     opts.struct_bytes = C.sizeof(L.DecodeOptsV3)
-    opts.parse = L.PARSE[parse]
+    opts.parse, opts.parse_flags = L.PARSE_MODES[parse]
     opts.format = _FORMATS[fmt]
     opts.flags = (L.DECODE_DEVICE_OUT if device_out else 0) | _SHA1[sha1] | (0 if pictures else L.DECODE_NO_PICTURES)
     opts.round_pictures = int(round_pictures or 0)

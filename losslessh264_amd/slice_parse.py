@@ -1,5 +1,6 @@
-"""CAVLC slice data apart from the header walk: the parser's deferred mode and the one piece of code that parses slice data for
-the device (csrc/lh264_slice.h), stepped on the host or run by slice_parse_kernel.  Checks and probes; not a decode path."""
+"""Slice data apart from the header walk: the parser's deferred mode and the code that parses slice data for the device
+(csrc/lh264_slice.h for CAVLC, csrc/lh264_slice_cabac.h for CABAC), stepped on the host or run by slice_parse_kernel /
+slice_parse_cabac_kernel.  Checks and probes; not a decode path."""
 import ctypes as C
 
 import numpy as np
@@ -9,23 +10,28 @@ from .parse import _read_frame
 
 
 class ParsedFile:
-    """frames, error text, file status, error_pictures; in deferred mode per picture the (slice index, ok, stop bit) of its deferred slices"""
+    """frames, error text, file status, error_pictures; in deferred mode per picture the (slice index, ok, stop bit) of its deferred
+    slices, and in deferred_cabac per picture whether each of them is a CABAC slice"""
 
 
-def parse_file_plain(data, deferred=False):
+def parse_file_plain(data, deferred=False, cabac=False):
     """the host front end over a whole file.  deferred=True: every CAVLC slice is deferred (lh264_parser_set_defer_slice_data) and then
-    parsed by lh264_parser_parse_deferred, picture by picture and slice by slice: what comes out must be what deferred=False gives"""
+    parsed by lh264_parser_parse_deferred, picture by picture and slice by slice: what comes out must be what deferred=False gives.
+    cabac=True (with deferred=True): the CABAC slices are deferred as well (lh264_parser_set_defer_cabac)"""
     lib = L.lib()
     p = lib.lh264_parser_create()
     try:
         if deferred:
             L.check(lib.lh264_parser_set_defer_slice_data(p, 1))
+        if cabac:
+            L.check(lib.lh264_parser_set_defer_cabac(p, 1))
         lib.lh264_parser_feed_file(p, bytes(data), len(data))
         r = ParsedFile()
-        r.deferred = []
+        r.deferred, r.deferred_cabac = [], []
         n = lib.lh264_parser_frame_count(p)
         for i in range(n):
             got = []
+            r.deferred_cabac.append([lib.lh264_parser_frame_deferred_cabac(p, i, s) == 1 for s in range(lib.lh264_parser_frame_deferred(p, i))])
             for s in range(lib.lh264_parser_frame_deferred(p, i)):
                 out = (C.c_int32 * 2)()
                 ok = lib.lh264_parser_parse_deferred(p, i, s, out)
@@ -44,15 +50,17 @@ class SlicePicture:
     pass
 
 
-def slice_parse(data, on_device=False, threads=0, tweak=None):
-    """lh264_debug_slice_parse -> (pictures, guards intact, the header walk's error text).  A picture has mb_w, mb_h, mbs, coeffs (n x 384),
-    slices and results: per slice (deferred, status, n_mbs, stop_bit).  tweak: (picture, slice, limit_mb)"""
+def slice_parse(data, on_device=False, threads=0, tweak=None, cabac=False):
+    """lh264_debug_slice_parse_opts -> (pictures, guards intact, the header walk's error text).  A picture has mb_w, mb_h, mbs, coeffs
+    (n x 384), slices and results: per slice (deferred, status, n_mbs, stop_bit).  tweak: (picture, slice, limit_mb) or (picture, slice,
+    limit_mb, the task's entropy-mode byte).  cabac=True: CABAC slices are deferred and walked too (csrc/lh264_slice_cabac.h)"""
     lib = L.lib()
     h = C.c_void_p()
-    tw = (C.c_int32 * 3)(*tweak) if tweak is not None else None
-    rc = lib.lh264_debug_slice_parse(bytes(data), len(data), 1 if on_device else 0, threads, tw, C.byref(h))
+    tw = (C.c_int32 * 4)(*(tuple(tweak) + (-1,))[:4]) if tweak is not None else None
+    flags = (L.SLICE_PARSE_ON_DEVICE if on_device else 0) | (L.SLICE_PARSE_CABAC if cabac else 0)
+    rc = lib.lh264_debug_slice_parse_opts(bytes(data), len(data), flags, threads, tw, C.byref(h))
     if rc != 0:
-        raise RuntimeError("lh264_debug_slice_parse: error %d" % rc)
+        raise RuntimeError("lh264_debug_slice_parse_opts: error %d" % rc)
     try:
         pics = []
         for i in range(lib.lh264_slice_dump_pictures(h)):

@@ -3,7 +3,7 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
