@@ -684,8 +684,20 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * tasks as well, in the same parse arena and with the same 12 bytes per slice coming down; slice_parse_cabac_kernel walks them, on the
  * same stream and ahead of the same synchronisation as slice_parse_kernel.  The stream then stays on the device route through CABAC
  * pictures; conceal and a status from either kernel send it to the host parser as before.  Without the flag nothing changes.
+ * opts->scale_log2 = s in {1, 2, 3} (the 64-byte struct; struct_bytes 40, 48 and 56: not read, 0): REDUCED-SIZE pictures, averaged on the
+ * device by decode_pack_scaled_kernel in place of the crop-and-copy kernel.  B = 1 << s.  For a picture whose cropped window is w x h
+ * (both even), cw = w / 2 and ch = h / 2: the delivered chroma size is ocw = ceil (cw / B), och = ceil (ch / B), the delivered luma size
+ * ow = 2 * ocw, oh = 2 * och (both even, so I420 / NV12 stay well formed).  Delivered luma sample (X, Y) =
+ * (sum + (1 << (2*s - 1))) >> (2*s), where sum runs over the B x B window samples at x = min (X*B + i, w - 1), y = min (Y*B + j, h - 1),
+ * 0 <= i, j < B; Cb and Cr: the same rule on their cw x ch planes.  Coordinates are clamped to the cropped window, never to the padded
+ * picture: what lies right of and below the window enters no mean.  The planes are averaged independently; chroma siting is NOT
+ * modelled (a luma sample and the chroma sample over it do not cover the same area of the picture exactly).  Packing is as at scale 0
+ * with ow and oh in place of w and h, pictures tight one behind the other; lh264_decoded_pic_t width / height / bytes / offset describe
+ * what is delivered, lh264_decoded_picture_source_size gives the window before scaling.  QCIF at s = 3: 22 x 18, 594 bytes.  The round's
+ * output buffers, the download, the handles, the sink, DEVICE_OUT and the digests all work on the delivered bytes; withheld pictures
+ * stay withheld, concealment and the parse routes are as at scale 0.  scale_log2 = 0 launches and delivers what the call did before.
  * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a parse_flags bit that is not defined or
- * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, a format out of range, a flag bit that is not
+ * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, scale_log2 above 3 or reserved2 not 0 in the 64-byte struct, a format out of range, a flag bit that is not
  * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
  * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
  * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
@@ -711,9 +723,12 @@ typedef struct lh264_decode_opts {
   uint32_t reserved0;                   /* (the tail padding of the 48-byte struct: callers of it left it undefined, it is not read) */
   uint32_t parse;                       /* LH264_PARSE_*; 0 = host.  (struct_bytes 40 and 48: host)             */
   uint32_t parse_flags;                 /* LH264_PARSE_FLAG_*; 0 = none.  (struct_bytes 40 and 48: not read)   */
+  uint32_t scale_log2;                  /* 0 = full size; 1..3 = means of 2x2 / 4x4 / 8x8 blocks.  (struct_bytes up to 56: not read, 0) */
+  uint32_t reserved2;                   /* 0                                                                    */
 } lh264_decode_opts_t;
 #define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
 #define LH264_DECODE_OPTS_BYTES_V2 48u  /* the struct before `parse` was added: still accepted                   */
+#define LH264_DECODE_OPTS_BYTES_V3 56u  /* the struct before `scale_log2` was added: still accepted, full size   */
 #define LH264_PARSE_HOST   0u           /* the host front end parses slice data (the default)                    */
 #define LH264_PARSE_DEVICE 1u           /* CAVLC slice data is parsed by slice_parse_kernel, one wave per slice  */
 #define LH264_PARSE_FLAG_CABAC 1u       /* with LH264_PARSE_DEVICE: CABAC slice data too, by slice_parse_cabac_kernel */
@@ -738,6 +753,9 @@ int lh264_decoded_pictures (const lh264_decoded_t* d);
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
 /* macroblocks of delivered picture idx that were concealed (0: the picture is what the stream says; < 0: bad argument) */
 int lh264_decoded_concealed (const lh264_decoded_t* d, int idx);
+/* the cropped window of delivered picture idx before scaling (= its width / height at scale_log2 0); width / height may be NULL.
+ * LH264_E_ARG: a bad index */
+int lh264_decoded_picture_source_size (const lh264_decoded_t* d, int idx, int32_t* width, int32_t* height);
 const uint8_t* lh264_decoded_bytes (const lh264_decoded_t* d, size_t* len);       /* host pointer; NULL in DEVICE_OUT and sink mode */
 const uint8_t* lh264_decoded_bytes_dev (const lh264_decoded_t* d, size_t* len);   /* device pointer in DEVICE_OUT mode, else NULL  */
 /* DEVICE_OUT mode: the stream's bytes copied into the caller's device memory (cap >= their length), complete on return */
@@ -757,14 +775,20 @@ int lh264_decode_last_timing (double* ms);
  * - with LH264_PARSE_FLAG_CABAC - slice_parse_cabac_kernel, the wait for their results) and out[1] the number of slices it parsed, in the last call (0, 0 under LH264_PARSE_HOST) */
 int lh264_decode_last_parse_timing (double* out);
 /* one picture to crop and pack (decode_pack_kernel): the planes' pixel (0,0) in a padded picture, the window, where the packed
- * picture begins.  crop_x/y/w/h are even.  lh264_debug_pack_cpu steps the kernel's code over HOST memory: a check of the crop / format
- * arithmetic where no device is present; not a decode path */
+ * picture begins.  crop_x/y/w/h are even.  `reserved` carries the job's scale_log2: 0 = the copy; 1..3 = the means defined at
+ * lh264_decode_batch (decode_pack_scaled_kernel), the packed picture then has the delivered size; anything else is LH264_E_ARG.
+ * lh264_debug_pack_cpu steps the kernels' code over HOST memory: a check of the crop / format / mean arithmetic where no device is
+ * present; not a decode path */
 typedef struct lh264_pack_job {
   const uint8_t* y; const uint8_t* u; const uint8_t* v;
   uint8_t* dst;
   int32_t stride_y, stride_c, crop_x, crop_y, crop_w, crop_h, format, reserved;
 } lh264_pack_job_t;
 int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
+/* the same jobs on the DEVICE: `jobs` is a host array whose pointers are device pointers.  The table is uploaded, the production kernel
+ * for the jobs' scale_log2 (all equal, else LH264_E_ARG) is launched - decode_pack_kernel at 0, decode_pack_scaled_kernel at 1..3 - and
+ * the call returns when it is through.  Without a device: LH264_E_NODEVICE.  For tests: windows no stream has */
+int lh264_debug_pack_dev (const lh264_pack_job_t* jobs, int n);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

@@ -25,6 +25,8 @@
     python -m losslessh264_amd --decode --sha1 [--nv12] [--conceal METHOD] out_dir in.264...   digests only, no .yuv: out_dir/<name>.sha1
                                                             holds a line `index width height frame_num idr hex` per picture and a last
                                                             line `stream hex`, the SHA-1 of all pictures in order (computed on the device)
+    python -m losslessh264_amd --decode [--sha1] --scale N ...   N = 1 | 2 | 3: reduced-size pictures, the means of 2x2 / 4x4 / 8x8
+                                                            blocks computed on the device (decode_batch (scale=N)); 0 = full size
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -156,10 +158,16 @@ def restore(src, dst):
 
 def decode(argv):
     import losslessh264_amd as lh
-    nv12, conceal, sha1, parse = False, None, False, "host"
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac"):
+    nv12, conceal, sha1, parse, scale = False, None, False, "host", 0
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale"):
         if argv[0] in ("--device-parse", "--device-parse-cabac"):
             parse, argv = ("device" if argv[0] == "--device-parse" else "device+cabac"), argv[1:]
+            continue
+        if argv[0] == "--scale":
+            if len(argv) < 2 or argv[1] not in ("0", "1", "2", "3"):
+                print("--scale: 0 | 1 | 2 | 3")
+                return 2
+            scale, argv = int(argv[1]), argv[2:]
             continue
         if argv[0] == "--nv12":
             nv12, argv = True, argv[1:]
@@ -175,11 +183,11 @@ def decode(argv):
         return 2
     ret = 0
     if sha1:
-        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse):
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

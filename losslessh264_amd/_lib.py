@@ -150,9 +150,13 @@ PARSE_MODES = {"host": (0, 0), "device": (1, 0), "device+cabac": (1, PARSE_FLAG_
 SLICE_PARSE_ON_DEVICE, SLICE_PARSE_CABAC = 1, 2
 PARSE_PATH = {0: "host", 1: "device", 2: "fallback"}
 assert C.sizeof(DecodeOptsV3) == 56
+class DecodeOptsV4(C.Structure):   # the struct as it is now: `scale_log2` behind the 56-byte struct
+    _fields_ = DecodeOptsV3._fields_ + [("scale_log2", C.c_uint32), ("reserved2", C.c_uint32)]
+DECODE_OPTS_BYTES_V3 = 56          # the struct before `scale_log2` (DecodeOptsV3): still accepted, full size
+assert C.sizeof(DecodeOptsV4) == 64
 # LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
 CONCEAL = {"off": 0, "slice_copy": 2, "slice_copy_cross_idr": 4, "slice_copy_cross_idr_freeze": 5, "mv_copy": 6, "mv_copy_freeze": 7}
-class PackJob(C.Structure):
+class PackJob(C.Structure):         # reserved: the job's scale_log2 (0 = the copy, 1..3 = the means)
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("dst", C.c_void_p),
                 ("stride_y", C.c_int32), ("stride_c", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
                 ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32)]
@@ -181,6 +185,8 @@ _SIGS.update({
     "lh264_decode_release": (None, []),
     "lh264_decode_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "lh264_debug_pack_cpu": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_debug_pack_dev": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_decoded_picture_source_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lh264_decoded_picture_sha1": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_decoded_stream_sha1": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lh264_debug_sha1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

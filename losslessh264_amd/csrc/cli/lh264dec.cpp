@@ -17,6 +17,8 @@
 //                                       cropped pictures as I420 (or NV12), appended by a sink run by run (the file's size bounds nothing)
 //   lh264dec --decode --sha1 [--nv12] out_dir a.264 ...   digests only, no .yuv: out_dir/<name>.sha1 with a line `index width height
 //                                       frame_num idr hex` per picture and a last line `stream hex`, the SHA-1 of all of them in order
+//   lh264dec --decode [--sha1] --scale N ...   N = 1 | 2 | 3: reduced-size pictures, the means of 2x2 / 4x4 / 8x8 blocks computed on the
+//                                       device (lh264.h: scale_log2); 0 = full size
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
 #include <stdio.h>
@@ -193,7 +195,7 @@ static int conceal_method (const char* name) {
   for (const auto& e : k) if (!strcmp (name, e.n)) return e.m;
   return -1;
 }
-static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */) {
+static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
   std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
@@ -206,7 +208,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
-  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0;
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale;
   std::vector<lh264_decoded_t*> h (n, nullptr);
   const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
   for (FILE* f : files.f) fclose (f);
@@ -223,13 +225,13 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
 
 // --decode --sha1: one digests-only lh264_decode_batch; no picture leaves the device
 static std::string hex20 (const uint8_t* d) { char b[41]; for (int k = 0; k < 20; k++) snprintf (b + 2 * k, 3, "%02x", d[k]); return std::string (b, 40); }
-static int decode_sha1_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */) {
+static int decode_sha1_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
   std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
   for (int i = 0; i < n; i++) { if (!load (srcs[i], in[i])) { perror (srcs[i].c_str()); return 2; } d[i] = in[i].data(); l[i] = in[i].size(); }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
-  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0;
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
   const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
@@ -283,7 +285,7 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, first = 2;
+    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, first = 2;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
       else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
@@ -293,15 +295,19 @@ int main (int argc, char** argv) {
         conceal = conceal_method (argv[first + 1]);
         if (conceal < 0) { fprintf (stderr, "--conceal: off | slice_copy | slice_copy_cross_idr | slice_copy_cross_idr_freeze | mv_copy | mv_copy_freeze\n"); return 2; }
         first += 2;
+      } else if (first + 1 < argc && !strcmp (argv[first], "--scale")) {
+        if (strlen (argv[first + 1]) != 1 || argv[first + 1][0] < '0' || argv[first + 1][0] > '3') { fprintf (stderr, "--scale: 0 | 1 | 2 | 3\n"); return 2; }
+        scale = argv[first + 1][0] - '0';
+        first += 2;
       } else break;
     }
-    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD] [--scale N] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
-    return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse) : decode_files (argv[first], srcs, nv12, conceal, device_parse);
+    return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD] [--scale N] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

@@ -110,6 +110,133 @@ __host__ __device__ inline void pack_band (const lh264_pack_job_t& j, int band, 
   }
 }
 
+// ---- the reduced-size pack step: scale_log2 = s in 1..3, B = 1 << s (the definition: include/lh264.h at lh264_decode_batch) ---------
+// A plane of w x h window samples is delivered as pw x ph means of B x B blocks, pw = ceil (w / B) for chroma and twice the chroma
+// size for luma; block coordinates are clamped to the WINDOW.  The bands are 16 DELIVERED luma rows (and their 8 chroma rows), the
+// pieces 4 bytes of the destination counted from the aligned address at or below the row's first byte: a whole piece whose 4 blocks
+// lie inside the window is one aligned 4-byte store fed by B unaligned loads of 4 * B bytes; heads, tails and pieces whose blocks
+// cross the window's right or bottom edge go sample by sample through the clamped rule.  Byte sums are 4-byte dot products against
+// 0x01 masks; the largest sum is 64 * 255.  No LDS; no byte outside the window is read, none outside the picture's bytes written.
+
+// the delivered luma size of a w x h window (both even) at scale s (0..3); the chroma planes are half of it each way
+__host__ __device__ inline void scaled_size (int w, int h, int s, int* ow, int* oh) {
+  const int B = 1 << s;
+  *ow = s ? 2 * (((w >> 1) + B - 1) >> s) : w;
+  *oh = s ? 2 * (((h >> 1) + B - 1) >> s) : h;
+}
+
+// acc + the bytes of x that mask picks (0x01 per byte)
+__host__ __device__ inline uint32_t byte_sum (uint32_t x, uint32_t mask, uint32_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_udot4 (x, mask, acc, false);
+#else
+  for (int k = 0; k < 4; k++) acc += (x >> (8 * k) & 0xffu) * (mask >> (8 * k) & 1u);
+  return acc;
+#endif
+}
+
+// N (2 or 4) neighbouring means whose blocks lie inside the window: B rows of N * B bytes from p -> mean k in byte k
+template <int S, int N>
+__host__ __device__ inline uint32_t means_whole (const uint8_t* p, int stride) {
+  constexpr int B = 1 << S, W = N * B / 4;
+  uint32_t acc[N];
+  for (int k = 0; k < N; k++) acc[k] = 0;
+  for (int r = 0; r < B; r++) {
+    uint32_t x[W];
+    __builtin_memcpy (x, p + (size_t)r * stride, W * 4);
+    if constexpr (S == 1) {
+      for (int k = 0; k < N / 2; k++) { acc[2 * k] = byte_sum (x[k], 0x00000101u, acc[2 * k]); acc[2 * k + 1] = byte_sum (x[k], 0x01010000u, acc[2 * k + 1]); }
+    } else {
+      for (int k = 0; k < N; k++) for (int q = 0; q < B / 4; q++) acc[k] = byte_sum (x[k * (B / 4) + q], 0x01010101u, acc[k]);
+    }
+  }
+  uint32_t o = 0;
+  for (int k = 0; k < N; k++) o |= ((acc[k] + (1u << (2 * S - 1))) >> (2 * S)) << (8 * k);
+  return o;
+}
+// the mean at (X, Y) by the definition: a plane whose window of w x h samples begins at p
+template <int S>
+__host__ __device__ inline uint8_t mean_clamped (const uint8_t* p, int stride, int w, int h, int X, int Y) {
+  constexpr int B = 1 << S;
+  uint32_t sum = 0;
+  for (int j = 0; j < B; j++) {
+    const int y = Y * B + j < h - 1 ? Y * B + j : h - 1;
+    const uint8_t* row = p + (size_t)y * stride;
+    for (int i = 0; i < B; i++) sum += row[X * B + i < w - 1 ? X * B + i : w - 1];
+  }
+  return (uint8_t) ((sum + (1u << (2 * S - 1))) >> (2 * S));
+}
+
+// piece p of delivered row Y (pw bytes at d) of one plane (window w x h at src)
+template <int S>
+__host__ __device__ inline void piece_means (uint8_t* d, const uint8_t* src, int stride, int w, int h, int pw, int Y, int p) {
+  constexpr int B = 1 << S;
+  int a = p * 4 - (int) ((uintptr_t)d & 3u), b = a + 4;
+  if (a >= 0 && b <= pw && b * B <= w && (Y + 1) * B <= h) {
+    * (uint32_t*) (d + a) = means_whole<S, 4> (src + (size_t)Y * B * stride + a * B, stride);
+    return;
+  }
+  if (a < 0) a = 0;
+  if (b > pw) b = pw;
+  for (int k = a; k < b; k++) d[k] = mean_clamped<S> (src, stride, w, h, k, Y);
+}
+// piece p of delivered NV12 chroma row Y (ow bytes at d): the Cb and Cr means (windows cw x ch at u and v) interleaved
+template <int S>
+__host__ __device__ inline void piece_means_interleave (uint8_t* d, const uint8_t* u, const uint8_t* v, int stride, int cw, int ch, int ow, int Y, int p) {
+  constexpr int B = 1 << S;
+  int a = p * 4 - (int) ((uintptr_t)d & 3u), b = a + 4;
+  if (a >= 0 && b <= ow && !(a & 1) && (b >> 1) * B <= cw && (Y + 1) * B <= ch) {
+    const size_t at = (size_t)Y * B * stride + (a >> 1) * B;
+    * (uint32_t*) (d + a) = interleave_lo (means_whole<S, 2> (u + at, stride), means_whole<S, 2> (v + at, stride));
+    return;
+  }
+  if (a < 0) a = 0;
+  if (b > ow) b = ow;
+  for (int k = a; k < b; k++) d[k] = mean_clamped<S> ((k & 1) ? v : u, stride, cw, ch, k >> 1, Y);
+}
+
+template <int S>
+__host__ __device__ inline void pack_band_scaled_by (const lh264_pack_job_t& j, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h, cw = w >> 1, ch = h >> 1;
+  int ow, oh;
+  scaled_size (w, h, S, &ow, &oh);
+  const int ocw = ow >> 1, och = oh >> 1;
+  const int r0 = band * kBandRows, r1 = r0 + kBandRows < oh ? r0 + kBandRows : oh;
+  if (r1 > r0) {
+    const int pieces = (ow + 6) >> 2, items = (r1 - r0) * pieces;
+    const uint8_t* s = j.y + (size_t)j.crop_y * j.stride_y + j.crop_x;
+    for (int it = t; it < items; it += nt) {
+      const int r = r0 + it / pieces, p = it % pieces;
+      piece_means<S> (j.dst + (size_t)r * ow, s, j.stride_y, w, h, ow, r, p);
+    }
+  }
+  const int c0 = band * (kBandRows / 2), c1 = c0 + kBandRows / 2 < och ? c0 + kBandRows / 2 : och;
+  if (c1 <= c0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  uint8_t* dc = j.dst + (size_t)ow * oh;
+  if (j.format == LH264_FMT_NV12) {
+    const int pieces = (ow + 6) >> 2, items = (c1 - c0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = c0 + it / pieces, p = it % pieces;
+      piece_means_interleave<S> (dc + (size_t)r * ow, j.u + co, j.v + co, j.stride_c, cw, ch, ow, r, p);
+    }
+  } else {
+    const int pieces = (ocw + 6) >> 2, per_plane = (c1 - c0) * pieces;
+    for (int it = t; it < 2 * per_plane; it += nt) {
+      const int plane = it >= per_plane, q = it - plane * per_plane;
+      const int r = c0 + q / pieces, p = q % pieces;
+      piece_means<S> (dc + (size_t)plane * ocw * och + (size_t)r * ocw, (plane ? j.v : j.u) + co, j.stride_c, cw, ch, ocw, r, p);
+    }
+  }
+}
+// band `band` (of DELIVERED rows) of one job whose `reserved` word is its scale_log2 (1..3; anything else: nothing is done),
+// worked on by item t of nt (the host steps it with t = 0, nt = 1)
+__host__ __device__ inline void pack_band_scaled (const lh264_pack_job_t& j, int band, int t, int nt) {
+  if (j.reserved == 1) pack_band_scaled_by<1> (j, band, t, nt);
+  else if (j.reserved == 2) pack_band_scaled_by<2> (j, band, t, nt);
+  else if (j.reserved == 3) pack_band_scaled_by<3> (j, band, t, nt);
+}
+
 }  // namespace lh264pack
 
 // one workgroup per (picture, band)
@@ -117,6 +244,15 @@ __global__ void __launch_bounds__ (256) decode_pack_kernel (const lh264_pack_job
   const lh264_pack_job_t j = jobs[blockIdx.x];
   if ((int)blockIdx.y * lh264pack::kBandRows >= j.crop_h) return;
   lh264pack::pack_band (j, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+// one workgroup per (picture, band of 16 delivered luma rows): the jobs of a launch share one scale_log2 in 1..3
+__global__ void __launch_bounds__ (256) decode_pack_scaled_kernel (const lh264_pack_job_t* __restrict__ jobs) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.reserved < 1 || j.reserved > 3) return;
+  int ow, oh;
+  lh264pack::scaled_size (j.crop_w, j.crop_h, j.reserved, &ow, &oh);
+  if ((int)blockIdx.y * lh264pack::kBandRows >= oh) return;
+  lh264pack::pack_band_scaled (j, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
@@ -133,6 +269,7 @@ struct lh264_decoded {
   std::string error;
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
+  std::vector<int32_t> source_wh;               // per picture: width, height of its cropped window before scaling
   int parse_path = LH264_PARSE_PATH_HOST;
   long device_cabac_slices = 0;                 // ... of them CABAC slices (slice_parse_cabac_kernel)
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
@@ -271,7 +408,7 @@ struct RoundChain {
   DStream* s = nullptr;
   int first_picture = 0;
   std::vector<lh264_decoded_pic_t> pics;
-  std::vector<int32_t> concealed;
+  std::vector<int32_t> concealed, source_wh;
   size_t at = 0, bytes = 0;                          // in the round's output buffer
   size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
 };
@@ -303,10 +440,37 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n) {
   for (int k = 0; k < n; k++) {
     const lh264_pack_job_t& j = jobs[k];
     if (!j.y || !j.u || !j.v || !j.dst || j.crop_w <= 0 || j.crop_h <= 0 || ((j.crop_w | j.crop_h | j.crop_x | j.crop_y) & 1) || j.crop_x < 0 || j.crop_y < 0 ||
-        (j.format != LH264_FMT_I420 && j.format != LH264_FMT_NV12)) return LH264_E_ARG;
-    for (int band = 0; band * lh264pack::kBandRows < j.crop_h; band++) lh264pack::pack_band (j, band, 0, 1);
+        (j.format != LH264_FMT_I420 && j.format != LH264_FMT_NV12) || j.reserved < 0 || j.reserved > 3) return LH264_E_ARG;
+    if (!j.reserved) { for (int band = 0; band * lh264pack::kBandRows < j.crop_h; band++) lh264pack::pack_band (j, band, 0, 1); continue; }
+    int ow, oh;
+    lh264pack::scaled_size (j.crop_w, j.crop_h, j.reserved, &ow, &oh);
+    for (int band = 0; band * lh264pack::kBandRows < oh; band++) lh264pack::pack_band_scaled (j, band, 0, 1);
   }
   return LH264_OK;
+}
+
+int lh264_debug_pack_dev (const lh264_pack_job_t* jobs, int n) {
+  if (!jobs || n < 0) return LH264_E_ARG;
+  int max_bands = 0;
+  for (int k = 0; k < n; k++) {
+    const lh264_pack_job_t& j = jobs[k];
+    if (!j.y || !j.u || !j.v || !j.dst || j.crop_w <= 0 || j.crop_h <= 0 || ((j.crop_w | j.crop_h | j.crop_x | j.crop_y) & 1) || j.crop_x < 0 || j.crop_y < 0 ||
+        (j.format != LH264_FMT_I420 && j.format != LH264_FMT_NV12) || j.reserved < 0 || j.reserved > 3 || j.reserved != jobs[0].reserved) return LH264_E_ARG;
+    int ow, oh;
+    lh264pack::scaled_size (j.crop_w, j.crop_h, j.reserved, &ow, &oh);
+    max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows);
+  }
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  if (!n) return LH264_OK;
+  lh264_pack_job_t* d_jobs = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_pack_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_pack_job_t), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    if (jobs[0].reserved) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n, (unsigned)max_bands), dim3 (256), 0, 0, d_jobs);
+    else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n, (unsigned)max_bands), dim3 (256), 0, 0, d_jobs);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs);
+  return ok ? LH264_OK : LH264_E_HIP;
 }
 
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
@@ -361,15 +525,18 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
                ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
   const int conceal = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V2 ? (int)opts->conceal : 0;
-  const uint32_t parse = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? opts->parse : LH264_PARSE_HOST;
+  const uint32_t parse = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V3 ? opts->parse : LH264_PARSE_HOST;
   if (parse != LH264_PARSE_HOST && parse != LH264_PARSE_DEVICE) return LH264_E_ARG;
-  const uint32_t parse_flags = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t) ? opts->parse_flags : 0;
+  const uint32_t parse_flags = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V3 ? opts->parse_flags : 0;
   if ((parse_flags & ~LH264_PARSE_FLAG_CABAC) || (parse_flags && parse != LH264_PARSE_DEVICE)) return LH264_E_ARG;
+  const bool opts_v4 = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t);
+  if (opts_v4 && (opts->scale_log2 > 3 || opts->reserved2 != 0)) return LH264_E_ARG;
+  const int scale = opts_v4 ? (int)opts->scale_log2 : 0;      // 0: decode_pack_kernel, as ever; 1..3: decode_pack_scaled_kernel
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -492,6 +659,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         }
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
+        r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
         if (sha) take_digests (c, r, (int)k);
       }
     } else {
@@ -502,6 +670,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         if (!device_out && !no_pictures) r.bytes.insert (r.bytes.end(), hb + c.at, hb + c.at + c.bytes);
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
+        r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
         if (sha) take_digests (c, r, k);
       });
     }
@@ -682,7 +851,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { bytes += (size_t)f->crop_w * f->crop_h * 3 / 2; shown++; } }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::scaled_size (f->crop_w, f->crop_h, scale, &ow, &oh); bytes += (size_t)ow * oh * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -775,16 +944,20 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         jb.flags = f.is_ref ? 0 : LH264_JOB_NO_EXPAND;
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
+        pj.reserved = scale;
         if (f.frozen) { if (!on_dev) mo += nm; so += f.slices.size(); j++; continue; }      // withheld: a reference like any other, but no window to pack (crop_h 0)
         pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
         pj.dst = d_out + at;
         pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
         pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
-        const size_t bytes = (size_t)f.crop_w * f.crop_h * 3 / 2;
+        int ow, oh;
+        lh264pack::scaled_size (f.crop_w, f.crop_h, scale, &ow, &oh);      // what is delivered
+        const size_t bytes = (size_t)ow * oh * 3 / 2;
         lh264_decoded_pic_t dp;
-        dp.width = f.crop_w; dp.height = f.crop_h; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
+        dp.width = ow; dp.height = oh; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
         rc.pics.push_back (dp);
         rc.concealed.push_back (f.concealed);
+        rc.source_wh.push_back (f.crop_w); rc.source_wh.push_back (f.crop_h);
         at += bytes; off += bytes;
         if (!on_dev) mo += nm;
         so += f.slices.size(); j++;
@@ -812,7 +985,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     }
     for (int c = 0; c < n_chains; c++) {
       DStream& s = *rd.chains[c].s;
-      for (auto& f : s.sel) max_bands = std::max (max_bands, (f->crop_h + lh264pack::kBandRows - 1) / lh264pack::kBandRows);
+      for (auto& f : s.sel) { int ow, oh; lh264pack::scaled_size (f->crop_w, f->crop_h, scale, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
       // the slots the round leaves free: pictures the DPB behind the round's last picture does not hold
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
       for (Slot& sl : s.pool) if (sl.pic_id >= 0 && std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end()) sl.pic_id = -1;
@@ -832,7 +1005,11 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
                 (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
-      if (ok) { hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>()); ok = hipGetLastError() == hipSuccess; }
+      if (ok) {
+        if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
+        else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
+        ok = hipGetLastError() == hipSuccess;
+      }
       if (ok && sha) {
         ok = up (A.d_sjobs, A.h_sjobs[rb].p, n_sjobs * sizeof (lh264_sha1_job_t));
         if (ok && n_sjobs) { hipLaunchKernelGGL (sha1_spans_kernel, dim3 ((unsigned) ((n_sjobs + 63) / 64)), dim3 (64), 0, st, A.d_sjobs.as<lh264_sha1_job_t>(), (int)n_sjobs); ok = hipGetLastError() == hipSuccess; }
@@ -929,6 +1106,12 @@ int lh264_decoded_stream_sha1 (const lh264_decoded_t* d, uint8_t out[20]) {
   if (d->status == LH264_E_HIP) return d->status;
   if (!(d->sha & LH264_DECODE_SHA1_STREAM)) return LH264_E_ARG;
   memcpy (out, d->stream_sha, 20);
+  return LH264_OK;
+}
+int lh264_decoded_picture_source_size (const lh264_decoded_t* d, int idx, int32_t* width, int32_t* height) {
+  if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->source_wh.size() != d->pics.size() * 2) return LH264_E_ARG;
+  if (width) *width = d->source_wh[(size_t)idx * 2];
+  if (height) *height = d->source_wh[(size_t)idx * 2 + 1];
   return LH264_OK;
 }
 int lh264_decoded_concealed (const lh264_decoded_t* d, int idx) {

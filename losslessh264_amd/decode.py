@@ -62,6 +62,15 @@ class DecodedBatch:
         """per delivered picture of stream i: the number of its macroblocks that were concealed (all 0 without conceal=)"""
         return [self._lib.lh264_decoded_concealed(self._h[i], k) for k in range(self._lib.lh264_decoded_pictures(self._h[i]))]
 
+    def source_sizes(self, i):
+        """[(width, height)] per delivered picture of stream i: its cropped window before scaling (= its size with scale=0)"""
+        out = []
+        w, h = C.c_int32(0), C.c_int32(0)
+        for k in range(self._lib.lh264_decoded_pictures(self._h[i])):
+            L.check(self._lib.lh264_decoded_picture_source_size(self._h[i], k, C.byref(w), C.byref(h)))
+            out.append((w.value, h.value))
+        return out
+
     def picture_sha1(self, i):
         """sha1="pictures" | "both": the SHA-1 of every delivered picture of stream i, as delivered (20-byte bytes objects)"""
         out = []
@@ -118,7 +127,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host"):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -133,8 +142,17 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     reference's decoder test keeps per stream).  pictures=False (with sha1): digests only, no picture leaves the device.
     parse: "host" (the default) | "device": CAVLC slice data is parsed on the device by slice_parse_kernel, one wave per slice; the host
     walks headers only.  "device+cabac": CABAC slice data as well, by slice_parse_cabac_kernel, so that a stream stays on the device route
-    through its CABAC pictures.  The bytes are the same; DecodedBatch.parse_path(i) tells the route each stream took."""
+    through its CABAC pictures.  The bytes are the same; DecodedBatch.parse_path(i) tells the route each stream took.
+    scale: 0 (full size) | 1 | 2 | 3 = s: reduced-size pictures, averaged on the device (decode_pack_scaled_kernel).  B = 1 << s.  For a
+    picture whose cropped window is w x h (both even), cw = w / 2 and ch = h / 2: the delivered chroma size is ocw = ceil (cw / B),
+    och = ceil (ch / B), the delivered luma size ow = 2 * ocw, oh = 2 * och.  Delivered luma sample (X, Y) =
+    (sum + (1 << (2*s - 1))) >> (2*s), sum over the B x B window samples at x = min (X*B + i, w - 1), y = min (Y*B + j, h - 1),
+    0 <= i, j < B; Cb and Cr: the same rule on their cw x ch planes.  Coordinates are clamped to the cropped window, never to the padded
+    picture.  The planes are averaged independently; chroma siting is not modelled.  Packing as ever with ow, oh in place of w, h;
+    DecodedBatch.pictures describes what is delivered, source_sizes the windows before scaling.  QCIF at scale=3: 22 x 18, 594 bytes."""
     lib = L.lib()
+    if scale not in (0, 1, 2, 3) or isinstance(scale, bool):
+        raise ValueError("scale must be 0, 1, 2 or 3")
     if fmt not in _FORMATS:
         raise ValueError("fmt must be 'i420' or 'nv12'")
     if conceal is not None and conceal not in L.CONCEAL:
@@ -149,8 +167,9 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
     lens = (C.c_size_t * n)(*[len(d) for d in keep])
-    opts = L.DecodeOptsV3()
-    opts.struct_bytes = C.sizeof(L.DecodeOptsV3)
+    opts = L.DecodeOptsV4()
+    opts.struct_bytes = C.sizeof(L.DecodeOptsV4)
+    opts.scale_log2 = int(scale)
     opts.parse, opts.parse_flags = L.PARSE_MODES[parse]
     opts.format = _FORMATS[fmt]
     opts.flags = (L.DECODE_DEVICE_OUT if device_out else 0) | _SHA1[sha1] | (0 if pictures else L.DECODE_NO_PICTURES)
@@ -186,9 +205,9 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0):
     """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
-    pictures, bytes)]"""
+    pictures, bytes)]; scale as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     names = [os.path.join(out_dir, os.path.basename(p) + ".yuv") for p in paths]
@@ -200,7 +219,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale)
     finally:
         for f in files:
             f.close()
@@ -209,12 +228,12 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host"):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
-    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]"""
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale as in decode_batch (the digests are of the delivered bytes)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale)
     res = []
     try:
         for i, p in enumerate(paths):

@@ -3,9 +3,10 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
+--scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
 
 One JSON line per measurement."""
@@ -35,6 +36,10 @@ def main(argv):
     if "--parse" in argv:
         parse = argv[argv.index("--parse") + 1]
         args.remove(parse)
+    scale = {}
+    if "--scale" in argv:
+        scale = {"scale": int(argv[argv.index("--scale") + 1])}
+        args.remove(argv[argv.index("--scale") + 1])
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
     data = open(path, "rb").read()
@@ -46,9 +51,9 @@ def main(argv):
         for r in range(runs):
             t0 = time.perf_counter()
             if mode == "digests":
-                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse)
+                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse, **scale)
             else:
-                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse)
+                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse, **scale)
             dt = time.perf_counter() - t0
             ms = (C.c_double * 6)()
             lib.lh264_decode_last_timing(ms)
@@ -65,7 +70,7 @@ def main(argv):
                                   output_MB=round(out_bytes / 1e6, 1), failed=len(bad),
                                   ms={"call": round(ms[0], 1), "parse": round(ms[1], 1), "staging": round(ms[2], 1), "enqueue": round(ms[3], 1),
                                       "wait_device": round(ms[4], 1), "delivery": round(ms[5], 1)},
-                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **extra, **route)), flush=True)
+                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **extra, **route, **scale)), flush=True)
     for r in range(runs if "parse" in modes else 0):
         dt, pics = lh.parse_batch_time(datas, threads=0, keep=False)
         print(json.dumps(dict(base, what="parse_batch_discard", run=r, seconds=round(dt, 4), MBps=round(mb / dt, 1), pictures_per_s=round(pics / dt))), flush=True)
