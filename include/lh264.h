@@ -205,7 +205,11 @@ typedef struct lh264_ctx_sym {
   uint32_t prior;     /* flat index into the table selected by `kind`                                  */
   int16_t  value;     /* the integer that is coded with that prior                                     */
   uint8_t  kind;      /* LH264_SYM_*                                                                   */
-  uint8_t  pad;
+  uint8_t  pad;       /* the tag the symbol's decisions are billed to (billing.h:6-55), part of the symbol: the coder takes a nonzero
+                         pad as it stands.  lh264_ctx_index_chains writes 17 for LUMA_DC, 18 for CHROMA_DC; for NZ4/NZ8 29 in a chroma
+                         block and 19 in a luma block; for AC4/AC8 29 in a chroma block, 19 for the first coefficient symbol of a luma
+                         block whose macroblock is not Intra16x16, and 24 for every other luma one.  0 = not given: the coder then
+                         takes the tag of a coefficient symbol out of `prior`                                          */
 } lh264_ctx_sym_t;
 enum { LH264_SYM_LUMA_DC = 0, LH264_SYM_CHROMA_DC = 1, LH264_SYM_NZ4 = 2, LH264_SYM_AC4 = 3, LH264_SYM_NZ8 = 4, LH264_SYM_AC8 = 5,
        /* the non-coefficient syntax symbols (row a10), produced by the host front end; for these `prior` is
@@ -245,9 +249,12 @@ typedef struct lh264_ctx_job {
   int32_t  mb_w, mb_h;
   /* COMPACT layout (ABI 3; sym_off_dev != NULL): the jobs of a call share ONE pool of symbols - syms_dev is the pool's first symbol in
    * every job, syms_cap its size in symbols -, macroblock k of this picture lies at syms_dev[*sym_base_dev + sym_off_dev[k]].  Both
-   * are WRITTEN by the call (a count pass over the levels: 8 bytes per coded symbol, a macroblock's run padded to a multiple of 8
-   * symbols = a 64-byte line, instead of 3,456 bytes per macroblock).  The pool is
-   * sized from lh264_ctx_count_chains; a pool that is too small is not written to (every n_syms reads 0, *total_dev tells the need). */
+   * are WRITTEN by the call (a count pass over the levels: 8 bytes per coded symbol instead of 3,456 bytes per macroblock).  The
+   * offsets are DENSE: sym_off_dev[k] is the sum of n_syms of the picture's macroblocks before k, *sym_base_dev the sum over the
+   * compact jobs before this one (a job in the fixed layout counts as 0); there is no padding between runs.  The pool is sized from
+   * lh264_ctx_count_chains.  Where it is too small, nothing at or beyond syms_cap symbols is written: a macroblock whose run ends at or
+   * before syms_cap is written whole with its n_syms, every other macroblock writes nothing and reads n_syms 0; sym_off, *sym_base and
+   * the *total_dev of the count call still tell the need. */
   uint32_t*            sym_off_dev;   /* mb_w*mb_h offsets (symbols) behind the picture's first symbol              */
   uint64_t*            sym_base_dev;  /* this picture's first symbol in the pool (one word per job)                 */
   uint64_t             syms_cap;      /* symbols there is room for at syms_dev                                      */

@@ -117,7 +117,7 @@ class CtxSession:
         ns = self.d_nsyms[g:g + n].cpu().numpy().view(np.uint16)
         off = self.d_symoff[g:g + n].cpu().numpy().view(np.uint32).astype(np.int64)
         base = int(self.d_symbase[self.job_of[(chain, frame)]].item())
-        tot = int(off[-1] + ns[-1]) if n else 0          # (every macroblock's run starts on a multiple of 8 symbols)
+        tot = int(off[-1] + ns[-1]) if n else 0          # (dense offsets: a macroblock's run starts where its predecessor's ends)
         pool = self.d_syms[base * 8:(base + tot) * 8].cpu().numpy().view(L.CTX_SYM_DTYPE)
         sy = np.zeros((n, L.CTX_MAX_SYMS), dtype=L.CTX_SYM_DTYPE)
         for k in range(n):
