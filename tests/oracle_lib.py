@@ -29,6 +29,8 @@ def lib():
                                          C.c_int, C.c_int, C.c_int]
         _lib.orc_recon_frame.restype = None
         _lib.orc_luma_dc_qmul.restype = C.c_int
+        _lib.orc_deblock_trace.argtypes = [C.c_void_p, C.c_int]
+        _lib.orc_deblock_trace.restype = None
     return _lib
 
 
@@ -87,6 +89,34 @@ def recon_frame(mbs, coeffs, slices, dst, refs, flags=0):
 
 
 NO_EXPAND, NO_DEBLOCK = 1, 2
+
+# orc_dbk_rec_t (oracle/oracle_recon.h): one line handed to an edge filter; before / after = p3 p2 p1 p0 q0 q1 q2 q3
+DBK_REC_DTYPE = np.dtype([("mb", "<i4"), ("x", "<i2"), ("y", "<i2"), ("plane", "u1"), ("dir", "u1"), ("edge", "u1"), ("bs", "u1"),
+                          ("alpha", "<i2"), ("beta", "<i2"), ("tc", "<i2"), ("idx_a", "<i2"), ("idx_b", "<i2"), ("idx_tc", "<i2"),
+                          ("before", "u1", 8), ("after", "u1", 8)])
+
+
+class TraceOverflow(Exception):
+    pass
+
+
+def recon_frame_traced(mbs, coeffs, slices, dst, refs, flags=0, cap=None):
+    """recon_frame with the filter's trace on -> the records (DBK_REC_DTYPE) in the order of filtering.  cap: records the buffer
+    holds (default: every line of every edge of the picture); more than that raises TraceOverflow."""
+    L = lib()
+    if cap is None:
+        cap = dst.mb_w * dst.mb_h * 2 * (4 * 16 + 2 * 2 * 8)
+    buf = np.zeros(cap + 1, dtype=DBK_REC_DTYPE)          # (one record of guard: it must stay zero)
+    L.orc_deblock_trace(buf.ctypes.data_as(C.c_void_p), cap)
+    try:
+        recon_frame(mbs, coeffs, slices, dst, refs, flags)
+        n, over = L.orc_deblock_trace_count(), L.orc_deblock_trace_overflow()
+    finally:
+        L.orc_deblock_trace(None, 0)
+    assert 0 <= n <= cap and not buf[cap:].tobytes().strip(b"\0"), "the trace wrote past its buffer"
+    if over:
+        raise TraceOverflow("more than %d records" % cap)
+    return buf[:n].copy()
 
 
 # ---- context-model oracle (oracle/oracle_model.c) ---------------------------------------------------------------

@@ -298,13 +298,46 @@ def _bs_thresholds(orc, ref, h):
             _agree(h, a.plane(p), b.plane(p) if ref else None, (c.name, p))
 
 
+def _deblock_directed(orc, ref, h):
+    """the directed filter pictures of tests/deblock_directed.py (thresholds, table entries, the three QP lookups, the stale tc0, short
+    cuts, order, slices): the unfiltered picture of each, filtered by the oracle's and by the reference's macroblock drivers"""
+    import deblock_directed as DD
+    n = 0
+    for fam, scenes in DD.families().items():
+        for s in scenes:
+            frames = s.frames()
+            pics = {}
+            for f in frames:
+                refs = [pics[r] for r in f.ref_ids]
+                pics[f.id] = O.HostPic(f.mb_w, f.mb_h)
+                O.recon_frame(f.mbs, f.coeffs, f.slices, pics[f.id], refs, 0)
+                a = O.HostPic(f.mb_w, f.mb_h)
+                O.recon_frame(f.mbs, f.coeffs, f.slices, a, refs, O.NO_DEBLOCK | O.NO_EXPAND)
+                b = O.HostPic(f.mb_w, f.mb_h)
+                b.buf[:] = a.buf
+                mbs = np.ascontiguousarray(f.mbs); sl = np.ascontiguousarray(f.slices)
+                sa = a.struct()
+                for si in range(len(sl)):
+                    orc.orc_deblock_slice(_p(mbs), _p(sl), si, C.byref(sa), f.mb_w, f.mb_h)
+                for p in range(3):
+                    assert np.array_equal(a.plane(p), pics[f.id].plane(p)), (s.name, f.id, p)   # slice by slice == the frame driver
+                if ref:
+                    sb = b.struct()
+                    ref.refk_deblock_picture(_p(mbs), _p(sl), f.mb_w, f.mb_h, C.c_void_p(sb.y), C.c_void_p(sb.u), C.c_void_p(sb.v), sb.stride_y, sb.stride_c)
+                for p in range(3):
+                    _agree(h, a.plane(p), b.plane(p) if ref else None, (s.name, f.id, p))
+                n += 1
+    return n
+
+
 INTRA_PRED = [("pred4x4", 14, 4), ("pred16x16", 7, 16), ("predc8x8", 7, 8)]
 # digest name -> (case, its arguments): what tests/golden/make_golden_ref_kernels.py runs against the reference
 CASES = {"idct4x4": (_idct4x4, ()), "idct8x8": (_idct8x8, ()), "dc_transforms": (_dc_transforms, ()),
          **{"intra_pred[%s]" % k[0]: (_intra_pred, k) for k in INTRA_PRED}, "intra_pred8x8l": (_intra_pred8x8l, ()), "mc": (_mc, ()),
          "deblock_edge_filters": (_deblock_edge_filters, ()), "deblock_macroblock_drivers": (_deblock_macroblock_drivers, ()),
          "expand": (_expand, ()),
-         "luma_dc_scaling_list": (_luma_dc_scaling_list, ()), "weight_prediction": (_weight_prediction, ()), "bs_thresholds": (_bs_thresholds, ())}
+         "luma_dc_scaling_list": (_luma_dc_scaling_list, ()), "weight_prediction": (_weight_prediction, ()), "bs_thresholds": (_bs_thresholds, ()),
+         "deblock_directed": (_deblock_directed, ())}
 
 
 # ---- the tests ------------------------------------------------------------------------------------------------------------------------
@@ -361,3 +394,7 @@ def test_weight_prediction():
 
 def test_bs_thresholds():
     _check("bs_thresholds", _bs_thresholds)
+
+
+def test_deblock_directed():
+    assert _check("deblock_directed", _deblock_directed) > 300

@@ -72,22 +72,43 @@ def _run(frames):
             assert np.array_equal(got[p], ref), "frame %d plane %d: %d samples differ" % (i, p, int(np.count_nonzero(got[p] != ref)))
 
 
-@pytest.mark.parametrize("seed", [101, 102, 103])
-def test_sub_partitions(seed):
-    _run(_to_sub_partitions(synth.make_stream(seed=seed, mb_w=9, mb_h=7, n_frames=4), seed))
+# the streams of the tests below (tests/test_deblock_directed.py counts what their filter lines reach)
+SUB_PARTITION_SEEDS, SUB_PARTITION_WEIGHTED_SEEDS, WEIGHTED_SEEDS = [101, 102, 103], [111, 112], [121, 122]
+CHROMA_QP_CASES = [(131, (6, 6)), (132, (-6, 4)), (133, (4, -6))]
 
 
-@pytest.mark.parametrize("seed", [111, 112])
-def test_sub_partitions_weighted(seed):
-    _run(_to_sub_partitions(synth.make_stream(seed=seed, mb_w=8, mb_h=6, n_frames=4, weighted=True), seed))
+def sub_partition_stream(seed):
+    return _to_sub_partitions(synth.make_stream(seed=seed, mb_w=9, mb_h=7, n_frames=4), seed)
 
 
-@pytest.mark.parametrize("seed", [121, 122])
-def test_weighted_prediction(seed):
-    _run(synth.make_stream(seed=seed, mb_w=11, mb_h=9, n_frames=4, weighted=True, density=0.2))
+def sub_partition_weighted_stream(seed):
+    return _to_sub_partitions(synth.make_stream(seed=seed, mb_w=8, mb_h=6, n_frames=4, weighted=True), seed)
 
 
-@pytest.mark.parametrize("seed,offsets", [(131, (6, 6)), (132, (-6, 4)), (133, (4, -6))])
-def test_chroma_qp_and_filter_offsets(seed, offsets):
+def weighted_stream(seed):
+    return synth.make_stream(seed=seed, mb_w=11, mb_h=9, n_frames=4, weighted=True, density=0.2)
+
+
+def chroma_qp_stream(seed, offsets):
     frames = synth.make_stream(seed=seed, mb_w=10, mb_h=8, n_frames=3, t8=(seed % 2 == 0), pcm=(seed == 133))
-    _run(_chroma_qp_spread(frames, seed, offsets))
+    return _chroma_qp_spread(frames, seed, offsets)
+
+
+@pytest.mark.parametrize("seed", SUB_PARTITION_SEEDS)
+def test_sub_partitions(seed):
+    _run(sub_partition_stream(seed))
+
+
+@pytest.mark.parametrize("seed", SUB_PARTITION_WEIGHTED_SEEDS)
+def test_sub_partitions_weighted(seed):
+    _run(sub_partition_weighted_stream(seed))
+
+
+@pytest.mark.parametrize("seed", WEIGHTED_SEEDS)
+def test_weighted_prediction(seed):
+    _run(weighted_stream(seed))
+
+
+@pytest.mark.parametrize("seed,offsets", CHROMA_QP_CASES)
+def test_chroma_qp_and_filter_offsets(seed, offsets):
+    _run(chroma_qp_stream(seed, offsets))
