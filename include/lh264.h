@@ -703,8 +703,25 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * what is delivered, lh264_decoded_picture_source_size gives the window before scaling.  QCIF at s = 3: 22 x 18, 594 bytes.  The round's
  * output buffers, the download, the handles, the sink, DEVICE_OUT and the digests all work on the delivered bytes; withheld pictures
  * stay withheld, concealment and the parse routes are as at scale 0.  scale_log2 = 0 launches and delivers what the call did before.
+ * opts->pick = LH264_PICK_INTRA or LH264_PICK_IDR (the 72-byte struct; struct_bytes up to 64: not read, LH264_PICK_ALL): only the SELECTED
+ * pictures are decoded and delivered, in decode order - INTRA: every picture that has at least one slice and whose slices are all I
+ * slices; IDR: the pictures whose slices are IDR slices.  Such a picture depends on no other, so each is byte for byte that picture of
+ * a LH264_PICK_ALL call with the same format, scale and output mode.  Offsets, the handles, the sink (first_picture counts delivered
+ * pictures), DEVICE_OUT, NO_PICTURES and both kinds of digest work on the delivered pictures only; lh264_decoded_picture_index gives a
+ * delivered picture's number among all pictures of the stream.  Of an unselected picture the front end walks the headers (NAL split,
+ * parameter sets, slice headers, reference marking, picture boundaries) and never looks at its slice data: no macroblock layer runs for
+ * it on the host, it is no task for the parse kernels and has no records, coefficients, pool slot, job or pack job
+ * (lh264_decoded_parsed_slices counts what was parsed).  The selected pictures' slice data is parsed by the host threads, or under
+ * LH264_PARSE_DEVICE by the kernels with the same fallback rules.  A failure in the header walk stops the stream there, as ever; a selected
+ * picture the full decode would refuse (uncovered macroblocks, an incomplete slice, a slice that does not parse) stops the stream at
+ * that picture with the same text, the selected pictures in front of it delivered.  DAMAGE INSIDE THE SLICE DATA OF AN UNSELECTED PICTURE
+ * IS NEITHER SEEN NOR REPORTED: a stream that LH264_PICK_ALL stops at such a picture is decoded to its end here.  A selected picture
+ * references nothing, so each is a chain of its own in lh264_recon_chains (its job carries LH264_JOB_NO_EXPAND, its reference slots
+ * point at the picture of 128s, its pool slot is free again behind its round): a stream spreads over as many workgroups as it has
+ * selected pictures in the round (lh264_decode_last_chains).  pick other than LH264_PICK_ALL together with conceal is LH264_E_ARG:
+ * concealment copies from the picture decoded before, which is not decoded here.
  * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a parse_flags bit that is not defined or
- * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, scale_log2 above 3 or reserved2 not 0 in the 64-byte struct, a format out of range, a flag bit that is not
+ * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, scale_log2 above 3 or reserved2 not 0 in the 64-byte struct, pick above 2, reserved3 not 0 or pick with conceal in the 72-byte struct, a format out of range, a flag bit that is not
  * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
  * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
  * are kept between calls, per device (lh264_decode_release frees them); concurrent calls on one device are serialised by a lock. */
@@ -732,10 +749,16 @@ typedef struct lh264_decode_opts {
   uint32_t parse_flags;                 /* LH264_PARSE_FLAG_*; 0 = none.  (struct_bytes 40 and 48: not read)   */
   uint32_t scale_log2;                  /* 0 = full size; 1..3 = means of 2x2 / 4x4 / 8x8 blocks.  (struct_bytes up to 56: not read, 0) */
   uint32_t reserved2;                   /* 0                                                                    */
+  uint32_t pick;                        /* LH264_PICK_*; 0 = every picture.  (struct_bytes up to 64: not read, 0) */
+  uint32_t reserved3;                   /* 0                                                                    */
 } lh264_decode_opts_t;
 #define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
 #define LH264_DECODE_OPTS_BYTES_V2 48u  /* the struct before `parse` was added: still accepted                   */
 #define LH264_DECODE_OPTS_BYTES_V3 56u  /* the struct before `scale_log2` was added: still accepted, full size   */
+#define LH264_DECODE_OPTS_BYTES_V4 64u  /* the struct before `pick` was added: still accepted, every picture     */
+#define LH264_PICK_ALL   0u             /* every picture of the stream (the default)                             */
+#define LH264_PICK_INTRA 1u             /* the pictures that have a slice and whose slices are all I slices      */
+#define LH264_PICK_IDR   2u             /* the pictures whose slices are IDR slices                              */
 #define LH264_PARSE_HOST   0u           /* the host front end parses slice data (the default)                    */
 #define LH264_PARSE_DEVICE 1u           /* CAVLC slice data is parsed by slice_parse_kernel, one wave per slice  */
 #define LH264_PARSE_FLAG_CABAC 1u       /* with LH264_PARSE_DEVICE: CABAC slice data too, by slice_parse_cabac_kernel */
@@ -755,6 +778,12 @@ int lh264_decoded_parse_path (const lh264_decoded_t* d);
 long long lh264_decoded_device_slices (const lh264_decoded_t* d);
 /* ... and how many of those were CABAC slices, parsed by slice_parse_cabac_kernel (0 without LH264_PARSE_FLAG_CABAC) */
 long long lh264_decoded_device_cabac_slices (const lh264_decoded_t* d);
+/* the distinct slices of the stream whose slice data was parsed, by the host front end or by a kernel (a slice that waited for another
+ * round, or that the host parsed again behind a fallback, counts once): with opts->pick the slices of the selected pictures only */
+long long lh264_decoded_parsed_slices (const lh264_decoded_t* d);
+/* the number of delivered picture idx among all pictures the front end found in the stream, in decode order from 0 (withheld and
+ * unselected pictures count).  With LH264_PICK_ALL and nothing withheld it equals idx.  LH264_E_ARG: a bad index */
+int lh264_decoded_picture_index (const lh264_decoded_t* d, int idx);
 const char* lh264_decoded_error (const lh264_decoded_t* d);
 int lh264_decoded_pictures (const lh264_decoded_t* d);
 int lh264_decoded_picture (const lh264_decoded_t* d, int idx, lh264_decoded_pic_t* out);
@@ -781,6 +810,14 @@ int lh264_decode_last_timing (double* ms);
 /* parse = LH264_PARSE_DEVICE: of ms[1] above, out[0] the milliseconds of the device parse stage (filling tasks, upload, slice_parse_kernel and
  * - with LH264_PARSE_FLAG_CABAC - slice_parse_cabac_kernel, the wait for their results) and out[1] the number of slices it parsed, in the last call (0, 0 under LH264_PARSE_HOST) */
 int lh264_decode_last_parse_timing (double* out);
+/* the launch shape of the last lh264_decode_batch call in this process: v[0] its rounds (lh264_recon_chains launches), v[1] the chains
+ * and v[2] the jobs (pictures) of all of them.  With LH264_PICK_ALL a chain is a stream's pictures of a round; with opts->pick every
+ * picture is a chain */
+int lh264_decode_last_chains (long long v[3]);
+/* the decode-order indices lh264_decode_batch would select from one Annex-B file under `pick` (LH264_PICK_*; LH264_PICK_ALL: every
+ * index), up to the first failure of the header walk: the first min (cap, *n) of them go to idx (may be NULL with cap 0), *n is
+ * their number whatever cap is.  Headers only, no device is needed.  LH264_E_ARG: a pick that is not defined, n NULL, cap < 0 */
+int lh264_parser_pick (const uint8_t* data, size_t len, uint32_t pick, int32_t* idx, int cap, int* n);
 /* one picture to crop and pack (decode_pack_kernel): the planes' pixel (0,0) in a padded picture, the window, where the packed
  * picture begins.  crop_x/y/w/h are even.  `reserved` carries the job's scale_log2: 0 = the copy; 1..3 = the means defined at
  * lh264_decode_batch (decode_pack_scaled_kernel), the packed picture then has the delivered size; anything else is LH264_E_ARG.

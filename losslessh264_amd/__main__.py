@@ -27,6 +27,9 @@
                                                             line `stream hex`, the SHA-1 of all pictures in order (computed on the device)
     python -m losslessh264_amd --decode [--sha1] --scale N ...   N = 1 | 2 | 3: reduced-size pictures, the means of 2x2 / 4x4 / 8x8
                                                             blocks computed on the device (decode_batch (scale=N)); 0 = full size
+    python -m losslessh264_amd --decode [--sha1] --pick intra|idr ...   only the pictures whose slices are all I slices / the IDR pictures
+                                                            are decoded and written (decode_batch (pick=...)); the index column of a
+                                                            .sha1 file is the picture's number in the stream.  Not with --conceal
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -158,8 +161,14 @@ def restore(src, dst):
 
 def decode(argv):
     import losslessh264_amd as lh
-    nv12, conceal, sha1, parse, scale = False, None, False, "host", 0
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale"):
+    nv12, conceal, sha1, parse, scale, pick = False, None, False, "host", 0, "all"
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick"):
+        if argv[0] == "--pick":
+            if len(argv) < 2 or argv[1] not in ("intra", "idr"):
+                print("--pick: intra | idr")
+                return 2
+            pick, argv = argv[1], argv[2:]
+            continue
         if argv[0] in ("--device-parse", "--device-parse-cabac"):
             parse, argv = ("device" if argv[0] == "--device-parse" else "device+cabac"), argv[1:]
             continue
@@ -178,16 +187,16 @@ def decode(argv):
                 print("--conceal: one of " + " | ".join(lh._lib.CONCEAL))
                 return 2
             conceal, argv = argv[1], argv[2:]
-    if len(argv) < 2:
+    if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)
         return 2
     ret = 0
     if sha1:
-        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale):
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

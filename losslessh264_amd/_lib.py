@@ -150,10 +150,15 @@ PARSE_MODES = {"host": (0, 0), "device": (1, 0), "device+cabac": (1, PARSE_FLAG_
 SLICE_PARSE_ON_DEVICE, SLICE_PARSE_CABAC = 1, 2
 PARSE_PATH = {0: "host", 1: "device", 2: "fallback"}
 assert C.sizeof(DecodeOptsV3) == 56
-class DecodeOptsV4(C.Structure):   # the struct as it is now: `scale_log2` behind the 56-byte struct
+class DecodeOptsV4(C.Structure):   # the struct before `pick`: `scale_log2` behind the 56-byte struct
     _fields_ = DecodeOptsV3._fields_ + [("scale_log2", C.c_uint32), ("reserved2", C.c_uint32)]
 DECODE_OPTS_BYTES_V3 = 56          # the struct before `scale_log2` (DecodeOptsV3): still accepted, full size
 assert C.sizeof(DecodeOptsV4) == 64
+class DecodeOptsV5(C.Structure):   # the struct as it is now: `pick` behind the 64-byte struct
+    _fields_ = DecodeOptsV4._fields_ + [("pick", C.c_uint32), ("reserved3", C.c_uint32)]
+DECODE_OPTS_BYTES_V4 = 64          # the struct before `pick` (DecodeOptsV4): still accepted, every picture
+assert C.sizeof(DecodeOptsV5) == 72
+PICK = {"all": 0, "intra": 1, "idr": 2}      # LH264_PICK_*
 # LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
 CONCEAL = {"off": 0, "slice_copy": 2, "slice_copy_cross_idr": 4, "slice_copy_cross_idr_freeze": 5, "mv_copy": 6, "mv_copy_freeze": 7}
 class PackJob(C.Structure):         # reserved: the job's scale_log2 (0 = the copy, 1..3 = the means)
@@ -170,6 +175,10 @@ _SIGS.update({
     "lh264_decoded_device_slices": (C.c_longlong, [C.c_void_p]),
     "lh264_decoded_device_cabac_slices": (C.c_longlong, [C.c_void_p]),
     "lh264_decode_last_parse_timing": (C.c_int, [C.POINTER(C.c_double)]),
+    "lh264_decoded_parsed_slices": (C.c_longlong, [C.c_void_p]),
+    "lh264_decoded_picture_index": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_decode_last_chains": (C.c_int, [C.POINTER(C.c_longlong)]),
+    "lh264_parser_pick": (C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     "lh264_decoded_status": (C.c_int, [C.c_void_p]),
     "lh264_decoded_error": (C.c_char_p, [C.c_void_p]),
     "lh264_decoded_pictures": (C.c_int, [C.c_void_p]),

@@ -598,6 +598,7 @@ struct Parser::Impl {
     cur->poc = prev_pic_poc;
     if (coef_unsorted) { sort_coeffs(); coef_unsorted = false; }
     cur->complete = true;
+    cur->index = self->pictures_done_;
     self->pictures_done_++;
     if (self->keep_frames_) self->frames_.push_back (std::move (cur));
     cur.reset();

@@ -185,6 +185,7 @@ struct DeferredSlice {
   long seq = 0, pictures_before = 0;
   bool resolved = false, ok = false;       // parse_deferred ran, and what it returned
   bool cabac = false;                      // the slice's PPS has entropy_coding_mode_flag set
+  bool counted = false;                    // for whoever resolves the slice: it is in their count of parsed slices (a slice may be parsed twice)
   // ... and where its reader stood then.  CAVLC: the bit reader's position, which is the rbsp stop bit of a slice that parsed.  CABAC:
   // Cabac::pos, the number of the next bit the arithmetic decoder would take in - 9 bits behind the (aligned) start of slice_data() once
   // the engine is initialised, again 9 bits behind the last sample of an I_PCM macroblock, and beyond the payload's end by as many
@@ -196,6 +197,7 @@ struct DeferredSlice {
 struct FrameOut {
   int id = 0, mb_w = 0, mb_h = 0, frame_num = 0, crop_w = 0, crop_h = 0, crop_x = 0, crop_y = 0;
   bool idr = false, is_ref = false, complete = false;
+  long index = 0;                       // the picture's number among the pictures its parser completed, in decode order from 0
   PoolVec<lh264_mb_t> mbs;
   ZeroBuf<int16_t> coeffs, levels;
   std::vector<lh264_slice_t> slices;

@@ -2,7 +2,8 @@
 // their pictures, cropped and packed as I420 or NV12, in host memory, in device memory or through a sink.  What the reference's console
 // application does picture by picture (h264dec.cpp:246-330: DecodeFrameNoDelay, then Write2File of the cropped planes), here per batch
 // of independent streams in ROUNDS: every stream of the round contributes its next few pictures, one lh264_recon_chains launch
-// reconstructs them (one chain per stream), decode_pack_kernel behind it crops and packs them into the round's output buffer, and the
+// reconstructs them (one chain per stream; with opts->pick only intra or IDR pictures are decoded, the others are walked by their headers,
+// and every picture is a chain of its own), decode_pack_kernel behind it crops and packs them into the round's output buffer, and the
 // download of that buffer runs on a second HIP stream while the host threads parse and stage the next round.  DESIGN.md section 4.6.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -273,6 +274,8 @@ struct lh264_decoded {
   int parse_path = LH264_PARSE_PATH_HOST;
   long device_cabac_slices = 0;                 // ... of them CABAC slices (slice_parse_cabac_kernel)
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
+  long parsed_slices = 0;                       // distinct slices whose slice data was parsed, on either route
+  std::vector<int32_t> index;                   // per delivered picture: its number among the stream's pictures in decode order
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
   uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
@@ -385,6 +388,7 @@ struct DStream {
   std::unique_ptr<Parser> parser;
   std::deque<std::unique_ptr<FrameOut>> pending;     // parsed, not yet in a round
   long next_picture = 0;                             // the stream's pictures in rounds so far
+  long seen = 0;                                     // the pictures the parser has handed over so far (opts->pick: selected or not)
   long delivered = 0;                                // ... those of them that are handed out (a frozen picture is reconstructed only)
   uint64_t out_off = 0;                              // ... and their packed bytes
   size_t pic_mbs = 0;                                // macroblocks of the stream's last picture (0: none seen yet)
@@ -408,11 +412,20 @@ struct RoundChain {
   DStream* s = nullptr;
   int first_picture = 0;
   std::vector<lh264_decoded_pic_t> pics;
-  std::vector<int32_t> concealed, source_wh;
+  std::vector<int32_t> concealed, source_wh, index;
   size_t at = 0, bytes = 0;                          // in the round's output buffer
   size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
 };
 struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0, dig_states_at = 0; bool live = false; };
+
+// opts->pick: is the picture one of those the call decodes?  (slice_type: 0 P, 2 I)
+bool picture_selected (const FrameOut& f, uint32_t pick) {
+  if (pick == LH264_PICK_ALL) return true;
+  if (f.slices.empty()) return false;
+  if (pick == LH264_PICK_IDR) return f.idr;
+  for (const lh264_slice_t& sl : f.slices) if (sl.slice_type != 2) return false;
+  return true;
+}
 
 std::string refuse_picture (const FrameOut& f) {
   const size_t n = (size_t)f.mb_w * f.mb_h;
@@ -426,6 +439,7 @@ std::string refuse_picture (const FrameOut& f) {
 
 lh264host::PerDevice<Arena> g_arena;      // one decode call at a time per device
 double g_timing[6] = {0, 0, 0, 0, 0, 0};
+long long g_chains[3] = {0, 0, 0};      // rounds, chains and jobs of the last call's lh264_recon_chains launches
 double g_parse_timing[2] = {0, 0};      // of g_timing[1]: the device parse stage (tasks, upload, slice_parse_kernel, results), and its slices
 
 const uint32_t kDefaultRoundPictures = 8;
@@ -525,7 +539,7 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V4 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
                ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
@@ -534,9 +548,13 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   if (parse != LH264_PARSE_HOST && parse != LH264_PARSE_DEVICE) return LH264_E_ARG;
   const uint32_t parse_flags = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V3 ? opts->parse_flags : 0;
   if ((parse_flags & ~LH264_PARSE_FLAG_CABAC) || (parse_flags && parse != LH264_PARSE_DEVICE)) return LH264_E_ARG;
-  const bool opts_v4 = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t);
+  const bool opts_v4 = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V4;
   if (opts_v4 && (opts->scale_log2 > 3 || opts->reserved2 != 0)) return LH264_E_ARG;
   const int scale = opts_v4 ? (int)opts->scale_log2 : 0;      // 0: decode_pack_kernel, as ever; 1..3: decode_pack_scaled_kernel
+  const bool opts_v5 = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t);
+  if (opts_v5 && (opts->pick > LH264_PICK_IDR || opts->reserved3 != 0 || (opts->pick != LH264_PICK_ALL && conceal != 0))) return LH264_E_ARG;
+  const uint32_t pick = opts_v5 ? opts->pick : LH264_PICK_ALL;
+  const bool picking = pick != LH264_PICK_ALL;      // unselected pictures are walked by their headers only, every selected one is a chain
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -557,6 +575,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
   const double t_call = now_s();
+  long long n_rounds = 0, n_launched = 0, n_launched_jobs = 0;      // lh264_decode_last_chains
   double t_parse = 0, t_stage = 0, t_enqueue = 0, t_wait = 0, t_deliver = 0, t_dev_parse = 0, n_dev_slices = 0;
 
   std::vector<std::unique_ptr<DStream>> active;
@@ -594,15 +613,24 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     while (fill && s.pending.size() < R && !P.file_finished()) {
       const size_t want = s.pic_mbs ? (R - s.pending.size()) * s.pic_mbs - 1 : 0;
       P.feed_file_some (want);
-      for (auto& f : P.frames()) { s.pic_mbs = (size_t)f->mb_w * f->mb_h; s.pending.push_back (std::move (f)); }
+      for (auto& f : P.frames()) {
+        s.pic_mbs = (size_t)f->mb_w * f->mb_h;
+        s.seen = f->index + 1;
+        // (slices parsed on the spot; the deferred ones are counted where they are resolved)
+        out[s.i]->parsed_slices += (long) (f->slices.size() - f->deferred.size());
+        // opts->pick: an unselected picture leaves here, its slice data unseen
+        if (picking && !picture_selected (*f, pick)) continue;
+        s.pending.push_back (std::move (f));
+      }
       P.frames().clear();
     }
     s.ending = false; s.end_code = LH264_OK; s.end_text.clear();
     const bool has_err = !tentative && !P.error().empty();
     const long limit = has_err ? P.error_pictures() : 0x7fffffffffffffffl;
     while (s.sel.size() < R) {
-      const long idx = s.next_picture + (long)s.sel.size();
-      if (idx >= limit) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + P.error(); break; }
+      // the picture's number in the stream: with opts->pick the next selected picture's own, or where the pictures seen so far end
+      const long idx = !picking ? s.next_picture + (long)s.sel.size() : !s.pending.empty() ? s.pending.front()->index : s.seen;
+      if (idx >= limit) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (picking ? limit : idx) + ": " + P.error(); break; }
       if (s.pending.empty()) {
         if (P.file_finished()) { s.ending = true; if (has_err) { s.end_code = LH264_E_UNSUPPORTED; s.end_text = P.error(); } }
         break;
@@ -660,6 +688,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
+        r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         if (sha) take_digests (c, r, (int)k);
       }
     } else {
@@ -671,6 +700,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
+        r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         if (sha) take_digests (c, r, k);
       });
     }
@@ -699,8 +729,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         s->parser->set_sparse_levels (true);       // (the parser has no mode without levels: their list is the cheapest form)
         s->parser->set_conceal (conceal);
         s->dev_route = parse_dev;
-        s->parser->set_defer_slice_data (parse_dev);
-        s->parser->set_defer_cabac (parse_cabac);
+        s->parser->set_defer_slice_data (parse_dev || picking);
+        s->parser->set_defer_cabac (parse_cabac || picking);
         s->parser->begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
         active.push_back (std::move (s));
         used += avg * R; admitted++;
@@ -708,8 +738,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     }
     if (active.empty()) break;
     const double t_a = now_s();
-    run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k], true, parse_dev); });
-    if (parse_dev) {
+    run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k], true, parse_dev || picking); });
+    if (parse_dev || picking) {
       // ---- the round's CAVLC slice data on the device: payloads and tasks up, slice_parse_kernel, 12 bytes per slice down; then the
       // round's pictures are picked as ever.  On the run stream, behind the round before (whose kernels still read the parse arena),
       // and waited for: the results decide what the round holds
@@ -727,6 +757,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
             if (!f.slices.empty() && s.dev_route) { s.dev_route = false; s.parser->set_defer_slice_data (false); }
             continue;
           }
+          // (opts->pick defers every slice, whoever parses it: without LH264_PARSE_FLAG_CABAC a CABAC picture is the host's all the same)
+          if (picking && !parse_cabac && f.deferred[0].cabac) { s.dev_route = false; continue; }
           if (!s.dev_route) continue;
           s.dev_at[&f] = {pm};
           pm += (size_t)f.mb_w * f.mb_h;
@@ -798,14 +830,16 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         // a status anywhere in a stream's round: the whole round of that stream goes back to the host parser, and the stream stays there
         for (size_t j = 0; j < nt; j++) if (res[j].status != lh264slice::SLICE_OK && refs[j].s->dev_route) {
           DStream& s = *refs[j].s;
-          s.dev_route = false; s.parser->set_defer_slice_data (false); s.dev_at.clear();
+          s.dev_route = false; s.dev_at.clear();
+          if (!picking) s.parser->set_defer_slice_data (false);
           out[s.i]->parse_path = LH264_PARSE_PATH_FALLBACK;
         }
         for (size_t j = 0; j < nt; j++) {
           const TRef& r = refs[j];
           if (!r.s->dev_route) continue;
           FrameOut& f = *r.f;
-          const lh264host::DeferredSlice& ds = f.deferred[r.def];
+          lh264host::DeferredSlice& ds = f.deferred[r.def];
+          if (!ds.counted) { ds.counted = true; out[r.s->i]->parsed_slices++; }
           if (out[r.s->i]->parse_path == LH264_PARSE_PATH_HOST) out[r.s->i]->parse_path = LH264_PARSE_PATH_DEVICE;
           out[r.s->i]->device_slices++;
           if (ds.cabac) out[r.s->i]->device_cabac_slices++;
@@ -823,12 +857,19 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
           f.slice_syn[(size_t)ds.sid] = ss;
         }
       }
-      t_dev_parse += now_s() - t_p0; n_dev_slices += (double)nt;
+      if (parse_dev) { t_dev_parse += now_s() - t_p0; n_dev_slices += (double)nt; }
       // whatever was deferred and did not stay on the device is parsed by the host parser now (a fallback, the pictures behind a CABAC
       // picture); then the round's pictures are picked with everything known
       run_parallel ((int)active.size(), threads, [&] (int k) {
         DStream& s = *active[k];
-        auto resolve = [&] (FrameOut& f) { if (!s.dev_at.count (&f)) for (size_t d = 0; d < f.deferred.size(); d++) s.parser->parse_deferred (f, d); };
+        auto resolve = [&] (FrameOut& f) {
+          if (s.dev_at.count (&f)) return;
+          for (size_t d = 0; d < f.deferred.size(); d++) {
+            lh264host::DeferredSlice& ds = f.deferred[d];
+            if (!ds.resolved && !ds.counted) { ds.counted = true; out[s.i]->parsed_slices++; }
+            s.parser->parse_deferred (f, d);
+          }
+        };
         for (auto& f : s.sel) resolve (*f);
         if (!s.dev_route) for (auto& f : s.pending) resolve (*f);
         unselect (s);
@@ -874,11 +915,15 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       continue;
     }
     const int n_chains = (int)rd.chains.size();
+    // the chains of the launch: a stream's pictures of the round one behind the other - or, with opts->pick, every picture on its own:
+    // it references nothing, so the stream spreads over as many workgroups as it has pictures in the round.  (Delivery and the
+    // stream's digest follow rd.chains, the streams, in both cases)
+    const int n_launch = picking ? (int)n_jobs : n_chains;
     alloc_ok = A.d_mbs.alloc (n_hmbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_hmbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
-               A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_chains + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
+               A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_launch + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
                A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
-               A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_chains + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
+               A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
     const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
     rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
     const size_t dig_bytes = rd.dig_states_at + (size_t)n_chains * sizeof (lh264_sha1_state_t);
@@ -913,7 +958,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       RoundChain& rc = rd.chains[c];
       DStream& s = *rc.s;
       size_t mo = place[c].mb0, so = place[c].sl0, po = place[c].sp0, j = place[c].job0, at = rc.at;
-      h_first[c] = (int32_t)j;
+      if (!picking) h_first[c] = (int32_t)j;
       uint64_t off = s.out_off;
       for (size_t q = 0; q < s.sel.size(); q++) {
         FrameOut& f = *s.sel[q];
@@ -936,12 +981,12 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
           // there and leaves its fresh picture's 128: the same samples.  The picture itself in that slot (what the ISVC object does) would
           // be read while it is being written, in wavefront order: not the oracle's result, and not a defined one.
           const uint8_t* base = s.grey;
-          if (k < f.ref_ids.size()) for (const Slot& sl : s.pool) if (sl.pic_id == f.ref_ids[k] && sl.base != me.base) { base = sl.base; break; }
+          if (!picking && k < f.ref_ids.size()) for (const Slot& sl : s.pool) if (sl.pic_id == f.ref_ids[k] && sl.base != me.base) { base = sl.base; break; }
           jb.ref[k] = pic_at (base);
         }
         jb.mb_w = f.mb_w; jb.mb_h = f.mb_h; jb.stride_y = s.geo.stride_y; jb.stride_c = s.geo.stride_c;
         jb.n_slices = (int32_t)f.slices.size();
-        jb.flags = f.is_ref ? 0 : LH264_JOB_NO_EXPAND;
+        jb.flags = f.is_ref && !picking ? 0 : LH264_JOB_NO_EXPAND;      // (opts->pick: nothing will read the picture's borders)
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
         pj.reserved = scale;
@@ -958,12 +1003,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         rc.pics.push_back (dp);
         rc.concealed.push_back (f.concealed);
         rc.source_wh.push_back (f.crop_w); rc.source_wh.push_back (f.crop_h);
+        rc.index.push_back ((int32_t)f.index);
         at += bytes; off += bytes;
         if (!on_dev) mo += nm;
         so += f.slices.size(); j++;
       }
     });
-    h_first[n_chains] = (int32_t)n_jobs;
+    if (picking) for (size_t j = 0; j < n_jobs; j++) h_first[j] = (int32_t)j;
+    h_first[n_launch] = (int32_t)n_jobs;
     if (sha) {
       // the span jobs: a picture is a message of its own (its record is scratch), a chain's bytes are the next span of its stream's
       // message, whose record stays on the device from round to round; a copy of it comes down with the round
@@ -988,7 +1035,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       for (auto& f : s.sel) { int ow, oh; lh264pack::scaled_size (f->crop_w, f->crop_h, scale, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
       // the slots the round leaves free: pictures the DPB behind the round's last picture does not hold
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
-      for (Slot& sl : s.pool) if (sl.pic_id >= 0 && std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end()) sl.pic_id = -1;
+      for (Slot& sl : s.pool) if (sl.pic_id >= 0 && (picking || std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end())) sl.pic_id = -1;      // (opts->pick: a slot is needed for its round only)
       s.next_picture += (long)s.sel.size();
       s.delivered += (long)rd.chains[c].pics.size();
       s.out_off += rd.chains[c].bytes;
@@ -1001,10 +1048,11 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       hipStream_t st = A.s_run;
       auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
       bool ok = up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
-                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_chains + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
+                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
                 (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
-      if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_chains, max_w, max_h, st) == LH264_OK;
+      if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
+      if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
       if (ok) {
         if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
@@ -1055,6 +1103,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   if (device_failed) for (int i = next_stream; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = device_error; }
   g_timing[0] = (now_s() - t_call) * 1e3; g_timing[1] = t_parse * 1e3; g_timing[2] = t_stage * 1e3; g_timing[3] = t_enqueue * 1e3; g_timing[4] = t_wait * 1e3; g_timing[5] = t_deliver * 1e3;
   g_parse_timing[0] = t_dev_parse * 1e3; g_parse_timing[1] = n_dev_slices;
+  g_chains[0] = n_rounds; g_chains[1] = n_launched; g_chains[2] = n_launched_jobs;
   if (trace_on()) fprintf (stderr, "[lh264 decode] %d streams: %.3f s (parse %.3f, staging %.3f, enqueue %.3f, waiting for the device %.3f, delivery %.3f); arena %.1f MB device, %.1f MB pinned\n",
                            n, g_timing[0] / 1e3, t_parse, t_stage, t_enqueue, t_wait, t_deliver, A.device_bytes() / 1e6, A.pinned_bytes() / 1e6);
   return LH264_OK;
@@ -1069,6 +1118,33 @@ int lh264_decode_last_parse_timing (double* out) {
   if (!out) return LH264_E_ARG;
   out[0] = g_parse_timing[0]; out[1] = g_parse_timing[1];
   return LH264_OK;
+}
+int lh264_decode_last_chains (long long v[3]) {
+  if (!v) return LH264_E_ARG;
+  for (int k = 0; k < 3; k++) v[k] = g_chains[k];
+  return LH264_OK;
+}
+// the header walk of lh264_decode_batch under opts->pick, and its choice: every slice deferred, none resolved
+int lh264_parser_pick (const uint8_t* data, size_t len, uint32_t pick, int32_t* idx, int cap, int* n) {
+  if (!n || cap < 0 || (cap && !idx) || pick > LH264_PICK_IDR || (!data && len)) return LH264_E_ARG;
+  Parser P;
+  P.set_sparse_coeffs (true); P.set_sparse_levels (true);
+  P.set_defer_slice_data (true); P.set_defer_cabac (true);
+  P.begin_file (data, data ? len : 0);
+  int count = 0;
+  while (!P.file_finished()) {
+    P.feed_file_some (0);
+    const long limit = P.error().empty() ? 0x7fffffffffffffffl : P.error_pictures();
+    for (auto& f : P.frames()) if (f->index < limit && picture_selected (*f, pick)) { if (count < cap) idx[count] = (int32_t)f->index; count++; }
+    P.frames().clear();
+  }
+  *n = count;
+  return LH264_OK;
+}
+long long lh264_decoded_parsed_slices (const lh264_decoded_t* d) { return d ? (long long)d->parsed_slices : 0; }
+int lh264_decoded_picture_index (const lh264_decoded_t* d, int idx) {
+  if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->index.size() != d->pics.size()) return LH264_E_ARG;
+  return d->index[idx];
 }
 int lh264_decoded_status (const lh264_decoded_t* d) { return d ? d->status : LH264_E_ARG; }
 int lh264_decoded_parse_path (const lh264_decoded_t* d) { return d ? d->parse_path : LH264_E_ARG; }

@@ -44,6 +44,16 @@ class DecodedBatch:
         """... and how many of them were CABAC slices, parsed by slice_parse_cabac_kernel (parse="device+cabac")"""
         return int(self._lib.lh264_decoded_device_cabac_slices(self._h[i]))
 
+    def parsed_slices(self, i):
+        """the distinct slices of stream i whose slice data was parsed, by the host front end or by a kernel: with pick= the slices of
+        the selected pictures only (an unselected picture is walked by its headers)"""
+        return int(self._lib.lh264_decoded_parsed_slices(self._h[i]))
+
+    def picture_indices(self, i):
+        """per delivered picture of stream i: its number among all pictures of the stream, in decode order from 0 (with pick="all" and
+        nothing withheld: 0, 1, 2, ...)"""
+        return [self._lib.lh264_decoded_picture_index(self._h[i], k) for k in range(self._lib.lh264_decoded_pictures(self._h[i]))]
+
     def error(self, i):
         return self._lib.lh264_decoded_error(self._h[i]).decode()
 
@@ -127,7 +137,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all"):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -149,8 +159,16 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     (sum + (1 << (2*s - 1))) >> (2*s), sum over the B x B window samples at x = min (X*B + i, w - 1), y = min (Y*B + j, h - 1),
     0 <= i, j < B; Cb and Cr: the same rule on their cw x ch planes.  Coordinates are clamped to the cropped window, never to the padded
     picture.  The planes are averaged independently; chroma siting is not modelled.  Packing as ever with ow, oh in place of w, h;
-    DecodedBatch.pictures describes what is delivered, source_sizes the windows before scaling.  QCIF at scale=3: 22 x 18, 594 bytes."""
+    DecodedBatch.pictures describes what is delivered, source_sizes the windows before scaling.  QCIF at scale=3: 22 x 18, 594 bytes.
+    pick: "all" (the default) | "intra" | "idr": only the selected pictures are decoded and delivered - "intra": the pictures whose
+    slices are all I slices, "idr": the IDR pictures.  Each is byte for byte that picture of the full decode; of the others the front end
+    walks the headers only and never sees the slice data, so damage there is neither seen nor reported.  DecodedBatch.picture_indices(i)
+    gives the delivered pictures' numbers in the stream, parsed_slices(i) what was parsed.  Not together with conceal."""
     lib = L.lib()
+    if pick not in L.PICK:
+        raise ValueError("pick must be 'all', 'intra' or 'idr'")
+    if pick != "all" and conceal not in (None, "off"):
+        raise ValueError("pick needs conceal off: concealment copies from the picture decoded before, which is not decoded")
     if scale not in (0, 1, 2, 3) or isinstance(scale, bool):
         raise ValueError("scale must be 0, 1, 2 or 3")
     if fmt not in _FORMATS:
@@ -167,8 +185,9 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
     lens = (C.c_size_t * n)(*[len(d) for d in keep])
-    opts = L.DecodeOptsV4()
-    opts.struct_bytes = C.sizeof(L.DecodeOptsV4)
+    opts = L.DecodeOptsV5()
+    opts.struct_bytes = C.sizeof(L.DecodeOptsV5)
+    opts.pick = L.PICK[pick]
     opts.scale_log2 = int(scale)
     opts.parse, opts.parse_flags = L.PARSE_MODES[parse]
     opts.format = _FORMATS[fmt]
@@ -205,9 +224,9 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all"):
     """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
-    pictures, bytes)]; scale as in decode_batch"""
+    pictures, bytes)]; scale and pick as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     names = [os.path.join(out_dir, os.path.basename(p) + ".yuv") for p in paths]
@@ -219,7 +238,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick)
     finally:
         for f in files:
             f.close()
@@ -228,12 +247,13 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all"):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
-    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale as in decode_batch (the digests are of the delivered bytes)"""
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale and pick as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
+    order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick)
     res = []
     try:
         for i, p in enumerate(paths):
@@ -241,10 +261,11 @@ def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host",
             st = b.status(i)
             pics = b.pictures(i) if st != L.E_HIP else []
             digs = b.picture_sha1(i) if pics else []
+            index = b.picture_indices(i) if pics else []
             total = b.stream_sha1(i).hex() if st != L.E_HIP else ""
             with open(name, "w") as f:
                 for k, (w, h, fn, idr, _off, _n) in enumerate(pics):
-                    f.write("%d %d %d %d %d %s\n" % (k, w, h, fn, idr, digs[k].hex()))
+                    f.write("%d %d %d %d %d %s\n" % (index[k], w, h, fn, idr, digs[k].hex()))
                 if st != L.E_HIP:
                     f.write("stream %s\n" % total)
             res.append((name, st, b.error(i), len(pics), total))

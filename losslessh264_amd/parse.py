@@ -126,6 +126,20 @@ def out_of_range(data):
         lib.lh264_parser_destroy(p)
 
 
+def pick(data, which):
+    """the decode-order indices of the pictures decode_batch (pick=which) selects from one Annex-B stream, up to the first failure of the
+    header walk (lh264_parser_pick): which = "all" | "intra" (every slice an I slice) | "idr".  Headers only; no device is needed."""
+    if which not in L.PICK:
+        raise ValueError("which must be 'all', 'intra' or 'idr'")
+    lib = L.lib()
+    data = bytes(data)
+    n = C.c_int(0)
+    L.check(lib.lh264_parser_pick(data, len(data), L.PICK[which], None, 0, C.byref(n)))
+    idx = (C.c_int32 * max(1, n.value))()
+    L.check(lib.lh264_parser_pick(data, len(data), L.PICK[which], idx, n.value, C.byref(n)))
+    return [int(idx[k]) for k in range(n.value)]
+
+
 def _file_text(data, query, tolerant=False):
     lib = L.lib()
     p = lib.lh264_parser_create()
