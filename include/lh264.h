@@ -720,7 +720,25 @@ int lh264_debug_dp_update (const uint32_t* words, const uint8_t* bits, uint32_t*
  * point at the picture of 128s, its pool slot is free again behind its round): a stream spreads over as many workgroups as it has
  * selected pictures in the round (lh264_decode_last_chains).  pick other than LH264_PICK_ALL together with conceal is LH264_E_ARG:
  * concealment copies from the picture decoded before, which is not decoded here.
- * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, a parse value that is not defined, a parse_flags bit that is not defined or
+ * opts->out_width = OW, opts->out_height = OH (the 88-byte struct; struct_bytes up to 72: not read, 0, 0): PICTURES OF ONE GIVEN SIZE.
+ * Every delivered picture of every stream is OW x OH (both even, 2..4096), resampled from its cropped window by an exact, integer area
+ * average on the device: decode_pack_resized_kernel takes the copy kernel's place in the round.  Each plane is resampled on its own, the
+ * luma plane from the w x h window to OW x OH, Cb and Cr from w/2 x h/2 to OW/2 x OH/2.  For one plane of w x h window samples p[y][x]
+ * delivered as ow x oh: the horizontal weight of source column x for delivered column X is
+ * wx (X, x) = max (0, min ((x+1)*ow, (X+1)*w) - max (x*ow, X*w)) - non-zero only for x in floor (X*w / ow) .. floor (((X+1)*w - 1) / ow),
+ * ow for every column strictly inside that span, the weights of one X sum to w; the vertical weight wy (Y, y) is the same with h and oh.
+ * S = the sum over y, x of wy (Y, y) * wx (X, x) * p[y][x], D = w*h, delivered sample (X, Y) = floor ((2*S + D) / (2*D)): round half up,
+ * in exact integers (S is kept in 64 bits: exact for every window the front end delivers).  No coordinate leaves the window: nothing
+ * right of or below it, and nothing of the padded picture, enters a mean.  The aspect ratio is NOT kept (a plain stretch); chroma siting
+ * is not modelled, as at scale_log2.  ow == w and oh == h gives the window itself; w = B*ow and h = B*oh, B in 2 / 4 / 8, gives the
+ * scale_log2 means byte for byte (QCIF at 88 x 72, 44 x 36, 22 x 18); a larger size than the window repeats samples and blends the seams.
+ * Packing is as ever with OW, OH in place of w, h.  lh264_decoded_pic_t width / height / bytes / offset describe what is delivered,
+ * lh264_decoded_picture_source_size gives the window.  The round's output buffers, the download, the handles, the sink, DEVICE_OUT and
+ * the digests work on the delivered bytes (lh264_decode_arena_bytes follows them: more than at full size where OW x OH is larger than
+ * the window); withheld pictures stay withheld; format, conceal, parse and pick act on what is decoded as without a size.  0, 0 launches
+ * and delivers what the call did before.
+ * Arguments are checked first (LH264_E_ARG: a struct_bytes this library does not know, one of out_width / out_height 0 and the other not, either of
+ * them odd or above 4096, a size together with scale_log2, reserved4 or reserved5 not 0 in the 88-byte struct, a parse value that is not defined, a parse_flags bit that is not defined or
  * LH264_PARSE_FLAG_CABAC with LH264_PARSE_HOST, scale_log2 above 3 or reserved2 not 0 in the 64-byte struct, pick above 2, reserved3 not 0 or pick with conceal in the 72-byte struct, a format out of range, a flag bit that is not
  * defined, sink together with LH264_DECODE_DEVICE_OUT, LH264_DECODE_NO_PICTURES without a digest flag or together with
  * LH264_DECODE_DEVICE_OUT or a sink, n < 0), then the device (LH264_E_NODEVICE); out is untouched in both cases.  Device and page-locked buffers
@@ -751,11 +769,14 @@ typedef struct lh264_decode_opts {
   uint32_t reserved2;                   /* 0                                                                    */
   uint32_t pick;                        /* LH264_PICK_*; 0 = every picture.  (struct_bytes up to 64: not read, 0) */
   uint32_t reserved3;                   /* 0                                                                    */
+  uint32_t out_width, out_height;       /* 0, 0 = the stream's size (or its scale); else every delivered picture is out_width x out_height: both even, 2..4096, scale_log2 0.  (struct_bytes up to 72: not read, 0) */
+  uint32_t reserved4, reserved5;        /* 0                                                                    */
 } lh264_decode_opts_t;
 #define LH264_DECODE_OPTS_BYTES_V1 40u  /* the struct before `conceal` was added: still accepted                 */
 #define LH264_DECODE_OPTS_BYTES_V2 48u  /* the struct before `parse` was added: still accepted                   */
 #define LH264_DECODE_OPTS_BYTES_V3 56u  /* the struct before `scale_log2` was added: still accepted, full size   */
 #define LH264_DECODE_OPTS_BYTES_V4 64u  /* the struct before `pick` was added: still accepted, every picture     */
+#define LH264_DECODE_OPTS_BYTES_V5 72u  /* the struct before `out_width` was added: still accepted, no size      */
 #define LH264_PICK_ALL   0u             /* every picture of the stream (the default)                             */
 #define LH264_PICK_INTRA 1u             /* the pictures that have a slice and whose slices are all I slices      */
 #define LH264_PICK_IDR   2u             /* the pictures whose slices are IDR slices                              */
@@ -833,6 +854,13 @@ int lh264_debug_pack_cpu (const lh264_pack_job_t* jobs, int n);
  * for the jobs' scale_log2 (all equal, else LH264_E_ARG) is launched - decode_pack_kernel at 0, decode_pack_scaled_kernel at 1..3 - and
  * the call returns when it is through.  Without a device: LH264_E_NODEVICE.  For tests: windows no stream has */
 int lh264_debug_pack_dev (const lh264_pack_job_t* jobs, int n);
+/* the same table delivered as out_w x out_h pictures (out_width / out_height at lh264_decode_batch): lh264_debug_resize_cpu steps the
+ * code of decode_pack_resized_kernel over HOST memory, lh264_debug_resize_dev uploads the table (its pointers are device pointers),
+ * launches the production kernel and returns when it is through.  LH264_E_ARG: a size that is not a pair of even values in 2..4096, a
+ * job whose `reserved` is not 0 or whose window is not even, positive and at most 16384 a side, jobs NULL, n <= 0; lh264_debug_resize_dev
+ * without a device: LH264_E_NODEVICE */
+int lh264_debug_resize_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h);
+int lh264_debug_resize_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

@@ -30,6 +30,9 @@
     python -m losslessh264_amd --decode [--sha1] --pick intra|idr ...   only the pictures whose slices are all I slices / the IDR pictures
                                                             are decoded and written (decode_batch (pick=...)); the index column of a
                                                             .sha1 file is the picture's number in the stream.  Not with --conceal
+    python -m losslessh264_amd --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096),
+                                                            resampled on the device by an exact area average (decode_batch
+                                                            (size=(W, H))); the aspect ratio is not kept.  Not with a non-zero --scale
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -159,10 +162,30 @@ def restore(src, dst):
     print("%s (+%d tagged streams) -> %s: %d bytes" % (src, len(tags), dst, len(out)))
 
 
+SIZE_USAGE = "--size: WxH, both even, 2..4096; not with a non-zero --scale"
+
+
+def parse_size(text):
+    """"WxH" -> (W, H), or None where it is not a pair of even numbers in 2..4096"""
+    import re
+    m = re.fullmatch(r"([0-9]{1,4})x([0-9]{1,4})", text)
+    if not m:
+        return None
+    w, h = int(m.group(1)), int(m.group(2))
+    return (w, h) if all(2 <= v <= 4096 and v % 2 == 0 for v in (w, h)) else None
+
+
 def decode(argv):
     import losslessh264_amd as lh
-    nv12, conceal, sha1, parse, scale, pick = False, None, False, "host", 0, "all"
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick"):
+    nv12, conceal, sha1, parse, scale, pick, size = False, None, False, "host", 0, "all", None
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size"):
+        if argv[0] == "--size":
+            size = parse_size(argv[1]) if len(argv) >= 2 else None
+            if size is None:
+                print(SIZE_USAGE)
+                return 2
+            argv = argv[2:]
+            continue
         if argv[0] == "--pick":
             if len(argv) < 2 or argv[1] not in ("intra", "idr"):
                 print("--pick: intra | idr")
@@ -187,16 +210,19 @@ def decode(argv):
                 print("--conceal: one of " + " | ".join(lh._lib.CONCEAL))
                 return 2
             conceal, argv = argv[1], argv[2:]
+    if size is not None and scale != 0:
+        print(SIZE_USAGE)
+        return 2
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)
         return 2
     ret = 0
     if sha1:
-        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick):
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

@@ -154,10 +154,14 @@ class DecodeOptsV4(C.Structure):   # the struct before `pick`: `scale_log2` behi
     _fields_ = DecodeOptsV3._fields_ + [("scale_log2", C.c_uint32), ("reserved2", C.c_uint32)]
 DECODE_OPTS_BYTES_V3 = 56          # the struct before `scale_log2` (DecodeOptsV3): still accepted, full size
 assert C.sizeof(DecodeOptsV4) == 64
-class DecodeOptsV5(C.Structure):   # the struct as it is now: `pick` behind the 64-byte struct
+class DecodeOptsV5(C.Structure):   # the struct before `out_width`: `pick` behind the 64-byte struct
     _fields_ = DecodeOptsV4._fields_ + [("pick", C.c_uint32), ("reserved3", C.c_uint32)]
 DECODE_OPTS_BYTES_V4 = 64          # the struct before `pick` (DecodeOptsV4): still accepted, every picture
 assert C.sizeof(DecodeOptsV5) == 72
+class DecodeOptsV6(C.Structure):   # the struct as it is now: the delivered size behind the 72-byte struct
+    _fields_ = DecodeOptsV5._fields_ + [("out_width", C.c_uint32), ("out_height", C.c_uint32), ("reserved4", C.c_uint32), ("reserved5", C.c_uint32)]
+DECODE_OPTS_BYTES_V5 = 72          # the struct before `out_width` (DecodeOptsV5): still accepted, no size
+assert C.sizeof(DecodeOptsV6) == 88
 PICK = {"all": 0, "intra": 1, "idr": 2}      # LH264_PICK_*
 # LH264_CONCEAL_*: the values of the reference's ERROR_CON_IDC; the FRAME_COPY pair (1, 3) is not provided
 CONCEAL = {"off": 0, "slice_copy": 2, "slice_copy_cross_idr": 4, "slice_copy_cross_idr_freeze": 5, "mv_copy": 6, "mv_copy_freeze": 7}
@@ -195,6 +199,8 @@ _SIGS.update({
     "lh264_decode_last_timing": (C.c_int, [C.POINTER(C.c_double)]),
     "lh264_debug_pack_cpu": (C.c_int, [C.c_void_p, C.c_int]),
     "lh264_debug_pack_dev": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_debug_resize_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "lh264_debug_resize_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "lh264_decoded_picture_source_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lh264_decoded_picture_sha1": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_decoded_stream_sha1": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -21,6 +21,8 @@
 //                                       device (lh264.h: scale_log2); 0 = full size
 //   lh264dec --decode [--sha1] --pick intra|idr ...   only the pictures whose slices are all I slices / the IDR pictures are decoded and
 //                                       written (lh264.h: pick); the index column of a .sha1 file is the picture's number in the stream.
+//   lh264dec --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096), resampled on the
+//                                       device by an exact area average (lh264.h: out_width, out_height).  Not with a non-zero --scale
 //                                       Not together with --conceal
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
@@ -198,7 +200,21 @@ static int conceal_method (const char* name) {
   for (const auto& e : k) if (!strcmp (name, e.n)) return e.m;
   return -1;
 }
-static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick) {
+// --size WxH: both even, 2..4096
+static const char* const kSizeUsage = "--size: WxH, both even, 2..4096; not with a non-zero --scale";
+static bool parse_size (const char* text, int* w, int* h) {
+  int v[2] = {0, 0}, k = 0, digits = 0;
+  for (const char* c = text; *c; c++) {
+    if (*c == 'x' && k == 0 && digits) { k = 1; digits = 0; continue; }
+    if (*c < '0' || *c > '9' || ++digits > 4) return false;
+    v[k] = v[k] * 10 + (*c - '0');
+  }
+  if (k != 1 || !digits) return false;
+  for (int q = 0; q < 2; q++) if (v[q] < 2 || v[q] > 4096 || (v[q] & 1)) return false;
+  *w = v[0]; *h = v[1];
+  return true;
+}
+static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick, int out_w, int out_h) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
   std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
@@ -211,7 +227,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
-  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick;
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   std::vector<lh264_decoded_t*> h (n, nullptr);
   const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
   for (FILE* f : files.f) fclose (f);
@@ -228,13 +244,13 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
 
 // --decode --sha1: one digests-only lh264_decode_batch; no picture leaves the device
 static std::string hex20 (const uint8_t* d) { char b[41]; for (int k = 0; k < 20; k++) snprintf (b + 2 * k, 3, "%02x", d[k]); return std::string (b, 40); }
-static int decode_sha1_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick) {
+static int decode_sha1_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick, int out_w, int out_h) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
   std::vector<const uint8_t*> d (n); std::vector<size_t> l (n);
   for (int i = 0; i < n; i++) { if (!load (srcs[i], in[i])) { perror (srcs[i].c_str()); return 2; } d[i] = in[i].data(); l[i] = in[i].size(); }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
-  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick;
+  o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
   const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
@@ -288,7 +304,7 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, first = 2; uint32_t pick = LH264_PICK_ALL;
+    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
       else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
@@ -307,16 +323,20 @@ int main (int argc, char** argv) {
         else if (!strcmp (argv[first + 1], "idr")) pick = LH264_PICK_IDR;
         else { fprintf (stderr, "--pick: intra | idr\n"); return 2; }
         first += 2;
+      } else if (first + 1 < argc && !strcmp (argv[first], "--size")) {
+        if (!parse_size (argv[first + 1], &out_w, &out_h)) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
+        first += 2;
       } else break;
     }
+    if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
-    return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick);
+    return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

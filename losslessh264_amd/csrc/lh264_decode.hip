@@ -238,6 +238,120 @@ __host__ __device__ inline void pack_band_scaled (const lh264_pack_job_t& j, int
   else if (j.reserved == 3) pack_band_scaled_by<3> (j, band, t, nt);
 }
 
+// ---- the pack step to one given size: out_width x out_height (the definition: include/lh264.h at lh264_decode_batch) ---------------
+// Every plane of w x h window samples is delivered as ow x oh exact area means: ow x oh for luma, half of it each way for chroma,
+// whatever the window is.  Delivered column X covers the interval [X*w, (X+1)*w) of a line on which every source column is ow long:
+// source columns x0 = X*w / ow .. x1 = ((X+1)*w - 1) / ow, the two end columns by what they share with the interval, every column
+// between them by ow; the weights of one X sum to w.  Rows likewise with h and oh.  S = the weighted sum, D = w*h, the sample is
+// (2*S + D) / (2*D), round half up.  A row's sum is at most 255*w; S is kept in 64 bits, since the front end delivers windows of up
+// to 139,264 macroblocks (35.7 M samples) and 2*S + D passes 2^32 at 8.4 M.  The bands are 16 delivered luma rows (and their 8 chroma
+// rows), the pieces 4 bytes of the destination counted from the aligned address at or below the row's first byte: a whole piece is
+// one aligned 4-byte store, heads and tails go sample by sample.  The spans and weights of a piece's row are worked out once per
+// piece, those of a column once per sample, never per source row.  The bytes between a span's end columns are summed by unaligned
+// 4-byte loads and dot products, the last 0..3 of them byte by byte: no byte outside the window is read, none outside the picture's
+// bytes written.  No LDS.
+
+// what a call delivers for a w x h window: out_w x out_h where a size is set (both non-zero), else the window at scale s
+__host__ __device__ inline void delivered_size (int w, int h, int s, int out_w, int out_h, int* ow, int* oh) {
+  if (out_w) { *ow = out_w; *oh = out_h; }
+  else scaled_size (w, h, s, ow, oh);
+}
+
+// the source columns (or rows) of one delivered column (or row): a .. b, `wa` of a and `wb` of b, every one between them whole.
+// (a == b: the one column carries the whole weight in wa, wb = 0)
+struct Span { int a, b; uint32_t wa, wb; };
+__host__ __device__ inline Span span_of (uint32_t X, uint32_t w, uint32_t ow) {
+  const uint32_t lo = X * w, hi = lo + w;      // (X < 4096, w <= 16384)
+  Span s;
+  s.a = (int) (lo / ow); s.b = (int) ((hi - 1) / ow);
+  if (s.a == s.b) { s.wa = w; s.wb = 0; }
+  else { s.wa = (uint32_t) (s.a + 1) * ow - lo; s.wb = hi - (uint32_t)s.b * ow; }
+  return s;
+}
+// the weighted sum of one source row over the span sx (every whole column weighs ow)
+__host__ __device__ inline uint32_t row_sum (const uint8_t* row, const Span& sx, uint32_t ow) {
+  const uint8_t* q = row + sx.a + 1;
+  int n = sx.b - sx.a - 1;
+  uint32_t mid = 0;
+  for (; n >= 4; n -= 4, q += 4) { uint32_t x; __builtin_memcpy (&x, q, 4); mid = byte_sum (x, 0x01010101u, mid); }
+  for (; n > 0; n--) mid += *q++;
+  return sx.wa * row[sx.a] + ow * mid + sx.wb * row[sx.b];
+}
+// floor ((2*S + D) / (2*D)) for a quotient of at most 255: a float estimate, then made exact against the remainder
+__host__ __device__ inline uint8_t rounded_mean (uint64_t S, uint64_t D) {
+  const uint64_t num = 2 * S + D, den = 2 * D;
+  uint32_t q = (uint32_t) ((float)num / (float)den);
+  int64_t r = (int64_t)num - (int64_t) (q * den);
+  while (r < 0) { q--; r += (int64_t)den; }
+  while (r >= (int64_t)den) { q++; r -= (int64_t)den; }
+  return (uint8_t)q;
+}
+// one plane as the resize step sees it: the window's first sample, its size, the delivered size
+struct ResizePlane { const uint8_t* p; int stride; uint32_t w, h, ow, oh; };
+// delivered sample X of the delivered row whose source rows are sy
+__host__ __device__ inline uint8_t resized_sample (const ResizePlane& pl, const Span& sy, int X) {
+  const Span sx = span_of ((uint32_t)X, pl.w, pl.ow);
+  const uint8_t* row = pl.p + (size_t)sy.a * pl.stride;
+  uint64_t S = (uint64_t)sy.wa * row_sum (row, sx, pl.ow);
+  for (int y = sy.a + 1; y < sy.b; y++) { row += pl.stride; S += (uint64_t)pl.oh * row_sum (row, sx, pl.ow); }
+  if (sy.wb) S += (uint64_t)sy.wb * row_sum (pl.p + (size_t)sy.b * pl.stride, sx, pl.ow);
+  return rounded_mean (S, (uint64_t)pl.w * pl.h);
+}
+// piece p of delivered row Y (n bytes at d): byte k is sample k of plane a - or, interleaved (NV12 chroma), sample k / 2 of a (k even) or b
+__host__ __device__ inline void piece_resized (uint8_t* d, int n, int Y, int p, const ResizePlane& a, const ResizePlane& b, bool interleaved) {
+  int k0 = p * 4 - (int) ((uintptr_t)d & 3u), k1 = k0 + 4;
+  const bool whole = k0 >= 0 && k1 <= n;
+  if (k0 < 0) k0 = 0;
+  if (k1 > n) k1 = n;
+  if (k1 <= k0) return;
+  const Span sy = span_of ((uint32_t)Y, a.h, a.oh);
+  uint32_t o = 0;
+  for (int k = k0; k < k1; k++) {
+    const uint8_t v = interleaved ? resized_sample ((k & 1) ? b : a, sy, k >> 1) : resized_sample (a, sy, k);
+    if (whole) o |= (uint32_t)v << (8 * (k - k0));
+    else d[k] = v;
+  }
+  if (whole) * (uint32_t*) (d + k0) = o;
+}
+// band `band` (16 delivered luma rows, 8 chroma rows) of one job delivered as ow x oh, worked on by item t of nt (the host steps it
+// with t = 0, nt = 1)
+__host__ __device__ inline void pack_band_resized (const lh264_pack_job_t& j, int ow, int oh, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h, ocw = ow >> 1, och = oh >> 1;
+  const int r0 = band * kBandRows, r1 = r0 + kBandRows < oh ? r0 + kBandRows : oh;
+  if (r1 > r0) {
+    const ResizePlane y = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh};
+    const int pieces = (ow + 6) >> 2, items = (r1 - r0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = r0 + it / pieces, p = it % pieces;
+      piece_resized (j.dst + (size_t)r * ow, ow, r, p, y, y, false);
+    }
+  }
+  const int c0 = band * (kBandRows / 2), c1 = c0 + kBandRows / 2 < och ? c0 + kBandRows / 2 : och;
+  if (c1 <= c0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  const ResizePlane u = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t)ocw, (uint32_t)och};
+  const ResizePlane v = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t)ocw, (uint32_t)och};
+  uint8_t* dc = j.dst + (size_t)ow * oh;
+  if (j.format == LH264_FMT_NV12) {
+    const int pieces = (ow + 6) >> 2, items = (c1 - c0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = c0 + it / pieces, p = it % pieces;
+      piece_resized (dc + (size_t)r * ow, ow, r, p, u, v, true);
+    }
+  } else {
+    const int pieces = (ocw + 6) >> 2, per_plane = (c1 - c0) * pieces;
+    for (int it = t; it < 2 * per_plane; it += nt) {
+      const int plane = it >= per_plane, q = it - plane * per_plane;
+      const int r = c0 + q / pieces, p = q % pieces;
+      piece_resized (dc + (size_t)plane * ocw * och + (size_t)r * ocw, ocw, r, p, plane ? v : u, u, false);
+    }
+  }
+}
+// what the resize entry points and the call accept as a size: both even, 2..4096
+inline bool size_ok (int64_t out_w, int64_t out_h) {
+  return out_w >= 2 && out_w <= 4096 && out_h >= 2 && out_h <= 4096 && !((out_w | out_h) & 1);
+}
+
 }  // namespace lh264pack
 
 // one workgroup per (picture, band)
@@ -254,6 +368,13 @@ __global__ void __launch_bounds__ (256) decode_pack_scaled_kernel (const lh264_p
   lh264pack::scaled_size (j.crop_w, j.crop_h, j.reserved, &ow, &oh);
   if ((int)blockIdx.y * lh264pack::kBandRows >= oh) return;
   lh264pack::pack_band_scaled (j, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+// one workgroup per (picture, band of 16 delivered luma rows): every job of the launch is delivered as out_w x out_h (a withheld
+// picture's job has no window and nothing is done for it)
+__global__ void __launch_bounds__ (256) decode_pack_resized_kernel (const lh264_pack_job_t* __restrict__ jobs, int out_w, int out_h) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.crop_w <= 0 || j.crop_h <= 0 || (int)blockIdx.y * lh264pack::kBandRows >= out_h) return;
+  lh264pack::pack_band_resized (j, out_w, out_h, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
@@ -487,6 +608,36 @@ int lh264_debug_pack_dev (const lh264_pack_job_t* jobs, int n) {
   return ok ? LH264_OK : LH264_E_HIP;
 }
 
+// a table of jobs the resize entry points take: windows the front end can deliver (even, up to 16,384 a side), reserved 0
+static bool resize_jobs_ok (const lh264_pack_job_t* jobs, int n, int out_w, int out_h) {
+  if (!jobs || n <= 0 || !lh264pack::size_ok (out_w, out_h)) return false;
+  for (int k = 0; k < n; k++) {
+    const lh264_pack_job_t& j = jobs[k];
+    if (!j.y || !j.u || !j.v || !j.dst || j.crop_w <= 0 || j.crop_h <= 0 || j.crop_w > 16384 || j.crop_h > 16384 || ((j.crop_w | j.crop_h | j.crop_x | j.crop_y) & 1) ||
+        j.crop_x < 0 || j.crop_y < 0 || (j.format != LH264_FMT_I420 && j.format != LH264_FMT_NV12) || j.reserved != 0) return false;
+  }
+  return true;
+}
+
+int lh264_debug_resize_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h) {
+  if (!resize_jobs_ok (jobs, n, out_w, out_h)) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) for (int band = 0; band * lh264pack::kBandRows < out_h; band++) lh264pack::pack_band_resized (jobs[k], out_w, out_h, band, 0, 1);
+  return LH264_OK;
+}
+
+int lh264_debug_resize_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h) {
+  if (!resize_jobs_ok (jobs, n, out_w, out_h)) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  lh264_pack_job_t* d_jobs = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_pack_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_pack_job_t), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n, (unsigned) ((out_h + lh264pack::kBandRows - 1) / lh264pack::kBandRows)), dim3 (256), 0, 0, d_jobs, out_w, out_h);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs);
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
   if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
@@ -539,7 +690,7 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
-  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V4 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
+  if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V5 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V4 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
                ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
@@ -551,10 +702,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
   const bool opts_v4 = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V4;
   if (opts_v4 && (opts->scale_log2 > 3 || opts->reserved2 != 0)) return LH264_E_ARG;
   const int scale = opts_v4 ? (int)opts->scale_log2 : 0;      // 0: decode_pack_kernel, as ever; 1..3: decode_pack_scaled_kernel
-  const bool opts_v5 = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t);
+  const bool opts_v5 = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V5;
   if (opts_v5 && (opts->pick > LH264_PICK_IDR || opts->reserved3 != 0 || (opts->pick != LH264_PICK_ALL && conceal != 0))) return LH264_E_ARG;
   const uint32_t pick = opts_v5 ? opts->pick : LH264_PICK_ALL;
   const bool picking = pick != LH264_PICK_ALL;      // unselected pictures are walked by their headers only, every selected one is a chain
+  const bool opts_v6 = opts && opts->struct_bytes == sizeof (lh264_decode_opts_t);
+  const bool sized = opts_v6 && (opts->out_width || opts->out_height);
+  if (opts_v6 && (opts->reserved4 != 0 || opts->reserved5 != 0 || (sized && (!lh264pack::size_ok (opts->out_width, opts->out_height) || scale != 0)))) return LH264_E_ARG;
+  const int out_w = sized ? (int)opts->out_width : 0, out_h = sized ? (int)opts->out_height : 0;      // 0, 0: the window (or its scale); else decode_pack_resized_kernel
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -892,7 +1047,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::scaled_size (f->crop_w, f->crop_h, scale, &ow, &oh); bytes += (size_t)ow * oh * 3 / 2; shown++; } }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += (size_t)ow * oh * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -996,7 +1151,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
         pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
         int ow, oh;
-        lh264pack::scaled_size (f.crop_w, f.crop_h, scale, &ow, &oh);      // what is delivered
+        lh264pack::delivered_size (f.crop_w, f.crop_h, scale, out_w, out_h, &ow, &oh);      // what is delivered
         const size_t bytes = (size_t)ow * oh * 3 / 2;
         lh264_decoded_pic_t dp;
         dp.width = ow; dp.height = oh; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
@@ -1032,7 +1187,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     }
     for (int c = 0; c < n_chains; c++) {
       DStream& s = *rd.chains[c].s;
-      for (auto& f : s.sel) { int ow, oh; lh264pack::scaled_size (f->crop_w, f->crop_h, scale, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
+      for (auto& f : s.sel) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
       // the slots the round leaves free: pictures the DPB behind the round's last picture does not hold
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
       for (Slot& sl : s.pool) if (sl.pic_id >= 0 && (picking || std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end())) sl.pic_id = -1;      // (opts->pick: a slot is needed for its round only)
@@ -1054,7 +1209,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
       if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
       if (ok) {
-        if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
+        if (out_w) hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), out_w, out_h);
+        else if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         ok = hipGetLastError() == hipSuccess;
       }

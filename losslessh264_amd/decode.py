@@ -22,8 +22,8 @@ class _DevSpan:
 class DecodedBatch:
     """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
 
-    def __init__(self, lib, handles, device_out, sink_keepalive=None):
-        self._lib, self._h, self.device_out, self._keep = lib, handles, device_out, sink_keepalive
+    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None):
+        self._lib, self._h, self.device_out, self._keep, self.size = lib, handles, device_out, sink_keepalive, size
 
     def __len__(self):
         return len(self._h)
@@ -125,6 +125,16 @@ class DecodedBatch:
             self.zero_copy = False
             return t
 
+    def frames(self, i):
+        """device_out=True together with size=(W, H): the pictures of stream i as a (pictures, H * 3 // 2, W) torch.uint8 view of
+        tensor(i) - rows 0..H-1 of a picture are its luma plane, the H / 2 rows behind them its chroma bytes as packed (I420: Cb then
+        Cr, two chroma rows per row of the view; NV12: the interleaved rows).  Every stream of the batch has the same picture shape"""
+        if not self.device_out or self.size is None:
+            raise RuntimeError("frames() needs decode_batch (device_out=True, size=(W, H))")
+        w, h = self.size
+        t = self.tensor(i)
+        return t.view(t.numel() // (w * h * 3 // 2), h * 3 // 2, w)      # (a stream that delivered nothing: 0 pictures)
+
     def free(self):
         for h in self._h:
             self._lib.lh264_decoded_free(h)
@@ -137,7 +147,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all"):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -163,8 +173,23 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     pick: "all" (the default) | "intra" | "idr": only the selected pictures are decoded and delivered - "intra": the pictures whose
     slices are all I slices, "idr": the IDR pictures.  Each is byte for byte that picture of the full decode; of the others the front end
     walks the headers only and never sees the slice data, so damage there is neither seen nor reported.  DecodedBatch.picture_indices(i)
-    gives the delivered pictures' numbers in the stream, parsed_slices(i) what was parsed.  Not together with conceal."""
+    gives the delivered pictures' numbers in the stream, parsed_slices(i) what was parsed.  Not together with conceal.
+    size: None | (W, H), both even ints in 2..4096, not together with scale: every delivered picture of every stream is W x H, resampled
+    from its cropped window by an exact, integer area average on the device (decode_pack_resized_kernel).  Each plane on its own: luma
+    from w x h to W x H, Cb and Cr from w/2 x h/2 to W/2 x H/2.  For a plane of w x h samples p[y][x] delivered as ow x oh: the weight of
+    source column x for delivered column X is wx (X, x) = max (0, min ((x+1)*ow, (X+1)*w) - max (x*ow, X*w)) (non-zero for x in
+    X*w // ow .. ((X+1)*w - 1) // ow, the weights of one X sum to w), wy (Y, y) the same with h, oh; S = the sum of wy * wx * p[y][x],
+    D = w*h, delivered sample = (2*S + D) // (2*D): round half up, exact.  No coordinate leaves the window; the aspect ratio is not
+    kept; chroma siting is not modelled.  size == the window gives the window, a window of B times the size (B = 2, 4, 8) the bytes of
+    scale = 1, 2, 3; a larger size repeats samples and blends the seams.  pictures / the sink / the digests describe what is
+    delivered, source_sizes the windows; with device_out=True, DecodedBatch.frames(i) is a (pictures, H * 3 // 2, W) view."""
     lib = L.lib()
+    if size is not None:
+        ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and 2 <= v <= 4096 and v % 2 == 0 for v in size)
+        if not ok:
+            raise ValueError("size must be None or a pair (W, H) of even ints in 2..4096")
+        if scale != 0:
+            raise ValueError("size and scale exclude one another")
     if pick not in L.PICK:
         raise ValueError("pick must be 'all', 'intra' or 'idr'")
     if pick != "all" and conceal not in (None, "off"):
@@ -185,8 +210,10 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
     lens = (C.c_size_t * n)(*[len(d) for d in keep])
-    opts = L.DecodeOptsV5()
-    opts.struct_bytes = C.sizeof(L.DecodeOptsV5)
+    opts = L.DecodeOptsV6()
+    opts.struct_bytes = C.sizeof(L.DecodeOptsV6)
+    if size is not None:
+        opts.out_width, opts.out_height = int(size[0]), int(size[1])
     opts.pick = L.PICK[pick]
     opts.scale_log2 = int(scale)
     opts.parse, opts.parse_flags = L.PARSE_MODES[parse]
@@ -214,7 +241,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
-    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None)
 
 
 def decode_arena_bytes():
@@ -224,9 +251,9 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all"):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None):
     """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
-    pictures, bytes)]; scale and pick as in decode_batch"""
+    pictures, bytes)]; scale, pick and size as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     names = [os.path.join(out_dir, os.path.basename(p) + ".yuv") for p in paths]
@@ -238,7 +265,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size)
     finally:
         for f in files:
             f.close()
@@ -247,13 +274,13 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all"):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
-    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale and pick as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick and size as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size)
     res = []
     try:
         for i, p in enumerate(paths):
