@@ -788,6 +788,73 @@ typedef struct lh264_decode_opts {
 #define LH264_PARSE_PATH_FALLBACK 2
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads,
                         const lh264_decode_opts_t* opts /* NULL = defaults */, lh264_decoded_t** out);
+/* ---- RGB pictures, colour-converted on the device: lh264_decode_batch_ex -------------------------------------------------------------
+ * The options above are frozen at 88 bytes; what comes after them travels in a struct of its own.  ext == NULL or ext->colour ==
+ * LH264_COLOUR_YUV is lh264_decode_batch, byte for byte and launch for launch (lh264_decode_batch is this call with ext == NULL).
+ * ORDER.  The conversion acts on the DELIVERED planes: first the window is copied, averaged (scale_log2) or resampled (out_width /
+ * out_height) exactly as without colour, which gives ow x oh luma and ow/2 x oh/2 Cb and Cr samples; then every luma sample (X, Y) is
+ * converted with the chroma sample (X >> 1, Y >> 1).  That is replication: chroma siting is NOT modelled, as everywhere else in this
+ * call.  So the RGB bytes of a call are the function below applied to the I420 bytes of the same call made without colour.
+ * STANDARD.  A matrix - BT.601: Kr = 299/1000, Kb = 114/1000; BT.709: Kr = 2126/10000, Kb = 722/10000; Kg = 1 - Kr - Kb - and a range,
+ * limited (y0 = 16, sy = 255/219, sc = 255/224) or full (y0 = 0, sy = sc = 1).  As real numbers, with D = Cb - 128 and E = Cr - 128:
+ *   R = sy*(Y - y0) + sc*2(1 - Kr)*E,   B = sy*(Y - y0) + sc*2(1 - Kb)*D,
+ *   G = sy*(Y - y0) - sc*(2Kb(1 - Kb)/Kg)*D - sc*(2Kr(1 - Kr)/Kg)*E.
+ * THE INTEGER FUNCTION (normative; what is delivered).  The five factors cy = sy, crv = sc*2(1 - Kr), cbu = sc*2(1 - Kb),
+ * cgu = sc*2Kb(1 - Kb)/Kg, cgv = sc*2Kr(1 - Kr)/Kg are the exact rationals times 65536, rounded half up to integers: the table
+ * LH264_COLOUR_FACTORS below, which the kernel, the host stepping and the documents all read (BT.601 full: crv = 91881; BT.601 limited:
+ * cy = 76309).  In int32, `>>` an arithmetic shift, clip8 a clamp to 0..255:
+ *   R = clip8 ((cy*(Y - y0) + crv*E + 32768) >> 16)
+ *   G = clip8 ((cy*(Y - y0) - cgu*D - cgv*E + 32768) >> 16)
+ *   B = clip8 ((cy*(Y - y0) + cbu*D + 32768) >> 16)
+ * Every sum stays below 2^27 in magnitude; there are no floats anywhere.  Against the real-valued formula rounded half up and clipped it
+ * differs by at most 1, in a small share of all (Y, Cb, Cr) triples (DESIGN.md section 4.6 has the count).
+ * LAYOUTS.  LH264_COLOUR_RGB24: oh rows of ow pixels stored R, G, B - 3*ow*oh bytes, tight.  LH264_COLOUR_RGBP: three ow x oh planes,
+ * R then G then B, tight.  Pictures lie one behind the other as ever; lh264_decoded_pic_t bytes / offset describe what is delivered
+ * (twice I420's bytes), and the round's output buffers, the download, the handles, the sink, DEVICE_OUT, NO_PICTURES and both digests
+ * work on those bytes.  Conceal, both parse routes, pick, scale_log2 and out_width / out_height act on what is decoded as without colour.
+ * decode_pack_rgb_kernel takes the pack kernel's place in the round and writes the RGB bytes in one pass: no I420 intermediate.
+ * WHICH STANDARD A STREAM GETS.  The front end reads the SPS VUI up to video_signal_type (aspect_ratio_info, overscan_info,
+ * video_signal_type with video_full_range_flag, colour_description_present_flag and matrix_coefficients) and no further.  matrix =
+ * LH264_MATRIX_AUTO: matrix_coefficients 1 gives BT.709; 5 or 6 give BT.601; 2 (unspecified), or no colour description, gives BT.601 -
+ * the project's material is QCIF to SD conformance content; any other value stops the stream with LH264_E_UNSUPPORTED and a text that
+ * names the value, at the first picture that carries it (a stream whose first SPS says so delivers nothing): a wrong colour is worse
+ * than a refusal, and the caller can name a matrix.  range = LH264_RANGE_AUTO: video_full_range_flag decides; absent means limited.  A
+ * named matrix or range overrides the stream's.  The standard is per picture (an SPS may change it inside a stream);
+ * lh264_decoded_picture_colour tells what was applied to delivered picture idx: *matrix LH264_MATRIX_BT601 or _BT709, *full_range 0 or 1
+ * (either may be NULL; LH264_E_ARG: a bad index, or a call without colour, which applied none).
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of lh264_decode_batch: a struct_bytes other than 24,
+ * colour, matrix or range above 2, a reserved word that is not 0, matrix or range set while colour is LH264_COLOUR_YUV, colour together
+ * with an opts->format other than LH264_FMT_I420. */
+#define LH264_COLOUR_YUV   0u
+#define LH264_COLOUR_RGB24 1u
+#define LH264_COLOUR_RGBP  2u
+#define LH264_MATRIX_AUTO  0u
+#define LH264_MATRIX_BT601 1u
+#define LH264_MATRIX_BT709 2u
+#define LH264_RANGE_AUTO    0u
+#define LH264_RANGE_LIMITED 1u
+#define LH264_RANGE_FULL    2u
+/* a standard in one byte, as the job tables carry it: bit 0 the matrix (0 BT.601, 1 BT.709), bit 1 the range (0 limited, 1 full);
+ * LH264_COLOUR_FACTORS[that byte] = {cy, crv, cbu, cgu, cgv}, y0 = 16 where bit 1 is clear */
+#define LH264_COLOUR_FACTORS { \
+  { 76309, 104597, 132201, 25675, 53279 },   /* BT.601 limited */ \
+  { 76309, 117489, 138438, 13975, 34925 },   /* BT.709 limited */ \
+  { 65536,  91881, 116130, 22553, 46802 },   /* BT.601 full    */ \
+  { 65536, 103206, 121609, 12276, 30679 } }  /* BT.709 full    */
+typedef struct lh264_decode_ext {
+  uint32_t struct_bytes;                /* 24                                                                   */
+  uint32_t colour;                      /* LH264_COLOUR_*; 0 = the planes as lh264_decode_batch delivers them   */
+  uint32_t matrix;                      /* LH264_MATRIX_*; 0 = what the stream's SPS says                       */
+  uint32_t range;                       /* LH264_RANGE_*; 0 = what the stream's SPS says                        */
+  uint32_t reserved0, reserved1;        /* 0                                                                    */
+} lh264_decode_ext_t;
+int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n, int threads,
+                           const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */, lh264_decoded_t** out);
+int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* matrix, int32_t* full_range);
+/* what the first SPS of an Annex-B file says about colour, without a device: *matrix_coefficients (2 = unspecified where the SPS
+ * carries none), *full_range (0 where it carries none), *present bit 0 = the VUI has a video_signal_type, bit 1 = it has a colour
+ * description.  Any of the three may be NULL.  LH264_E_ARG: data NULL; LH264_E_UNSUPPORTED: no SPS in the file that parses */
+int lh264_parser_colour (const uint8_t* data, size_t len, int32_t* matrix_coefficients, int32_t* full_range, int32_t* present);
 int lh264_decoded_status (const lh264_decoded_t* d);
 /* how the stream's slice data was parsed: LH264_PARSE_PATH_HOST (none of it on the device), _DEVICE (CAVLC slices by the kernel; CABAC
  * pictures and what follows the first of them by the host - with LH264_PARSE_FLAG_CABAC the slices of both entropy modes by the
@@ -861,6 +928,16 @@ int lh264_debug_pack_dev (const lh264_pack_job_t* jobs, int n);
  * without a device: LH264_E_NODEVICE */
 int lh264_debug_resize_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h);
 int lh264_debug_resize_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h);
+/* the same table delivered as RGB (lh264_decode_batch_ex): layout LH264_COLOUR_RGB24 or LH264_COLOUR_RGBP, std_per_job[k] the standard
+ * byte of job k (see LH264_COLOUR_FACTORS; a host array in both calls).  out_w, out_h != 0: every job as out_w x out_h, `reserved` 0;
+ * out_w == out_h == 0: each job by its `reserved` scale (0 = the window, 1..3 the means; the jobs of a table may differ).
+ * lh264_debug_rgb_cpu steps the code of decode_pack_rgb_kernel over HOST memory, lh264_debug_rgb_dev uploads the two tables (the jobs'
+ * pointers are device pointers), launches the production kernel and returns when it is through.  LH264_E_ARG: a layout or a standard
+ * byte that is not defined, a size that is neither 0, 0 nor a pair of even values in 2..4096, a `reserved` outside what the size
+ * allows, a format other than LH264_FMT_I420, a window that is not even, positive and at most 16384 a side, a NULL table, n <= 0;
+ * lh264_debug_rgb_dev without a device: LH264_E_NODEVICE */
+int lh264_debug_rgb_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job);
+int lh264_debug_rgb_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

@@ -33,6 +33,10 @@
     python -m losslessh264_amd --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096),
                                                             resampled on the device by an exact area average (decode_batch
                                                             (size=(W, H))); the aspect ratio is not kept.  Not with a non-zero --scale
+    python -m losslessh264_amd --decode [--sha1] --rgb rgb24|rgbp [--matrix auto|bt601|bt709] [--range auto|limited|full] ...   RGB pictures,
+                                                            colour-converted on the device (decode_batch (colour=...)): out_dir/<name>.rgb
+                                                            holds R, G, B per pixel (rgb24) or three planes per picture (rgbp); the
+                                                            matrix and range come from the stream's SPS unless named.  Not with --nv12
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -163,6 +167,7 @@ def restore(src, dst):
 
 
 SIZE_USAGE = "--size: WxH, both even, 2..4096; not with a non-zero --scale"
+RGB_USAGE = "--rgb: rgb24 | rgbp, not with --nv12; --matrix: auto | bt601 | bt709 and --range: auto | limited | full, with --rgb only"
 
 
 def parse_size(text):
@@ -178,7 +183,21 @@ def parse_size(text):
 def decode(argv):
     import losslessh264_amd as lh
     nv12, conceal, sha1, parse, scale, pick, size = False, None, False, "host", 0, "all", None
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size"):
+    colour, matrix, crange = None, None, None
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range"):
+        if argv[0] in ("--rgb", "--matrix", "--range"):
+            allowed = {"--rgb": ("rgb24", "rgbp"), "--matrix": tuple(lh._lib.MATRIX), "--range": tuple(lh._lib.RANGE)}[argv[0]]
+            if len(argv) < 2 or argv[1] not in allowed:
+                print(RGB_USAGE)
+                return 2
+            if argv[0] == "--rgb":
+                colour = argv[1]
+            elif argv[0] == "--matrix":
+                matrix = argv[1]
+            else:
+                crange = argv[1]
+            argv = argv[2:]
+            continue
         if argv[0] == "--size":
             size = parse_size(argv[1]) if len(argv) >= 2 else None
             if size is None:
@@ -213,16 +232,20 @@ def decode(argv):
     if size is not None and scale != 0:
         print(SIZE_USAGE)
         return 2
+    if (colour is not None and nv12) or (colour is None and (matrix is not None or crange is not None)):
+        print(RGB_USAGE)
+        return 2
+    ckw = dict(colour=colour, matrix=matrix or "auto", colour_range=crange or "auto")
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)
         return 2
     ret = 0
     if sha1:
-        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size):
+        for name, status, err, pics, total in lh.decode_to_sha1_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, **ckw):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, **ckw):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

@@ -169,12 +169,24 @@ class PackJob(C.Structure):         # reserved: the job's scale_log2 (0 = the co
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("dst", C.c_void_p),
                 ("stride_y", C.c_int32), ("stride_c", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
                 ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32)]
+class DecodeExt(C.Structure):       # lh264_decode_ext_t: what lh264_decode_batch_ex takes beside the frozen options
+    _fields_ = [("struct_bytes", C.c_uint32), ("colour", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+assert C.sizeof(DecodeExt) == 24
+COLOUR = {None: 0, "rgb24": 1, "rgbp": 2}                # LH264_COLOUR_*
+MATRIX = {"auto": 0, "bt601": 1, "bt709": 2}             # LH264_MATRIX_*
+RANGE = {"auto": 0, "limited": 1, "full": 2}             # LH264_RANGE_*
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
 assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 48 and C.sizeof(PackJob) == 64 and C.sizeof(RestoreOpts) == 12
 _SIGS.update({
     "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decode_batch_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_picture_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "lh264_parser_colour": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lh264_debug_rgb_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "lh264_debug_rgb_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "lh264_decoded_parse_path": (C.c_int, [C.c_void_p]),
     "lh264_decoded_device_slices": (C.c_longlong, [C.c_void_p]),
     "lh264_decoded_device_cabac_slices": (C.c_longlong, [C.c_void_p]),

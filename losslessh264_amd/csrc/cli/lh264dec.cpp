@@ -200,6 +200,12 @@ static int conceal_method (const char* name) {
   for (const auto& e : k) if (!strcmp (name, e.n)) return e.m;
   return -1;
 }
+// --rgb rgb24|rgbp [--matrix M] [--range R]: what lh264_decode_batch_ex takes beside the options (colour 0: lh264_decode_batch as ever)
+static lh264_decode_ext_t g_ext = {sizeof (lh264_decode_ext_t), LH264_COLOUR_YUV, LH264_MATRIX_AUTO, LH264_RANGE_AUTO, 0, 0};
+static const char* const kRgbUsage = "--rgb: rgb24 | rgbp, not with --nv12; --matrix: auto | bt601 | bt709 and --range: auto | limited | full, with --rgb only";
+static int one_of (const char* text, const char* a, const char* b, const char* c) {      // 0, 1, 2 or -1
+  return !strcmp (text, a) ? 0 : !strcmp (text, b) ? 1 : c && !strcmp (text, c) ? 2 : -1;
+}
 // --size WxH: both even, 2..4096
 static const char* const kSizeUsage = "--size: WxH, both even, 2..4096; not with a non-zero --scale";
 static bool parse_size (const char* text, int* w, int* h) {
@@ -222,14 +228,14 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   DecodeFiles files; files.f.assign (n, nullptr); files.bytes.assign (n, 0);
   std::vector<std::string> dsts (n);
   for (int i = 0; i < n; i++) {
-    dsts[i] = out_dir + "/" + base_name (srcs[i]) + ".yuv";
+    dsts[i] = out_dir + "/" + base_name (srcs[i]) + (g_ext.colour ? ".rgb" : ".yuv");
     files.f[i] = fopen (dsts[i].c_str(), "wb");
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
+  const int rc = lh264_decode_batch_ex (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, h.data());
   for (FILE* f : files.f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
@@ -253,7 +259,7 @@ static int decode_sha1_files (const std::string& out_dir, const std::vector<std:
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch (d.data(), l.data(), n, 0, &o, h.data());
+  const int rc = lh264_decode_batch_ex (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, h.data());
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
@@ -304,7 +310,7 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL;
+    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL; bool matrix_named = false;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
       else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
@@ -326,17 +332,26 @@ int main (int argc, char** argv) {
       } else if (first + 1 < argc && !strcmp (argv[first], "--size")) {
         if (!parse_size (argv[first + 1], &out_w, &out_h)) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
         first += 2;
+      } else if (first < argc && (!strcmp (argv[first], "--rgb") || !strcmp (argv[first], "--matrix") || !strcmp (argv[first], "--range"))) {
+        const char* v = first + 1 < argc ? argv[first + 1] : "";
+        const bool rgb = !strcmp (argv[first], "--rgb"), matrix = !strcmp (argv[first], "--matrix");
+        const int k = rgb ? one_of (v, "rgb24", "rgbp", nullptr) : matrix ? one_of (v, "auto", "bt601", "bt709") : one_of (v, "auto", "limited", "full");
+        if (k < 0) { fprintf (stderr, "%s\n", kRgbUsage); return 2; }
+        if (rgb) g_ext.colour = (uint32_t)k + LH264_COLOUR_RGB24;
+        else { (matrix ? g_ext.matrix : g_ext.range) = (uint32_t)k; matrix_named = true; }
+        first += 2;
       } else break;
     }
+    if ((g_ext.colour && nv12) || (!g_ext.colour && matrix_named)) { fprintf (stderr, "%s\n", kRgbUsage); return 2; }
     if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

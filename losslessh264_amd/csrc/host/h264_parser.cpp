@@ -361,6 +361,23 @@ struct Parser::Impl {
       s.crop_l = (int)cl; s.crop_r = (int)cr; s.crop_t = (int)ct; s.crop_b = (int)cb;
     }
     if (br.err) { fail ("truncated SPS"); return; }
+    // the VUI up to video_signal_type (E.1.1), for the colour conversion of the decode direction.  On a copy of the reader, and it
+    // only reads: an SPS that ends here, or whose VUI is cut short, is the SPS it always was and carries no colour information
+    {
+      BitReader v = br;
+      int mc = 2, present = 0; bool full = false;
+      if (v.u1()) {                                            // vui_parameters_present_flag
+        if (v.u1() && v.u (8) == 255) v.skip (32);             // aspect_ratio_info: aspect_ratio_idc, Extended_SAR: sar_width, sar_height
+        if (v.u1()) v.u1();                                    // overscan_info: overscan_appropriate_flag
+        if (v.u1()) {                                          // video_signal_type
+          present = 1;
+          v.u (3);                                             // video_format
+          full = v.u1();
+          if (v.u1()) { present = 3; v.u (16); mc = (int)v.u (8); }      // colour_primaries, transfer_characteristics, matrix_coefficients
+        }
+      }
+      if (!v.err) { s.matrix_coefficients = mc; s.full_range = full; s.colour_present = present; }
+    }
     s.valid = true;
     sps[id] = s;
   }
@@ -708,6 +725,7 @@ struct Parser::Impl {
     cur->id = next_frame_id++;
     cur->mb_w = S.mb_w; cur->mb_h = S.mb_h; cur->frame_num = sh.frame_num; cur->idr = sh.idr;
     cur->idr_pic_id = sh.idr_pic_id; cur->nal_ref_idc = sh.nal_ref_idc;
+    cur->matrix_coefficients = S.matrix_coefficients; cur->full_range = S.full_range;
     cur->crop_x = 2 * S.crop_l; cur->crop_y = 2 * S.crop_t;
     cur->crop_w = S.mb_w * 16 - 2 * (S.crop_l + S.crop_r); cur->crop_h = S.mb_h * 16 - 2 * (S.crop_t + S.crop_b);
     const size_t n = (size_t)S.mb_w * S.mb_h;
@@ -1907,6 +1925,23 @@ int Parser::parse_headers (const uint8_t* nal, size_t len, HeaderInfo& o) {
   o.is_slice = true; o.hdr_bits = (int)br.pos; o.mb_w = S.mb_w; o.mb_h = S.mb_h;
   o.cabac = P.cabac; o.transform_8x8 = P.transform_8x8; o.constrained_intra_pred = P.constrained_intra_pred;
   return 0;
+}
+bool Parser::first_sps_colour (const uint8_t* d, size_t n, int* matrix_coefficients, int* full_range, int* present) {
+  for (size_t i = 0; i + 3 < n; i++) {
+    if (d[i] || d[i + 1] || d[i + 2] != 1 || (d[i + 3] & 31) != 7) continue;
+    size_t end = i + 4;
+    while (end < n && !(end + 2 < n && d[end] == 0 && d[end + 1] == 0 && d[end + 2] <= 1)) end++;
+    Parser P;
+    HeaderInfo hi;
+    if (P.parse_headers (d + i + 3, end - (i + 3), hi) < 0 || !P.error().empty()) continue;
+    for (const auto& kv : P.d_->sps) if (kv.second.valid) {
+      if (matrix_coefficients) *matrix_coefficients = kv.second.matrix_coefficients;
+      if (full_range) *full_range = kv.second.full_range ? 1 : 0;
+      if (present) *present = kv.second.colour_present;
+      return true;
+    }
+  }
+  return false;
 }
 const std::vector<uint8_t>& Parser::last_rbsp() const { return d_->rbsp; }
 const std::string& Parser::out_of_range() const { return d_->symbolizer.out_of_range(); }

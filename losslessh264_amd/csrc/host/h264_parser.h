@@ -63,6 +63,9 @@ struct Sps {
   int crop_l = 0, crop_r = 0, crop_t = 0, crop_b = 0;
   bool scaling_matrix_present = false;
   uint8_t sl4[6][16], sl8[2][64];       // raster order, after fall-back rule A
+  // the VUI up to video_signal_type (E.1.1), read and nothing else: matrix_coefficients (2 = unspecified where there is no colour
+  // description), video_full_range_flag, and which of the two the SPS carried (bit 0 video_signal_type, bit 1 colour description)
+  int matrix_coefficients = 2; bool full_range = false; int colour_present = 0;
 };
 struct Pps {
   bool valid = false;
@@ -197,7 +200,8 @@ struct DeferredSlice {
 struct FrameOut {
   int id = 0, mb_w = 0, mb_h = 0, frame_num = 0, crop_w = 0, crop_h = 0, crop_x = 0, crop_y = 0;
   bool idr = false, is_ref = false, complete = false;
-  long index = 0;                       // the picture's number among the pictures its parser completed, in decode order from 0
+  int matrix_coefficients = 2; bool full_range = false;      // of the picture's SPS (Sps::matrix_coefficients, full_range)
+  long index = 0;                      // the picture's number among the pictures its parser completed, in decode order from 0
   PoolVec<lh264_mb_t> mbs;
   ZeroBuf<int16_t> coeffs, levels;
   std::vector<lh264_slice_t> slices;
@@ -331,6 +335,9 @@ class Parser {
   // (a deferred slice lies in front of whatever failed after it).  false: the slice failed, or there is no such slice
   bool parse_deferred (FrameOut& f, size_t slice);
   static bool conceal_method_ok (int method);
+  // what the first SPS of an Annex-B file that parses says about colour (Sps::matrix_coefficients, full_range, colour_present);
+  // false: there is none
+  static bool first_sps_colour (const uint8_t* data, size_t len, int* matrix_coefficients, int* full_range, int* present);
   int conceal() const { return conceal_; }
   // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
   // carry (Symbolizer::out_of_range: an mb_skip_run above 511, 16 active references).  Not an error of the stream: it parses and decodes

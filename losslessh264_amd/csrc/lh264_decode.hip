@@ -5,6 +5,8 @@
 // reconstructs them (one chain per stream; with opts->pick only intra or IDR pictures are decoded, the others are walked by their headers,
 // and every picture is a chain of its own), decode_pack_kernel behind it crops and packs them into the round's output buffer, and the
 // download of that buffer runs on a second HIP stream while the host threads parse and stage the next round.  DESIGN.md section 4.6.
+// lh264_decode_batch_ex is the same call with a second struct of options: with a colour, decode_pack_rgb_kernel takes the pack kernel's
+// place and the round's output buffer holds RGB24 or planar RGB pictures, converted from the planes the pack step would have delivered.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -352,6 +354,154 @@ inline bool size_ok (int64_t out_w, int64_t out_h) {
   return out_w >= 2 && out_w <= 4096 && out_h >= 2 && out_h <= 4096 && !((out_w | out_h) & 1);
 }
 
+// ---- the pack step to RGB: lh264_decode_batch_ex (the definition: include/lh264.h at lh264_decode_batch_ex) -------------------------
+// The delivered planes are never stored: a sample of the ow x oh luma plane or of the ow/2 x oh/2 chroma planes is worked out where it
+// is needed, by the rule of the job's sizing - the window's own sample, mean_clamped / means_whole of the reduced-size step, or
+// resized_sample of the step to one size - and goes through the integer function with the factors of LH264_COLOUR_FACTORS.  The bands
+// are 16 delivered luma rows = 8 PAIRS of rows; a pair's rows are cut into pieces of 8 pixels' bytes (24 in RGB24, 8 per plane in
+// RGBP) of the DESTINATION, counted from the aligned address at or below the first byte of the pair's upper row - and of its lower row,
+// whose alignment differs by 0 or 2 (a row is 3*ow or ow bytes, ow even).  An item is one piece of both rows: it converts the 2x2 quads
+// under its bytes, each quad's chroma sample and chroma terms once for its four pixels (a quad on the seam of two pieces is worked out
+// by both: 5 or 6 quads per item where 4 are its own), lays the pixels out as the row's byte stream in registers, and shifts the
+// stream to the piece's alignment.  A whole piece leaves as aligned 4-byte stores, the pieces at a row's head and tail byte by byte: no
+// byte outside the window is read, none outside the picture's bytes written.  No LDS.
+constexpr int32_t kColourFactors[4][5] = LH264_COLOUR_FACTORS;
+constexpr int kRgbQuads = 6;       // the quads an item can touch: 8 pixels' bytes at any alignment of either row lie within 12 pixels
+
+// clamp to 0..255.  On the device one v_med3_i32, written out: left to the compiler, two neighbouring clamps of shifted sums are fused
+// into gfx950's v_ashr_pk_u8_i32, and the bytes that came back from an MI355X for exactly those pairs were not the clamp's where a sum
+// was negative
+__host__ __device__ inline uint32_t clip8 (int32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int32_t r;
+  asm ("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(255));
+  return (uint32_t)r;
+#else
+  return v < 0 ? 0u : v > 255 ? 255u : (uint32_t)v;
+#endif
+}
+
+// delivered sample (X, Y) of one plane under sizing M: 0 the window, 1..3 the means of scale_log2, 4 the given size (sy: the rows of Y)
+template <int M>
+__host__ __device__ inline int plane_sample (const ResizePlane& pl, const Span& sy, int X, int Y) {
+  if constexpr (M == 0) return pl.p[(size_t)Y * pl.stride + X];
+  else if constexpr (M <= 3) return mean_clamped<M> (pl.p, pl.stride, (int)pl.w, (int)pl.h, X, Y);
+  else return resized_sample (pl, sy, X);
+}
+// delivered luma samples (X, Y) and (X + 1, Y), X even: the second in bits 8..15
+template <int M>
+__host__ __device__ inline uint32_t luma_pair (const ResizePlane& pl, const Span& sy, int X, int Y) {
+  if constexpr (M >= 1 && M <= 3) {
+    constexpr int B = 1 << M;
+    if ((X + 2) * B <= (int)pl.w && (Y + 1) * B <= (int)pl.h) return means_whole<M, 2> (pl.p + (size_t)Y * B * pl.stride + X * B, pl.stride) & 0xffffu;
+  }
+  return (uint32_t)plane_sample<M> (pl, sy, X, Y) | (uint32_t)plane_sample<M> (pl, sy, X + 1, Y) << 8;
+}
+
+// piece p of row pair R of one job delivered as ow x oh in layout L (LH264_COLOUR_RGB24 / _RGBP) with the factors f and luma offset y0
+template <int M, int L>
+__host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, int ow, int oh,
+                                           const int32_t* f, int y0, int R, int p) {
+  constexpr int BPP = L == (int)LH264_COLOUR_RGB24 ? 3 : 1, NP = L == (int)LH264_COLOUR_RGB24 ? 1 : 3;      // bytes per pixel and planes of the destination
+  constexpr int PB = 8 * BPP, ND = PB / 4, NW = 12 * BPP / 4;                                                 // a piece's bytes and words; the words of 12 pixels
+  const int row_bytes = BPP * ow;
+  uint8_t* d[2] = {dst + (size_t) (2 * R) * row_bytes, dst + (size_t) (2 * R + 1) * row_bytes};
+  int a[2];
+  for (int rr = 0; rr < 2; rr++) a[rr] = p * PB - (int) ((uintptr_t)d[rr] & 3u);
+  if ((a[0] < a[1] ? a[0] : a[1]) >= row_bytes) return;
+  // the first pixel of the item's 12: the even pixel at or below the first byte of either row's piece (a may be -3 .. -1 at a row's head)
+  const int amin = a[0] < a[1] ? a[0] : a[1];
+  const int x0 = 2 * ((amin + 2 * BPP * 4) / (2 * BPP) - 4);
+  Span sy[2], sc;
+  if constexpr (M == 4) { sy[0] = span_of ((uint32_t) (2 * R), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1), py.h, py.oh); sc = span_of ((uint32_t)R, pu.h, pu.oh); }
+  else { sy[0] = sy[1] = sc = Span(); }
+  // the 12 pixels of both rows as byte streams: RGB24 one stream of 36 bytes, RGBP three of 12
+  uint32_t W[2][NP][NW + 1];
+  for (int rr = 0; rr < 2; rr++) for (int c = 0; c < NP; c++) for (int k = 0; k <= NW; k++) W[rr][c][k] = 0;
+  _Pragma ("unroll")
+  for (int q = 0; q < kRgbQuads; q++) {
+    const int X = x0 + 2 * q;
+    if (X < 0 || X >= ow) continue;
+    const int D = plane_sample<M> (pu, sc, X >> 1, R) - 128, E = plane_sample<M> (pv, sc, X >> 1, R) - 128;
+    const int32_t tr = f[1] * E + 32768, tg = 32768 - f[3] * D - f[4] * E, tb = f[2] * D + 32768;
+    _Pragma ("unroll")
+    for (int rr = 0; rr < 2; rr++) {
+      const uint32_t yy = luma_pair<M> (py, sy[rr], X, 2 * R + rr);
+      _Pragma ("unroll")
+      for (int i = 0; i < 2; i++) {
+        const int32_t yt = f[0] * ((int32_t) (yy >> (8 * i) & 0xffu) - y0);
+        const uint32_t r = clip8 ((yt + tr) >> 16), g = clip8 ((yt + tg) >> 16), b = clip8 ((yt + tb) >> 16);
+        const int k = 2 * q + i;                                   // the pixel's place among the 12
+        if constexpr (L == (int)LH264_COLOUR_RGB24) {
+          const uint32_t px = r | g << 8 | b << 16;
+          const int bit = 24 * k;                                  // (compile-time once the loops are unrolled)
+          W[rr][0][bit >> 5] |= px << (bit & 31);
+          if ((bit & 31) > 8) W[rr][0][(bit >> 5) + 1] |= px >> (32 - (bit & 31));
+        } else {
+          W[rr][0][k >> 2] |= r << (8 * (k & 3)); W[rr][1][k >> 2] |= g << (8 * (k & 3)); W[rr][2][k >> 2] |= b << (8 * (k & 3));
+        }
+      }
+    }
+  }
+  for (int rr = 0; rr < 2; rr++) {
+    if (a[rr] >= row_bytes) continue;
+    const int s = a[rr] - BPP * x0;                                // where the piece begins in the stream: 0 .. 2*BPP + 1
+    const int h = s >> 2, sh = 8 * (s & 3);
+    const bool whole = a[rr] >= 0 && a[rr] + PB <= row_bytes;
+    for (int c = 0; c < NP; c++) {
+      uint8_t* o = d[rr] + (size_t)c * ow * oh + a[rr];
+      _Pragma ("unroll")
+      for (int j = 0; j < ND; j++) {
+        // word j of the piece = stream bytes s + 4*j .. s + 4*j + 3; s < 8, so it begins in word j or j + 1 (j + 2 <= NW in both layouts)
+        const uint32_t lo = h ? W[rr][c][j + 1] : W[rr][c][j], hi = h ? W[rr][c][j + 2] : W[rr][c][j + 1];
+        const uint32_t v = sh ? lo >> sh | hi << (32 - sh) : lo;
+        if (whole) * (uint32_t*) (o + 4 * j) = v;
+        else for (int i = 0; i < 4; i++) { const int at = a[rr] + 4 * j + i; if (at >= 0 && at < row_bytes) o[4 * j + i] = (uint8_t) (v >> (8 * i)); }
+      }
+    }
+  }
+}
+
+// band `band` (16 delivered luma rows) of one job delivered as ow x oh RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
+template <int M, int L>
+__host__ __device__ inline void pack_band_rgb_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h;
+  const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
+  if (R1 <= R0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  int32_t f[5];
+  for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
+  const int y0 = (std_byte & 2) ? 0 : 16;
+  constexpr int PB = L == (int)LH264_COLOUR_RGB24 ? 24 : 8;
+  const int row_bytes = (L == (int)LH264_COLOUR_RGB24 ? 3 : 1) * ow;
+  const int pieces = (row_bytes + 3 + PB - 1) / PB, items = (R1 - R0) * pieces;
+  for (int it = t; it < items; it += nt) piece_rgb<M, L> (j.dst, py, pu, pv, ow, oh, f, y0, R0 + it / pieces, it % pieces);
+}
+// ... of a job whose sizing is its `reserved` scale (out_w == 0) or the given size; layout and standard byte as given.  Anything that is
+// not defined: nothing is done
+__host__ __device__ inline void pack_band_rgb (const lh264_pack_job_t& j, int out_w, int out_h, int layout, int std_byte, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved < 0 || j.reserved > 3 || (out_w && j.reserved)) return;
+  int ow, oh;
+  delivered_size (j.crop_w, j.crop_h, j.reserved, out_w, out_h, &ow, &oh);
+  const int m = out_w ? 4 : j.reserved;
+  if (layout == (int)LH264_COLOUR_RGB24) {
+    if (m == 0) pack_band_rgb_as<0, (int)LH264_COLOUR_RGB24> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 1) pack_band_rgb_as<1, (int)LH264_COLOUR_RGB24> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 2) pack_band_rgb_as<2, (int)LH264_COLOUR_RGB24> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 3) pack_band_rgb_as<3, (int)LH264_COLOUR_RGB24> (j, ow, oh, std_byte, band, t, nt);
+    else pack_band_rgb_as<4, (int)LH264_COLOUR_RGB24> (j, ow, oh, std_byte, band, t, nt);
+  } else if (layout == (int)LH264_COLOUR_RGBP) {
+    if (m == 0) pack_band_rgb_as<0, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 1) pack_band_rgb_as<1, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 2) pack_band_rgb_as<2, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
+    else if (m == 3) pack_band_rgb_as<3, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
+    else pack_band_rgb_as<4, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
+  }
+}
+
 }  // namespace lh264pack
 
 // one workgroup per (picture, band)
@@ -377,6 +527,13 @@ __global__ void __launch_bounds__ (256) decode_pack_resized_kernel (const lh264_
   lh264pack::pack_band_resized (j, out_w, out_h, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
+// one workgroup per (picture, band of 16 delivered luma rows): the jobs as RGB in one layout, job k by the standard byte std[k]; out_w,
+// out_h the given size or 0, 0 (then each job by its `reserved` scale).  A withheld picture's job has no window and nothing is done for it
+__global__ void __launch_bounds__ (256) decode_pack_rgb_kernel (const lh264_pack_job_t* __restrict__ jobs, const uint8_t* __restrict__ std, int out_w, int out_h, int layout) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  lh264pack::pack_band_rgb (j, out_w, out_h, layout, (int)std[blockIdx.x], (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
 // One lane per span job, 64 jobs per wave (a message is serial; the width comes from the batch).  The host orders a launch's jobs by
 // descending length, so the lanes of a wave end near one another.  No LDS, no wave waits for another; every bound is the job's.
@@ -397,6 +554,7 @@ struct lh264_decoded {
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
   long parsed_slices = 0;                       // distinct slices whose slice data was parsed, on either route
   std::vector<int32_t> index;                   // per delivered picture: its number among the stream's pictures in decode order
+  std::vector<uint8_t> colour;                  // lh264_decode_batch_ex with colour: per delivered picture the standard byte that was applied
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
   uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
@@ -461,6 +619,7 @@ struct PicCache {
 struct Arena {
   DevBuf d_mbs, d_coef, d_sparse, d_sl, d_jobs, d_first, d_pack, d_out[2];
   PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
+  DevBuf d_std; PinBuf h_std[2];      // lh264_decode_batch_ex with colour: the standard byte of every pack job, beside d_pack
   // digests: the span jobs, a round's results (20 bytes per picture, then a copy of every chain's stream record), the records of the
   // picture messages (scratch), and one record per stream of the batch that lives as long as the call
   DevBuf d_sjobs, d_dig, d_rec, d_state;
@@ -487,12 +646,12 @@ struct Arena {
   }
   size_t device_bytes() const {
     size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
-    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef}) n += b->cap;
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef, &d_std}) n += b->cap;
     return n;
   }
   size_t pinned_bytes() const {
     size_t n = h_pbytes.cap + h_ptasks.cap + h_pres.cap;
-    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap;
+    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap + h_std[b].cap;
     return n;
   }
 };
@@ -534,6 +693,7 @@ struct RoundChain {
   int first_picture = 0;
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed, source_wh, index;
+  std::vector<uint8_t> colour;                       // lh264_decode_batch_ex with colour: per delivered picture its standard byte
   size_t at = 0, bytes = 0;                          // in the round's output buffer
   size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
 };
@@ -556,6 +716,18 @@ std::string refuse_picture (const FrameOut& f) {
   if (f.crop_w <= 0 || f.crop_h <= 0 || (f.crop_w & 1) || (f.crop_h & 1) || f.crop_x < 0 || f.crop_y < 0 || (f.crop_x & 1) || (f.crop_y & 1) ||
       f.crop_x + f.crop_w > f.mb_w * 16 || f.crop_y + f.crop_h > f.mb_h * 16) return "a crop window outside the picture";
   return "";
+}
+
+// the standard byte of a picture under the call's matrix and range (see LH264_COLOUR_FACTORS); 0xff: the matrix is left to the stream
+// and its matrix_coefficients has no conversion here
+uint8_t picture_standard (const FrameOut& f, uint32_t matrix, uint32_t range) {
+  int m;
+  if (matrix != LH264_MATRIX_AUTO) m = matrix == LH264_MATRIX_BT709;
+  else if (f.matrix_coefficients == 1) m = 1;
+  else if (f.matrix_coefficients == 2 || f.matrix_coefficients == 5 || f.matrix_coefficients == 6) m = 0;
+  else return 0xff;
+  const int full = range != LH264_RANGE_AUTO ? range == LH264_RANGE_FULL : f.full_range;
+  return (uint8_t) (m | full << 1);
 }
 
 lh264host::PerDevice<Arena> g_arena;      // one decode call at a time per device
@@ -638,6 +810,45 @@ int lh264_debug_resize_dev (const lh264_pack_job_t* jobs, int n, int out_w, int 
   return ok ? LH264_OK : LH264_E_HIP;
 }
 
+// a table the RGB entry points take: windows the front end can deliver, I420, a layout and standard bytes that are defined, and a sizing:
+// the given size with reserved 0, or 0, 0 with reserved 0..3.  *max_bands: the bands of the tallest delivered picture
+static bool rgb_jobs_ok (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, int* max_bands) {
+  if (!jobs || !std_per_job || n <= 0 || (layout != (int)LH264_COLOUR_RGB24 && layout != (int)LH264_COLOUR_RGBP)) return false;
+  if ((out_w || out_h) && !lh264pack::size_ok (out_w, out_h)) return false;
+  *max_bands = 1;
+  for (int k = 0; k < n; k++) {
+    const lh264_pack_job_t& j = jobs[k];
+    if (!j.y || !j.u || !j.v || !j.dst || j.crop_w <= 0 || j.crop_h <= 0 || j.crop_w > 16384 || j.crop_h > 16384 || ((j.crop_w | j.crop_h | j.crop_x | j.crop_y) & 1) ||
+        j.crop_x < 0 || j.crop_y < 0 || j.format != LH264_FMT_I420 || j.reserved < 0 || j.reserved > (out_w ? 0 : 3) || std_per_job[k] > 3) return false;
+    int ow, oh;
+    lh264pack::delivered_size (j.crop_w, j.crop_h, j.reserved, out_w, out_h, &ow, &oh);
+    *max_bands = std::max (*max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows);
+  }
+  return true;
+}
+
+int lh264_debug_rgb_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job) {
+  int max_bands = 0;
+  if (!rgb_jobs_ok (jobs, n, out_w, out_h, layout, std_per_job, &max_bands)) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) for (int band = 0; band < max_bands; band++) lh264pack::pack_band_rgb (jobs[k], out_w, out_h, layout, std_per_job[k], band, 0, 1);
+  return LH264_OK;
+}
+
+int lh264_debug_rgb_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job) {
+  int max_bands = 0;
+  if (!rgb_jobs_ok (jobs, n, out_w, out_h, layout, std_per_job, &max_bands)) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  lh264_pack_job_t* d_jobs = nullptr; uint8_t* d_std = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_pack_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_pack_job_t), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMalloc ((void**)&d_std, (size_t)n) == hipSuccess && hipMemcpy (d_std, std_per_job, (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL (decode_pack_rgb_kernel, dim3 ((unsigned)n, (unsigned)max_bands), dim3 (256), 0, 0, d_jobs, d_std, out_w, out_h, layout);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs); hipFree (d_std);
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
   if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
@@ -689,7 +900,17 @@ int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, 
 }
 
 int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex (data, len, n, threads, opts, nullptr, out);
+}
+
+int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
+  if (ext && (ext->struct_bytes != sizeof (lh264_decode_ext_t) || ext->colour > LH264_COLOUR_RGBP || ext->matrix > LH264_MATRIX_BT709 || ext->range > LH264_RANGE_FULL ||
+              ext->reserved0 != 0 || ext->reserved1 != 0 || (ext->colour == LH264_COLOUR_YUV && (ext->matrix != LH264_MATRIX_AUTO || ext->range != LH264_RANGE_AUTO)) ||
+              (ext->colour != LH264_COLOUR_YUV && opts && opts->format != LH264_FMT_I420))) return LH264_E_ARG;
+  // 0: the planes, decode_pack_kernel and its siblings as ever; else decode_pack_rgb_kernel in their place, 3 bytes per delivered luma sample
+  const int colour = ext ? (int)ext->colour : 0;
+  const uint32_t ext_matrix = ext ? ext->matrix : LH264_MATRIX_AUTO, ext_range = ext ? ext->range : LH264_RANGE_AUTO;
   if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V5 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V4 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
@@ -794,7 +1015,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       // a change of resolution ends the round: the next one starts with a new pool.  (Asked first: on the device route the tentative
       // pass stopped here too, so the picture's slice data is not parsed yet and there is nothing to refuse it by)
       if (!s.sel.empty() && (f.mb_w != s.sel[0]->mb_w || f.mb_h != s.sel[0]->mb_h)) break;
-      const std::string why = tentative ? std::string() : refuse_picture (f);
+      std::string why = tentative ? std::string() : refuse_picture (f);
+      if (!tentative && why.empty() && colour && picture_standard (f, ext_matrix, ext_range) > 3) why = "matrix_coefficients " + std::to_string (f.matrix_coefficients) + " has no conversion here (BT.601: 5, 6, 2 or none; BT.709: 1): name a matrix";
       if (!why.empty()) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + why; break; }
       s.sel.push_back (std::move (s.pending.front())); s.pending.pop_front();
     }
@@ -844,6 +1066,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
+        r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, (int)k);
       }
     } else {
@@ -856,6 +1079,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
+        r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, k);
       });
     }
@@ -1047,7 +1271,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += (size_t)ow * oh * 3 / 2; shown++; } }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += colour ? (size_t)ow * oh * 3 : (size_t)ow * oh * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -1078,7 +1302,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
                A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_launch + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
                A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
-               A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t));
+               A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
+               (!colour || (A.d_std.alloc (n_jobs) && A.h_std[rb].alloc (n_jobs)));
     const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
     rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
     const size_t dig_bytes = rd.dig_states_at + (size_t)n_chains * sizeof (lh264_sha1_state_t);
@@ -1108,6 +1333,7 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
     // ---- staging (host threads): records to the page-locked buffers, the job tables
     lh264_mb_t* h_mbs = A.h_mbs[rb].as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse[rb].as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl[rb].as<lh264_slice_t>();
     lh264_frame_job_t* h_jobs = A.h_jobs[rb].as<lh264_frame_job_t>(); int32_t* h_first = A.h_first[rb].as<int32_t>(); lh264_pack_job_t* h_pack = A.h_pack[rb].as<lh264_pack_job_t>();
+    uint8_t* h_std = colour ? A.h_std[rb].as<uint8_t>() : nullptr;
     uint8_t* const d_out = A.d_out[rb].as<uint8_t>();
     run_parallel (n_chains, threads, [&] (int c) {
       RoundChain& rc = rd.chains[c];
@@ -1145,6 +1371,8 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
         pj.reserved = scale;
+        const uint8_t std_byte = colour ? picture_standard (f, ext_matrix, ext_range) : 0;      // (a picture select() let through: its standard is defined)
+        if (colour) h_std[j] = std_byte & 3;
         if (f.frozen) { if (!on_dev) mo += nm; so += f.slices.size(); j++; continue; }      // withheld: a reference like any other, but no window to pack (crop_h 0)
         pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
         pj.dst = d_out + at;
@@ -1152,13 +1380,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
         pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
         int ow, oh;
         lh264pack::delivered_size (f.crop_w, f.crop_h, scale, out_w, out_h, &ow, &oh);      // what is delivered
-        const size_t bytes = (size_t)ow * oh * 3 / 2;
+        const size_t bytes = colour ? (size_t)ow * oh * 3 : (size_t)ow * oh * 3 / 2;
         lh264_decoded_pic_t dp;
         dp.width = ow; dp.height = oh; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
         rc.pics.push_back (dp);
         rc.concealed.push_back (f.concealed);
         rc.source_wh.push_back (f.crop_w); rc.source_wh.push_back (f.crop_h);
         rc.index.push_back ((int32_t)f.index);
+        if (colour) rc.colour.push_back (std_byte);
         at += bytes; off += bytes;
         if (!on_dev) mo += nm;
         so += f.slices.size(); j++;
@@ -1203,13 +1432,14 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
       hipStream_t st = A.s_run;
       auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
       bool ok = up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
-                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) &&
+                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) && (!colour || up (A.d_std, h_std, n_jobs)) &&
                 (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
       if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
       if (ok) {
-        if (out_w) hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), out_w, out_h);
+        if (colour) hipLaunchKernelGGL (decode_pack_rgb_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour);
+        else if (out_w) hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), out_w, out_h);
         else if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         ok = hipGetLastError() == hipSuccess;
@@ -1295,6 +1525,21 @@ int lh264_parser_pick (const uint8_t* data, size_t len, uint32_t pick, int32_t* 
     P.frames().clear();
   }
   *n = count;
+  return LH264_OK;
+}
+int lh264_parser_colour (const uint8_t* data, size_t len, int32_t* matrix_coefficients, int32_t* full_range, int32_t* present) {
+  if (!data) return LH264_E_ARG;
+  int mc = 2, fr = 0, pr = 0;
+  if (!Parser::first_sps_colour (data, len, &mc, &fr, &pr)) return LH264_E_UNSUPPORTED;
+  if (matrix_coefficients) *matrix_coefficients = mc;
+  if (full_range) *full_range = fr;
+  if (present) *present = pr;
+  return LH264_OK;
+}
+int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* matrix, int32_t* full_range) {
+  if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->colour.size() != d->pics.size()) return LH264_E_ARG;
+  if (matrix) *matrix = (d->colour[idx] & 1) ? LH264_MATRIX_BT709 : LH264_MATRIX_BT601;
+  if (full_range) *full_range = d->colour[idx] >> 1 & 1;
   return LH264_OK;
 }
 long long lh264_decoded_parsed_slices (const lh264_decoded_t* d) { return d ? (long long)d->parsed_slices : 0; }

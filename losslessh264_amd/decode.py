@@ -22,8 +22,8 @@ class _DevSpan:
 class DecodedBatch:
     """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
 
-    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None):
-        self._lib, self._h, self.device_out, self._keep, self.size = lib, handles, device_out, sink_keepalive, size
+    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None):
+        self._lib, self._h, self.device_out, self._keep, self.size, self.colour = lib, handles, device_out, sink_keepalive, size, colour
 
     def __len__(self):
         return len(self._h)
@@ -81,6 +81,18 @@ class DecodedBatch:
             out.append((w.value, h.value))
         return out
 
+    def colours(self, i):
+        """colour="rgb24" | "rgbp": [(matrix, colour_range)] per delivered picture of stream i, the standard that was applied to it -
+        matrix "bt601" | "bt709", colour_range "limited" | "full" (what the stream's SPS says, or what the call named)"""
+        if self.colour is None:
+            raise RuntimeError("decode_batch was not called with colour=")
+        out = []
+        m, f = C.c_uint32(0), C.c_int32(0)
+        for k in range(self._lib.lh264_decoded_pictures(self._h[i])):
+            L.check(self._lib.lh264_decoded_picture_colour(self._h[i], k, C.byref(m), C.byref(f)))
+            out.append(("bt709" if m.value == L.MATRIX["bt709"] else "bt601", "full" if f.value else "limited"))
+        return out
+
     def picture_sha1(self, i):
         """sha1="pictures" | "both": the SHA-1 of every delivered picture of stream i, as delivered (20-byte bytes objects)"""
         out = []
@@ -128,11 +140,16 @@ class DecodedBatch:
     def frames(self, i):
         """device_out=True together with size=(W, H): the pictures of stream i as a (pictures, H * 3 // 2, W) torch.uint8 view of
         tensor(i) - rows 0..H-1 of a picture are its luma plane, the H / 2 rows behind them its chroma bytes as packed (I420: Cb then
-        Cr, two chroma rows per row of the view; NV12: the interleaved rows).  Every stream of the batch has the same picture shape"""
+        Cr, two chroma rows per row of the view; NV12: the interleaved rows).  Every stream of the batch has the same picture shape.
+        With colour="rgb24" the view is (pictures, H, W, 3), with colour="rgbp" (pictures, 3, H, W)"""
         if not self.device_out or self.size is None:
             raise RuntimeError("frames() needs decode_batch (device_out=True, size=(W, H))")
         w, h = self.size
         t = self.tensor(i)
+        if self.colour == "rgb24":
+            return t.view(t.numel() // (w * h * 3), h, w, 3)
+        if self.colour == "rgbp":
+            return t.view(t.numel() // (w * h * 3), 3, h, w)
         return t.view(t.numel() // (w * h * 3 // 2), h * 3 // 2, w)      # (a stream that delivered nothing: 0 pictures)
 
     def free(self):
@@ -147,7 +164,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -182,8 +199,25 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     D = w*h, delivered sample = (2*S + D) // (2*D): round half up, exact.  No coordinate leaves the window; the aspect ratio is not
     kept; chroma siting is not modelled.  size == the window gives the window, a window of B times the size (B = 2, 4, 8) the bytes of
     scale = 1, 2, 3; a larger size repeats samples and blends the seams.  pictures / the sink / the digests describe what is
-    delivered, source_sizes the windows; with device_out=True, DecodedBatch.frames(i) is a (pictures, H * 3 // 2, W) view."""
+    delivered, source_sizes the windows; with device_out=True, DecodedBatch.frames(i) is a (pictures, H * 3 // 2, W) view.
+    colour: None | "rgb24" | "rgbp", with fmt="i420" only: RGB pictures, colour-converted on the device in the pack pass
+    (decode_pack_rgb_kernel through lh264_decode_batch_ex; no I420 intermediate).  The conversion acts on the delivered planes - the
+    window, its scale= means or its size= resampling, exactly as without colour - and converts every luma sample (X, Y) with the chroma
+    sample (X >> 1, Y >> 1): the RGB bytes are an exact integer function (include/lh264.h, LH264_COLOUR_FACTORS) of the I420 bytes of
+    the same call without colour.  "rgb24": H rows of W pixels stored R, G, B; "rgbp": three W x H planes R, G, B; 3*W*H bytes a
+    picture, one behind the other.  matrix: "auto" (the SPS VUI's matrix_coefficients: 1 is BT.709; 5, 6, 2 or none BT.601; anything
+    else stops the stream with LH264_E_UNSUPPORTED and a text naming the value) | "bt601" | "bt709".  colour_range: "auto" (the VUI's
+    video_full_range_flag; absent: limited) | "limited" | "full".  DecodedBatch.colours(i) tells what was applied per picture;
+    frames(i) is then (pictures, H, W, 3) or (pictures, 3, H, W)."""
     lib = L.lib()
+    if colour not in L.COLOUR:
+        raise ValueError("colour must be None, 'rgb24' or 'rgbp'")
+    if matrix not in L.MATRIX or colour_range not in L.RANGE:
+        raise ValueError("matrix must be 'auto', 'bt601' or 'bt709' and colour_range 'auto', 'limited' or 'full'")
+    if colour is None and (matrix != "auto" or colour_range != "auto"):
+        raise ValueError("matrix and colour_range need colour=")
+    if colour is not None and fmt != "i420":
+        raise ValueError("colour needs fmt='i420'")
     if size is not None:
         ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and 2 <= v <= 4096 and v % 2 == 0 for v in size)
         if not ok:
@@ -236,12 +270,17 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         cb = L.DECODE_SINK_FN(_cb)
         opts.sink = cb
     outs = (C.c_void_p * n)()
-    rc = lib.lh264_decode_batch(ptrs, lens, n, threads, C.byref(opts), outs)
+    if colour is None:
+        rc = lib.lh264_decode_batch(ptrs, lens, n, threads, C.byref(opts), outs)
+    else:
+        ext = L.DecodeExt()
+        ext.struct_bytes, ext.colour, ext.matrix, ext.range = C.sizeof(L.DecodeExt), L.COLOUR[colour], L.MATRIX[matrix], L.RANGE[colour_range]
+        rc = lib.lh264_decode_batch_ex(ptrs, lens, n, threads, C.byref(opts), C.byref(ext), outs)
     if rc == L.E_NODEVICE:
         raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
-    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour)
 
 
 def decode_arena_bytes():
@@ -251,12 +290,12 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None):
-    """out_dir/<basename>.yuv for every input, through one decode_batch with a sink that appends to the files -> [(path, status, error,
-    pictures, bytes)]; scale, pick and size as in decode_batch"""
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
+    """out_dir/<basename>.yuv - with colour= <basename>.rgb - for every input, through one decode_batch with a sink that appends to the
+    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix and colour_range as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    names = [os.path.join(out_dir, os.path.basename(p) + ".yuv") for p in paths]
+    names = [os.path.join(out_dir, os.path.basename(p) + (".yuv" if colour is None else ".rgb")) for p in paths]
     files = [open(q, "wb") for q in names]
     total = [0] * len(paths)
 
@@ -265,7 +304,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range)
     finally:
         for f in files:
             f.close()
@@ -274,13 +313,13 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
     per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick and size as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range)
     res = []
     try:
         for i, p in enumerate(paths):

@@ -140,6 +140,19 @@ def pick(data, which):
     return [int(idx[k]) for k in range(n.value)]
 
 
+def stream_colour(data):
+    """what the first SPS of an Annex-B stream says about colour (lh264_parser_colour; no device is needed) -> (matrix_coefficients,
+    full_range, present): matrix_coefficients 2 (unspecified) and full_range False where the SPS carries none; present bit 0 = its VUI
+    has a video_signal_type, bit 1 = a colour description.  None: no SPS that parses"""
+    data = bytes(data)
+    mc, fr, pr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = L.lib().lh264_parser_colour(data, len(data), C.byref(mc), C.byref(fr), C.byref(pr))
+    if rc == L.E_UNSUPPORTED:
+        return None
+    L.check(rc)
+    return mc.value, bool(fr.value), pr.value
+
+
 def _file_text(data, query, tolerant=False):
     lib = L.lib()
     p = lib.lh264_parser_create()
