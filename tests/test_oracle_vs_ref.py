@@ -330,6 +330,34 @@ def _deblock_directed(orc, ref, h):
     return n
 
 
+def _intra_directed(orc, ref, h):
+    """the predictors at the directed edge contents of tests/intra_directed.py, where uniform random images do not reach: binary
+    samples, the steepest ramps of both signs in both directions (|H| = |V| = 9180: both clips of the plane predictors, negative sums
+    under the arithmetic shift), gentle ramps, sums that all differ, and two neighbouring values (every residue of the roundings);
+    every mode, for 8x8 every top-left and top-right setting.  -> the number of predictions"""
+    import intra_directed as ID
+    rng = np.random.default_rng(23)
+    st, off = 64, 8 * 64 + 16
+    n = 0
+    for cls in list(ID.CLASSES) + ["ties"]:
+        for it in range(12):
+            for kind, nmodes, size in INTRA_PRED + [("pred8x8l", 14, 8)]:
+                top, left = ID.edge_vectors(rng, cls, size)
+                img = rng.integers(0, 256, (40, st)).astype(np.uint8)
+                img[7, 15:15 + len(top)] = top              # p[-1..2 size - 1, -1] of the block at (16, 8)
+                img[8:8 + size, 15] = left
+                for mode in range(nmodes):
+                    for tl, tr in ([(0, 0), (0, 1), (1, 0), (1, 1)] if kind == "pred8x8l" else [(None, None)]):
+                        a, b = img.copy(), img.copy()
+                        extra = () if tl is None else (tl, tr)
+                        getattr(orc, "orc_" + kind)(C.c_void_p(a.ctypes.data + off), st, mode, *extra)
+                        if ref:
+                            getattr(ref, "refk_" + kind)(C.c_void_p(b.ctypes.data + off), st, mode, *extra)
+                        _agree(h, a, b if ref else None, (cls, kind, mode, tl, tr))
+                        n += 1
+    return n
+
+
 INTRA_PRED = [("pred4x4", 14, 4), ("pred16x16", 7, 16), ("predc8x8", 7, 8)]
 # digest name -> (case, its arguments): what tests/golden/make_golden_ref_kernels.py runs against the reference
 CASES = {"idct4x4": (_idct4x4, ()), "idct8x8": (_idct8x8, ()), "dc_transforms": (_dc_transforms, ()),
@@ -337,7 +365,7 @@ CASES = {"idct4x4": (_idct4x4, ()), "idct8x8": (_idct8x8, ()), "dc_transforms": 
          "deblock_edge_filters": (_deblock_edge_filters, ()), "deblock_macroblock_drivers": (_deblock_macroblock_drivers, ()),
          "expand": (_expand, ()),
          "luma_dc_scaling_list": (_luma_dc_scaling_list, ()), "weight_prediction": (_weight_prediction, ()), "bs_thresholds": (_bs_thresholds, ()),
-         "deblock_directed": (_deblock_directed, ())}
+         "deblock_directed": (_deblock_directed, ()), "intra_directed": (_intra_directed, ())}
 
 
 # ---- the tests ------------------------------------------------------------------------------------------------------------------------
@@ -398,3 +426,7 @@ def test_bs_thresholds():
 
 def test_deblock_directed():
     assert _check("deblock_directed", _deblock_directed) > 300
+
+
+def test_intra_directed():
+    assert _check("intra_directed", _intra_directed) == 9 * 12 * (14 + 7 + 7 + 4 * 14)
