@@ -851,6 +851,41 @@ typedef struct lh264_decode_ext {
 int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n, int threads,
                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */, lh264_decoded_t** out);
 int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* matrix, int32_t* full_range);
+/* ---- float RGB tensors, normalised on the device: lh264_decode_batch_ex2 ---------------------------------------------------------------
+ * Both structs above are frozen; the sample words travel in a third.  sample == NULL, or type == LH264_SAMPLE_U8 with all six floats
+ * +0.0 (every bit clear), is lh264_decode_batch_ex, byte for byte and launch for launch (lh264_decode_batch_ex is this call with NULL).
+ * THE DEFINITION (normative).  A sample type is uint8 (the bytes of the calls above), float32, float16 or bfloat16.  With a float type,
+ * element e of a delivered picture is a function of byte e of that picture in the same call made with LH264_SAMPLE_U8.  With c that
+ * byte (0..255) and ch its channel (0 = R, 1 = G, 2 = B):
+ *   v32 = fma ((float) c, mul[ch], add[ch])       one IEEE-754 binary32 fused multiply-add, round to nearest even
+ *   LH264_SAMPLE_F32:  v32
+ *   LH264_SAMPLE_F16:  v32 rounded to binary16, nearest even   (overflow gives infinity: there is no saturation)
+ *   LH264_SAMPLE_BF16: v32 rounded to bfloat16, nearest even
+ * mul[3] and add[3] are six binary32 values of the caller's.  Underflow is gradual in all three types: nothing is flushed to zero.  The
+ * bits are what is defined, the sign of a zero included (fma (0, -1, +0.0) is +0.0, fma (0, -1, -0.0) is -0.0).
+ * LAYOUT.  The uint8 call's with elements in place of bytes: LH264_COLOUR_RGB24 is oh rows of ow pixels stored R, G, B, LH264_COLOUR_RGBP
+ * three ow x oh planes; elements are little-endian and tight; a picture is 3*ow*oh*es bytes, es = 4, 2, 2.  lh264_decoded_pic_t bytes /
+ * offset describe what is delivered, and the round's output buffers, the download, the handles, the sink, DEVICE_OUT, NO_PICTURES, both
+ * digests and lh264_decode_arena_bytes work on those bytes, as for RGB.  Conceal, both parse routes, pick, scale_log2, out_width /
+ * out_height, matrix and range act as without a float type.  ow and oh are even, so every picture and every row of it begins at a
+ * multiple of 4 bytes from the stream's first byte (of 8, in fact); the call checks that of every round's output offsets.
+ * decode_pack_sample_kernel takes decode_pack_rgb_kernel's place in the round: the uint8 RGB never reaches memory.
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of the calls above: a struct_bytes other than 32, a type
+ * above 3, LH264_SAMPLE_U8 with a float that is not +0.0, a float type with ext NULL or ext->colour == LH264_COLOUR_YUV, a mul or add
+ * that is not finite.  lh264_decoded_sample_type: the LH264_SAMPLE_* of the call that made the handle (LH264_E_ARG: d NULL). */
+#define LH264_SAMPLE_U8   0u
+#define LH264_SAMPLE_F32  1u
+#define LH264_SAMPLE_F16  2u
+#define LH264_SAMPLE_BF16 3u
+typedef struct lh264_decode_sample {
+  uint32_t struct_bytes;                /* 32                                                                   */
+  uint32_t type;                        /* LH264_SAMPLE_*                                                       */
+  float    mul[3], add[3];              /* per channel R, G, B                                                  */
+} lh264_decode_sample_t;
+int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n, int threads,
+                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
+                            const lh264_decode_sample_t* sample /* NULL = uint8 */, lh264_decoded_t** out);
+int lh264_decoded_sample_type (const lh264_decoded_t* d);
 /* what the first SPS of an Annex-B file says about colour, without a device: *matrix_coefficients (2 = unspecified where the SPS
  * carries none), *full_range (0 where it carries none), *present bit 0 = the VUI has a video_signal_type, bit 1 = it has a colour
  * description.  Any of the three may be NULL.  LH264_E_ARG: data NULL; LH264_E_UNSUPPORTED: no SPS in the file that parses */
@@ -938,6 +973,16 @@ int lh264_debug_resize_dev (const lh264_pack_job_t* jobs, int n, int out_w, int 
  * lh264_debug_rgb_dev without a device: LH264_E_NODEVICE */
 int lh264_debug_rgb_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job);
 int lh264_debug_rgb_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job);
+/* the same table delivered as float RGB (lh264_decode_batch_ex2): the arguments above and the sample struct, which must name a float
+ * type.  lh264_debug_sample_cpu steps the code of decode_pack_sample_kernel over HOST memory with t = 0, nt = 1, lh264_debug_sample_dev
+ * uploads the two tables, launches the production kernel and returns when it is through.  LH264_E_ARG: everything the RGB entry points
+ * refuse, a sample struct lh264_decode_batch_ex2 refuses or whose type is LH264_SAMPLE_U8 or that is NULL, a job whose dst is not a
+ * multiple of 4; lh264_debug_sample_dev without a device: LH264_E_NODEVICE */
+int lh264_debug_sample_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
+int lh264_debug_sample_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
+/* the host stepping's conversions of n binary32 values to 16 bits (type LH264_SAMPLE_F16 or _BF16, anything else LH264_E_ARG): what
+ * lh264_debug_sample_cpu rounds with, laid open so that a test can show it is nearest even at every boundary.  No device is needed */
+int lh264_debug_sample_round (uint32_t type, const float* v, size_t n, uint16_t* out);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

@@ -37,6 +37,10 @@
                                                             colour-converted on the device (decode_batch (colour=...)): out_dir/<name>.rgb
                                                             holds R, G, B per pixel (rgb24) or three planes per picture (rgbp); the
                                                             matrix and range come from the stream's SPS unless named.  Not with --nv12
+    python -m losslessh264_amd --decode [--sha1] --rgb rgb24|rgbp --sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c] ...   float RGB pictures,
+                                                            cast and normalised on the device in the same pass (decode_batch (dtype=...,
+                                                            mul=..., add=...)): element = fma (byte, mul[channel], add[channel]) in
+                                                            binary32, rounded to the type; out_dir/<name>.f32 | .f16 | .bf16, little-endian
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -168,6 +172,21 @@ def restore(src, dst):
 
 SIZE_USAGE = "--size: WxH, both even, 2..4096; not with a non-zero --scale"
 RGB_USAGE = "--rgb: rgb24 | rgbp, not with --nv12; --matrix: auto | bt601 | bt709 and --range: auto | limited | full, with --rgb only"
+SAMPLE_USAGE = "--sample: f32 | f16 | bf16, with --rgb only; --mul and --add: three finite numbers a,b,c (R, G, B), with --sample only"
+SAMPLE_NAMES = {"f32": "float32", "f16": "float16", "bf16": "bfloat16"}
+
+
+def parse_three(text):
+    """"a,b,c" -> three floats that are finite as binary32, or None"""
+    import numpy as np
+    parts = text.split(",")
+    try:
+        v = [float(x) for x in parts]
+    except ValueError:
+        return None
+    with np.errstate(over="ignore"):
+        ok = len(v) == 3 and all(x.strip() == x and x for x in parts) and bool(np.all(np.isfinite(np.asarray(v, dtype=np.float64).astype(np.float32))))
+    return tuple(v) if ok else None
 
 
 def parse_size(text):
@@ -184,7 +203,21 @@ def decode(argv):
     import losslessh264_amd as lh
     nv12, conceal, sha1, parse, scale, pick, size = False, None, False, "host", 0, "all", None
     colour, matrix, crange = None, None, None
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range"):
+    dtype, mul, add = None, None, None
+    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+        if argv[0] in ("--sample", "--mul", "--add"):
+            value = None if len(argv) < 2 else SAMPLE_NAMES.get(argv[1]) if argv[0] == "--sample" else parse_three(argv[1])
+            if value is None:
+                print(SAMPLE_USAGE)
+                return 2
+            if argv[0] == "--sample":
+                dtype = value
+            elif argv[0] == "--mul":
+                mul = value
+            else:
+                add = value
+            argv = argv[2:]
+            continue
         if argv[0] in ("--rgb", "--matrix", "--range"):
             allowed = {"--rgb": ("rgb24", "rgbp"), "--matrix": tuple(lh._lib.MATRIX), "--range": tuple(lh._lib.RANGE)}[argv[0]]
             if len(argv) < 2 or argv[1] not in allowed:
@@ -235,7 +268,10 @@ def decode(argv):
     if (colour is not None and nv12) or (colour is None and (matrix is not None or crange is not None)):
         print(RGB_USAGE)
         return 2
-    ckw = dict(colour=colour, matrix=matrix or "auto", colour_range=crange or "auto")
+    if (dtype is not None and colour is None) or (dtype is None and (mul is not None or add is not None)):
+        print(SAMPLE_USAGE)
+        return 2
+    ckw = dict(colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)
         return 2

@@ -176,6 +176,10 @@ assert C.sizeof(DecodeExt) == 24
 COLOUR = {None: 0, "rgb24": 1, "rgbp": 2}                # LH264_COLOUR_*
 MATRIX = {"auto": 0, "bt601": 1, "bt709": 2}             # LH264_MATRIX_*
 RANGE = {"auto": 0, "limited": 1, "full": 2}             # LH264_RANGE_*
+class DecodeSample(C.Structure):    # lh264_decode_sample_t: what lh264_decode_batch_ex2 takes beside the two frozen structs
+    _fields_ = [("struct_bytes", C.c_uint32), ("type", C.c_uint32), ("mul", C.c_float * 3), ("add", C.c_float * 3)]
+assert C.sizeof(DecodeSample) == 32
+SAMPLE = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}      # LH264_SAMPLE_*
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
@@ -183,6 +187,11 @@ assert DECODED_PIC_DTYPE.itemsize == 32 and C.sizeof(DecodeOpts) == 48 and C.siz
 _SIGS.update({
     "lh264_decode_batch": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decode_batch_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decode_batch_ex2": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_sample_type": (C.c_int, [C.c_void_p]),
+    "lh264_debug_sample_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_debug_sample_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_debug_sample_round": (C.c_int, [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lh264_decoded_picture_colour": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "lh264_parser_colour": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lh264_debug_rgb_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

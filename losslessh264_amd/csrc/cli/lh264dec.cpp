@@ -24,8 +24,11 @@
 //   lh264dec --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096), resampled on the
 //                                       device by an exact area average (lh264.h: out_width, out_height).  Not with a non-zero --scale
 //                                       Not together with --conceal
+//   lh264dec --decode [--sha1] --rgb rgb24|rgbp --sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c] ...   float RGB pictures, cast and
+//                                       normalised on the device (lh264.h: lh264_decode_batch_ex2) -> out_dir/<name>.f32 | .f16 | .bf16
 //
 // Written against include/lh264.h and include/lh264_isvc.h only; links liblh264.so.
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -206,6 +209,23 @@ static const char* const kRgbUsage = "--rgb: rgb24 | rgbp, not with --nv12; --ma
 static int one_of (const char* text, const char* a, const char* b, const char* c) {      // 0, 1, 2 or -1
   return !strcmp (text, a) ? 0 : !strcmp (text, b) ? 1 : c && !strcmp (text, c) ? 2 : -1;
 }
+// --sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]: what lh264_decode_batch_ex2 takes beside both (type 0: lh264_decode_batch_ex as ever)
+static lh264_decode_sample_t g_sample = {sizeof (lh264_decode_sample_t), LH264_SAMPLE_U8, {0, 0, 0}, {0, 0, 0}};
+static const char* const kSampleUsage = "--sample: f32 | f16 | bf16, with --rgb only; --mul and --add: three finite numbers a,b,c (R, G, B), with --sample only";
+static bool parse_three (const char* text, float* v) {      // "a,b,c", every one finite as binary32
+  for (int k = 0; k < 3; k++) {
+    if (!*text || *text == ' ' || *text == ',') return false;
+    char* end = nullptr;
+    const float x = (float)strtod (text, &end);
+    if (end == text || *end != (k < 2 ? ',' : 0) || !std::isfinite (x)) return false;
+    v[k] = x;
+    text = end + 1;
+  }
+  return true;
+}
+static const char* out_suffix() {
+  return !g_ext.colour ? ".yuv" : g_sample.type == LH264_SAMPLE_F32 ? ".f32" : g_sample.type == LH264_SAMPLE_F16 ? ".f16" : g_sample.type == LH264_SAMPLE_BF16 ? ".bf16" : ".rgb";
+}
 // --size WxH: both even, 2..4096
 static const char* const kSizeUsage = "--size: WxH, both even, 2..4096; not with a non-zero --scale";
 static bool parse_size (const char* text, int* w, int* h) {
@@ -228,14 +248,14 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   DecodeFiles files; files.f.assign (n, nullptr); files.bytes.assign (n, 0);
   std::vector<std::string> dsts (n);
   for (int i = 0; i < n; i++) {
-    dsts[i] = out_dir + "/" + base_name (srcs[i]) + (g_ext.colour ? ".rgb" : ".yuv");
+    dsts[i] = out_dir + "/" + base_name (srcs[i]) + out_suffix();
     files.f[i] = fopen (dsts[i].c_str(), "wb");
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, h.data());
+  const int rc = lh264_decode_batch_ex2 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, h.data());
   for (FILE* f : files.f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
@@ -259,7 +279,7 @@ static int decode_sha1_files (const std::string& out_dir, const std::vector<std:
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, h.data());
+  const int rc = lh264_decode_batch_ex2 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, h.data());
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
@@ -310,7 +330,7 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
-    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL; bool matrix_named = false;
+    bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL; bool matrix_named = false, add_named = false, mul_named = false;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
       else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
@@ -340,18 +360,31 @@ int main (int argc, char** argv) {
         if (rgb) g_ext.colour = (uint32_t)k + LH264_COLOUR_RGB24;
         else { (matrix ? g_ext.matrix : g_ext.range) = (uint32_t)k; matrix_named = true; }
         first += 2;
+      } else if (first < argc && (!strcmp (argv[first], "--sample") || !strcmp (argv[first], "--mul") || !strcmp (argv[first], "--add"))) {
+        const char* v = first + 1 < argc ? argv[first + 1] : "";
+        if (!strcmp (argv[first], "--sample")) {
+          const int k = one_of (v, "f32", "f16", "bf16");
+          if (k < 0) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
+          g_sample.type = (uint32_t)k + LH264_SAMPLE_F32;
+        } else {
+          if (!parse_three (v, !strcmp (argv[first], "--mul") ? g_sample.mul : g_sample.add)) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
+          (!strcmp (argv[first], "--mul") ? mul_named : add_named) = true;
+        }
+        first += 2;
       } else break;
     }
     if ((g_ext.colour && nv12) || (!g_ext.colour && matrix_named)) { fprintf (stderr, "%s\n", kRgbUsage); return 2; }
+    if ((g_sample.type && !g_ext.colour) || (!g_sample.type && (add_named || mul_named))) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
+    if (g_sample.type && !mul_named) g_sample.mul[0] = g_sample.mul[1] = g_sample.mul[2] = 1.0f;
     if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R]] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R]] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

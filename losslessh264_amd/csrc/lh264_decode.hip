@@ -7,6 +7,8 @@
 // download of that buffer runs on a second HIP stream while the host threads parse and stage the next round.  DESIGN.md section 4.6.
 // lh264_decode_batch_ex is the same call with a second struct of options: with a colour, decode_pack_rgb_kernel takes the pack kernel's
 // place and the round's output buffer holds RGB24 or planar RGB pictures, converted from the planes the pack step would have delivered.
+// lh264_decode_batch_ex2 adds a third struct, the sample type: with a float type decode_pack_sample_kernel takes that place and the
+// buffer holds float32, float16 or bfloat16 elements, one fused multiply-add of each RGB byte, which itself is never stored.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -398,6 +400,25 @@ __host__ __device__ inline uint32_t luma_pair (const ResizePlane& pl, const Span
   return (uint32_t)plane_sample<M> (pl, sy, X, Y) | (uint32_t)plane_sample<M> (pl, sy, X + 1, Y) << 8;
 }
 
+// the 2x2 quad whose first pixel is delivered luma sample (X, 2*R), X even: the chroma sample and the chroma terms once for its four
+// pixels -> o[rr][i][c] = channel c (0 R, 1 G, 2 B) of pixel (X + i, 2*R + rr).  The one place where a pixel is converted: piece_rgb
+// and piece_sample both read their bytes here
+template <int M>
+__host__ __device__ inline void quad_rgb (const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, const Span* sy, const Span& sc,
+                                          const int32_t* f, int y0, int X, int R, uint32_t o[2][2][3]) {
+  const int D = plane_sample<M> (pu, sc, X >> 1, R) - 128, E = plane_sample<M> (pv, sc, X >> 1, R) - 128;
+  const int32_t tr = f[1] * E + 32768, tg = 32768 - f[3] * D - f[4] * E, tb = f[2] * D + 32768;
+  _Pragma ("unroll")
+  for (int rr = 0; rr < 2; rr++) {
+    const uint32_t yy = luma_pair<M> (py, sy[rr], X, 2 * R + rr);
+    _Pragma ("unroll")
+    for (int i = 0; i < 2; i++) {
+      const int32_t yt = f[0] * ((int32_t) (yy >> (8 * i) & 0xffu) - y0);
+      o[rr][i][0] = clip8 ((yt + tr) >> 16); o[rr][i][1] = clip8 ((yt + tg) >> 16); o[rr][i][2] = clip8 ((yt + tb) >> 16);
+    }
+  }
+}
+
 // piece p of row pair R of one job delivered as ow x oh in layout L (LH264_COLOUR_RGB24 / _RGBP) with the factors f and luma offset y0
 template <int M, int L>
 __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, int ow, int oh,
@@ -422,15 +443,13 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
   for (int q = 0; q < kRgbQuads; q++) {
     const int X = x0 + 2 * q;
     if (X < 0 || X >= ow) continue;
-    const int D = plane_sample<M> (pu, sc, X >> 1, R) - 128, E = plane_sample<M> (pv, sc, X >> 1, R) - 128;
-    const int32_t tr = f[1] * E + 32768, tg = 32768 - f[3] * D - f[4] * E, tb = f[2] * D + 32768;
+    uint32_t px[2][2][3];
+    quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X, R, px);
     _Pragma ("unroll")
     for (int rr = 0; rr < 2; rr++) {
-      const uint32_t yy = luma_pair<M> (py, sy[rr], X, 2 * R + rr);
       _Pragma ("unroll")
       for (int i = 0; i < 2; i++) {
-        const int32_t yt = f[0] * ((int32_t) (yy >> (8 * i) & 0xffu) - y0);
-        const uint32_t r = clip8 ((yt + tr) >> 16), g = clip8 ((yt + tg) >> 16), b = clip8 ((yt + tb) >> 16);
+        const uint32_t r = px[rr][i][0], g = px[rr][i][1], b = px[rr][i][2];
         const int k = 2 * q + i;                                   // the pixel's place among the 12
         if constexpr (L == (int)LH264_COLOUR_RGB24) {
           const uint32_t px = r | g << 8 | b << 16;
@@ -502,6 +521,172 @@ __host__ __device__ inline void pack_band_rgb (const lh264_pack_job_t& j, int ou
   }
 }
 
+// ---- the pack step to float RGB: lh264_decode_batch_ex2 with a float sample type (the definition: include/lh264.h at that call) -------
+// Element e of a picture is fma ((float) c, mul[ch], add[ch]) of byte e of the RGB picture above, as binary32, binary16 or bfloat16; the
+// bytes come from quad_rgb, the code piece_rgb reads, and never reach memory.  Every row of every plane begins at a multiple of 4 bytes
+// (ow and oh are even, the picture's first byte is 4-aligned), so nothing is shifted to the destination: the bands are 16 delivered luma
+// rows = 8 pairs of rows, an item is 8 pixels of both rows of a pair counted from pixel 0 - 4 quads, 24 elements a row in RGB24, 8 a
+// row and plane in RGBP.  A row of a plane whose address is a multiple of 16 leaves as aligned 16-byte stores (an item's bytes are a
+// multiple of 16 in every type and layout, so the row's alignment is every item's: the choice is uniform over the workgroup), any other
+// row and the last item of a row whose ow is no multiple of 8 (its 1..3 quads) as aligned 4-byte stores.  Lane t takes items t, t + nt,
+// ..: neighbouring lanes write neighbouring bytes.  No byte outside the window is read, none outside the picture's bytes written.  No LDS.
+
+// (the walk below is inlined into the kernel whatever its size: called as a function it would take the job through scratch memory)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LH264_SAMPLE_INLINE __attribute__ ((always_inline)) inline
+#else
+#define LH264_SAMPLE_INLINE inline
+#endif
+
+// binary32 -> the bits of binary16, round to nearest even, gradual underflow, overflow to infinity.  On the device the conversion
+// instruction (the mode's rounding is nearest even and half denormals are kept: hipcc's defaults); on the host integer arithmetic
+__host__ __device__ inline uint32_t half_bits (float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_bit_cast (uint16_t, (_Float16)v);
+#else
+  uint32_t x;
+  __builtin_memcpy (&x, &v, 4);
+  const uint32_t sign = x >> 16 & 0x8000u, a = x & 0x7fffffffu;
+  if (a >= 0x7f800000u) return sign | 0x7c00u | (a > 0x7f800000u ? 0x200u : 0u);
+  if (a >= 0x38800000u) {                                          // 2^-14 and above: a normal half, or infinity
+    uint32_t r = a - 0x38000000u;                                  // the exponent rebiased by 112; the carry of the rounding may enter it
+    r = (r + 0xfffu + (r >> 13 & 1u)) >> 13;
+    return sign | (r > 0x7c00u ? 0x7c00u : r);
+  }
+  const int s = 126 - (int) (a >> 23);                             // a subnormal half: m * 2^(e - 150) in units of 2^-24 is m >> s
+  if (s > 24) return sign;                                         // below 2^-25: nearer to zero than to the smallest half
+  const uint32_t m = (a & 0x7fffffu) | 0x800000u, rem = m & ((1u << s) - 1u), half = 1u << (s - 1);
+  uint32_t q = m >> s;
+  if (rem > half || (rem == half && (q & 1u))) q++;
+  return sign | q;                                                 // (q == 0x400 is the smallest normal half: the same bits)
+#endif
+}
+// binary32 -> the bits of bfloat16, round to nearest even (subnormals as they come: a bfloat16 is the upper half of a binary32)
+__host__ __device__ inline uint32_t bfloat_bits (float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_bit_cast (uint16_t, (__bf16)v);
+#else
+  uint32_t x;
+  __builtin_memcpy (&x, &v, 4);
+  if ((x & 0x7fffffffu) > 0x7f800000u) return x >> 16 | 0x40u;
+  return (x + 0x7fffu + (x >> 16 & 1u)) >> 16;
+#endif
+}
+// element `lo`, and in the 16-bit types the element `hi` behind it, as one word of the destination
+template <int T>
+__host__ __device__ inline uint32_t sample_word (float lo, float hi) {
+  if constexpr (T == (int)LH264_SAMPLE_F32) return __builtin_bit_cast (uint32_t, lo);
+  else if constexpr (T == (int)LH264_SAMPLE_F16) return half_bits (lo) | half_bits (hi) << 16;
+  else return bfloat_bits (lo) | bfloat_bits (hi) << 16;
+}
+
+// item p (pixels 8*p .. 8*p + 7) of row pair R of one job delivered as ow x oh in layout L, sample type T (LH264_SAMPLE_F32 / _F16 /
+// _BF16), with the colour factors f, luma offset y0 and the caller's mul / add
+template <int M, int L, int T>
+__host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, int ow, int oh,
+                                              const int32_t* f, int y0, const float* mul, const float* add, int R, int p) {
+  constexpr bool kPacked = L == (int)LH264_COLOUR_RGB24;
+  constexpr int ES = T == (int)LH264_SAMPLE_F32 ? 4 : 2, NP = kPacked ? 1 : 3;      // an element's bytes; the planes of the destination
+  constexpr int EQ = kPacked ? 6 : 2;                                                // the elements of a quad in one row of one plane
+  constexpr int WQ = EQ * ES / 4, NW = 4 * WQ;                                       // ... and their words: 6, 3, 2, 1 and 24, 12, 8, 4
+  const int X0 = 8 * p;
+  if (X0 >= ow) return;
+  const int nq = (ow - X0) >> 1 < 4 ? (ow - X0) >> 1 : 4;                            // the item's quads: 4, at a row's tail 1..3
+  Span sy[2], sc;
+  if constexpr (M == 4) { sy[0] = span_of ((uint32_t) (2 * R), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1), py.h, py.oh); sc = span_of ((uint32_t)R, pu.h, pu.oh); }
+  else { sy[0] = sy[1] = sc = Span(); }
+  uint32_t W[2][NP][NW];                                                             // the item's words, per row and plane
+  for (int rr = 0; rr < 2; rr++) for (int c = 0; c < NP; c++) for (int k = 0; k < NW; k++) W[rr][c][k] = 0;
+  _Pragma ("unroll")
+  for (int q = 0; q < 4; q++) {
+    if (q >= nq) continue;
+    uint32_t px[2][2][3];
+    quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X0 + 2 * q, R, px);
+    _Pragma ("unroll")
+    for (int rr = 0; rr < 2; rr++) {
+      float v[2][3];
+      _Pragma ("unroll")
+      for (int i = 0; i < 2; i++) {
+        _Pragma ("unroll")
+        for (int c = 0; c < 3; c++) v[i][c] = __builtin_fmaf ((float)px[rr][i][c], mul[c], add[c]);      // one fused multiply-add: the definition's
+      }
+      // the quad's elements of this row in memory order: R G B R G B in one plane, or the pixel pair in each of three
+      if constexpr (kPacked) {
+        const float e[6] = {v[0][0], v[0][1], v[0][2], v[1][0], v[1][1], v[1][2]};
+        _Pragma ("unroll")
+        for (int k = 0; k < WQ; k++) W[rr][0][WQ * q + k] = ES == 4 ? sample_word<T> (e[k], 0.0f) : sample_word<T> (e[(2 * k) % 6], e[(2 * k + 1) % 6]);
+      } else {
+        _Pragma ("unroll")
+        for (int c = 0; c < 3; c++) {
+          if constexpr (ES == 4) { W[rr][c][2 * q] = sample_word<T> (v[0][c], 0.0f); W[rr][c][2 * q + 1] = sample_word<T> (v[1][c], 0.0f); }
+          else W[rr][c][q] = sample_word<T> (v[0][c], v[1][c]);
+        }
+      }
+    }
+  }
+  const size_t row_bytes = (size_t) (kPacked ? 3 : 1) * ow * ES, plane_bytes = (size_t)ow * oh * ES;
+  _Pragma ("unroll")
+  for (int rr = 0; rr < 2; rr++) {
+    _Pragma ("unroll")
+    for (int c = 0; c < NP; c++) {
+      uint8_t* row = dst + (size_t)c * plane_bytes + (size_t) (2 * R + rr) * row_bytes;
+      uint8_t* o = row + (size_t)p * (NW * 4);
+      if (nq == 4 && !((uintptr_t)row & 15u)) {
+        _Pragma ("unroll")
+        for (int k = 0; k < NW / 4; k++) { uint4 x; x.x = W[rr][c][4 * k]; x.y = W[rr][c][4 * k + 1]; x.z = W[rr][c][4 * k + 2]; x.w = W[rr][c][4 * k + 3]; * (uint4*) (o + 16 * k) = x; }
+      } else {
+        _Pragma ("unroll")
+        for (int q = 0; q < 4; q++) {
+          if (q >= nq) continue;
+          _Pragma ("unroll")
+          for (int k = 0; k < WQ; k++) * (uint32_t*) (o + 4 * (WQ * q + k)) = W[rr][c][WQ * q + k];
+        }
+      }
+    }
+  }
+}
+
+// band `band` (16 delivered luma rows) of one job delivered as ow x oh float RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
+template <int M, int L, int T>
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h;
+  const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
+  if (R1 <= R0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  int32_t f[5];
+  for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
+  const int y0 = (std_byte & 2) ? 0 : 16;
+  const int pieces = (ow + 7) >> 3, items = (R1 - R0) * pieces;
+  for (int it = t; it < items; it += nt) piece_sample<M, L, T> (j.dst, py, pu, pv, ow, oh, f, y0, mul, add, R0 + it / pieces, it % pieces);
+}
+template <int L, int T>
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_sized (const lh264_pack_job_t& j, int ow, int oh, int m, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+  if (m == 0) pack_band_sample_as<0, L, T> (j, ow, oh, std_byte, mul, add, band, t, nt);
+  else if (m == 1) pack_band_sample_as<1, L, T> (j, ow, oh, std_byte, mul, add, band, t, nt);
+  else if (m == 2) pack_band_sample_as<2, L, T> (j, ow, oh, std_byte, mul, add, band, t, nt);
+  else if (m == 3) pack_band_sample_as<3, L, T> (j, ow, oh, std_byte, mul, add, band, t, nt);
+  else pack_band_sample_as<4, L, T> (j, ow, oh, std_byte, mul, add, band, t, nt);
+}
+template <int L>
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_typed (const lh264_pack_job_t& j, int ow, int oh, int m, int type, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+  if (type == (int)LH264_SAMPLE_F32) pack_band_sample_sized<L, (int)LH264_SAMPLE_F32> (j, ow, oh, m, std_byte, mul, add, band, t, nt);
+  else if (type == (int)LH264_SAMPLE_F16) pack_band_sample_sized<L, (int)LH264_SAMPLE_F16> (j, ow, oh, m, std_byte, mul, add, band, t, nt);
+  else if (type == (int)LH264_SAMPLE_BF16) pack_band_sample_sized<L, (int)LH264_SAMPLE_BF16> (j, ow, oh, m, std_byte, mul, add, band, t, nt);
+}
+// ... of a job whose sizing is its `reserved` scale (out_w == 0) or the given size; layout, standard byte and sample as given.  Anything
+// that is not defined, and a destination that is no multiple of 4: nothing is done
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample (const lh264_pack_job_t& j, int out_w, int out_h, int layout, int std_byte, const lh264_decode_sample_t& sm, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved < 0 || j.reserved > 3 || (out_w && j.reserved) || ((uintptr_t)j.dst & 3u)) return;
+  int ow, oh;
+  delivered_size (j.crop_w, j.crop_h, j.reserved, out_w, out_h, &ow, &oh);
+  const int m = out_w ? 4 : j.reserved;
+  if (layout == (int)LH264_COLOUR_RGB24) pack_band_sample_typed<(int)LH264_COLOUR_RGB24> (j, ow, oh, m, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+  else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_typed<(int)LH264_COLOUR_RGBP> (j, ow, oh, m, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+}
+
 }  // namespace lh264pack
 
 // one workgroup per (picture, band)
@@ -534,6 +719,13 @@ __global__ void __launch_bounds__ (256) decode_pack_rgb_kernel (const lh264_pack
   lh264pack::pack_band_rgb (j, out_w, out_h, layout, (int)std[blockIdx.x], (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
+// one workgroup per (picture, band of 16 delivered luma rows): the jobs as float RGB - decode_pack_rgb_kernel's arguments and the sample
+// struct (a float type, six finite factors).  Every job's dst is a multiple of 4
+__global__ void __launch_bounds__ (256) decode_pack_sample_kernel (const lh264_pack_job_t* __restrict__ jobs, const uint8_t* __restrict__ std, int out_w, int out_h, int layout, lh264_decode_sample_t sample) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  lh264pack::pack_band_sample (j, out_w, out_h, layout, (int)std[blockIdx.x], sample, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
 // One lane per span job, 64 jobs per wave (a message is serial; the width comes from the batch).  The host orders a launch's jobs by
 // descending length, so the lanes of a wave end near one another.  No LDS, no wave waits for another; every bound is the job's.
@@ -555,6 +747,7 @@ struct lh264_decoded {
   long parsed_slices = 0;                       // distinct slices whose slice data was parsed, on either route
   std::vector<int32_t> index;                   // per delivered picture: its number among the stream's pictures in decode order
   std::vector<uint8_t> colour;                  // lh264_decode_batch_ex with colour: per delivered picture the standard byte that was applied
+  int sample_type = (int)LH264_SAMPLE_U8;       // lh264_decode_batch_ex2: the LH264_SAMPLE_* of the call
   std::vector<uint8_t> bytes;                   // host mode
   uint8_t* dev = nullptr; size_t dev_len = 0, dev_cap = 0; int device = 0;      // LH264_DECODE_DEVICE_OUT
   uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
@@ -849,6 +1042,52 @@ int lh264_debug_rgb_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out
   return ok ? LH264_OK : LH264_E_HIP;
 }
 
+// a sample struct the call takes: 32 bytes, a type that is defined, with LH264_SAMPLE_U8 six floats whose bits are all clear, with a
+// float type six finite floats
+static bool sample_ok (const lh264_decode_sample_t* s) {
+  if (s->struct_bytes != sizeof (lh264_decode_sample_t) || s->type > LH264_SAMPLE_BF16) return false;
+  for (int k = 0; k < 6; k++) {
+    uint32_t x;
+    memcpy (&x, k < 3 ? &s->mul[k] : &s->add[k - 3], 4);
+    if (s->type == LH264_SAMPLE_U8 ? x != 0 : (x & 0x7f800000u) == 0x7f800000u) return false;
+  }
+  return true;
+}
+// ... and what the float entry points take: a float type, every destination a multiple of 4
+static bool sample_jobs_ok (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, const lh264_decode_sample_t* sample, int* max_bands) {
+  if (!sample || !sample_ok (sample) || sample->type == LH264_SAMPLE_U8 || !rgb_jobs_ok (jobs, n, out_w, out_h, layout, std_per_job, max_bands)) return false;
+  for (int k = 0; k < n; k++) if ((uintptr_t)jobs[k].dst & 3u) return false;
+  return true;
+}
+
+int lh264_debug_sample_cpu (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!sample_jobs_ok (jobs, n, out_w, out_h, layout, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) for (int band = 0; band < max_bands; band++) lh264pack::pack_band_sample (jobs[k], out_w, out_h, layout, std_per_job[k], *sample, band, 0, 1);
+  return LH264_OK;
+}
+
+int lh264_debug_sample_dev (const lh264_pack_job_t* jobs, int n, int out_w, int out_h, int layout, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!sample_jobs_ok (jobs, n, out_w, out_h, layout, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  lh264_pack_job_t* d_jobs = nullptr; uint8_t* d_std = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_pack_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_pack_job_t), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMalloc ((void**)&d_std, (size_t)n) == hipSuccess && hipMemcpy (d_std, std_per_job, (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL (decode_pack_sample_kernel, dim3 ((unsigned)n, (unsigned)max_bands), dim3 (256), 0, 0, d_jobs, d_std, out_w, out_h, layout, *sample);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs); hipFree (d_std);
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
+int lh264_debug_sample_round (uint32_t type, const float* v, size_t n, uint16_t* out) {
+  if ((type != LH264_SAMPLE_F16 && type != LH264_SAMPLE_BF16) || (n && (!v || !out))) return LH264_E_ARG;
+  for (size_t k = 0; k < n; k++) out[k] = (uint16_t) (type == LH264_SAMPLE_F16 ? lh264pack::half_bits (v[k]) : lh264pack::bfloat_bits (v[k]));
+  return LH264_OK;
+}
+
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
   if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
@@ -904,7 +1143,19 @@ int lh264_decode_batch (const uint8_t* const* data, const size_t* len, int n, in
 }
 
 int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex2 (data, len, n, threads, opts, ext, nullptr, out);
+}
+
+int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
+  if (ext && ext->struct_bytes != sizeof (lh264_decode_ext_t)) return LH264_E_ARG;      // (before ext->colour is read below)
+  if (sample && (!sample_ok (sample) || (sample->type != LH264_SAMPLE_U8 && (!ext || ext->colour == LH264_COLOUR_YUV)))) return LH264_E_ARG;
+  // 0: bytes, the pack kernels as ever; else decode_pack_sample_kernel in decode_pack_rgb_kernel's place, es bytes per element
+  const int stype = sample ? (int)sample->type : (int)LH264_SAMPLE_U8;
+  const size_t es = stype == (int)LH264_SAMPLE_U8 ? 1 : stype == (int)LH264_SAMPLE_F32 ? 4 : 2;
+  lh264_decode_sample_t sample_arg;
+  memset (&sample_arg, 0, sizeof (sample_arg));
+  if (sample) sample_arg = *sample;
   if (ext && (ext->struct_bytes != sizeof (lh264_decode_ext_t) || ext->colour > LH264_COLOUR_RGBP || ext->matrix > LH264_MATRIX_BT709 || ext->range > LH264_RANGE_FULL ||
               ext->reserved0 != 0 || ext->reserved1 != 0 || (ext->colour == LH264_COLOUR_YUV && (ext->matrix != LH264_MATRIX_AUTO || ext->range != LH264_RANGE_AUTO)) ||
               (ext->colour != LH264_COLOUR_YUV && opts && opts->format != LH264_FMT_I420))) return LH264_E_ARG;
@@ -946,7 +1197,7 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
   if (threads < 1) threads = 1;
   int device = 0;
   if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
-  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sha = opts ? opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM) : 0; }
+  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sample_type = stype; out[i]->sha = opts ? opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM) : 0; }
   auto arena_lock = g_arena.lock (device);
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
@@ -1266,12 +1517,12 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
     std::vector<Place> place;
     size_t n_mbs = 0, n_hmbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0;      // n_hmbs: the macroblocks whose records the host stages (not those in the parse arena)
     int max_w = 1, max_h = 1, max_bands = 1;
-    bool alloc_ok = true;
+    bool alloc_ok = true, offsets_ok = true;
     for (auto& sp : active) {
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += colour ? (size_t)ow * oh * 3 : (size_t)ow * oh * 3 / 2; shown++; } }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += colour ? (size_t)ow * oh * 3 * es : (size_t)ow * oh * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -1284,6 +1535,9 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
       n_out += shown;
       place.push_back ({n_hmbs, n_sl, n_sp, n_jobs});
       n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
+      // a float type: every picture, and so every row, begins at a multiple of 4 bytes - the chain at one of 16, a picture 3*ow*oh*es
+      // bytes behind the one before (decode_pack_sample_kernel stores nothing narrower)
+      if (stype) for (auto& f : s.sel) if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); if (((size_t)ow * oh * 3 * es | rd.out_bytes) & 3) offsets_ok = false; }
       rd.out_bytes += (bytes + 15) & ~ (size_t)15;
       max_w = std::max (max_w, f0.mb_w); max_h = std::max (max_h, f0.mb_h);
       rd.chains.push_back (std::move (c));
@@ -1312,7 +1566,7 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
     // picture slots (serial: the cache is shared).  A picture takes a slot that was free when the round began; a slot becomes free
     // behind the round when its picture is in no DPB any more - the round's pictures are all packed by then
     std::vector<std::vector<int>> slot_of (n_chains);
-    for (int c = 0; c < n_chains && alloc_ok; c++) {
+    for (int c = 0; c < n_chains && alloc_ok && offsets_ok; c++) {
       DStream& s = *rd.chains[c].s;
       s.grey = A.pics.grey (s.geo.bytes, A.s_run);
       if (!s.grey) { alloc_ok = false; break; }
@@ -1329,7 +1583,7 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
         slot_of[c].push_back (at);
       }
     }
-    if (!alloc_ok) { fail_device ("device allocation failed"); for (auto& s : active) s->sel.clear(); deliver (rounds[rb ^ 1], rb ^ 1); continue; }
+    if (!alloc_ok || !offsets_ok) { fail_device (offsets_ok ? "device allocation failed" : "a float picture would not begin at a multiple of 4 bytes"); for (auto& s : active) s->sel.clear(); deliver (rounds[rb ^ 1], rb ^ 1); continue; }
     // ---- staging (host threads): records to the page-locked buffers, the job tables
     lh264_mb_t* h_mbs = A.h_mbs[rb].as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse[rb].as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl[rb].as<lh264_slice_t>();
     lh264_frame_job_t* h_jobs = A.h_jobs[rb].as<lh264_frame_job_t>(); int32_t* h_first = A.h_first[rb].as<int32_t>(); lh264_pack_job_t* h_pack = A.h_pack[rb].as<lh264_pack_job_t>();
@@ -1380,7 +1634,7 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
         pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
         int ow, oh;
         lh264pack::delivered_size (f.crop_w, f.crop_h, scale, out_w, out_h, &ow, &oh);      // what is delivered
-        const size_t bytes = colour ? (size_t)ow * oh * 3 : (size_t)ow * oh * 3 / 2;
+        const size_t bytes = colour ? (size_t)ow * oh * 3 * es : (size_t)ow * oh * 3 / 2;
         lh264_decoded_pic_t dp;
         dp.width = ow; dp.height = oh; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
         rc.pics.push_back (dp);
@@ -1438,7 +1692,8 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
       if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
       if (ok) {
-        if (colour) hipLaunchKernelGGL (decode_pack_rgb_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour);
+        if (stype) hipLaunchKernelGGL (decode_pack_sample_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour, sample_arg);
+        else if (colour) hipLaunchKernelGGL (decode_pack_rgb_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour);
         else if (out_w) hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), out_w, out_h);
         else if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
         else hipLaunchKernelGGL (decode_pack_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
@@ -1542,6 +1797,7 @@ int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* m
   if (full_range) *full_range = d->colour[idx] >> 1 & 1;
   return LH264_OK;
 }
+int lh264_decoded_sample_type (const lh264_decoded_t* d) { return d ? d->sample_type : LH264_E_ARG; }
 long long lh264_decoded_parsed_slices (const lh264_decoded_t* d) { return d ? (long long)d->parsed_slices : 0; }
 int lh264_decoded_picture_index (const lh264_decoded_t* d, int idx) {
   if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->index.size() != d->pics.size()) return LH264_E_ARG;

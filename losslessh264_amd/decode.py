@@ -22,8 +22,10 @@ class _DevSpan:
 class DecodedBatch:
     """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
 
-    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None):
+    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None, dtype="uint8", affine=None):
         self._lib, self._h, self.device_out, self._keep, self.size, self.colour = lib, handles, device_out, sink_keepalive, size, colour
+        # dtype: the dtype= of the call; affine: the six binary32 values it passed, ((mul R, G, B), (add R, G, B)), None with "uint8"
+        self.dtype, self.affine = dtype, affine
 
     def __len__(self):
         return len(self._h)
@@ -141,11 +143,15 @@ class DecodedBatch:
         """device_out=True together with size=(W, H): the pictures of stream i as a (pictures, H * 3 // 2, W) torch.uint8 view of
         tensor(i) - rows 0..H-1 of a picture are its luma plane, the H / 2 rows behind them its chroma bytes as packed (I420: Cb then
         Cr, two chroma rows per row of the view; NV12: the interleaved rows).  Every stream of the batch has the same picture shape.
-        With colour="rgb24" the view is (pictures, H, W, 3), with colour="rgbp" (pictures, 3, H, W)"""
+        With colour="rgb24" the view is (pictures, H, W, 3), with colour="rgbp" (pictures, 3, H, W); with a float dtype= it has that
+        dtype (torch.float32 | float16 | bfloat16): tensor(i) stays the uint8 bytes, this is tensor(i).view(dtype) in the same shape"""
         if not self.device_out or self.size is None:
             raise RuntimeError("frames() needs decode_batch (device_out=True, size=(W, H))")
         w, h = self.size
         t = self.tensor(i)
+        if self.dtype != "uint8":
+            import torch
+            t = t.view({"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}[self.dtype])
         if self.colour == "rgb24":
             return t.view(t.numel() // (w * h * 3), h, w, 3)
         if self.colour == "rgbp":
@@ -164,7 +170,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -208,8 +214,26 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     picture, one behind the other.  matrix: "auto" (the SPS VUI's matrix_coefficients: 1 is BT.709; 5, 6, 2 or none BT.601; anything
     else stops the stream with LH264_E_UNSUPPORTED and a text naming the value) | "bt601" | "bt709".  colour_range: "auto" (the VUI's
     video_full_range_flag; absent: limited) | "limited" | "full".  DecodedBatch.colours(i) tells what was applied per picture;
-    frames(i) is then (pictures, H, W, 3) or (pictures, 3, H, W)."""
+    frames(i) is then (pictures, H, W, 3) or (pictures, 3, H, W).
+    dtype: "uint8" (the default) | "float32" | "float16" | "bfloat16", a float dtype with colour= only: float RGB pictures, cast and
+    normalised on the device in the same pack pass (decode_pack_sample_kernel through lh264_decode_batch_ex2; the uint8 RGB never
+    reaches memory).  Element e of a picture is v = fma (float32 (c), mul[ch], add[ch]) - one binary32 fused multiply-add - of byte c
+    at place e of the same call with dtype="uint8", ch its channel (0 R, 1 G, 2 B); "float32" delivers v, "float16" / "bfloat16" v
+    rounded to nearest even (float16 overflows to infinity; no type flushes subnormals).  The layout is colour='s with elements in
+    place of bytes, little-endian: 3*W*H*4 (or *2) bytes a picture; pictures, the sink, data, tensor and the digests are of those bytes.
+    mul / add: None (1, 1, 1 / 0, 0, 0) or three finite numbers, rounded to binary32 once; normalise (mean, std) makes them.
+    DecodedBatch.dtype is the dtype of the call, .affine the six binary32 values passed; frames(i) is the typed view."""
     lib = L.lib()
+    if not isinstance(dtype, str) or dtype not in L.SAMPLE:
+        raise ValueError("dtype must be 'uint8', 'float32', 'float16' or 'bfloat16'")
+    if dtype == "uint8":
+        if mul is not None or add is not None:
+            raise ValueError("mul and add need a float dtype")
+        affine = None
+    else:
+        if colour is None:
+            raise ValueError("a float dtype needs colour=")
+        affine = (_three(mul, 1.0, "mul"), _three(add, 0.0, "add"))
     if colour not in L.COLOUR:
         raise ValueError("colour must be None, 'rgb24' or 'rgbp'")
     if matrix not in L.MATRIX or colour_range not in L.RANGE:
@@ -275,12 +299,45 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     else:
         ext = L.DecodeExt()
         ext.struct_bytes, ext.colour, ext.matrix, ext.range = C.sizeof(L.DecodeExt), L.COLOUR[colour], L.MATRIX[matrix], L.RANGE[colour_range]
-        rc = lib.lh264_decode_batch_ex(ptrs, lens, n, threads, C.byref(opts), C.byref(ext), outs)
+        if affine is None:
+            rc = lib.lh264_decode_batch_ex(ptrs, lens, n, threads, C.byref(opts), C.byref(ext), outs)
+        else:
+            sm = L.DecodeSample()
+            sm.struct_bytes, sm.type = C.sizeof(L.DecodeSample), L.SAMPLE[dtype]
+            for k in range(3):
+                sm.mul[k], sm.add[k] = affine[0][k], affine[1][k]
+            rc = lib.lh264_decode_batch_ex2(ptrs, lens, n, threads, C.byref(opts), C.byref(ext), C.byref(sm), outs)
     if rc == L.E_NODEVICE:
         raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
-    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine)
+
+
+def _three(v, default, name):
+    """mul= / add= of decode_batch -> three Python floats that are binary32 values (rounded once, by numpy)"""
+    if v is None:
+        return (default,) * 3
+    ok = isinstance(v, (tuple, list, np.ndarray)) and len(v) == 3 and all(isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) for x in v)
+    if ok:
+        with np.errstate(over="ignore"):
+            r = np.asarray([float(x) for x in v], dtype=np.float64).astype(np.float32)
+        ok = bool(np.all(np.isfinite(r)))
+    if not ok:
+        raise ValueError("%s must be None or three finite numbers (finite as binary32 too)" % name)
+    return tuple(float(x) for x in r)
+
+
+def normalise(mean, std):
+    """(mul, add) for decode_batch (dtype=<a float type>, mul=, add=) from a per-channel mean and deviation in 0..1 units (R, G, B), so
+    that an element is (c / 255 - mean) / std: mul = 1 / (255 * std), add = -mean / std, computed in float64 and rounded to binary32.
+    These six ROUNDED values, not the real numbers, define the output: an element is fma (float32 (c), mul, add) of them, bit for bit,
+    which differs from (c / 255 - mean) / std evaluated in any other order or precision by rounding error"""
+    m, s = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    if m.shape != (3,) or s.shape != (3,) or not np.all(np.isfinite(m)) or not np.all(np.isfinite(s)) or np.any(s == 0):
+        raise ValueError("mean and std must be three finite numbers each, std not 0")
+    mul, add = (1.0 / (255.0 * s)).astype(np.float32), (-m / s).astype(np.float32)
+    return tuple(float(x) for x in mul), tuple(float(x) for x in add)
 
 
 def decode_arena_bytes():
@@ -290,12 +347,15 @@ def decode_arena_bytes():
     return d.value, p.value
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
-    """out_dir/<basename>.yuv - with colour= <basename>.rgb - for every input, through one decode_batch with a sink that appends to the
-    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix and colour_range as in decode_batch"""
+_SUFFIX = {"uint8": ".rgb", "float32": ".f32", "float16": ".f16", "bfloat16": ".bf16"}
+
+
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
+    """out_dir/<basename>.yuv - with colour= <basename>.rgb, with a float dtype= <basename>.f32 | .f16 | .bf16 - for every input, through one decode_batch with a sink that appends to the
+    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul and add as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    names = [os.path.join(out_dir, os.path.basename(p) + (".yuv" if colour is None else ".rgb")) for p in paths]
+    names = [os.path.join(out_dir, os.path.basename(p) + (".yuv" if colour is None else _SUFFIX.get(dtype, ".rgb"))) for p in paths]
     files = [open(q, "wb") for q in names]
     total = [0] * len(paths)
 
@@ -304,7 +364,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add)
     finally:
         for f in files:
             f.close()
@@ -313,13 +373,13 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto"):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
     per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick and size as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add)
     res = []
     try:
         for i, p in enumerate(paths):

@@ -3,12 +3,14 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
 --size WxH asks for pictures of that size (decode_batch (size=(W, H)), both even, 2..4096, not with --scale) and adds "size" to the rows;
 --colour rgb24|rgbp asks for RGB pictures (decode_batch (colour=...), not with --nv12) and adds "colour" to the rows;
+--dtype float32|float16|bfloat16 asks for float RGB pictures (decode_batch (dtype=...), with --colour only; the factors are
+normalise of the ImageNet means and deviations) and adds "dtype" to the rows;
 --pick intra|idr decodes the selected pictures only (decode_batch (pick=...)) and adds "pick" to the rows; every row carries
 parsed_slices (the slices whose data was parsed, all streams) and the launch shape of the call (rounds, chains, jobs);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
@@ -54,6 +56,10 @@ def main(argv):
     if "--colour" in argv:
         scale = dict(scale, colour=argv[argv.index("--colour") + 1])
         args.remove(argv[argv.index("--colour") + 1])
+    if "--dtype" in argv:
+        mul, add = lh.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
+        scale = dict(scale, dtype=argv[argv.index("--dtype") + 1])
+        args.remove(argv[argv.index("--dtype") + 1])
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
     data = open(path, "rb").read()
@@ -64,10 +70,11 @@ def main(argv):
     for mode in [m for m in modes if m != "parse"]:
         for r in range(runs):
             t0 = time.perf_counter()
+            factors = dict(mul=mul, add=add) if "dtype" in scale else {}
             if mode == "digests":
-                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse, **scale)
+                b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse, **scale, **factors)
             else:
-                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse, **scale)
+                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse, **scale, **factors)
             dt = time.perf_counter() - t0
             ms = (C.c_double * 6)()
             lib.lh264_decode_last_timing(ms)
