@@ -79,12 +79,25 @@ __constant__ uint8_t kTables[52 + 52 + 52 * 4] = {
 #define TAB_TC0 104
 
 // ---- workgroup-shared LDS ----------------------------------------------------------------------
+// What is fixed for a frame and read by the phases that are not inlined: they take it from here (a broadcast LDS read, made scalar)
+// instead of by value in a dozen argument registers.  At most two frames of a chain are in flight, so two blocks do, frame j using
+// block j & 1: a wave writes the block on entering frame j, behind its wait for every row of frame j - 2 and older to be stored, and
+// the last read of the block by frame j - 2 (inter_phase of its last macroblock) precedes that row's `stored`.  Every wave entering
+// a frame writes the same values.
+struct FrameLds {
+  uint64_t prev_dy;          // luma plane of the previous job of the chain (0: none): the only other frame that can be in flight
+  int32_t  sy, sc, mb_w, mb_h;
+  int32_t  prev_base;        // global index of the previous job's row 0
+  int32_t  prev_h_nw;        // its height in macroblock rows (low half) and the waves of the workgroup (high half)
+};
 struct WgLds {
-  int      progress[16];   // per wave: (rows it has started - 1) << 12 | macroblocks finished in its current row
-  int      stored[16];     // per wave: index (among its own rows) of the last row whose HBM stores, including the
+  int      progress[8];    // per wave: (rows it has started - 1) << 12 | macroblocks finished in its current row
+  int      stored[8];      // per wave: index (among its own rows) of the last row whose HBM stores, including the
                            // padding that row is responsible for, have completed; -1 = none
+  FrameLds frame[2];       // (in the 64 bytes that progress and stored had for waves 8..15, which no launch has)
   uint8_t  tab[52 + 52 + 208];
 };
+static_assert (sizeof (FrameLds) == 32 && sizeof (WgLds) == 128 + 312, "WgLds keeps its size");
 
 // ---- per-wave LDS ------------------------------------------------------------------------------
 struct WaveLds {
@@ -105,6 +118,10 @@ struct WaveLds {
   uint64_t refp[LH264_MAX_REFS][3];   // reference plane pointers of this wave's current job
   int32_t  known_prefix;     // every global row <= known_prefix is known to be stored (cache of wait_prefix)
 };
+// the glue of process_mb addresses the tiles and the carry as one array each: lane l moves dword l
+static_assert (offsetof (WaveLds, T) == 0 && offsetof (WaveLds, C) == 640 && sizeof (WaveLds::C) == 320, "tile layout");
+static_assert (offsetof (WaveLds, lfC) == offsetof (WaveLds, lfY) + 80, "carry layout");
+#define TILE_C(p) ((p) ? 800 : 640)      // byte offset of chroma tile p from the luma tile (a select, not a multiply)
 
 __device__ __forceinline__ int tY (int r, int c) { return (r + 4) * 32 + (c + 4); }
 __device__ __forceinline__ int tC (int r, int c) { return (r + 2) * 16 + (c + 4); }
@@ -113,6 +130,13 @@ __device__ __forceinline__ int clip3 (int v, int lo, int hi) { return min (max (
 __device__ __forceinline__ int zidx (int bx, int by) { return (bx & 1) | ((by & 1) << 1) | ((bx >> 1) << 2) | ((by >> 1) << 3); }
 __device__ __forceinline__ int tab_idx (int v) { return clip3 (v, 0, 51); }
 __device__ __forceinline__ int uni (int v) { return __builtin_amdgcn_readfirstlane (v); }
+// a * b + c for a < 2^24 and a wave-uniform b < 2^24 (rows times a stride): one full-rate instruction where the 32-bit multiply
+// takes four issue slots
+__device__ __forceinline__ uint32_t mad24 (uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t r;
+  asm ("v_mad_u32_u24 %0, %1, %2, %3" : "=v" (r) : "v" (a), "s" (b), "v" (c));
+  return r;
+}
 
 // order LDS traffic between the lanes of one wave.  The DS instructions of a wave execute in issue order, so
 // a later ds_read observes an earlier ds_write of any lane; all that is needed is to stop the COMPILER from
@@ -209,10 +233,7 @@ struct FrameCtx {
   const GLB lh264_mb_t* mbs; const GLB int16_t* coeffs; const GLB lh264_slice_t* slices;
   GLB uint8_t* dy; GLB uint8_t* du; GLB uint8_t* dv;
   int mb_w, mb_h, sy, sc, flags;
-  // the previous job of the chain (the only other frame that can still be in flight)
-  uint64_t prev_dy;          // its luma plane pointer (0: none)
-  int prev_base, prev_h;     // global index of its row 0, its height in macroblock rows
-  int nw;                    // waves in the workgroup
+  int prev_base;             // global index of row 0 of the previous job of the chain (the only other frame that can still be in flight)
 };
 
 // Block until every global row <= g_need has been stored (rows are owned round-robin: the next unfinished row of wave
@@ -233,16 +254,21 @@ __device__ __forceinline__ void wait_prefix (const LDS WgLds& G, LDS WaveLds& L,
 
 struct Pref { v2i l, c; uint32_t rec; };   // what is fetched one macroblock ahead (per lane)
 
+// a wave-uniform pointer, pinned to a scalar register pair: what is added to it stays a 32-bit lane offset of the load or store
+// (scalar base + vector offset addressing) instead of being folded with the lane's part into a 64-bit vector address that is
+// kept, or rebuilt, per macroblock
+template <typename T> __device__ __forceinline__ T* sbase (T* p) { asm ("" : "+s" (p)); return p; }
+
 __device__ __forceinline__ Pref prefetch_mb (const FrameCtx& F, int k, bool has_top, int lane) {
   Pref p;
-  const GLB int16_t* cf = F.coeffs + (size_t)k * 384;
+  const GLB int16_t* cf = sbase (F.coeffs + (size_t)k * 384);
   p.l = * (const GLB v2i*) (cf + 4 * lane);
   p.c = mk2 (0, 0);
   p.rec = 0;
   if (lane < 32) {
-    p.c = * (const GLB v2i*) (cf + 256 + 4 * lane);
-    p.rec = ((const GLB uint32_t*) (F.mbs + k))[lane];
-  } else if (has_top) p.rec = ((const GLB uint32_t*) (F.mbs + k - F.mb_w))[lane - 32];
+    p.c = * (const GLB v2i*) (sbase (cf + 256) + 4 * lane);
+    p.rec = ((const GLB uint32_t*)sbase (F.mbs + k))[lane];
+  } else if (has_top) p.rec = ((const GLB uint32_t*)sbase (F.mbs + k - F.mb_w))[lane - 32];
   return p;
 }
 
@@ -759,14 +785,18 @@ __device__ __forceinline__ void partition_of (int mb_type, RecView m, int bx, in
   }
 }
 
-// what the inter phase needs of the frame context, passed BY VALUE: a reference to the caller's FrameCtx would turn
-// every field access in this non-inlined function into a scratch load followed by "s_waitcnt vmcnt(0)", which also
-// drains the reference fetches in flight.
-struct InterCtx { uint64_t prev_dy; int sy, sc, mb_w, mb_h, prev_base, prev_h, nw; };
+// The frame context comes from the frame's LDS block (FrameLds), read here with LDS-qualified loads and made scalar: a reference
+// to the caller's FrameCtx would turn every field access in this non-inlined function into a scratch load followed by
+// "s_waitcnt vmcnt(0)", which also drains the reference fetches in flight, and passing it by value cost the caller 17 moves into
+// argument registers per macroblock.
+struct InterCtx { int sy, sc, mb_w, mb_h; };
 
 // GetInterPred rec_mb.cpp:344-545, BaseMC :247-274, WeightPrediction :276-341 (+ residual add)
-__device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const LDS WgLds& G, RecView m, SliceView sl, int mb_type,
+__device__ LH264_PHASE void inter_phase (LDS WaveLds& L, const LDS WgLds& G, const LDS FrameLds& FR, RecView m, SliceView sl, int mb_type,
                                           int mbx, int mby, bool has_res, int lane) {
+  InterCtx F;
+  F.sy = uni (FR.sy); F.sc = uni (FR.sc); F.mb_w = uni (FR.mb_w); F.mb_h = uni (FR.mb_h);
+  const uint64_t prev_dy = FR.prev_dy;
   const int b = lane >> 2, r = lane & 3;
   const int bx = (b & 1) | ((b >> 2) & 1) << 1, by = ((b >> 1) & 1) | ((b >> 3) & 1) << 1;
   const int ly = 4 * by + r, lx0 = 4 * bx;
@@ -796,15 +826,16 @@ __device__ LH264_PHASE void inter_phase (const InterCtx F, LDS WaveLds& L, const
     L.mvi[lane][3] = ox | oy << 8 | pw << 16 | ph << 24;
     // last luma row this block can touch in the frame that may still be in flight: its 4 rows, 3 more under a
     // vertical 6-tap; chroma: 2 rows, 1 more under a vertical fraction (in luma units)
-    if (L.refp[slot][0] == F.prev_dy) need = max (syy + 3 + ((fy & 3) ? 3 : 0), 2 * (cys + 1 + ((fy & 7) ? 1 : 0)) + 1);
+    if (L.refp[slot][0] == prev_dy) need = max (syy + 3 + ((fy & 3) ? 3 : 0), 2 * (cys + 1 + ((fy & 7) ? 1 : 0)) + 1);
   }
-  if (F.prev_dy) {
+  if (__ballot (prev_dy != 0)) {                    // (wave-uniform)
 #pragma unroll
     for (int msk = 1; msk < 16; msk <<= 1) need = max (need, __shfl_xor (need, msk));
     need = uni (need);
     if (need != -0x7fffffff) {
-      const int rneed = clip3 (need >> 4, 0, F.prev_h - 1);
-      wait_prefix (G, L, F.prev_base + min (rneed + 1, F.prev_h - 1), F.nw);
+      const int hn = uni (FR.prev_h_nw), prev_h = hn & 0xffff;
+      const int rneed = clip3 (need >> 4, 0, prev_h - 1);
+      wait_prefix (G, L, uni (FR.prev_base) + min (rneed + 1, prev_h - 1), hn >> 16);
     }
   }
   wsync();
@@ -1030,11 +1061,23 @@ __device__ LH264_PHASE void deblock_phase (LDS WaveLds& L, const LDS WgLds& G, R
   const int qc = chroma ? m.qp_c (cpl) : m.qp_y();
   const int ql = (qc + (chroma ? lm.qp_c (cpl) : lm.qp_y()) + 1) >> 1;
   const int qt = (qc + (chroma ? tm.qp_c (cpl) : tm.qp_y()) + 1) >> 1;
-  const int iac = tab_idx (qc + ao), ial = tab_idx (ql + ao), iat = tab_idx (qt + ao);
-  const int alc = tab[TAB_ALPHA + iac], all_ = tab[TAB_ALPHA + ial], alt = tab[TAB_ALPHA + iat];
-  const int bec = tab[TAB_BETA + tab_idx (qc + bo)], bel = tab[TAB_BETA + tab_idx (ql + bo)], bet = tab[TAB_BETA + tab_idx (qt + bo)];
-  const uint32_t tcc = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * iac], tcl = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * ial],
-                 tct = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * iat];
+  const int iac = tab_idx (qc + ao);
+  const int alc = tab[TAB_ALPHA + iac], bec = tab[TAB_BETA + tab_idx (qc + bo)];
+  const uint32_t tcc = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * iac];
+  // The two macroblock edges take the mean of two QPs.  Where every line of the macroblock (all 32 lanes here: luma and both chroma
+  // planes) finds both means equal to its own QP - a stream of one QP, the usual case - the inner edges' lookup serves all three.
+  int all_ = alc, alt = alc, bel = bec, bet = bec;
+  uint32_t tcl = tcc, tct = tcc;
+#ifdef LH264_ABL_QP3         // timing ablation only (same pictures): three lookups always
+  if (true) {
+#else
+  if (__ballot (ql != qc || qt != qc)) {            // (wave-uniform)
+#endif
+    const int ial = tab_idx (ql + ao), iat = tab_idx (qt + ao);
+    all_ = tab[TAB_ALPHA + ial]; alt = tab[TAB_ALPHA + iat];
+    bel = tab[TAB_BETA + tab_idx (ql + bo)]; bet = tab[TAB_BETA + tab_idx (qt + bo)];
+    tcl = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * ial]; tct = * (const LDS uint32_t*)&tab[TAB_TC0 + 4 * iat];
+  }
   // Reference behaviour kept bit for bit: for an INTRA macroblock whose Cb and Cr QPs differ, FilteringEdgeChromaHV looks tc0 up
   // in its "chroma v" loop only; its "chroma h" loop (deblocking.cpp:786-807) filters the inner edge of each plane with what that
   // loop left behind - Cr's tc0 whenever Cr's alpha | beta is nonzero.  So Cb's inner horizontal edge takes Cr's tc0 then.
@@ -1143,7 +1186,7 @@ __device__ __forceinline__ void wait_row_above (volatile LDS int* prog_above, in
   }
 }
 
-__device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, const LDS WgLds& G, const RowBufs& B, const Pref& pf,
+__device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, const LDS WgLds& G, const LDS FrameLds& FR, const RowBufs& B, const Pref& pf,
                                             int mbx, int mby, int par, int& slc_id, bool pub_line, bool pub_left, int lane,
                                             volatile LDS int* prog_above, int need_above
 #ifdef LH264_STAMP
@@ -1151,6 +1194,7 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
 #endif
                                            ) {
   LDS uint8_t* T = L.T;
+  LDS uint8_t* const tile = L.T;             // luma tile and, behind it (TILE_C), the two chroma tiles as one array
   // The row above must be two macroblocks ahead (top-right neighbour of intra prediction; raster order of the in-loop filter).  Only
   // an INTRA macroblock needs that before it starts: inter prediction and the residual read nothing of the row above, so every other
   // macroblock predicts first and waits where its filter takes the neighbours' filtered samples - the wait overlaps its own work.
@@ -1186,12 +1230,12 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
     if (lane < 8) * (LDS uint32_t*)&T[tY (-1, -4 + 4 * lane)] = * (const LDS uint32_t*)&B.lineTop[16 + 16 * mbx - 4 + 4 * lane];
     else if (lane < 16) {
       const int p = (lane - 8) >> 2, q = (lane - 8) & 3;
-      * (LDS uint32_t*)&L.C[p][tC (-1, -4 + 4 * q)] = * (const LDS uint32_t*)&B.lineTop[B.LY + p * B.LC + 8 + 8 * mbx - 4 + 4 * q];
+      * (LDS uint32_t*)&tile[TILE_C (p) + tC (-1, -4 + 4 * q)] = * (const LDS uint32_t*)&B.lineTop[B.LY + (p ? B.LC : 0) + 8 + 8 * mbx - 4 + 4 * q];
     }
   }
   if (intra && mbx > 0) {
     if (lane >= 16 && lane < 32) T[tY (lane - 16, -1)] = L.leftY[lane - 16];
-    else if (lane >= 32 && lane < 48) { const int p = (lane - 32) >> 3, q = (lane - 32) & 7; L.C[p][tC (q, -1)] = L.leftC[p][q]; }
+    else if (lane >= 32 && lane < 48) { const int p = (lane - 32) >> 3, q = (lane - 32) & 7; tile[TILE_C (p) + tC (q, -1)] = L.leftC[0][lane - 32]; }
   }
   wsync();
 
@@ -1218,7 +1262,7 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
       if (lane < 32) {
         const v2i cv = pf.c;
         const int p = lane >> 4, yy2 = (lane >> 1) & 7, xx2 = 4 * (lane & 1);
-        * (LDS uint32_t*)&L.C[p][tC (yy2, xx2)] = (cv.x & 0xff) | ((cv.x >> 16) & 0xff) << 8 | (cv.y & 0xff) << 16 | ((cv.y >> 16) & 0xff) << 24;
+        * (LDS uint32_t*)&tile[TILE_C (p) + tC (yy2, xx2)] = (cv.x & 0xff) | ((cv.x >> 16) & 0xff) << 8 | (cv.y & 0xff) << 16 | ((cv.y >> 16) & 0xff) << 24;
       }
     } else if (intra) {
       if (i16) intra16_phase (L, uni (m.intra_mode (0)), lane);
@@ -1226,17 +1270,14 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
       else intra4x4_phase (L, m, lane);
       intra_chroma_phase (L, uni (m.chroma_mode()), lane);
     } else if (mb_type & LH264_MB_INTER) {
-      InterCtx ic;
-      ic.prev_dy = F.prev_dy; ic.sy = F.sy; ic.sc = F.sc; ic.mb_w = F.mb_w; ic.mb_h = F.mb_h;
-      ic.prev_base = F.prev_base; ic.prev_h = F.prev_h; ic.nw = F.nw;
 #ifndef LH264_ABL_NOINTER    // timing ablation only (wrong pictures)
-      inter_phase (ic, L, G, m, sl, mb_type, mbx, mby, has_res, lane);
+      inter_phase (L, G, FR, m, sl, mb_type, mbx, mby, has_res, lane);
 #endif
     }
   } else {
     // macroblock not covered by any slice (lost data): pass the picture's current samples through
-    * (LDS uint32_t*)&T[tY (ly, lx0)] = * (const GLB uint32_t*) (F.dy + (size_t) (mby * 16 + ly) * F.sy + mbx * 16 + lx0);
-    if (lane < 32) * (LDS uint32_t*)&L.C[cp][tC (cy, cx0)] = * (const GLB uint32_t*) ((cp ? F.dv : F.du) + (size_t) (mby * 8 + cy) * F.sc + mbx * 8 + cx0);
+    * (LDS uint32_t*)&T[tY (ly, lx0)] = * (const GLB uint32_t*) (F.dy + ((size_t) (mby * 16) * F.sy + mbx * 16) + mad24 (ly, F.sy, lx0));
+    if (lane < 32) * (LDS uint32_t*)&tile[TILE_C (cp) + tC (cy, cx0)] = * (const GLB uint32_t*) ((cp ? F.dv : F.du) + ((size_t) (mby * 8) * F.sc + mbx * 8) + mad24 (cy, F.sc, cx0));
   }
   wsync();
 
@@ -1244,11 +1285,11 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
   // ---- 4. publish unfiltered bottom row / right column, when an intra macroblock will read them -----
   if (pub_line) {
     if (lane < 4) * (LDS uint32_t*)&B.lineCur[16 + 16 * mbx + 4 * lane] = * (const LDS uint32_t*)&T[tY (15, 4 * lane)];
-    else if (lane < 8) { const int p = (lane - 4) >> 1, q = (lane - 4) & 1; * (LDS uint32_t*)&B.lineCur[B.LY + p * B.LC + 8 + 8 * mbx + 4 * q] = * (const LDS uint32_t*)&L.C[p][tC (7, 4 * q)]; }
+    else if (lane < 8) { const int p = (lane - 4) >> 1, q = (lane - 4) & 1; * (LDS uint32_t*)&B.lineCur[B.LY + (p ? B.LC : 0) + 8 + 8 * mbx + 4 * q] = * (const LDS uint32_t*)&tile[TILE_C (p) + tC (7, 4 * q)]; }
   }
   if (pub_left) {
     if (lane >= 16 && lane < 32) L.leftY[lane - 16] = T[tY (lane - 16, 15)];
-    else if (lane >= 32 && lane < 48) { const int p = (lane - 32) >> 3, q = (lane - 32) & 7; L.leftC[p][q] = L.C[p][tC (q, 7)]; }
+    else if (lane >= 32 && lane < 48) { const int p = (lane - 32) >> 3, q = (lane - 32) & 7; L.leftC[0][lane - 32] = tile[TILE_C (p) + tC (q, 7)]; }
   }
   if (pub_line || pub_left) wsync();
 
@@ -1267,73 +1308,87 @@ __device__ __forceinline__ void process_mb (const FrameCtx& F, LDS WaveLds& L, c
     if (top_av) top_av = tm.slice_id() == sid;
   }
   if (!early_wait) wait_row_above (prog_above, need_above, mby > 0);
-  // neighbours' filtered samples: left 4 columns carried from the previous step, top rows from `fline`
-  if (mbx > 0) {
-    if (lane < 20) * (LDS uint32_t*)&T[tY (lane - 4, -4)] = L.lfY[lane];
-    else if (lane < 40) { const int p = (lane - 20) / 10, q = (lane - 20) % 10; * (LDS uint32_t*)&L.C[p][tC (q - 2, -4)] = L.lfC[p][q]; }
-  }
-  if (mby > 0) {
-    if (lane >= 40 && lane < 56) {
-      const int rr = (lane - 40) >> 2, q = lane & 3;
-      * (LDS uint32_t*)&T[tY (-4 + rr, 4 * q)] = * (const LDS uint32_t*)&B.fTop[rr * B.FW + mbx * 16 + 4 * q];
-    } else if (lane >= 56) {
-      const int p = (lane - 56) >> 2, rr = (lane >> 1) & 1, q = lane & 1;
-      * (LDS uint32_t*)&L.C[p][tC (-2 + rr, 4 * q)] = * (const LDS uint32_t*)&B.fTop[4 * B.FW + (p * 2 + rr) * (B.FW >> 1) + mbx * 8 + 4 * q];
-    }
+  // neighbours' filtered samples: left 4 columns carried from the previous step, top rows from `fline`.
+  // The carry (lfY, lfC) and the tiles (T, C) are one array each: lane l < 40 moves dword l of the carry, whose place in the tiles is
+  // row l of the luma tile (32 bytes a row) or row l - 20 of the chroma tiles (16 bytes a row, 10 rows each).
+  const int carry_off = lane < 20 ? 32 * lane : 16 * lane + 320;      // tile offset of columns -4..-1 of the lane's row
+  if (mbx > 0 && lane < 40) * (LDS uint32_t*)&tile[carry_off] = L.lfY[lane];
+  if (mby > 0 && lane >= 40) {
+    // lanes 40..55: luma rows -4..-1 x 4 dwords; lanes 56..63: chroma plane p rows -2, -1 x 2 dwords.  `fline` holds 4 luma rows of
+    // FW bytes, then 4 chroma rows (plane, row) of FW / 2 bytes: row a of FW / 2 bytes each
+    const bool ch = lane >= 56;
+    const int j = ch ? (lane - 56) >> 1 : (lane - 40) >> 2;           // luma row, or chroma (plane * 2 + row)
+    const int q = ch ? lane & 1 : lane & 3;
+    const int dst = ch ? TILE_C (j >> 1) + tC (-2 + (j & 1), 4 * q) : tY (-4 + j, 4 * q);
+    const int src = (int)mad24 (ch ? 8 + j : 2 * j, B.FW >> 1, 4 * q) + (ch ? mbx * 8 : mbx * 16);
+    * (LDS uint32_t*)&tile[dst] = * (const LDS uint32_t*)&B.fTop[src];
   }
   wsync();
   STAMP (5);
   if (filt) deblock_phase (L, G, m, lm, tm, sl, left_av, top_av, lane);
   STAMP (6);
   // carry the (filtered) right 4 columns to the next macroblock of this row
-  if (lane < 20) L.lfY[lane] = * (const LDS uint32_t*)&T[tY (lane - 4, 12)];
-  else if (lane < 40) { const int p = (lane - 20) / 10, q = (lane - 20) % 10; L.lfC[p][q] = * (const LDS uint32_t*)&L.C[p][tC (q - 2, 4)]; }
+  if (lane < 40) L.lfY[lane] = * (const LDS uint32_t*)&tile[carry_off + (lane < 20 ? 16 : 8)];
 
   // ---- 6. write the samples that became final: 16x16 window at (-4,-3), chroma 8x8 at (-4,-1) --------
+  // Every store goes to a wave-uniform 64-bit base (the window's first sample) plus the lane's unsigned 32-bit offset row * stride + col.
   const bool last_x = mbx == F.mb_w - 1, last_y = mby == F.mb_h - 1;
+  const bool has_l = mbx > 0, has_t = mby > 0;
 #ifndef LH264_ABL_NOSTORE    // timing ablation only (no pictures)
+  GLB uint8_t* const wy = F.dy + ((ptrdiff_t) (mby * 16 - 3) * F.sy + (mbx * 16 - 4));
+  const ptrdiff_t wc_off = (ptrdiff_t) (mby * 8 - 1) * F.sc + (mbx * 8 - 4);
+  GLB uint8_t* const wu = F.du + wc_off;
+  GLB uint8_t* const wv = F.dv + wc_off;
   {
-    const int rr = -3 + (lane >> 2), cc = -4 + 4 * (lane & 3);
-    if ((rr >= 0 || mby > 0) && (cc >= 0 || mbx > 0))
-      * (GLB uint32_t*) (F.dy + (ptrdiff_t) (mby * 16 + rr) * F.sy + mbx * 16 + cc) = * (const LDS uint32_t*)&T[tY (rr, cc)];
-    if (lane < 32) {
-      const int p = lane >> 4, r2 = -1 + ((lane >> 1) & 7), c2 = -4 + 4 * (lane & 1);
-      if ((r2 >= 0 || mby > 0) && (c2 >= 0 || mbx > 0))
-        * (GLB uint32_t*) ((p ? F.dv : F.du) + (ptrdiff_t) (mby * 8 + r2) * F.sc + mbx * 8 + c2) = * (const LDS uint32_t*)&L.C[p][tC (r2, c2)];
+    const int wr = lane >> 2, wc = lane & 3;             // window row 0..15 (picture row -3 + wr), dword 0..3
+    if ((wr >= 3 || has_t) && (wc || has_l))
+      * (GLB uint32_t*) (wy + mad24 (wr, F.sy, 4 * wc)) = * (const LDS uint32_t*)&tile[32 * (wr + 1) + 4 * wc];
+    {                                                    // lanes 0..15 U, 16..31 V: one store each from its own uniform base
+      const int p = (lane >> 4) & 1, cr = (lane >> 1) & 7, cc = lane & 1;    // window row 0..7 (picture row -1 + cr), dword 0..1
+      const bool on = lane < 32 && (cr || has_t) && (cc || has_l);
+      const uint32_t v = * (const LDS uint32_t*)&tile[TILE_C (p) + 16 * (cr + 1) + 4 * cc];
+      const uint32_t o = mad24 (cr, F.sc, 4 * cc);
+      if (on && !p) * (GLB uint32_t*) (wu + o) = v;
+      if (on && p) * (GLB uint32_t*) (wv + o) = v;
     }
   }
-  if (last_x) {                     // right-most columns never get a successor
-    if (lane < 16) {
-      const int rr = -3 + lane;
-      if (rr >= 0 || mby > 0) * (GLB uint32_t*) (F.dy + (ptrdiff_t) (mby * 16 + rr) * F.sy + mbx * 16 + 12) = * (const LDS uint32_t*)&T[tY (rr, 12)];
-    } else if (lane < 32) {
-      const int p = (lane - 16) >> 3, r2 = -1 + (lane & 7);
-      if (r2 >= 0 || mby > 0) * (GLB uint32_t*) ((p ? F.dv : F.du) + (ptrdiff_t) (mby * 8 + r2) * F.sc + mbx * 8 + 4) = * (const LDS uint32_t*)&L.C[p][tC (r2, 4)];
-    }
+  if (last_x) {                     // right-most columns never get a successor: lanes 0..15 luma, 16..23 U, 24..31 V
+    const int p = (lane >> 3) & 1, cr = lane & 7;
+    const bool luma = lane < 16;
+    const uint32_t v = * (const LDS uint32_t*)&tile[luma ? 32 * (lane + 1) + 16 : TILE_C (p) + 16 * (cr + 1) + 8];
+    const uint32_t o = luma ? mad24 (lane, F.sy, 16) : mad24 (cr, F.sc, 8);
+    const bool con = lane < 32 && !luma && (cr || has_t);
+    if (luma && (lane >= 3 || has_t)) * (GLB uint32_t*) (wy + o) = v;
+    if (con && !p) * (GLB uint32_t*) (wu + o) = v;
+    if (con && p) * (GLB uint32_t*) (wv + o) = v;
   }
+  // the bottom rows, to the picture (last_y) or to `fline`: 8 lanes a row, of which dwords 0..4 (chroma 4 lanes, 0..2) exist: columns
+  // -4..15 (-4..7), the first one only behind a left neighbour, the last one only at the last macroblock of the row
+  const int bq = lane & 7, bcq = lane & 3;
+  const bool bl_on = bq < 5 && (bq || has_l) && (bq < 4 || last_x);
+  const bool bc_on = bcq < 3 && (bcq || has_l) && (bcq < 2 || last_x);
   if (last_y) {                     // bottom rows never get a successor
-    if (lane < 15) {
-      const int rr = 13 + lane / 5, cc = -4 + 4 * (lane % 5);
-      if ((cc >= 0 || mbx > 0) && (cc < 12 || last_x))
-        * (GLB uint32_t*) (F.dy + (ptrdiff_t) (mby * 16 + rr) * F.sy + mbx * 16 + cc) = * (const LDS uint32_t*)&T[tY (rr, cc)];
-    } else if (lane >= 16 && lane < 22) {
-      const int p = (lane - 16) / 3, c2 = -4 + 4 * ((lane - 16) % 3);
-      if ((c2 >= 0 || mbx > 0) && (c2 < 4 || last_x))
-        * (GLB uint32_t*) ((p ? F.dv : F.du) + (ptrdiff_t) (mby * 8 + 7) * F.sc + mbx * 8 + c2) = * (const LDS uint32_t*)&L.C[p][tC (7, c2)];
+    if (lane < 24) {                // luma rows 13..15 = window rows 16..18
+      const int wr = 16 + (lane >> 3);
+      if (bl_on) * (GLB uint32_t*) (wy + mad24 (wr, F.sy, 4 * bq)) = * (const LDS uint32_t*)&tile[32 * (wr + 1) + 4 * bq];
+    } else if (lane >= 32 && lane < 40) {   // chroma row 7 = window row 8 of either plane
+      const int p = (lane >> 2) & 1;
+      const uint32_t v = * (const LDS uint32_t*)&tile[TILE_C (p) + 16 * 9 + 4 * bcq];
+      const uint32_t o = 8u * F.sc + 4u * bcq;
+      if (bc_on && !p) * (GLB uint32_t*) (wu + o) = v;
+      if (bc_on && p) * (GLB uint32_t*) (wv + o) = v;
     }
   }
 #endif
   STAMP (7);
   // filtered bottom rows for the row below: tile rows 12..15 x cols [-4,11] (+ [12,15] at the last MB)
   if (!last_y) {
-    if (lane < 20) {
-      const int rr = lane / 5, q = lane % 5, cc = -4 + 4 * q;
-      if ((cc >= 0 || mbx > 0) && (cc < 12 || last_x))
-        * (LDS uint32_t*)&B.fCur[rr * B.FW + mbx * 16 + cc] = * (const LDS uint32_t*)&T[tY (12 + rr, cc)];
-    } else if (lane >= 32 && lane < 44) {
-      const int i = lane - 32, p = i / 6, rr = (i % 6) / 3, q = i % 3, c2 = -4 + 4 * q;
-      if ((c2 >= 0 || mbx > 0) && (c2 < 4 || last_x))
-        * (LDS uint32_t*)&B.fCur[4 * B.FW + (p * 2 + rr) * (B.FW >> 1) + mbx * 8 + c2] = * (const LDS uint32_t*)&L.C[p][tC (6 + rr, c2)];
+    if (lane < 32) {
+      const int rr = lane >> 3;
+      if (bl_on) * (LDS uint32_t*)&B.fCur[(int)mad24 (rr, B.FW, 4 * bq) + mbx * 16 - 4] = * (const LDS uint32_t*)&tile[32 * (16 + rr) + 4 * bq];
+    } else if (lane < 48) {
+      const int j = (lane - 32) >> 2;                    // plane * 2 + row
+      if (bc_on) * (LDS uint32_t*)&B.fCur[(int)mad24 (8 + j, B.FW >> 1, 4 * bcq) + mbx * 8 - 4] = * (const LDS uint32_t*)&tile[TILE_C (j >> 1) + 16 * (8 + (j & 1)) + 4 * bcq];
     }
   }
   wsync();
@@ -1419,7 +1474,7 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
   volatile LDS int* stored = G.stored;
 
   for (int i = tid; i < (int)sizeof (G.tab); i += blockDim.x) G.tab[i] = kTables[i];
-  if (tid < 16) { progress[tid] = 0; stored[tid] = -1; }
+  if (tid < 8) { progress[tid] = 0; stored[tid] = -1; }
   if (lane == 0) L.known_prefix = -1;
   __syncthreads();
 
@@ -1433,7 +1488,7 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
   bool overlap_ok = false;
   int slc_id = -1;
   FrameCtx F;
-  F.nw = NW; F.prev_dy = 0; F.prev_base = 0; F.prev_h = 1;
+  F.prev_base = 0;
   RowBufs B;
   int lu = 0;
   STAMP_DECL
@@ -1452,12 +1507,14 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
       B.LY = F.mb_w * 16 + 48; B.LC = F.mb_w * 8 + 24; B.FW = F.mb_w * 16;
       lu = B.LY + 2 * B.LC;
       wsync();
-      if (lane < LH264_MAX_REFS * 3) L.refp[lane / 3][lane % 3] = ((const uint64_t*)&J->ref[lane / 3])[lane % 3];
+      static_assert (sizeof (lh264_pic_t) == 24, "refp mirrors lh264_frame_job_t::ref word for word");
+      if (lane < LH264_MAX_REFS * 3) (&L.refp[0][0])[lane] = ((const uint64_t*)J->ref)[lane];
       overlap_ok = false;
-      F.prev_dy = 0;
+      uint64_t prev_dy = 0;
+      int prev_h = 1;
       if (ji > first) {
         const lh264_frame_job_t* P = J - 1;
-        F.prev_dy = (uint64_t) (uintptr_t)P->dst.y_dev; F.prev_h = P->mb_h; F.prev_base = base - P->mb_h;
+        prev_dy = (uint64_t) (uintptr_t)P->dst.y_dev; prev_h = P->mb_h; F.prev_base = base - P->mb_h;
 #ifndef LH264_NO_OVERLAP
         // two frames may be in flight only if this frame's picture is not one the previous frame still reads
         overlap_ok = true;
@@ -1467,6 +1524,14 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
       }
       slc_id = -1;
       cur_ji = ji;
+      wsync();
+      // everything older than the previous frame must be complete (and the previous frame too if pictures alias)
+      if (ji > first) wait_prefix (G, L, (overlap_ok ? F.prev_base : base) - 1, NW);
+      // ... so nothing reads the frame block of frame ji - 2 any more: it becomes this frame's
+      if (lane == 0) {
+        LDS FrameLds& W = G.frame[ji & 1];
+        W.prev_dy = prev_dy; W.sy = F.sy; W.sc = F.sc; W.mb_w = F.mb_w; W.mb_h = F.mb_h; W.prev_base = F.prev_base; W.prev_h_nw = prev_h | NW << 16;
+      }
       wsync();
     }
     // everything older than the previous frame must be complete (and the previous frame too if pictures alias)
@@ -1485,8 +1550,8 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
     for (int x = 0; x < F.mb_w; x++) {
       if ((x & 63) == 0) {                   // (before the prefetch: these two loads are waited for at once)
         int t = 0, u = 0;
-        if (row + 1 < F.mb_h && x + lane < F.mb_w) t = * (const GLB uint16_t*) (F.mbs + (size_t) (row + 1) * F.mb_w + x + lane);
-        if (x + 1 + lane < F.mb_w) u = * (const GLB uint16_t*) (F.mbs + (size_t)row * F.mb_w + x + 1 + lane);
+        if (row + 1 < F.mb_h && x + lane < F.mb_w) t = * (const GLB uint16_t*) (sbase (F.mbs + (size_t) (row + 1) * F.mb_w + x) + lane);
+        if (x + 1 + lane < F.mb_w) u = * (const GLB uint16_t*) (sbase (F.mbs + (size_t)row * F.mb_w + x + 1) + lane);
         below = __ballot ((t & LH264_MB_INTRA) != 0);
         ahead = __ballot ((u & LH264_MB_INTRA) != 0);
       }
@@ -1510,9 +1575,9 @@ recon_chain_kernel (const lh264_frame_job_t* __restrict__ jobs, const int32_t* _
       const int lane_mb = lane;
 #endif
 #ifdef LH264_STAMP
-      process_mb (F, L, G, B, pf, x, row, x & 1, slc_id, pub_line, pub_left, lane_mb, &progress[wprev], need, st_t0, st_acc);
+      process_mb (F, L, G, G.frame[ji & 1], B, pf, x, row, x & 1, slc_id, pub_line, pub_left, lane_mb, &progress[wprev], need, st_t0, st_acc);
 #else
-      process_mb (F, L, G, B, pf, x, row, x & 1, slc_id, pub_line, pub_left, lane_mb, &progress[wprev], need);
+      process_mb (F, L, G, G.frame[ji & 1], B, pf, x, row, x & 1, slc_id, pub_line, pub_left, lane_mb, &progress[wprev], need);
 #endif
       if (lane == 0) progress[wave] = (jw << 12) | (x + 1);
       pf = nx;
