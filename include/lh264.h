@@ -886,6 +886,68 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
                             const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
                             const lh264_decode_sample_t* sample /* NULL = uint8 */, lh264_decoded_t** out);
 int lh264_decoded_sample_type (const lh264_decoded_t* d);
+/* ---- fitted views: a caller's crop, cover and letterbox: lh264_decode_batch_ex3 ----------------------------------------------------------
+ * The three structs above are frozen; the view travels in a fourth.  view == NULL is lh264_decode_batch_ex2, byte for byte and launch for
+ * launch (lh264_decode_batch_ex2 is this call with NULL).
+ * THE DEFINITION (normative).  A view is applied per delivered picture, BEFORE any sizing.  Let w x h be the picture's cropped SPS window
+ * (even, as ever).  All arithmetic below is in integers and `/` is floor.
+ * CALLER'S CROP (optional): a rectangle {x, y, w, h} in window coordinates, all four even, x, y >= 0, w, h >= 2, x + w <= the window's
+ * width, y + h <= its height.  With a crop the rectangle takes the window's place in every definition of the calls above: the copy, the
+ * scale_log2 means (clamping is to the crop, never to what lies outside it), the resampling, colour and float.  Nothing outside the
+ * rectangle enters any delivered sample.  w = h = 0 means no crop.  crops[i] is stream i's (n_crops = n), or crops[0] every stream's
+ * (n_crops = 1).  A crop that does not fit a picture's window can only be known at that picture (a stream may change size): it stops the
+ * stream there with LH264_E_ARG and a text that names the picture, the rectangle and the window; the pictures in front of it are delivered.
+ * FIT (needs out_width / out_height = OW x OH); w, h below are the window after the caller's crop.
+ *   LH264_FIT_STRETCH: the whole window is resampled to OW x OH, as without a view.
+ *   LH264_FIT_COVER: the largest centred sub-rectangle of the window with the output's aspect, stretched to OW x OH.
+ *     w*OH > h*OW: sh = h, sw = max (2, 2 * ((h*OW + OH) / (2*OH)));  w*OH < h*OW: sw = w, sh = max (2, 2 * ((w*OH + OW) / (2*OW)));
+ *     equality: the whole window.  sx = 2 * ((w - sw) / 4), sy = 2 * ((h - sh) / 4).  The source is {sx, sy, sw, sh} inside the window,
+ *     resampled to OW x OH by the rule of out_width / out_height.
+ *   LH264_FIT_CONTAIN: the whole window resampled into the largest centred even rectangle of the output, the rest filled.
+ *     w*OH > h*OW: dw = OW, dh = max (2, 2 * ((h*OW + w) / (2*w)));  w*OH < h*OW: dh = OH, dw = max (2, 2 * ((w*OH + h) / (2*h)));
+ *     equality: the whole output.  dx = 2 * ((OW - dw) / 4), dy = 2 * ((OH - dh) / 4).  Luma sample (X, Y) of the delivered OW x OH plane
+ *     is the resampling of the w x h window to dw x dh at (X - dx, Y - dy) where that lies in [0, dw) x [0, dh); elsewhere it is fill_y.
+ *     Cb and Cr: the same rule with every quantity halved, and fill_cb, fill_cr.
+ * Every rectangle is even, at least 2 x 2 and inside the window or the output.  The aspect ratio is kept to the nearest even sample, NOT
+ * exactly.  176 x 144 to 224 x 224: cover reads {16, 0, 144, 144}, contain writes {0, 20, 224, 184}; 1920 x 1080: {420, 0, 1080, 1080}
+ * and {0, 48, 224, 126}.  lh264_view_rects is this rule and needs no device.
+ * Colour and float types act on the DELIVERED planes exactly as without a view: the RGB bytes of a view call are the integer function
+ * applied to the I420 bytes of the same call without colour, bars included (a bar pixel is the conversion of fill_y, fill_cb, fill_cr),
+ * the float elements the fma of those bytes.  Every rectangle is even, so a 2x2 quad is wholly picture or wholly bar.
+ * Crop and cover narrow the source rectangle of the pack jobs and launch the kernels of the calls above; contain launches their placed
+ * siblings (decode_pack_placed_kernel, decode_pack_rgb_placed_kernel, decode_pack_sample_placed_kernel), which write the bars by plain
+ * stores.  Offsets, handles, the sink, DEVICE_OUT, NO_PICTURES, both digests and the arena follow the delivered bytes as ever; conceal,
+ * both parse routes, pick, format, scale_log2, colour and the sample type act as without a view.  lh264_decoded_picture_source_size
+ * keeps returning the SPS window; lh264_decoded_picture_view gives the source rectangle in window coordinates and the destination
+ * rectangle in the delivered picture (either may be NULL; without a view {0, 0, w, h} and {0, 0, ow, oh}; LH264_E_ARG: a bad index).
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of the calls above: a struct_bytes other than 32, fit
+ * above 2, a fit other than stretch without out_width / out_height, fill non-zero without LH264_FIT_CONTAIN or with bits 24..31 set, a
+ * reserved word that is not 0, n_crops not 0, 1 or n, n_crops != 0 with crops NULL, a crop with a negative or odd member, a crop with
+ * exactly one of w, h zero. */
+typedef struct lh264_rect { int32_t x, y, w, h; } lh264_rect_t;
+#define LH264_FIT_STRETCH 0u
+#define LH264_FIT_COVER   1u
+#define LH264_FIT_CONTAIN 2u
+typedef struct lh264_decode_view {
+  uint32_t struct_bytes;                /* 32                                                                   */
+  uint32_t fit;                         /* LH264_FIT_*                                                          */
+  uint32_t fill;                        /* fill_y | fill_cb << 8 | fill_cr << 16; read under LH264_FIT_CONTAIN only */
+  uint32_t n_crops;                     /* 0: none; 1: crops[0] for every stream; n: crops[i] for stream i      */
+  const lh264_rect_t* crops;
+  uint32_t reserved0, reserved1;        /* 0                                                                    */
+} lh264_decode_view_t;
+int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n, int threads,
+                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
+                            const lh264_decode_sample_t* sample /* NULL = uint8 */, const lh264_decode_view_t* view /* NULL = none */, lh264_decoded_t** out);
+int lh264_decoded_picture_view (const lh264_decoded_t* d, int idx, lh264_rect_t* src, lh264_rect_t* dst);
+/* the rule above for a w x h window (even, 2..16384), a crop (NULL or w = h = 0: none), a fit and a size (0, 0: none, stretch only):
+ * *src the source rectangle in window coordinates, *dst the destination rectangle in the delivered picture (without a size: {0, 0} and
+ * the source's own size).  Either may be NULL.  LH264_E_ARG: a window, crop, fit or size the call above would refuse, a crop that does
+ * not fit the window */
+int lh264_view_rects (int32_t w, int32_t h, const lh264_rect_t* crop, uint32_t fit, int32_t out_w, int32_t out_h, lh264_rect_t* src, lh264_rect_t* dst);
+/* the cropped window of the first SPS of an Annex-B file that parses, without a device: what a caller needs to choose crops before it
+ * decodes.  width / height may be NULL.  LH264_E_ARG: data NULL; LH264_E_UNSUPPORTED: no SPS in the file that parses */
+int lh264_parser_window (const uint8_t* data, size_t len, int32_t* width, int32_t* height);
 /* what the first SPS of an Annex-B file says about colour, without a device: *matrix_coefficients (2 = unspecified where the SPS
  * carries none), *full_range (0 where it carries none), *present bit 0 = the VUI has a video_signal_type, bit 1 = it has a colour
  * description.  Any of the three may be NULL.  LH264_E_ARG: data NULL; LH264_E_UNSUPPORTED: no SPS in the file that parses */
@@ -983,6 +1045,20 @@ int lh264_debug_sample_dev (const lh264_pack_job_t* jobs, int n, int out_w, int 
 /* the host stepping's conversions of n binary32 values to 16 bits (type LH264_SAMPLE_F16 or _BF16, anything else LH264_E_ARG): what
  * lh264_debug_sample_cpu rounds with, laid open so that a test can show it is nearest even at every boundary.  No device is needed */
 int lh264_debug_sample_round (uint32_t type, const float* v, size_t n, uint16_t* out);
+/* where a job's picture is placed in an out_w x out_h picture (LH264_FIT_CONTAIN): the window is resampled to w x h at (x, y), every
+ * sample outside that rectangle is the fill (fill_y | fill_cb << 8 | fill_cr << 16).  x, y, w, h are even, w, h >= 2, the rectangle
+ * lies inside the delivered picture; `reserved` is 0.  The kernels read one record per pack job from a table beside the jobs' */
+typedef struct lh264_pack_place { int32_t x, y, w, h; uint32_t fill, reserved; } lh264_pack_place_t;
+/* the same table delivered as out_w x out_h pictures with job k placed by places[k]: colour == 0 the planes in each job's format
+ * (decode_pack_placed_kernel), colour LH264_COLOUR_RGB24 / _RGBP RGB bytes (decode_pack_rgb_placed_kernel; std_per_job as above, may be
+ * NULL with colour 0), and with a sample struct that names a float type float RGB (decode_pack_sample_placed_kernel; sample NULL or
+ * LH264_SAMPLE_U8: bytes).  lh264_debug_view_cpu steps the kernels' code over HOST memory with t = 0, nt = 1, lh264_debug_view_dev
+ * uploads the tables (the jobs' pointers are device pointers), launches the production kernel and returns when it is through.
+ * LH264_E_ARG: everything the sibling for that path refuses (out_w, out_h are a size here, never 0, 0), places NULL, a place rectangle
+ * that is odd, below 2 x 2 or outside out_w x out_h, a fill above 24 bits, a place whose `reserved` is not 0; lh264_debug_view_dev
+ * without a device: LH264_E_NODEVICE */
+int lh264_debug_view_cpu (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
+int lh264_debug_view_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

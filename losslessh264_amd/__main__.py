@@ -41,6 +41,12 @@
                                                             cast and normalised on the device in the same pass (decode_batch (dtype=...,
                                                             mul=..., add=...)): element = fma (byte, mul[channel], add[channel]) in
                                                             binary32, rounded to the type; out_dir/<name>.f32 | .f16 | .bf16, little-endian
+    python -m losslessh264_amd --decode [--sha1] [--crop x,y,w,h] [--size WxH --fit cover|contain [--fill y,cb,cr]] ...   fitted views
+                                                            (decode_batch (crop=..., fit=..., fill=...)): --crop takes a rectangle of every
+                                                            picture's window (four even numbers) in the window's place; --fit cover
+                                                            resamples the largest centred part of it with the size's aspect, --fit contain
+                                                            the whole of it into the largest centred part of the size, the rest filled
+                                                            with y,cb,cr (default 16,128,128).  --fit needs --size, --fill --fit contain
 
 Compress runs the host front end and the HIP context-index + coder kernels (needs the GPU); the optional YUV dump runs the
 HIP reconstruct kernel and writes the cropped I420 pictures like the reference's decoder.  Restore is host code.
@@ -173,6 +179,7 @@ def restore(src, dst):
 SIZE_USAGE = "--size: WxH, both even, 2..4096; not with a non-zero --scale"
 RGB_USAGE = "--rgb: rgb24 | rgbp, not with --nv12; --matrix: auto | bt601 | bt709 and --range: auto | limited | full, with --rgb only"
 SAMPLE_USAGE = "--sample: f32 | f16 | bf16, with --rgb only; --mul and --add: three finite numbers a,b,c (R, G, B), with --sample only"
+VIEW_USAGE = "--fit: cover | contain, with --size only; --fill: y,cb,cr in 0..255, with --fit contain only; --crop: x,y,w,h, four even numbers, x, y >= 0, w, h >= 2"
 SAMPLE_NAMES = {"f32": "float32", "f16": "float16", "bf16": "bfloat16"}
 
 
@@ -187,6 +194,15 @@ def parse_three(text):
     with np.errstate(over="ignore"):
         ok = len(v) == 3 and all(x.strip() == x and x for x in parts) and bool(np.all(np.isfinite(np.asarray(v, dtype=np.float64).astype(np.float32))))
     return tuple(v) if ok else None
+
+
+def parse_ints(text, n, top):
+    """"a,b,.." -> n ints in 0..top, or None"""
+    import re
+    if not re.fullmatch(r"[0-9]{1,5}(,[0-9]{1,5}){%d}" % (n - 1), text):
+        return None
+    v = tuple(int(x) for x in text.split(","))
+    return v if all(x <= top for x in v) else None
 
 
 def parse_size(text):
@@ -204,7 +220,25 @@ def decode(argv):
     nv12, conceal, sha1, parse, scale, pick, size = False, None, False, "host", 0, "all", None
     colour, matrix, crange = None, None, None
     dtype, mul, add = None, None, None
-    while argv and argv[0] in ("--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+    fit, fill, crop = None, None, None
+    while argv and argv[0] in ("--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+        if argv[0] in ("--fit", "--fill", "--crop"):
+            value = None
+            if len(argv) >= 2:
+                value = (argv[1] if argv[1] in ("cover", "contain") else None) if argv[0] == "--fit" else parse_ints(argv[1], 3, 255) if argv[0] == "--fill" else parse_ints(argv[1], 4, 16384)
+            if argv[0] == "--crop" and value is not None and (any(x & 1 for x in value) or value[2] < 2 or value[3] < 2):
+                value = None
+            if value is None:
+                print(VIEW_USAGE)
+                return 2
+            if argv[0] == "--fit":
+                fit = value
+            elif argv[0] == "--fill":
+                fill = value
+            else:
+                crop = value
+            argv = argv[2:]
+            continue
         if argv[0] in ("--sample", "--mul", "--add"):
             value = None if len(argv) < 2 else SAMPLE_NAMES.get(argv[1]) if argv[0] == "--sample" else parse_three(argv[1])
             if value is None:
@@ -271,7 +305,11 @@ def decode(argv):
     if (dtype is not None and colour is None) or (dtype is None and (mul is not None or add is not None)):
         print(SAMPLE_USAGE)
         return 2
-    ckw = dict(colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
+    if (fit is not None and size is None) or (fill is not None and fit != "contain"):
+        print(VIEW_USAGE)
+        return 2
+    vkw = dict(fit=fit or "stretch", fill=fill, crop=crop)
+    ckw = dict(vkw, colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)
         return 2

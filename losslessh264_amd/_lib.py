@@ -180,6 +180,15 @@ class DecodeSample(C.Structure):    # lh264_decode_sample_t: what lh264_decode_b
     _fields_ = [("struct_bytes", C.c_uint32), ("type", C.c_uint32), ("mul", C.c_float * 3), ("add", C.c_float * 3)]
 assert C.sizeof(DecodeSample) == 32
 SAMPLE = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}      # LH264_SAMPLE_*
+class Rect(C.Structure):            # lh264_rect_t
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+class DecodeView(C.Structure):      # lh264_decode_view_t: what lh264_decode_batch_ex3 takes beside the three frozen structs
+    _fields_ = [("struct_bytes", C.c_uint32), ("fit", C.c_uint32), ("fill", C.c_uint32), ("n_crops", C.c_uint32),
+                ("crops", C.POINTER(Rect)), ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+class PackPlace(C.Structure):       # lh264_pack_place_t: where a pack job's picture lies in the delivered one, and the bars' fill
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("fill", C.c_uint32), ("reserved", C.c_uint32)]
+assert C.sizeof(Rect) == 16 and C.sizeof(DecodeView) == 32 and C.sizeof(PackPlace) == 24
+FIT = {"stretch": 0, "cover": 1, "contain": 2}            # LH264_FIT_*
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
@@ -189,6 +198,12 @@ _SIGS.update({
     "lh264_decode_batch_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decode_batch_ex2": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decoded_sample_type": (C.c_int, [C.c_void_p]),
+    "lh264_decode_batch_ex3": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_picture_view": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_view_rects": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lh264_parser_window": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lh264_debug_view_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_debug_view_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_debug_sample_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_debug_sample_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_debug_sample_round": (C.c_int, [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -24,6 +24,10 @@
 //   lh264dec --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096), resampled on the
 //                                       device by an exact area average (lh264.h: out_width, out_height).  Not with a non-zero --scale
 //                                       Not together with --conceal
+//   lh264dec --decode [--sha1] [--crop x,y,w,h] [--size WxH --fit cover|contain [--fill y,cb,cr]] ...   fitted views (lh264.h:
+//                                       lh264_decode_batch_ex3): a rectangle of every picture's window in the window's place; the largest
+//                                       centred part of it with the size's aspect (cover), or the whole of it inside the size, the rest
+//                                       filled (contain; default 16,128,128)
 //   lh264dec --decode [--sha1] --rgb rgb24|rgbp --sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c] ...   float RGB pictures, cast and
 //                                       normalised on the device (lh264.h: lh264_decode_batch_ex2) -> out_dir/<name>.f32 | .f16 | .bf16
 //
@@ -223,6 +227,22 @@ static bool parse_three (const char* text, float* v) {      // "a,b,c", every on
   }
   return true;
 }
+// [--crop x,y,w,h] [--fit cover|contain [--fill y,cb,cr]]: what lh264_decode_batch_ex3 takes beside the three (nothing named: NULL, the
+// call as ever)
+static lh264_rect_t g_crop = {0, 0, 0, 0};
+static lh264_decode_view_t g_view = {sizeof (lh264_decode_view_t), LH264_FIT_STRETCH, 0, 0, nullptr, 0, 0};
+static bool g_view_named = false;
+static const char* const kViewUsage = "--fit: cover | contain, with --size only; --fill: y,cb,cr in 0..255, with --fit contain only; --crop: x,y,w,h, four even numbers, x, y >= 0, w, h >= 2";
+static bool parse_ints (const char* text, int n, int top, int* v) {      // "a,b,..": n numbers in 0..top
+  for (int k = 0; k < n; k++) {
+    int digits = 0; v[k] = 0;
+    for (; *text >= '0' && *text <= '9'; text++) { if (++digits > 5) return false; v[k] = v[k] * 10 + (*text - '0'); }
+    if (!digits || v[k] > top || *text != (k < n - 1 ? ',' : 0)) return false;
+    text++;
+  }
+  return true;
+}
+static const lh264_decode_view_t* view_arg() { return g_view_named ? &g_view : nullptr; }
 static const char* out_suffix() {
   return !g_ext.colour ? ".yuv" : g_sample.type == LH264_SAMPLE_F32 ? ".f32" : g_sample.type == LH264_SAMPLE_F16 ? ".f16" : g_sample.type == LH264_SAMPLE_BF16 ? ".bf16" : ".rgb";
 }
@@ -255,7 +275,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex2 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, h.data());
+  const int rc = lh264_decode_batch_ex3 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), h.data());
   for (FILE* f : files.f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
@@ -279,7 +299,7 @@ static int decode_sha1_files (const std::string& out_dir, const std::vector<std:
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex2 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, h.data());
+  const int rc = lh264_decode_batch_ex3 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), h.data());
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
@@ -330,6 +350,7 @@ int main (int argc, char** argv) {
     return compress_single (srcs, dsts);
   }
   if (argc >= 4 && !strcmp (argv[1], "--decode")) {
+    bool fill_named = false;
     bool nv12 = false, sha1 = false; int device_parse = 0, conceal = 0, scale = 0, out_w = 0, out_h = 0, first = 2; uint32_t pick = LH264_PICK_ALL; bool matrix_named = false, add_named = false, mul_named = false;
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
@@ -360,6 +381,22 @@ int main (int argc, char** argv) {
         if (rgb) g_ext.colour = (uint32_t)k + LH264_COLOUR_RGB24;
         else { (matrix ? g_ext.matrix : g_ext.range) = (uint32_t)k; matrix_named = true; }
         first += 2;
+      } else if (first < argc && (!strcmp (argv[first], "--fit") || !strcmp (argv[first], "--fill") || !strcmp (argv[first], "--crop"))) {
+        const char* v = first + 1 < argc ? argv[first + 1] : "";
+        int q[4] = {0, 0, 0, 0};
+        if (!strcmp (argv[first], "--fit")) {
+          const int k = one_of (v, "cover", "contain", nullptr);
+          if (k < 0) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
+          g_view.fit = (uint32_t)k + LH264_FIT_COVER;
+        } else if (!strcmp (argv[first], "--fill")) {
+          if (!parse_ints (v, 3, 255, q)) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
+          g_view.fill = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16; fill_named = true;
+        } else {
+          if (!parse_ints (v, 4, 16384, q) || ((q[0] | q[1] | q[2] | q[3]) & 1) || q[2] < 2 || q[3] < 2) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
+          g_crop = {q[0], q[1], q[2], q[3]}; g_view.n_crops = 1; g_view.crops = &g_crop;
+        }
+        g_view_named = true;
+        first += 2;
       } else if (first < argc && (!strcmp (argv[first], "--sample") || !strcmp (argv[first], "--mul") || !strcmp (argv[first], "--add"))) {
         const char* v = first + 1 < argc ? argv[first + 1] : "";
         if (!strcmp (argv[first], "--sample")) {
@@ -377,14 +414,16 @@ int main (int argc, char** argv) {
     if ((g_sample.type && !g_ext.colour) || (!g_sample.type && (add_named || mul_named))) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
     if (g_sample.type && !mul_named) g_sample.mul[0] = g_sample.mul[1] = g_sample.mul[2] = 1.0f;
     if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
+    if ((g_view.fit != LH264_FIT_STRETCH && !out_w) || (fill_named && g_view.fit != LH264_FIT_CONTAIN)) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
+    if (g_view.fit == LH264_FIT_CONTAIN && !fill_named) g_view.fill = 16u | 128u << 8 | 128u << 16;
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--scale N | --size WxH] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

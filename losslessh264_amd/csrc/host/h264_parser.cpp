@@ -1943,6 +1943,23 @@ bool Parser::first_sps_colour (const uint8_t* d, size_t n, int* matrix_coefficie
   }
   return false;
 }
+bool Parser::first_sps_window (const uint8_t* d, size_t n, int* width, int* height) {
+  for (size_t i = 0; i + 3 < n; i++) {
+    if (d[i] || d[i + 1] || d[i + 2] != 1 || (d[i + 3] & 31) != 7) continue;
+    size_t end = i + 4;
+    while (end < n && !(end + 2 < n && d[end] == 0 && d[end + 1] == 0 && d[end + 2] <= 1)) end++;
+    Parser P;
+    HeaderInfo hi;
+    if (P.parse_headers (d + i + 3, end - (i + 3), hi) < 0 || !P.error().empty()) continue;
+    for (const auto& kv : P.d_->sps) if (kv.second.valid) {
+      const auto& S = kv.second;      // (the window a picture of this SPS gets where its first slice is met)
+      if (width) *width = S.mb_w * 16 - 2 * (S.crop_l + S.crop_r);
+      if (height) *height = S.mb_h * 16 - 2 * (S.crop_t + S.crop_b);
+      return true;
+    }
+  }
+  return false;
+}
 const std::vector<uint8_t>& Parser::last_rbsp() const { return d_->rbsp; }
 const std::string& Parser::out_of_range() const { return d_->symbolizer.out_of_range(); }
 std::vector<uint8_t> Parser::escapes() const { return d_->symbolizer.escapes(); }

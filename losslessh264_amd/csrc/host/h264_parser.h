@@ -338,6 +338,8 @@ class Parser {
   // what the first SPS of an Annex-B file that parses says about colour (Sps::matrix_coefficients, full_range, colour_present);
   // false: there is none
   static bool first_sps_colour (const uint8_t* data, size_t len, int* matrix_coefficients, int* full_range, int* present);
+  // ... and its cropped window (what a picture of that SPS delivers at full size)
+  static bool first_sps_window (const uint8_t* data, size_t len, int* width, int* height);
   int conceal() const { return conceal_; }
   // empty, or why the symbols of the pictures parsed so far do not restore the stream: the first syntax value its prior table cannot
   // carry (Symbolizer::out_of_range: an mb_skip_run above 511, 16 active references).  Not an error of the stream: it parses and decodes

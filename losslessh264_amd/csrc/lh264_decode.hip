@@ -356,6 +356,80 @@ inline bool size_ok (int64_t out_w, int64_t out_h) {
   return out_w >= 2 && out_w <= 4096 && out_h >= 2 && out_h <= 4096 && !((out_w | out_h) & 1);
 }
 
+// ---- the placed pack step: LH264_FIT_CONTAIN (the definition: include/lh264.h at lh264_decode_batch_ex3) ---------------------------
+// The window is resampled to pl.w x pl.h - resized_sample with the plane's ow, oh set to that and the coordinates shifted - and lies at
+// (pl.x, pl.y) of the ow x oh picture; every other sample is the fill.  Bands and pieces are those of the step to one size.  A piece
+// whose bytes lie wholly in a bar is one aligned 4-byte store of a word built from the fill and computes nothing, a piece wholly inside
+// the rectangle is the resize step's piece, only a piece on a seam decides per sample.  All rectangles are even, so the chroma planes'
+// are the luma's halved.  No byte outside the window is read, none outside the picture's bytes written.  No LDS.
+
+// piece p of delivered row Y (n bytes at d): bytes b0 .. b1 - 1 of rows y0 .. y0 + a.oh - 1 are the picture's, byte k of them sample
+// k - b0 of plane a (interleaved: sample (k - b0) / 2 of a or b, b0 even); every other byte is fa (k even) or fb (k odd)
+__host__ __device__ inline void piece_placed (uint8_t* d, int n, int Y, int p, const ResizePlane& a, const ResizePlane& b, bool interleaved,
+                                              int b0, int b1, int y0, uint32_t fa, uint32_t fb) {
+  int k0 = p * 4 - (int) ((uintptr_t)d & 3u), k1 = k0 + 4;
+  const bool whole = k0 >= 0 && k1 <= n;
+  if (k0 < 0) k0 = 0;
+  if (k1 > n) k1 = n;
+  if (k1 <= k0) return;
+  if (Y < y0 || Y >= y0 + (int)a.oh || k1 <= b0 || k0 >= b1) {      // wholly in a bar
+    if (whole) { const uint32_t pair = (k0 & 1) ? fb | fa << 8 : fa | fb << 8; * (uint32_t*) (d + k0) = pair | pair << 16; }
+    else for (int k = k0; k < k1; k++) d[k] = (uint8_t) ((k & 1) ? fb : fa);
+    return;
+  }
+  const Span sy = span_of ((uint32_t) (Y - y0), a.h, a.oh);
+  uint32_t o = 0;
+  for (int k = k0; k < k1; k++) {
+    uint8_t v;
+    if (k < b0 || k >= b1) v = (uint8_t) ((k & 1) ? fb : fa);
+    else { const int x = k - b0; v = interleaved ? resized_sample ((x & 1) ? b : a, sy, x >> 1) : resized_sample (a, sy, x); }
+    if (whole) o |= (uint32_t)v << (8 * (k - k0));
+    else d[k] = v;
+  }
+  if (whole) * (uint32_t*) (d + k0) = o;
+}
+// band `band` (16 delivered luma rows, 8 chroma rows) of one job delivered as ow x oh with its window placed by pl, worked on by item
+// t of nt (the host steps it with t = 0, nt = 1)
+__host__ __device__ inline void pack_band_placed (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int ow, int oh, int band, int t, int nt) {
+  const int w = j.crop_w, h = j.crop_h, ocw = ow >> 1, och = oh >> 1;
+  const uint32_t fy = pl.fill & 0xffu, fcb = pl.fill >> 8 & 0xffu, fcr = pl.fill >> 16 & 0xffu;
+  const int r0 = band * kBandRows, r1 = r0 + kBandRows < oh ? r0 + kBandRows : oh;
+  if (r1 > r0) {
+    const ResizePlane y = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pl.w, (uint32_t)pl.h};
+    const int pieces = (ow + 6) >> 2, items = (r1 - r0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = r0 + it / pieces, p = it % pieces;
+      piece_placed (j.dst + (size_t)r * ow, ow, r, p, y, y, false, pl.x, pl.x + pl.w, pl.y, fy, fy);
+    }
+  }
+  const int c0 = band * (kBandRows / 2), c1 = c0 + kBandRows / 2 < och ? c0 + kBandRows / 2 : och;
+  if (c1 <= c0) return;
+  const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
+  const ResizePlane u = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1)};
+  const ResizePlane v = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1)};
+  uint8_t* dc = j.dst + (size_t)ow * oh;
+  if (j.format == LH264_FMT_NV12) {
+    const int pieces = (ow + 6) >> 2, items = (c1 - c0) * pieces;
+    for (int it = t; it < items; it += nt) {
+      const int r = c0 + it / pieces, p = it % pieces;
+      piece_placed (dc + (size_t)r * ow, ow, r, p, u, v, true, pl.x, pl.x + pl.w, pl.y >> 1, fcb, fcr);
+    }
+  } else {
+    const int pieces = (ocw + 6) >> 2, per_plane = (c1 - c0) * pieces;
+    for (int it = t; it < 2 * per_plane; it += nt) {
+      const int plane = it >= per_plane, q = it - plane * per_plane;
+      const int r = c0 + q / pieces, p = q % pieces;
+      const uint32_t f = plane ? fcr : fcb;
+      piece_placed (dc + (size_t)plane * ocw * och + (size_t)r * ocw, ocw, r, p, plane ? v : u, u, false, pl.x >> 1, (pl.x + pl.w) >> 1, pl.y >> 1, f, f);
+    }
+  }
+}
+// what the placed entry points and the call accept as a place: an even rectangle of at least 2 x 2 inside out_w x out_h, a 24-bit fill
+inline bool place_ok (const lh264_pack_place_t& pl, int out_w, int out_h) {
+  return pl.x >= 0 && pl.y >= 0 && pl.w >= 2 && pl.h >= 2 && !((pl.x | pl.y | pl.w | pl.h) & 1) && pl.x <= out_w - pl.w && pl.y <= out_h - pl.h &&
+         !(pl.fill >> 24) && pl.reserved == 0;
+}
+
 // ---- the pack step to RGB: lh264_decode_batch_ex (the definition: include/lh264.h at lh264_decode_batch_ex) -------------------------
 // The delivered planes are never stored: a sample of the ow x oh luma plane or of the ow/2 x oh/2 chroma planes is worked out where it
 // is needed, by the rule of the job's sizing - the window's own sample, mean_clamped / means_whole of the reduced-size step, or
@@ -419,10 +493,22 @@ __host__ __device__ inline void quad_rgb (const ResizePlane& py, const ResizePla
   }
 }
 
+// sizing M = 5, "placed" (LH264_FIT_CONTAIN): the planes' ow x oh is the rectangle the window is resampled to, which lies at (x, y) of
+// the delivered picture; every pixel outside it is the conversion of the fill.  x, y and the rectangle are even, so a quad is wholly
+// picture - quad_rgb<4> with the coordinates shifted - or wholly bar
+struct Placed { int x, y; uint32_t fill; };
+// the bar's pixel: quad_rgb's arithmetic on (fill_y, fill_cb, fill_cr), once per item
+__host__ __device__ inline void bar_rgb (uint32_t fill, const int32_t* f, int y0, uint32_t o[3]) {
+  const int D = (int) (fill >> 8 & 0xffu) - 128, E = (int) (fill >> 16 & 0xffu) - 128;
+  const int32_t yt = f[0] * ((int32_t) (fill & 0xffu) - y0);
+  o[0] = clip8 ((yt + f[1] * E + 32768) >> 16); o[1] = clip8 ((yt + 32768 - f[3] * D - f[4] * E) >> 16); o[2] = clip8 ((yt + f[2] * D + 32768) >> 16);
+}
+
 // piece p of row pair R of one job delivered as ow x oh in layout L (LH264_COLOUR_RGB24 / _RGBP) with the factors f and luma offset y0
+// (pc: read under M = 5 only)
 template <int M, int L>
 __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, int ow, int oh,
-                                           const int32_t* f, int y0, int R, int p) {
+                                           const int32_t* f, int y0, int R, int p, const Placed& pc) {
   constexpr int BPP = L == (int)LH264_COLOUR_RGB24 ? 3 : 1, NP = L == (int)LH264_COLOUR_RGB24 ? 1 : 3;      // bytes per pixel and planes of the destination
   constexpr int PB = 8 * BPP, ND = PB / 4, NW = 12 * BPP / 4;                                                 // a piece's bytes and words; the words of 12 pixels
   const int row_bytes = BPP * ow;
@@ -436,6 +522,14 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
   Span sy[2], sc;
   if constexpr (M == 4) { sy[0] = span_of ((uint32_t) (2 * R), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1), py.h, py.oh); sc = span_of ((uint32_t)R, pu.h, pu.oh); }
   else { sy[0] = sy[1] = sc = Span(); }
+  // M = 5: the bar's pixel, and whether the pair's rows cross the rectangle at all (then their spans, counted from its first row)
+  uint32_t bar[3] = {0, 0, 0};
+  bool rows_in = false;
+  if constexpr (M == 5) {
+    bar_rgb (pc.fill, f, y0, bar);
+    rows_in = 2 * R >= pc.y && 2 * R < pc.y + (int)py.oh;
+    if (rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
+  }
   // the 12 pixels of both rows as byte streams: RGB24 one stream of 36 bytes, RGBP three of 12
   uint32_t W[2][NP][NW + 1];
   for (int rr = 0; rr < 2; rr++) for (int c = 0; c < NP; c++) for (int k = 0; k <= NW; k++) W[rr][c][k] = 0;
@@ -444,7 +538,10 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
     const int X = x0 + 2 * q;
     if (X < 0 || X >= ow) continue;
     uint32_t px[2][2][3];
-    quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X, R, px);
+    if constexpr (M == 5) {
+      if (rows_in && X >= pc.x && X < pc.x + (int)py.ow) quad_rgb<4> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
+      else for (int rr = 0; rr < 2; rr++) for (int i = 0; i < 2; i++) for (int c = 0; c < 3; c++) px[rr][i][c] = bar[c];
+    } else quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X, R, px);
     _Pragma ("unroll")
     for (int rr = 0; rr < 2; rr++) {
       _Pragma ("unroll")
@@ -482,22 +579,25 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
 }
 
 // band `band` (16 delivered luma rows) of one job delivered as ow x oh RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
+// (pl: the job's place, read under M = 5 only - the planes are then resampled to pl->w x pl->h)
 template <int M, int L>
-__host__ __device__ inline void pack_band_rgb_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, int band, int t, int nt) {
+__host__ __device__ inline void pack_band_rgb_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr) {
   const int w = j.crop_w, h = j.crop_h;
   const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
   if (R1 <= R0) return;
   const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
-  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh};
-  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
-  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  const int pw = M == 5 ? pl->w : ow, ph = M == 5 ? pl->h : oh;
+  const Placed pc = M == 5 ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
   int32_t f[5];
   for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
   const int y0 = (std_byte & 2) ? 0 : 16;
   constexpr int PB = L == (int)LH264_COLOUR_RGB24 ? 24 : 8;
   const int row_bytes = (L == (int)LH264_COLOUR_RGB24 ? 3 : 1) * ow;
   const int pieces = (row_bytes + 3 + PB - 1) / PB, items = (R1 - R0) * pieces;
-  for (int it = t; it < items; it += nt) piece_rgb<M, L> (j.dst, py, pu, pv, ow, oh, f, y0, R0 + it / pieces, it % pieces);
+  for (int it = t; it < items; it += nt) piece_rgb<M, L> (j.dst, py, pu, pv, ow, oh, f, y0, R0 + it / pieces, it % pieces, pc);
 }
 // ... of a job whose sizing is its `reserved` scale (out_w == 0) or the given size; layout and standard byte as given.  Anything that is
 // not defined: nothing is done
@@ -519,6 +619,12 @@ __host__ __device__ inline void pack_band_rgb (const lh264_pack_job_t& j, int ou
     else if (m == 3) pack_band_rgb_as<3, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
     else pack_band_rgb_as<4, (int)LH264_COLOUR_RGBP> (j, ow, oh, std_byte, band, t, nt);
   }
+}
+// ... of a job placed by pl in an out_w x out_h picture (LH264_FIT_CONTAIN)
+__host__ __device__ inline void pack_band_rgb_placed (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int out_w, int out_h, int layout, int std_byte, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved) return;
+  if (layout == (int)LH264_COLOUR_RGB24) pack_band_rgb_as<5, (int)LH264_COLOUR_RGB24> (j, out_w, out_h, std_byte, band, t, nt, &pl);
+  else if (layout == (int)LH264_COLOUR_RGBP) pack_band_rgb_as<5, (int)LH264_COLOUR_RGBP> (j, out_w, out_h, std_byte, band, t, nt, &pl);
 }
 
 // ---- the pack step to float RGB: lh264_decode_batch_ex2 with a float sample type (the definition: include/lh264.h at that call) -------
@@ -584,7 +690,7 @@ __host__ __device__ inline uint32_t sample_word (float lo, float hi) {
 // _BF16), with the colour factors f, luma offset y0 and the caller's mul / add
 template <int M, int L, int T>
 __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const ResizePlane& py, const ResizePlane& pu, const ResizePlane& pv, int ow, int oh,
-                                              const int32_t* f, int y0, const float* mul, const float* add, int R, int p) {
+                                              const int32_t* f, int y0, const float* mul, const float* add, int R, int p, const Placed& pc) {
   constexpr bool kPacked = L == (int)LH264_COLOUR_RGB24;
   constexpr int ES = T == (int)LH264_SAMPLE_F32 ? 4 : 2, NP = kPacked ? 1 : 3;      // an element's bytes; the planes of the destination
   constexpr int EQ = kPacked ? 6 : 2;                                                // the elements of a quad in one row of one plane
@@ -595,20 +701,36 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
   Span sy[2], sc;
   if constexpr (M == 4) { sy[0] = span_of ((uint32_t) (2 * R), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1), py.h, py.oh); sc = span_of ((uint32_t)R, pu.h, pu.oh); }
   else { sy[0] = sy[1] = sc = Span(); }
+  // M = 5: the bar's three elements, once per item, and whether the pair's rows cross the rectangle (piece_rgb has the same lines)
+  float barv[3] = {0.0f, 0.0f, 0.0f};
+  bool rows_in = false;
+  if constexpr (M == 5) {
+    uint32_t bar[3];
+    bar_rgb (pc.fill, f, y0, bar);
+    for (int c = 0; c < 3; c++) barv[c] = __builtin_fmaf ((float)bar[c], mul[c], add[c]);
+    rows_in = 2 * R >= pc.y && 2 * R < pc.y + (int)py.oh;
+    if (rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
+  }
   uint32_t W[2][NP][NW];                                                             // the item's words, per row and plane
   for (int rr = 0; rr < 2; rr++) for (int c = 0; c < NP; c++) for (int k = 0; k < NW; k++) W[rr][c][k] = 0;
   _Pragma ("unroll")
   for (int q = 0; q < 4; q++) {
     if (q >= nq) continue;
     uint32_t px[2][2][3];
-    quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X0 + 2 * q, R, px);
+    bool in_bar = false;
+    if constexpr (M == 5) {
+      const int X = X0 + 2 * q;
+      in_bar = !(rows_in && X >= pc.x && X < pc.x + (int)py.ow);
+      if (!in_bar) quad_rgb<4> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
+      else for (int rr = 0; rr < 2; rr++) for (int i = 0; i < 2; i++) for (int c = 0; c < 3; c++) px[rr][i][c] = 0;
+    } else quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X0 + 2 * q, R, px);
     _Pragma ("unroll")
     for (int rr = 0; rr < 2; rr++) {
       float v[2][3];
       _Pragma ("unroll")
       for (int i = 0; i < 2; i++) {
         _Pragma ("unroll")
-        for (int c = 0; c < 3; c++) v[i][c] = __builtin_fmaf ((float)px[rr][i][c], mul[c], add[c]);      // one fused multiply-add: the definition's
+        for (int c = 0; c < 3; c++) v[i][c] = (M == 5 && in_bar) ? barv[c] : __builtin_fmaf ((float)px[rr][i][c], mul[c], add[c]);      // one fused multiply-add: the definition's
       }
       // the quad's elements of this row in memory order: R G B R G B in one plane, or the pixel pair in each of three
       if constexpr (kPacked) {
@@ -648,19 +770,21 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
 
 // band `band` (16 delivered luma rows) of one job delivered as ow x oh float RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
 template <int M, int L, int T>
-__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, const float* mul, const float* add, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr) {
   const int w = j.crop_w, h = j.crop_h;
   const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
   if (R1 <= R0) return;
   const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
-  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)ow, (uint32_t)oh};
-  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
-  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (ow >> 1), (uint32_t) (oh >> 1)};
+  const int pw = M == 5 ? pl->w : ow, ph = M == 5 ? pl->h : oh;      // (pl: the job's place, read under M = 5 only)
+  const Placed pc = M == 5 ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
   int32_t f[5];
   for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
   const int y0 = (std_byte & 2) ? 0 : 16;
   const int pieces = (ow + 7) >> 3, items = (R1 - R0) * pieces;
-  for (int it = t; it < items; it += nt) piece_sample<M, L, T> (j.dst, py, pu, pv, ow, oh, f, y0, mul, add, R0 + it / pieces, it % pieces);
+  for (int it = t; it < items; it += nt) piece_sample<M, L, T> (j.dst, py, pu, pv, ow, oh, f, y0, mul, add, R0 + it / pieces, it % pieces, pc);
 }
 template <int L, int T>
 __host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_sized (const lh264_pack_job_t& j, int ow, int oh, int m, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
@@ -685,6 +809,18 @@ __host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample (const lh264_pack_
   const int m = out_w ? 4 : j.reserved;
   if (layout == (int)LH264_COLOUR_RGB24) pack_band_sample_typed<(int)LH264_COLOUR_RGB24> (j, ow, oh, m, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
   else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_typed<(int)LH264_COLOUR_RGBP> (j, ow, oh, m, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+}
+// ... of a job placed by pl in an out_w x out_h picture (LH264_FIT_CONTAIN)
+template <int L>
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_placed_in (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int ow, int oh, int type, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+  if (type == (int)LH264_SAMPLE_F32) pack_band_sample_as<5, L, (int)LH264_SAMPLE_F32> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl);
+  else if (type == (int)LH264_SAMPLE_F16) pack_band_sample_as<5, L, (int)LH264_SAMPLE_F16> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl);
+  else if (type == (int)LH264_SAMPLE_BF16) pack_band_sample_as<5, L, (int)LH264_SAMPLE_BF16> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl);
+}
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_placed (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int out_w, int out_h, int layout, int std_byte, const lh264_decode_sample_t& sm, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved || ((uintptr_t)j.dst & 3u)) return;
+  if (layout == (int)LH264_COLOUR_RGB24) pack_band_sample_placed_in<(int)LH264_COLOUR_RGB24> (j, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+  else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_placed_in<(int)LH264_COLOUR_RGBP> (j, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
 }
 
 }  // namespace lh264pack
@@ -726,6 +862,25 @@ __global__ void __launch_bounds__ (256) decode_pack_sample_kernel (const lh264_p
   lh264pack::pack_band_sample (j, out_w, out_h, layout, (int)std[blockIdx.x], sample, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
+// LH264_FIT_CONTAIN: the three kernels above with every job's window placed by places[job] in the out_w x out_h picture and the bars
+// filled (a withheld picture's job has no window and nothing is done for it).  Kernels of their own: the launches above stay as they were
+__global__ void __launch_bounds__ (256) decode_pack_placed_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, int out_w, int out_h) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.crop_w <= 0 || j.crop_h <= 0 || (int)blockIdx.y * lh264pack::kBandRows >= out_h) return;
+  const lh264_pack_place_t pl = places[blockIdx.x];
+  lh264pack::pack_band_placed (j, pl, out_w, out_h, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+__global__ void __launch_bounds__ (256) decode_pack_rgb_placed_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, const uint8_t* __restrict__ std, int out_w, int out_h, int layout) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  const lh264_pack_place_t pl = places[blockIdx.x];
+  lh264pack::pack_band_rgb_placed (j, pl, out_w, out_h, layout, (int)std[blockIdx.x], (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+__global__ void __launch_bounds__ (256) decode_pack_sample_placed_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, const uint8_t* __restrict__ std, int out_w, int out_h, int layout, lh264_decode_sample_t sample) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  const lh264_pack_place_t pl = places[blockIdx.x];
+  lh264pack::pack_band_sample_placed (j, pl, out_w, out_h, layout, (int)std[blockIdx.x], sample, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
 // One lane per span job, 64 jobs per wave (a message is serial; the width comes from the batch).  The host orders a launch's jobs by
 // descending length, so the lanes of a wave end near one another.  No LDS, no wave waits for another; every bound is the job's.
@@ -741,6 +896,7 @@ struct lh264_decoded {
   std::vector<lh264_decoded_pic_t> pics;
   std::vector<int32_t> concealed;               // per picture: its concealed macroblocks
   std::vector<int32_t> source_wh;               // per picture: width, height of its cropped window before scaling
+  std::vector<int32_t> view;                    // per picture: its source rectangle in the window, its destination rectangle in the delivered picture (x, y, w, h each)
   int parse_path = LH264_PARSE_PATH_HOST;
   long device_cabac_slices = 0;                 // ... of them CABAC slices (slice_parse_cabac_kernel)
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
@@ -813,6 +969,7 @@ struct Arena {
   DevBuf d_mbs, d_coef, d_sparse, d_sl, d_jobs, d_first, d_pack, d_out[2];
   PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
   DevBuf d_std; PinBuf h_std[2];      // lh264_decode_batch_ex with colour: the standard byte of every pack job, beside d_pack
+  DevBuf d_place; PinBuf h_place[2];  // lh264_decode_batch_ex3 with LH264_FIT_CONTAIN: the place of every pack job, beside d_pack
   // digests: the span jobs, a round's results (20 bytes per picture, then a copy of every chain's stream record), the records of the
   // picture messages (scratch), and one record per stream of the batch that lives as long as the call
   DevBuf d_sjobs, d_dig, d_rec, d_state;
@@ -839,12 +996,12 @@ struct Arena {
   }
   size_t device_bytes() const {
     size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
-    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef, &d_std}) n += b->cap;
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef, &d_std, &d_place}) n += b->cap;
     return n;
   }
   size_t pinned_bytes() const {
     size_t n = h_pbytes.cap + h_ptasks.cap + h_pres.cap;
-    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap + h_std[b].cap;
+    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap + h_std[b].cap + h_place[b].cap;
     return n;
   }
 };
@@ -885,8 +1042,8 @@ struct RoundChain {
   DStream* s = nullptr;
   int first_picture = 0;
   std::vector<lh264_decoded_pic_t> pics;
-  std::vector<int32_t> concealed, source_wh, index;
-  std::vector<uint8_t> colour;                       // lh264_decode_batch_ex with colour: per delivered picture its standard byte
+  std::vector<int32_t> concealed, source_wh, index, view;
+  std::vector<uint8_t> colour;                      // lh264_decode_batch_ex with colour: per delivered picture its standard byte
   size_t at = 0, bytes = 0;                          // in the round's output buffer
   size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
 };
@@ -923,7 +1080,36 @@ uint8_t picture_standard (const FrameOut& f, uint32_t matrix, uint32_t range) {
   return (uint8_t) (m | full << 1);
 }
 
-lh264host::PerDevice<Arena> g_arena;      // one decode call at a time per device
+// ---- views (the definition: include/lh264.h at lh264_decode_batch_ex3) ------------------------------------------------------------
+// a caller's crop that is one: even, not negative, at least 2 x 2 - or none (w = h = 0)
+bool crop_ok (const lh264_rect_t& c) {
+  return c.x >= 0 && c.y >= 0 && c.w >= 0 && c.h >= 0 && !((c.x | c.y | c.w | c.h) & 1) && (c.w == 0) == (c.h == 0);
+}
+bool crop_fits (const lh264_rect_t& c, int w, int h) { return c.x <= w - c.w && c.y <= h - c.h; }
+// the fit of a w x h window (after the caller's crop) to OW x OH: the source inside the window, the destination inside the output
+void fit_rects (int w, int h, uint32_t fit, int OW, int OH, lh264_rect_t* src, lh264_rect_t* dst) {
+  *src = {0, 0, w, h}; *dst = {0, 0, OW, OH};
+  const int64_t a = (int64_t)w * OH, b = (int64_t)h * OW;
+  if (fit == LH264_FIT_COVER && a != b) {
+    if (a > b) src->w = std::max (2, 2 * (int) ((b + OH) / (2 * (int64_t)OH)));
+    else src->h = std::max (2, 2 * (int) ((a + OW) / (2 * (int64_t)OW)));
+    src->x = 2 * ((w - src->w) / 4); src->y = 2 * ((h - src->h) / 4);
+  } else if (fit == LH264_FIT_CONTAIN && a != b) {
+    if (a > b) dst->h = std::max (2, 2 * (int) ((b + w) / (2 * (int64_t)w)));
+    else dst->w = std::max (2, 2 * (int) ((a + h) / (2 * (int64_t)h)));
+    dst->x = 2 * ((OW - dst->w) / 4); dst->y = 2 * ((OH - dst->h) / 4);
+  }
+}
+// the view of a picture whose window is w x h under a crop that fits (w = 0: none), a fit and a size (0, 0: the window at scale s):
+// the source in window coordinates, the destination in the delivered ow x oh picture
+void view_of (int w, int h, const lh264_rect_t& crop, uint32_t fit, int s, int out_w, int out_h, lh264_rect_t* src, lh264_rect_t* dst, int* ow, int* oh) {
+  const lh264_rect_t c = crop.w ? crop : lh264_rect_t {0, 0, w, h};
+  if (out_w) { fit_rects (c.w, c.h, fit, out_w, out_h, src, dst); *ow = out_w; *oh = out_h; }
+  else { *src = {0, 0, c.w, c.h}; lh264pack::scaled_size (c.w, c.h, s, ow, oh); *dst = {0, 0, *ow, *oh}; }
+  src->x += c.x; src->y += c.y;
+}
+
+lh264host::PerDevice<Arena> g_arena;     // one decode call at a time per device
 double g_timing[6] = {0, 0, 0, 0, 0, 0};
 long long g_chains[3] = {0, 0, 0};      // rounds, chains and jobs of the last call's lh264_recon_chains launches
 double g_parse_timing[2] = {0, 0};      // of g_timing[1]: the device parse stage (tasks, upload, slice_parse_kernel, results), and its slices
@@ -1088,6 +1274,50 @@ int lh264_debug_sample_round (uint32_t type, const float* v, size_t n, uint16_t*
   return LH264_OK;
 }
 
+// a table the placed entry points take: what the sibling of the path takes with a size, and a place per job that is one
+static bool view_jobs_ok (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample, int* max_bands) {
+  if (!places || !lh264pack::size_ok (out_w, out_h)) return false;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  if (sample && !sample_ok (sample)) return false;
+  if (typed ? !sample_jobs_ok (jobs, n, out_w, out_h, colour, std_per_job, sample, max_bands) :
+      colour ? !rgb_jobs_ok (jobs, n, out_w, out_h, colour, std_per_job, max_bands) : !resize_jobs_ok (jobs, n, out_w, out_h)) return false;
+  *max_bands = (out_h + lh264pack::kBandRows - 1) / lh264pack::kBandRows;
+  for (int k = 0; k < n; k++) if (!lh264pack::place_ok (places[k], out_w, out_h)) return false;
+  return true;
+}
+
+int lh264_debug_view_cpu (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!view_jobs_ok (jobs, places, n, out_w, out_h, colour, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  for (int k = 0; k < n; k++) for (int band = 0; band < max_bands; band++) {
+    if (typed) lh264pack::pack_band_sample_placed (jobs[k], places[k], out_w, out_h, colour, std_per_job[k], *sample, band, 0, 1);
+    else if (colour) lh264pack::pack_band_rgb_placed (jobs[k], places[k], out_w, out_h, colour, std_per_job[k], band, 0, 1);
+    else lh264pack::pack_band_placed (jobs[k], places[k], out_w, out_h, band, 0, 1);
+  }
+  return LH264_OK;
+}
+
+int lh264_debug_view_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!view_jobs_ok (jobs, places, n, out_w, out_h, colour, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  lh264_pack_job_t* d_jobs = nullptr; lh264_pack_place_t* d_places = nullptr; uint8_t* d_std = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_pack_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_pack_job_t), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMalloc ((void**)&d_places, (size_t)n * sizeof (lh264_pack_place_t)) == hipSuccess && hipMemcpy (d_places, places, (size_t)n * sizeof (lh264_pack_place_t), hipMemcpyHostToDevice) == hipSuccess &&
+            (!colour || (hipMalloc ((void**)&d_std, (size_t)n) == hipSuccess && hipMemcpy (d_std, std_per_job, (size_t)n, hipMemcpyHostToDevice) == hipSuccess));
+  if (ok) {
+    const dim3 grid ((unsigned)n, (unsigned)max_bands);
+    if (typed) hipLaunchKernelGGL (decode_pack_sample_placed_kernel, grid, dim3 (256), 0, 0, d_jobs, d_places, d_std, out_w, out_h, colour, *sample);
+    else if (colour) hipLaunchKernelGGL (decode_pack_rgb_placed_kernel, grid, dim3 (256), 0, 0, d_jobs, d_places, d_std, out_w, out_h, colour);
+    else hipLaunchKernelGGL (decode_pack_placed_kernel, grid, dim3 (256), 0, 0, d_jobs, d_places, out_w, out_h);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs); hipFree (d_places); hipFree (d_std);
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
   if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
@@ -1147,7 +1377,19 @@ int lh264_decode_batch_ex (const uint8_t* const* data, const size_t* len, int n,
 }
 
 int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex3 (data, len, n, threads, opts, ext, sample, nullptr, out);
+}
+
+int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
+  if (view && (view->struct_bytes != sizeof (lh264_decode_view_t) || view->fit > LH264_FIT_CONTAIN || view->reserved0 != 0 || view->reserved1 != 0 ||
+               (view->fill && (view->fit != LH264_FIT_CONTAIN || view->fill >> 24)) || (view->n_crops != 0 && view->n_crops != 1 && view->n_crops != (uint32_t)n) ||
+               (view->n_crops != 0 && !view->crops))) return LH264_E_ARG;
+  if (view) for (uint32_t k = 0; k < view->n_crops; k++) if (!crop_ok (view->crops[k])) return LH264_E_ARG;
+  // the view: the fit, the bars' fill, and every stream's crop (w = 0: none)
+  const uint32_t fit = view ? view->fit : LH264_FIT_STRETCH, fill = view ? view->fill : 0;
+  std::vector<lh264_rect_t> crops ((size_t)n, lh264_rect_t {0, 0, 0, 0});
+  if (view && view->n_crops) for (int i = 0; i < n; i++) crops[i] = view->crops[view->n_crops == 1 ? 0 : i];
   if (ext && ext->struct_bytes != sizeof (lh264_decode_ext_t)) return LH264_E_ARG;      // (before ext->colour is read below)
   if (sample && (!sample_ok (sample) || (sample->type != LH264_SAMPLE_U8 && (!ext || ext->colour == LH264_COLOUR_YUV)))) return LH264_E_ARG;
   // 0: bytes, the pack kernels as ever; else decode_pack_sample_kernel in decode_pack_rgb_kernel's place, es bytes per element
@@ -1182,6 +1424,8 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
   const bool sized = opts_v6 && (opts->out_width || opts->out_height);
   if (opts_v6 && (opts->reserved4 != 0 || opts->reserved5 != 0 || (sized && (!lh264pack::size_ok (opts->out_width, opts->out_height) || scale != 0)))) return LH264_E_ARG;
   const int out_w = sized ? (int)opts->out_width : 0, out_h = sized ? (int)opts->out_height : 0;      // 0, 0: the window (or its scale); else decode_pack_resized_kernel
+  if (fit != LH264_FIT_STRETCH && !out_w) return LH264_E_ARG;
+  const bool placed = fit == LH264_FIT_CONTAIN;      // the placed kernels and a place per pack job (else the kernels of the calls above, whatever the crop)
   if (!Parser::conceal_method_ok (conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   const int format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -1269,8 +1513,21 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
       std::string why = tentative ? std::string() : refuse_picture (f);
       if (!tentative && why.empty() && colour && picture_standard (f, ext_matrix, ext_range) > 3) why = "matrix_coefficients " + std::to_string (f.matrix_coefficients) + " has no conversion here (BT.601: 5, 6, 2 or none; BT.709: 1): name a matrix";
       if (!why.empty()) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (idx) + ": " + why; break; }
+      // the caller's crop against this picture's window (a stream may change size): the stream stops here, as for the matrix
+      const lh264_rect_t& cr = crops[s.i];
+      if (!tentative && cr.w && !crop_fits (cr, f.crop_w, f.crop_h)) {
+        s.ending = true; s.end_code = LH264_E_ARG;
+        s.end_text = "picture " + std::to_string (idx) + ": the crop {" + std::to_string (cr.x) + ", " + std::to_string (cr.y) + ", " + std::to_string (cr.w) + ", " + std::to_string (cr.h) +
+                     "} does not fit the picture's " + std::to_string (f.crop_w) + " x " + std::to_string (f.crop_h) + " window";
+        break;
+      }
       s.sel.push_back (std::move (s.pending.front())); s.pending.pop_front();
     }
+  };
+  // what the call delivers for a picture of stream s: its view's size (a picture select() let through: the crop fits)
+  auto delivered = [&] (const DStream& s, const FrameOut& f, int* ow, int* oh) {
+    lh264_rect_t vs, vd;
+    view_of (f.crop_w, f.crop_h, crops[s.i], fit, scale, out_w, out_h, &vs, &vd, ow, oh);
   };
   auto unselect = [&] (DStream& s) {                // the round was full: the pictures wait for the next one
     for (size_t q = s.sel.size(); q-- > 0; ) s.pending.push_front (std::move (s.sel[q]));
@@ -1316,6 +1573,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
+        r.view.insert (r.view.end(), c.view.begin(), c.view.end());
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, (int)k);
@@ -1329,6 +1587,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
         r.pics.insert (r.pics.end(), c.pics.begin(), c.pics.end());
         r.concealed.insert (r.concealed.end(), c.concealed.begin(), c.concealed.end());
         r.source_wh.insert (r.source_wh.end(), c.source_wh.begin(), c.source_wh.end());
+        r.view.insert (r.view.end(), c.view.begin(), c.view.end());
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, k);
@@ -1522,7 +1781,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
       DStream& s = *sp;
       if (s.sel.empty()) continue;
       size_t m = 0, mh = 0, sl = 0, ents = 0, bytes = 0, shown = 0;
-      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); bytes += colour ? (size_t)ow * oh * 3 * es : (size_t)ow * oh * 3 / 2; shown++; } }
+      for (auto& f : s.sel) { m += (size_t)f->mb_w * f->mb_h; if (!s.dev_at.count (f.get())) mh += (size_t)f->mb_w * f->mb_h; sl += f->slices.size(); ents += f->sparse_coeffs.size(); if (!f->frozen) { int ow, oh; delivered (s, *f, &ow, &oh); bytes += colour ? (size_t)ow * oh * 3 * es : (size_t)ow * oh * 3 / 2; shown++; } }
       if (!rd.chains.empty() && n_mbs + m > group_mbs) { unselect (s); continue; }
       const FrameOut& f0 = *s.sel[0];
       if (f0.mb_w != s.geo.mb_w || f0.mb_h != s.geo.mb_h) {
@@ -1537,7 +1796,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
       n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       // a float type: every picture, and so every row, begins at a multiple of 4 bytes - the chain at one of 16, a picture 3*ow*oh*es
       // bytes behind the one before (decode_pack_sample_kernel stores nothing narrower)
-      if (stype) for (auto& f : s.sel) if (!f->frozen) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); if (((size_t)ow * oh * 3 * es | rd.out_bytes) & 3) offsets_ok = false; }
+      if (stype) for (auto& f : s.sel) if (!f->frozen) { int ow, oh; delivered (s, *f, &ow, &oh); if (((size_t)ow * oh * 3 * es | rd.out_bytes) & 3) offsets_ok = false; }
       rd.out_bytes += (bytes + 15) & ~ (size_t)15;
       max_w = std::max (max_w, f0.mb_w); max_h = std::max (max_h, f0.mb_h);
       rd.chains.push_back (std::move (c));
@@ -1557,7 +1816,8 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
                A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
                A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
-               (!colour || (A.d_std.alloc (n_jobs) && A.h_std[rb].alloc (n_jobs)));
+               (!colour || (A.d_std.alloc (n_jobs) && A.h_std[rb].alloc (n_jobs))) &&
+               (!placed || (A.d_place.alloc (n_jobs * sizeof (lh264_pack_place_t)) && A.h_place[rb].alloc (n_jobs * sizeof (lh264_pack_place_t))));
     const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
     rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
     const size_t dig_bytes = rd.dig_states_at + (size_t)n_chains * sizeof (lh264_sha1_state_t);
@@ -1588,6 +1848,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
     lh264_mb_t* h_mbs = A.h_mbs[rb].as<lh264_mb_t>(); uint64_t* h_sparse = A.h_sparse[rb].as<uint64_t>(); lh264_slice_t* h_sl = A.h_sl[rb].as<lh264_slice_t>();
     lh264_frame_job_t* h_jobs = A.h_jobs[rb].as<lh264_frame_job_t>(); int32_t* h_first = A.h_first[rb].as<int32_t>(); lh264_pack_job_t* h_pack = A.h_pack[rb].as<lh264_pack_job_t>();
     uint8_t* h_std = colour ? A.h_std[rb].as<uint8_t>() : nullptr;
+    lh264_pack_place_t* h_place = placed ? A.h_place[rb].as<lh264_pack_place_t>() : nullptr;
     uint8_t* const d_out = A.d_out[rb].as<uint8_t>();
     run_parallel (n_chains, threads, [&] (int c) {
       RoundChain& rc = rd.chains[c];
@@ -1624,6 +1885,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
         jb.flags = f.is_ref && !picking ? 0 : LH264_JOB_NO_EXPAND;      // (opts->pick: nothing will read the picture's borders)
         lh264_pack_job_t& pj = h_pack[j];
         memset (&pj, 0, sizeof (pj));
+        if (placed) memset (&h_place[j], 0, sizeof (lh264_pack_place_t));
         pj.reserved = scale;
         const uint8_t std_byte = colour ? picture_standard (f, ext_matrix, ext_range) : 0;      // (a picture select() let through: its standard is defined)
         if (colour) h_std[j] = std_byte & 3;
@@ -1631,9 +1893,13 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
         pj.y = jb.dst.y_dev; pj.u = jb.dst.u_dev; pj.v = jb.dst.v_dev;
         pj.dst = d_out + at;
         pj.stride_y = s.geo.stride_y; pj.stride_c = s.geo.stride_c;
-        pj.crop_x = f.crop_x; pj.crop_y = f.crop_y; pj.crop_w = f.crop_w; pj.crop_h = f.crop_h; pj.format = format;
-        int ow, oh;
-        lh264pack::delivered_size (f.crop_w, f.crop_h, scale, out_w, out_h, &ow, &oh);      // what is delivered
+        // the picture's view: the source rectangle takes the window's place in the job, the destination goes to the job's place
+        lh264_rect_t vs, vd;
+        int ow, oh;                                                                         // what is delivered
+        view_of (f.crop_w, f.crop_h, crops[s.i], fit, scale, out_w, out_h, &vs, &vd, &ow, &oh);
+        pj.crop_x = f.crop_x + vs.x; pj.crop_y = f.crop_y + vs.y; pj.crop_w = vs.w; pj.crop_h = vs.h; pj.format = format;
+        if (placed) { h_place[j].x = vd.x; h_place[j].y = vd.y; h_place[j].w = vd.w; h_place[j].h = vd.h; h_place[j].fill = fill; }
+        for (const lh264_rect_t* r : {&vs, &vd}) { rc.view.push_back (r->x); rc.view.push_back (r->y); rc.view.push_back (r->w); rc.view.push_back (r->h); }
         const size_t bytes = colour ? (size_t)ow * oh * 3 * es : (size_t)ow * oh * 3 / 2;
         lh264_decoded_pic_t dp;
         dp.width = ow; dp.height = oh; dp.frame_num = f.frame_num; dp.idr = f.idr ? 1 : 0; dp.offset = off; dp.bytes = bytes;
@@ -1670,7 +1936,7 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
     }
     for (int c = 0; c < n_chains; c++) {
       DStream& s = *rd.chains[c].s;
-      for (auto& f : s.sel) { int ow, oh; lh264pack::delivered_size (f->crop_w, f->crop_h, scale, out_w, out_h, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
+      for (auto& f : s.sel) { int ow, oh; delivered (s, *f, &ow, &oh); max_bands = std::max (max_bands, (oh + lh264pack::kBandRows - 1) / lh264pack::kBandRows); }
       // the slots the round leaves free: pictures the DPB behind the round's last picture does not hold
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
       for (Slot& sl : s.pool) if (sl.pic_id >= 0 && (picking || std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end())) sl.pic_id = -1;      // (opts->pick: a slot is needed for its round only)
@@ -1686,13 +1952,19 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
       hipStream_t st = A.s_run;
       auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
       bool ok = up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
-                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) && (!colour || up (A.d_std, h_std, n_jobs)) &&
+                up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) && (!colour || up (A.d_std, h_std, n_jobs)) && (!placed || up (A.d_place, h_place, n_jobs * sizeof (lh264_pack_place_t))) &&
                 (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
       if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
       if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
       if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
       if (ok) {
-        if (stype) hipLaunchKernelGGL (decode_pack_sample_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour, sample_arg);
+        if (placed) {
+          const lh264_pack_place_t* d_place = A.d_place.as<lh264_pack_place_t>();
+          if (stype) hipLaunchKernelGGL (decode_pack_sample_placed_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), d_place, A.d_std.as<uint8_t>(), out_w, out_h, colour, sample_arg);
+          else if (colour) hipLaunchKernelGGL (decode_pack_rgb_placed_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), d_place, A.d_std.as<uint8_t>(), out_w, out_h, colour);
+          else hipLaunchKernelGGL (decode_pack_placed_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), d_place, out_w, out_h);
+        }
+        else if (stype) hipLaunchKernelGGL (decode_pack_sample_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour, sample_arg);
         else if (colour) hipLaunchKernelGGL (decode_pack_rgb_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), A.d_std.as<uint8_t>(), out_w, out_h, colour);
         else if (out_w) hipLaunchKernelGGL (decode_pack_resized_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), out_w, out_h);
         else if (scale) hipLaunchKernelGGL (decode_pack_scaled_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>());
@@ -1845,6 +2117,33 @@ int lh264_decoded_picture_source_size (const lh264_decoded_t* d, int idx, int32_
   if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->source_wh.size() != d->pics.size() * 2) return LH264_E_ARG;
   if (width) *width = d->source_wh[(size_t)idx * 2];
   if (height) *height = d->source_wh[(size_t)idx * 2 + 1];
+  return LH264_OK;
+}
+int lh264_decoded_picture_view (const lh264_decoded_t* d, int idx, lh264_rect_t* src, lh264_rect_t* dst) {
+  if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->view.size() != d->pics.size() * 8) return LH264_E_ARG;
+  const int32_t* v = &d->view[(size_t)idx * 8];
+  if (src) *src = {v[0], v[1], v[2], v[3]};
+  if (dst) *dst = {v[4], v[5], v[6], v[7]};
+  return LH264_OK;
+}
+int lh264_view_rects (int32_t w, int32_t h, const lh264_rect_t* crop, uint32_t fit, int32_t out_w, int32_t out_h, lh264_rect_t* src, lh264_rect_t* dst) {
+  if (w < 2 || h < 2 || w > 16384 || h > 16384 || ((w | h) & 1) || fit > LH264_FIT_CONTAIN) return LH264_E_ARG;
+  if ((out_w || out_h) ? !lh264pack::size_ok (out_w, out_h) : fit != LH264_FIT_STRETCH) return LH264_E_ARG;
+  const lh264_rect_t c = crop ? *crop : lh264_rect_t {0, 0, 0, 0};
+  if (!crop_ok (c) || (c.w && !crop_fits (c, w, h))) return LH264_E_ARG;
+  lh264_rect_t vs, vd;
+  int ow, oh;
+  view_of (w, h, c, fit, 0, out_w, out_h, &vs, &vd, &ow, &oh);
+  if (src) *src = vs;
+  if (dst) *dst = vd;
+  return LH264_OK;
+}
+int lh264_parser_window (const uint8_t* data, size_t len, int32_t* width, int32_t* height) {
+  if (!data) return LH264_E_ARG;
+  int w = 0, h = 0;
+  if (!Parser::first_sps_window (data, len, &w, &h)) return LH264_E_UNSUPPORTED;
+  if (width) *width = w;
+  if (height) *height = h;
   return LH264_OK;
 }
 int lh264_decoded_concealed (const lh264_decoded_t* d, int idx) {

@@ -83,6 +83,17 @@ class DecodedBatch:
             out.append((w.value, h.value))
         return out
 
+    def views(self, i):
+        """[(src, dst)] per delivered picture of stream i, each an (x, y, w, h): the source rectangle in the picture's window - the
+        caller's crop, narrowed by fit="cover" - and the destination rectangle in the delivered picture (the letterboxed part under
+        fit="contain").  Without crop= and fit=: (0, 0, w, h) of the window and (0, 0, width, height) of what is delivered"""
+        out = []
+        s, d = L.Rect(), L.Rect()
+        for k in range(self._lib.lh264_decoded_pictures(self._h[i])):
+            L.check(self._lib.lh264_decoded_picture_view(self._h[i], k, C.byref(s), C.byref(d)))
+            out.append(((s.x, s.y, s.w, s.h), (d.x, d.y, d.w, d.h)))
+        return out
+
     def colours(self, i):
         """colour="rgb24" | "rgbp": [(matrix, colour_range)] per delivered picture of stream i, the standard that was applied to it -
         matrix "bt601" | "bt709", colour_range "limited" | "full" (what the stream's SPS says, or what the call named)"""
@@ -170,7 +181,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -222,7 +233,20 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     rounded to nearest even (float16 overflows to infinity; no type flushes subnormals).  The layout is colour='s with elements in
     place of bytes, little-endian: 3*W*H*4 (or *2) bytes a picture; pictures, the sink, data, tensor and the digests are of those bytes.
     mul / add: None (1, 1, 1 / 0, 0, 0) or three finite numbers, rounded to binary32 once; normalise (mean, std) makes them.
-    DecodedBatch.dtype is the dtype of the call, .affine the six binary32 values passed; frames(i) is the typed view."""
+    DecodedBatch.dtype is the dtype of the call, .affine the six binary32 values passed; frames(i) is the typed view.
+    crop: None | (x, y, w, h) for every stream | a list with one entry per stream, each (x, y, w, h) or None: a rectangle in the
+    coordinates of the picture's cropped window, all four even, x, y >= 0, w, h >= 2.  It takes the window's place in everything above:
+    the copy, the scale= means (clamped to the crop), the size= resampling, colour and dtype; nothing outside it enters a delivered
+    sample.  A crop that does not fit a picture's window stops that stream at that picture with LH264_E_ARG and a text naming the
+    picture, the rectangle and the window; the pictures in front of it are delivered.  stream_window (data) gives a stream's window
+    without decoding it.
+    fit: "stretch" (the default) | "cover" | "contain", the latter two with size= only; w x h below is the window after crop=, OW x OH the
+    size, all arithmetic in integers.  "cover": the largest centred sub-rectangle of the window with the size's aspect, resampled to the
+    size - resize-to-cover plus centre crop in one pass.  "contain" (letterbox): the whole window resampled into the largest centred even
+    rectangle of the size, every sample outside it fill = (y, cb, cr), default (16, 128, 128); with colour= a bar pixel is the conversion
+    of the fill, with a float dtype its fma.  The rectangles are even and keep the aspect to the nearest even sample, not exactly:
+    view_rects (w, h, crop, fit, size) is the rule (include/lh264.h at lh264_decode_batch_ex3), DecodedBatch.views(i) what was applied.
+    source_sizes keeps giving the windows; frames(i) keeps its shapes."""
     lib = L.lib()
     if not isinstance(dtype, str) or dtype not in L.SAMPLE:
         raise ValueError("dtype must be 'uint8', 'float32', 'float16' or 'bfloat16'")
@@ -242,6 +266,19 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise ValueError("matrix and colour_range need colour=")
     if colour is not None and fmt != "i420":
         raise ValueError("colour needs fmt='i420'")
+    if fit not in L.FIT:
+        raise ValueError("fit must be 'stretch', 'cover' or 'contain'")
+    if fit != "stretch" and size is None:
+        raise ValueError("fit needs size=")
+    if fill is not None and fit != "contain":
+        raise ValueError("fill needs fit='contain'")
+    fill_word = 0
+    if fit == "contain":
+        f3 = (16, 128, 128) if fill is None else fill
+        if not (isinstance(f3, (tuple, list)) and len(f3) == 3 and all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 255 for v in f3)):
+            raise ValueError("fill must be None or three ints (y, cb, cr) in 0..255")
+        fill_word = f3[0] | f3[1] << 8 | f3[2] << 16
+    crops = _crops(crop, len(datas))
     if size is not None:
         ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and 2 <= v <= 4096 and v % 2 == 0 for v in size)
         if not ok:
@@ -294,7 +331,24 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         cb = L.DECODE_SINK_FN(_cb)
         opts.sink = cb
     outs = (C.c_void_p * n)()
-    if colour is None:
+    if fit != "stretch" or crops is not None:
+        # a view: every struct the call takes, the colour and sample ones where they are asked for
+        view = L.DecodeView()
+        view.struct_bytes, view.fit, view.fill = C.sizeof(L.DecodeView), L.FIT[fit], fill_word
+        if crops is not None:
+            rects = (L.Rect * len(crops))(*[L.Rect(*c) for c in crops])
+            view.n_crops, view.crops = len(crops), rects
+        ext = sm = None
+        if colour is not None:
+            ext = L.DecodeExt()
+            ext.struct_bytes, ext.colour, ext.matrix, ext.range = C.sizeof(L.DecodeExt), L.COLOUR[colour], L.MATRIX[matrix], L.RANGE[colour_range]
+        if affine is not None:
+            sm = L.DecodeSample()
+            sm.struct_bytes, sm.type = C.sizeof(L.DecodeSample), L.SAMPLE[dtype]
+            for k in range(3):
+                sm.mul[k], sm.add[k] = affine[0][k], affine[1][k]
+        rc = lib.lh264_decode_batch_ex3(ptrs, lens, n, threads, C.byref(opts), C.byref(ext) if ext is not None else None, C.byref(sm) if sm is not None else None, C.byref(view), outs)
+    elif colour is None:
         rc = lib.lh264_decode_batch(ptrs, lens, n, threads, C.byref(opts), outs)
     else:
         ext = L.DecodeExt()
@@ -312,6 +366,53 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
     return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine)
+
+
+def _rect(c):
+    ok = isinstance(c, (tuple, list)) and len(c) == 4 and all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= 16384 and v % 2 == 0 for v in c) and c[2] >= 2 and c[3] >= 2
+    if not ok:
+        raise ValueError("a crop is (x, y, w, h): four even ints, x, y >= 0, w, h >= 2")
+    return tuple(c)
+
+
+def _crops(crop, n):
+    """crop= of decode_batch -> None, or the rectangles the call passes: one for every stream, or one per stream ((0, 0, 0, 0): none)"""
+    if crop is None:
+        return None
+    if isinstance(crop, list) and (len(crop) == 0 or crop[0] is None or isinstance(crop[0], (tuple, list))):
+        if len(crop) != n:
+            raise ValueError("a list of crops has one entry per stream")
+        if all(c is None for c in crop):
+            return None
+        return [(0, 0, 0, 0) if c is None else _rect(c) for c in crop]
+    return [_rect(crop)]
+
+
+def view_rects(w, h, crop=None, fit="stretch", size=None):
+    """the view of a w x h window under crop= / fit= / size= of decode_batch -> (src, dst), each (x, y, w, h): the source rectangle in
+    the window and the destination rectangle in the delivered picture (without a size: the source's own size at (0, 0)).  The rule of
+    include/lh264.h at lh264_decode_batch_ex3, computed by the library without a device; ValueError for what decode_batch refuses and
+    for a crop that does not fit the window"""
+    if fit not in L.FIT:
+        raise ValueError("fit must be 'stretch', 'cover' or 'contain'")
+    c = L.Rect(*_rect(crop)) if crop is not None else None
+    s, d = L.Rect(), L.Rect()
+    ow, oh = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    if L.lib().lh264_view_rects(int(w), int(h), C.byref(c) if c is not None else None, L.FIT[fit], ow, oh, C.byref(s), C.byref(d)) != 0:
+        raise ValueError("view_rects: a window, crop, fit or size that is not defined, or a crop that does not fit the window")
+    return (s.x, s.y, s.w, s.h), (d.x, d.y, d.w, d.h)
+
+
+def stream_window(data):
+    """(width, height) of the cropped window of the first SPS of an Annex-B file that parses - what its pictures deliver at full size,
+    and the coordinates crop= is given in; None where no SPS parses.  Headers only, no device"""
+    data = bytes(data)
+    w, h = C.c_int32(0), C.c_int32(0)
+    rc = L.lib().lh264_parser_window(data, len(data), C.byref(w), C.byref(h))
+    if rc == L.E_UNSUPPORTED:
+        return None
+    L.check(rc)
+    return w.value, h.value
 
 
 def _three(v, default, name):
@@ -350,9 +451,9 @@ def decode_arena_bytes():
 _SUFFIX = {"uint8": ".rgb", "float32": ".f32", "float16": ".f16", "bfloat16": ".bf16"}
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
     """out_dir/<basename>.yuv - with colour= <basename>.rgb, with a float dtype= <basename>.f32 | .f16 | .bf16 - for every input, through one decode_batch with a sink that appends to the
-    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul and add as in decode_batch"""
+    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     names = [os.path.join(out_dir, os.path.basename(p) + (".yuv" if colour is None else _SUFFIX.get(dtype, ".rgb"))) for p in paths]
@@ -364,7 +465,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop)
     finally:
         for f in files:
             f.close()
@@ -373,13 +474,13 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
     return res
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
-    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick and size as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick, size, fit, fill and crop as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop)
     res = []
     try:
         for i, p in enumerate(paths):

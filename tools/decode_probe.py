@@ -3,7 +3,7 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
@@ -11,6 +11,8 @@ lh264_parse_batch_discard - the host front end alone - on the same batch in the 
 --colour rgb24|rgbp asks for RGB pictures (decode_batch (colour=...), not with --nv12) and adds "colour" to the rows;
 --dtype float32|float16|bfloat16 asks for float RGB pictures (decode_batch (dtype=...), with --colour only; the factors are
 normalise of the ImageNet means and deviations) and adds "dtype" to the rows;
+--fit cover|contain asks for a fitted view (decode_batch (fit=...), with --size only; contain fills with 16, 128, 128) and --crop x,y,w,h
+for a rectangle of every picture's window (decode_batch (crop=...)); they add "fit" and "crop" to the rows;
 --pick intra|idr decodes the selected pictures only (decode_batch (pick=...)) and adds "pick" to the rows; every row carries
 parsed_slices (the slices whose data was parsed, all streams) and the launch shape of the call (rounds, chains, jobs);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
@@ -60,6 +62,13 @@ def main(argv):
         mul, add = lh.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
         scale = dict(scale, dtype=argv[argv.index("--dtype") + 1])
         args.remove(argv[argv.index("--dtype") + 1])
+    if "--fit" in argv:
+        scale = dict(scale, fit=argv[argv.index("--fit") + 1])
+        args.remove(argv[argv.index("--fit") + 1])
+    if "--crop" in argv:
+        text = argv[argv.index("--crop") + 1]
+        scale = dict(scale, crop=tuple(int(v) for v in text.split(",")))
+        args.remove(text)
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
     data = open(path, "rb").read()
