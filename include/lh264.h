@@ -940,6 +940,79 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
                             const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
                             const lh264_decode_sample_t* sample /* NULL = uint8 */, const lh264_decode_view_t* view /* NULL = none */, lh264_decoded_t** out);
 int lh264_decoded_picture_view (const lh264_decoded_t* d, int idx, lh264_rect_t* src, lh264_rect_t* dst);
+/* ---- motion fields: vectors, references, macroblock data: lh264_decode_batch_ex4 --------------------------------------------------------
+ * The four structs above are frozen; the fields travel in a fifth.  motion == NULL or fields == 0 is lh264_decode_batch_ex3, byte for
+ * byte and launch for launch (lh264_decode_batch_ex3 is this call with NULL).
+ * THE DEFINITION (normative).  For every DELIVERED picture of a stream two blocks, which cover the CODED picture of mb_w x mb_h
+ * macroblocks, not the cropped window; nothing in scale_log2, out_width / out_height, the view, colour or the sample type touches them.
+ * MOTION BLOCK: int16, little-endian, three planes of (4*mb_h) x (4*mb_w), plane after plane: 96 bytes a macroblock.  Cell (X, Y)
+ * belongs to macroblock (X >> 2, Y >> 2) and to its raster 4x4 block b = (Y & 3) * 4 + (X & 3).
+ *   planes 0, 1: dx, dy = mv[b][0], mv[b][1] of the macroblock's record (lh264_mb_t): quarter-pel, the final vector, for P_Skip the
+ *     inferred one.  A record with LH264_MB_CONCEAL gives mv[0] in all sixteen cells, the vector the reconstruct kernel reads (the front
+ *     end fills all sixteen vectors of such a record with that vector and its ref_idx with 0, so both readings agree on its records).
+ *   plane 2: `back`, how many pictures back in decode order the cell predicts from: lh264_decoded_picture_index of this picture minus
+ *     that of the reference picture (withheld and unselected pictures count).  r = ref_idx[(b >> 3) * 2 + ((b & 3) >> 1)], slot =
+ *     slices[slice_id].ref_slot[r], the picture is the one behind job reference `slot`.  back = -1 where that names no decoded picture:
+ *     r or slot outside 0..15, a slice_id past the picture's table, a slot past the job's references, a reference the decoder no longer
+ *     holds, the picture of 128s (the P pictures in front of a lost first IDR; a concealed macroblock whose source is the 128 picture).
+ *   A cell of an intra macroblock (mb_type & LH264_MB_INTRA), of an uncovered one (mb_type 0) and of a record whose kind below is 0 is
+ *   0, 0, 0 whatever the record holds.
+ * MACROBLOCK BLOCK: uint8, eight planes of mb_h x mb_w: 8 bytes a macroblock.
+ *   [0] kind, the first of these that mb_type has a bit of: 1 I4x4, 2 I8x8, 3 I16x16, 4 I_PCM, 5 P_Skip, 6 P16x16, 7 P16x8, 8 P8x16,
+ *       9 P8x8, 10 P8x8ref0; 0: none of them (not covered)        [1] qp_y        [2] cbp
+ *   [3] flags: bit 0 LH264_MBF_T8x8, bit 1 concealed (LH264_MB_CONCEAL)        [4..7] sub_type[0..3] for kinds 9 and 10, else 0
+ * Per stream the motion blocks of its delivered pictures lie tight one behind the other in one buffer, the macroblock blocks in a
+ * second; every block begins at a multiple of 8 bytes.  lh264_decoded_picture_motion gives a picture's geometry and offsets: crop_x,
+ * crop_y place the delivered window in the coded picture, so fields line up with pixels (luma sample (x, y) of the window lies in cell
+ * ((crop_x + x) >> 2, (crop_y + y) >> 2)).  lh264_decoded_motion gives the two buffers in host memory, lh264_decoded_motion_dev in device
+ * memory under LH264_DECODE_DEVICE_OUT (each gives NULL in the other mode; any out pointer may be NULL), lh264_decoded_motion_copy_dev
+ * copies both into the caller's device memory (either destination may be NULL; cap >= the length), complete on return.  All of them
+ * return LH264_E_ARG on a handle whose call asked for no fields, and on a bad index.
+ * With fields the pictures are delivered exactly as without them, in every mode; a sink receives the pictures, the fields stay on the
+ * handle.  conceal, both device parse routes, pick (every delivered picture is intra: all cells 0), round_pictures and group_mbs act as
+ * ever; withheld pictures deliver no fields; a stream that stops delivers the fields of the pictures in front of the stop.
+ * MOTION ONLY: with fields, LH264_DECODE_NO_PICTURES is accepted without a digest flag, and together with LH264_DECODE_DEVICE_OUT (the
+ * fields then stay on the device); with a sink it stays LH264_E_ARG.  Without a digest flag no picture pool is used and no reconstruct,
+ * pack or digest kernel is launched: lh264_decode_last_chains reports 0 rounds, chains and jobs, the picture records are those of the
+ * digests-only call.  decode_pack_motion_kernel gathers the records where the round's parse or upload left them, in front of the
+ * reconstruct launch.
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of the calls above: a struct_bytes other than 16, fields
+ * above 1, a reserved word that is not 0. */
+#define LH264_MOTION_FIELDS 1u
+typedef struct lh264_decode_motion {
+  uint32_t struct_bytes;                /* 16                                                                   */
+  uint32_t fields;                      /* 0: none (the call is lh264_decode_batch_ex3); LH264_MOTION_FIELDS    */
+  uint32_t reserved0, reserved1;        /* 0                                                                    */
+} lh264_decode_motion_t;
+typedef struct lh264_decoded_motion { int32_t mb_w, mb_h, crop_x, crop_y; uint64_t motion_offset, info_offset; } lh264_decoded_motion_t;
+int lh264_decode_batch_ex4 (const uint8_t* const* data, const size_t* len, int n, int threads,
+                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
+                            const lh264_decode_sample_t* sample /* NULL = uint8 */, const lh264_decode_view_t* view /* NULL = none */,
+                            const lh264_decode_motion_t* motion /* NULL = no fields */, lh264_decoded_t** out);
+int lh264_decoded_picture_motion (const lh264_decoded_t* d, int idx, lh264_decoded_motion_t* out);
+int lh264_decoded_motion (const lh264_decoded_t* d, const int16_t** motion, size_t* motion_bytes, const uint8_t** info, size_t* info_bytes);
+int lh264_decoded_motion_dev (const lh264_decoded_t* d, const int16_t** motion, size_t* motion_bytes, const uint8_t** info, size_t* info_bytes);
+int lh264_decoded_motion_copy_dev (const lh264_decoded_t* d, void* motion_dst_dev, size_t motion_cap, void* info_dst_dev, size_t info_cap);
+/* the last call's decode_pack_motion_kernel launches in this process: *ms their milliseconds on the device (between events around each
+ * launch), *bytes the field bytes they wrote (104 a macroblock).  Either may be NULL; 0, 0 after a call without fields */
+int lh264_decode_last_motion (double* ms, unsigned long long* bytes);
+/* one delivered picture's fields to gather (decode_pack_motion_kernel): its mb_w * mb_h records in raster order, its slice table, where
+ * the two blocks begin, and back[slot] for every job reference slot (-1: no picture).  The blocks begin at multiples of 8 bytes.
+ * lh264_debug_motion_cpu steps the kernel's code over HOST memory with t = 0, nt = 1; lh264_debug_motion_dev uploads the table (its
+ * pointers are device pointers), launches the production kernel and returns when it is through.  LH264_E_ARG: jobs NULL, n < 0, a NULL
+ * pointer in a job (slices may be NULL with n_slices 0), mb_w or mb_h outside 1..1024, n_slices outside 0..65535, a reserved word that is
+ * not 0, a motion or info destination that is not a multiple of 8, and from lh264_debug_motion_dev records that do not begin at a
+ * multiple of 16 (the kernel fetches them by 16-byte loads); a bad job anywhere: nothing of the table is done.  lh264_debug_motion_dev
+ * without a device: LH264_E_NODEVICE */
+typedef struct lh264_motion_job {
+  const lh264_mb_t* mbs; const lh264_slice_t* slices;
+  int16_t* motion; uint8_t* info;
+  int32_t mb_w, mb_h, n_slices, reserved;
+  int16_t back[LH264_MAX_REFS];
+} lh264_motion_job_t;
+#define LH264_MOTION_CHUNK_MBS 64       /* the macroblocks of one macroblock row that a workgroup of the kernel handles */
+int lh264_debug_motion_cpu (const lh264_motion_job_t* jobs, int n);
+int lh264_debug_motion_dev (const lh264_motion_job_t* jobs, int n);
 /* the rule above for a w x h window (even, 2..16384), a crop (NULL or w = h = 0: none), a fit and a size (0, 0: none, stretch only):
  * *src the source rectangle in window coordinates, *dst the destination rectangle in the delivered picture (without a size: {0, 0} and
  * the source's own size).  Either may be NULL.  LH264_E_ARG: a window, crop, fit or size the call above would refuse, a crop that does

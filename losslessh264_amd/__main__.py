@@ -22,6 +22,10 @@
                                                             by a sink run by run.  METHOD: lost slices are concealed as the reference's
                                                             decoder does (slice_copy | slice_copy_cross_idr | mv_copy |
                                                             slice_copy_cross_idr_freeze | mv_copy_freeze) instead of ending the stream
+    python -m losslessh264_amd --decode --motion | --motion-only ...   beside the pictures (--motion-only: and no picture file) every stream's
+                                                            motion fields, out_dir/<name>.mv (int16: dx, dy, pictures back per 4x4 block) and
+                                                            <name>.mbi (uint8: kind, qp, cbp, flags, sub types per macroblock) of its
+                                                            delivered pictures, gathered on the device (decode_batch (motion=True))
     python -m losslessh264_amd --decode --sha1 [--nv12] [--conceal METHOD] out_dir in.264...   digests only, no .yuv: out_dir/<name>.sha1
                                                             holds a line `index width height frame_num idr hex` per picture and a last
                                                             line `stream hex`, the SHA-1 of all pictures in order (computed on the device)
@@ -221,7 +225,8 @@ def decode(argv):
     colour, matrix, crange = None, None, None
     dtype, mul, add = None, None, None
     fit, fill, crop = None, None, None
-    while argv and argv[0] in ("--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+    motion = 0      # 1: --motion, 2: --motion-only
+    while argv and argv[0] in ("--motion", "--motion-only", "--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
         if argv[0] in ("--fit", "--fill", "--crop"):
             value = None
             if len(argv) >= 2:
@@ -287,6 +292,9 @@ def decode(argv):
                 return 2
             scale, argv = int(argv[1]), argv[2:]
             continue
+        if argv[0] in ("--motion", "--motion-only"):
+            motion, argv = max(motion, 1 if argv[0] == "--motion" else 2), argv[1:]
+            continue
         if argv[0] == "--nv12":
             nv12, argv = True, argv[1:]
         elif argv[0] == "--sha1":
@@ -308,6 +316,9 @@ def decode(argv):
     if (fit is not None and size is None) or (fill is not None and fit != "contain"):
         print(VIEW_USAGE)
         return 2
+    if motion and sha1:
+        print("--motion, --motion-only: not with --sha1")
+        return 2
     vkw = dict(fit=fit or "stretch", fill=fill, crop=crop)
     ckw = dict(vkw, colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
@@ -319,7 +330,7 @@ def decode(argv):
             print("%s: %d pictures, stream %s%s" % (name, pics, total, "  [stopped: %s]" % err if status else ""))
             ret = ret or (1 if status else 0)
         return ret
-    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, **ckw):
+    for name, status, err, pics, nbytes in lh.decode_to_files(argv[1:], argv[0], fmt="nv12" if nv12 else "i420", conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, motion=motion, **ckw):
         print("%s: %d pictures, %d bytes%s" % (name, pics, nbytes, "  [stopped: %s]" % err if status else ""))
         ret = ret or (1 if status else 0)
     return ret

@@ -189,6 +189,16 @@ class PackPlace(C.Structure):       # lh264_pack_place_t: where a pack job's pic
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("fill", C.c_uint32), ("reserved", C.c_uint32)]
 assert C.sizeof(Rect) == 16 and C.sizeof(DecodeView) == 32 and C.sizeof(PackPlace) == 24
 FIT = {"stretch": 0, "cover": 1, "contain": 2}            # LH264_FIT_*
+class DecodeMotion(C.Structure):    # lh264_decode_motion_t: what lh264_decode_batch_ex4 takes beside the four frozen structs
+    _fields_ = [("struct_bytes", C.c_uint32), ("fields", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+class DecodedMotion(C.Structure):   # lh264_decoded_motion_t: a delivered picture's field geometry and where its two blocks begin
+    _fields_ = [("mb_w", C.c_int32), ("mb_h", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("motion_offset", C.c_uint64), ("info_offset", C.c_uint64)]
+class MotionJob(C.Structure):       # lh264_motion_job_t: one picture's records to gather into a motion block and a macroblock block
+    _fields_ = [("mbs", C.c_void_p), ("slices", C.c_void_p), ("motion", C.c_void_p), ("info", C.c_void_p),
+                ("mb_w", C.c_int32), ("mb_h", C.c_int32), ("n_slices", C.c_int32), ("reserved", C.c_int32), ("back", C.c_int16 * 16)]
+assert C.sizeof(DecodeMotion) == 16 and C.sizeof(DecodedMotion) == 32 and C.sizeof(MotionJob) == 80
+MOTION_FIELDS = 1                   # LH264_MOTION_FIELDS
+MOTION_CHUNK_MBS = 64               # LH264_MOTION_CHUNK_MBS: the macroblocks of a row one workgroup of decode_pack_motion_kernel handles
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("threads", C.c_int32), ("flags", C.c_uint32)]
@@ -200,6 +210,14 @@ _SIGS.update({
     "lh264_decoded_sample_type": (C.c_int, [C.c_void_p]),
     "lh264_decode_batch_ex3": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decoded_picture_view": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_decode_batch_ex4": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_picture_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lh264_decoded_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "lh264_decoded_motion_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "lh264_decoded_motion_copy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "lh264_decode_last_motion": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]),
+    "lh264_debug_motion_cpu": (C.c_int, [C.c_void_p, C.c_int]),
+    "lh264_debug_motion_dev": (C.c_int, [C.c_void_p, C.c_int]),
     "lh264_view_rects": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "lh264_parser_window": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lh264_debug_view_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

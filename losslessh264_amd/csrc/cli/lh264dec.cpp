@@ -260,6 +260,9 @@ static bool parse_size (const char* text, int* w, int* h) {
   *w = v[0]; *h = v[1];
   return true;
 }
+// --motion | --motion-only: what lh264_decode_batch_ex4 takes beside the four (0: NULL, the call as ever); 2: the fields and no picture
+static int g_motion = 0;
+static const char* const kMotionUsage = "--motion, --motion-only: not with --sha1";
 static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick, int out_w, int out_h) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
@@ -267,20 +270,29 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   for (int i = 0; i < n; i++) { if (!load (srcs[i], in[i])) { perror (srcs[i].c_str()); return 2; } d[i] = in[i].data(); l[i] = in[i].size(); }
   DecodeFiles files; files.f.assign (n, nullptr); files.bytes.assign (n, 0);
   std::vector<std::string> dsts (n);
-  for (int i = 0; i < n; i++) {
+  for (int i = 0; i < n && g_motion != 2; i++) {
     dsts[i] = out_dir + "/" + base_name (srcs[i]) + out_suffix();
     files.f[i] = fopen (dsts[i].c_str(), "wb");
     if (!files.f[i]) { perror (dsts[i].c_str()); for (FILE* f : files.f) if (f) fclose (f); return 2; }
   }
   lh264_decode_opts_t o; memset (&o, 0, sizeof (o));
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.sink = decode_sink; o.user = &files; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
+  if (g_motion == 2) { o.sink = nullptr; o.user = nullptr; o.flags = LH264_DECODE_NO_PICTURES; }
+  const lh264_decode_motion_t motion = {sizeof (lh264_decode_motion_t), LH264_MOTION_FIELDS, 0, 0};
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex3 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), h.data());
-  for (FILE* f : files.f) fclose (f);
+  const int rc = lh264_decode_batch_ex4 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), g_motion ? &motion : nullptr, h.data());
+  for (FILE* f : files.f) if (f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
     const int st = lh264_decoded_status (h[i]);
+    if (g_motion) {
+      // the stream's motion blocks and macroblock blocks, as the handle holds them: <name>.mv and <name>.mbi
+      const int16_t* mv = nullptr; const uint8_t* mbi = nullptr; size_t mv_bytes = 0, mbi_bytes = 0;
+      const std::string stem = out_dir + "/" + base_name (srcs[i]);
+      if (lh264_decoded_motion (h[i], &mv, &mv_bytes, &mbi, &mbi_bytes) != LH264_OK || !save (stem + ".mv", (const uint8_t*)mv, mv_bytes) || !save (stem + ".mbi", mbi, mbi_bytes)) { fprintf (stderr, "cannot write %s.mv / .mbi\n", stem.c_str()); ret = 2; }
+      if (g_motion == 2) { dsts[i] = stem + ".mv"; files.bytes[i] = mv_bytes + mbi_bytes; }
+    }
     printf ("%s -> %s: %d pictures, %zu bytes%s%s\n", srcs[i].c_str(), dsts[i].c_str(), lh264_decoded_pictures (h[i]), files.bytes[i], st == LH264_OK ? "" : "  [stopped: ", st == LH264_OK ? "" : (std::string (lh264_decoded_error (h[i])) + "]").c_str());
     if (st != LH264_OK) ret = 1;
     lh264_decoded_free (h[i]);
@@ -355,6 +367,8 @@ int main (int argc, char** argv) {
     for (;;) {
       if (first < argc && !strcmp (argv[first], "--nv12")) { nv12 = true; first++; }
       else if (first < argc && !strcmp (argv[first], "--sha1")) { sha1 = true; first++; }
+      else if (first < argc && !strcmp (argv[first], "--motion")) { if (!g_motion) g_motion = 1; first++; }
+      else if (first < argc && !strcmp (argv[first], "--motion-only")) { g_motion = 2; first++; }
       else if (first < argc && !strcmp (argv[first], "--device-parse")) { if (!device_parse) device_parse = 1; first++; }
       else if (first < argc && !strcmp (argv[first], "--device-parse-cabac")) { device_parse = 2; first++; }
       else if (first + 1 < argc && !strcmp (argv[first], "--conceal")) {
@@ -414,16 +428,17 @@ int main (int argc, char** argv) {
     if ((g_sample.type && !g_ext.colour) || (!g_sample.type && (add_named || mul_named))) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
     if (g_sample.type && !mul_named) g_sample.mul[0] = g_sample.mul[1] = g_sample.mul[2] = 1.0f;
     if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
+    if (g_motion && sha1) { fprintf (stderr, "%s\n", kMotionUsage); return 2; }
     if ((g_view.fit != LH264_FIT_STRETCH && !out_w) || (fill_named && g_view.fit != LH264_FIT_CONTAIN)) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
     if (g_view.fit == LH264_FIT_CONTAIN && !fill_named) g_view.fill = 16u | 128u << 8 | 128u << 16;
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

@@ -823,7 +823,125 @@ __host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_placed (const lh26
   else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_placed_in<(int)LH264_COLOUR_RGBP> (j, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
 }
 
+// ---- the motion fields: lh264_decode_batch_ex4 (the definition: include/lh264.h at that call) ---------------------------------------
+// A gather / transpose from the 128-byte records to dense planes; nothing of a reconstructed picture is read.  The unit of work is a
+// CHUNK: up to kMotionChunkMbs neighbouring macroblocks of one macroblock row.  Its records are fetched once (on the device: 16-byte loads
+// into LDS, a record 33 words apart, so that the lanes of a wave - one macroblock each - read one field of 64 records from 64 banks)
+// and every field is read from there as 32-bit words.  An item of the motion block is the four cells of one cell row of one macroblock
+// in one plane: one aligned 8-byte store (a block begins at a multiple of 8 bytes and a cell row of a macroblock is 8 bytes), item k
+// and k + 1 are neighbouring macroblocks: the lanes of a wave write a plane row's bytes one behind the other.  The reference lookups of
+// plane 2 are two per item, one per quadrant the row crosses.  An item of the macroblock block is a PIECE of one plane's row: 8 bytes of
+// the destination counted from the aligned address at or below the chunk's first byte (a plane row begins wherever the row before
+// ended); a whole piece is one aligned 8-byte store, heads and tails go byte by byte and touch nothing outside the chunk's bytes.
+constexpr int kMotionChunkMbs = LH264_MOTION_CHUNK_MBS;
+constexpr int kMotionRecStride = 33;       // words between two records in LDS
+
+// [0] of the macroblock block
+__host__ __device__ inline uint32_t motion_kind (uint32_t mb_type) {
+  if (mb_type & LH264_MB_I4x4) return 1;
+  if (mb_type & LH264_MB_I8x8) return 2;
+  if (mb_type & LH264_MB_I16x16) return 3;
+  if (mb_type & LH264_MB_IPCM) return 4;
+  if (mb_type & LH264_MB_SKIP) return 5;
+  if (mb_type & LH264_MB_P16x16) return 6;
+  if (mb_type & LH264_MB_P16x8) return 7;
+  if (mb_type & LH264_MB_P8x16) return 8;
+  if (mb_type & LH264_MB_P8x8) return 9;
+  if (mb_type & LH264_MB_P8x8REF0) return 10;
+  return 0;
+}
+// `back` of quadrant q of the record whose words are rec
+__host__ __device__ inline uint32_t motion_back (const uint32_t* rec, int q, const lh264_slice_t* slices, int n_slices, const int16_t* back) {
+  const int r = (int8_t) (rec[8] >> (8 * q));
+  const int sid = (int) (rec[6] >> 16);
+  if (r < 0 || r >= LH264_MAX_REFS || sid >= n_slices) return 0xffffu;
+  const int slot = slices[sid].ref_slot[r];
+  if (slot < 0 || slot >= LH264_MAX_REFS) return 0xffffu;
+  return (uint32_t) (uint16_t)back[slot];
+}
+// cells 4 * mbx .. 4 * mbx + 3 of cell row y (0..3) of the macroblock in plane p: four int16
+__host__ __device__ inline uint2 motion_cells (const uint32_t* rec, int p, int y, const lh264_slice_t* slices, int n_slices, const int16_t* back) {
+  const uint32_t type = rec[0] & 0xffffu;
+  uint2 o = {0u, 0u};
+  if (motion_kind (type) < 5) return o;
+  if (p == 2) {
+    const uint32_t b0 = motion_back (rec, (y >> 1) * 2, slices, n_slices, back), b1 = motion_back (rec, (y >> 1) * 2 + 1, slices, n_slices, back);
+    o.x = b0 | b0 << 16; o.y = b1 | b1 << 16;
+    return o;
+  }
+  const uint32_t* mv = rec + 15 + ((type & LH264_MB_CONCEAL) ? 0 : 4 * y);       // (mv[b] is word 15 + b: dx below dy)
+  const bool one = (type & LH264_MB_CONCEAL) != 0;
+  const int sh = 16 * p;
+  const uint32_t c0 = mv[0] >> sh & 0xffffu, c1 = (one ? mv[0] : mv[1]) >> sh & 0xffffu, c2 = (one ? mv[0] : mv[2]) >> sh & 0xffffu, c3 = (one ? mv[0] : mv[3]) >> sh & 0xffffu;
+  o.x = c0 | c1 << 16; o.y = c2 | c3 << 16;
+  return o;
+}
+// the macroblock's byte in plane pl of the macroblock block
+__host__ __device__ inline uint32_t motion_info (const uint32_t* rec, int pl) {
+  const uint32_t type = rec[0] & 0xffffu;
+  if (pl == 0) return motion_kind (type);
+  if (pl == 1) return rec[0] >> 24;
+  if (pl == 2) return rec[0] >> 16 & 0xffu;
+  if (pl == 3) return (rec[1] >> 16 & LH264_MBF_T8x8) | ((type & LH264_MB_CONCEAL) ? 2u : 0u);
+  const uint32_t k = motion_kind (type);
+  return k == 9 || k == 10 ? rec[7] >> (8 * (pl - 4)) & 0xffu : 0u;
+}
+// macroblocks c0 .. c0 + n - 1 of macroblock row `row` of one job, worked on by item t of nt (the lanes of a workgroup; the host steps
+// it with t = 0, nt = 1).  rec_at (m): the 32 words of the chunk's record m; back: the job's table
+template <class RecAt>
+__host__ __device__ inline void motion_chunk (const lh264_motion_job_t& j, const int16_t* back, int row, int c0, int n, const RecAt& rec_at, int t, int nt) {
+  const size_t cw = 4 * (size_t)j.mb_w, plane = cw * 4 * (size_t)j.mb_h;
+  for (int it = t; it < 12 * n; it += nt) {
+    const int m = it % n, py = it / n, p = py >> 2, y = py & 3;
+    const uint2 v = motion_cells (rec_at (m), p, y, j.slices, j.n_slices, back);
+    * (uint2*) (j.motion + (size_t)p * plane + (size_t) (4 * row + y) * cw + 4 * (size_t) (c0 + m)) = v;
+  }
+  const size_t ip = (size_t)j.mb_w * j.mb_h;
+  const int pieces = (n + 14) >> 3;
+  for (int it = t; it < 8 * pieces; it += nt) {
+    const int pl = it / pieces, pc = it % pieces;
+    uint8_t* d = j.info + (size_t)pl * ip + (size_t)row * j.mb_w + c0;
+    int a = pc * 8 - (int) ((uintptr_t)d & 7u), b = a + 8;
+    if (a >= 0 && b <= n) {
+      uint2 o = {0u, 0u};
+      for (int k = 0; k < 4; k++) { o.x |= motion_info (rec_at (a + k), pl) << (8 * k); o.y |= motion_info (rec_at (a + 4 + k), pl) << (8 * k); }
+      * (uint2*) (d + a) = o;
+      continue;
+    }
+    if (a < 0) a = 0;
+    if (b > n) b = n;
+    for (int k = a; k < b; k++) d[k] = (uint8_t)motion_info (rec_at (k), pl);
+  }
+}
+// what the entry points accept as a job: sizes the front end can deliver, destinations at multiples of 8 bytes
+inline bool motion_job_ok (const lh264_motion_job_t& j) {
+  return j.mbs && j.motion && j.info && (j.slices || !j.n_slices) && j.mb_w >= 1 && j.mb_w <= 1024 && j.mb_h >= 1 && j.mb_h <= 1024 && j.n_slices >= 0 && j.n_slices <= 65535 &&
+         j.reserved == 0 && !((uintptr_t)j.motion & 7u) && !((uintptr_t)j.info & 7u);
+}
+inline int motion_chunks (int mb_w) { return (mb_w + kMotionChunkMbs - 1) / kMotionChunkMbs; }
+
 }  // namespace lh264pack
+
+// one workgroup per (picture, chunk of a macroblock row): the chunk's records go to LDS once, then every lane takes items of both blocks
+__global__ void __launch_bounds__ (256) decode_pack_motion_kernel (const lh264_motion_job_t* __restrict__ jobs) {
+  __shared__ uint32_t s_rec[lh264pack::kMotionChunkMbs * lh264pack::kMotionRecStride];
+  __shared__ int16_t s_back[LH264_MAX_REFS];
+  const lh264_motion_job_t j = jobs[blockIdx.x];
+  const int chunks = (j.mb_w + lh264pack::kMotionChunkMbs - 1) / lh264pack::kMotionChunkMbs;
+  if ((int)blockIdx.y >= j.mb_h * chunks) return;
+  const int row = (int)blockIdx.y / chunks, c0 = ((int)blockIdx.y % chunks) * lh264pack::kMotionChunkMbs;
+  const int n = j.mb_w - c0 < lh264pack::kMotionChunkMbs ? j.mb_w - c0 : lh264pack::kMotionChunkMbs;
+  const int t = (int)threadIdx.x;
+  if (t < LH264_MAX_REFS) s_back[t] = jobs[blockIdx.x].back[t];
+  const uint4* src = (const uint4*) (j.mbs + (size_t)row * j.mb_w + c0);      // (records are 128 bytes and begin at a multiple of 16)
+  for (int q = t; q < 8 * n; q += 256) {
+    const uint4 v = src[q];
+    uint32_t* d = s_rec + (q >> 3) * lh264pack::kMotionRecStride + (q & 7) * 4;
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  }
+  __syncthreads();
+  lh264pack::motion_chunk (j, s_back, row, c0, n, [&] (int m) { return (const uint32_t*)s_rec + m * lh264pack::kMotionRecStride; }, t, 256);
+}
 
 // one workgroup per (picture, band)
 __global__ void __launch_bounds__ (256) decode_pack_kernel (const lh264_pack_job_t* __restrict__ jobs) {
@@ -910,13 +1028,22 @@ struct lh264_decoded {
   std::vector<uint8_t> pic_sha;                 // 20 bytes per delivered picture
   lh264_sha1_state_t stream_state;              // the stream's message behind the last round delivered
   uint8_t stream_sha[20];
+  // lh264_decode_batch_ex4 with fields: per delivered picture its geometry and offsets, the stream's motion blocks and macroblock
+  // blocks in host memory, or in device memory (LH264_DECODE_DEVICE_OUT)
+  uint32_t fields = 0;
+  std::vector<lh264_decoded_motion_t> motion_geo;
+  std::vector<uint8_t> mot, mbi;
+  uint8_t* mot_dev = nullptr; size_t mot_len = 0, mot_cap = 0;
+  uint8_t* mbi_dev = nullptr; size_t mbi_len = 0, mbi_cap = 0;
   lh264_decoded() { lh264sha1::init (&stream_state); memset (stream_sha, 0, 20); }
   ~lh264_decoded() {
-    if (!dev) return;
+    if (!dev && !mot_dev && !mbi_dev) return;
     int cur = 0;
     hipGetDevice (&cur);
     if (cur != device) hipSetDevice (device);
-    hipFree (dev);
+    if (dev) hipFree (dev);
+    if (mot_dev) hipFree (mot_dev);
+    if (mbi_dev) hipFree (mbi_dev);
     if (cur != device) hipSetDevice (cur);
   }
 };
@@ -970,6 +1097,9 @@ struct Arena {
   PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
   DevBuf d_std; PinBuf h_std[2];      // lh264_decode_batch_ex with colour: the standard byte of every pack job, beside d_pack
   DevBuf d_place; PinBuf h_place[2];  // lh264_decode_batch_ex3 with LH264_FIT_CONTAIN: the place of every pack job, beside d_pack
+  // lh264_decode_batch_ex4 with fields: the round's motion jobs, its motion blocks and macroblock blocks (downloaded like d_out)
+  DevBuf d_mjobs, d_mot[2], d_mbi[2]; PinBuf h_mjobs[2], h_mot[2], h_mbi[2];
+  hipEvent_t e_mot[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // around the round's decode_pack_motion_kernel launch (created on first use)
   // digests: the span jobs, a round's results (20 bytes per picture, then a copy of every chain's stream record), the records of the
   // picture messages (scratch), and one record per stream of the batch that lives as long as the call
   DevBuf d_sjobs, d_dig, d_rec, d_state;
@@ -990,18 +1120,18 @@ struct Arena {
     return ok;
   }
   ~Arena() {
-    for (int b = 0; b < 2; b++) { if (e_run[b]) hipEventDestroy (e_run[b]); if (e_down[b]) hipEventDestroy (e_down[b]); }
+    for (int b = 0; b < 2; b++) { if (e_run[b]) hipEventDestroy (e_run[b]); if (e_down[b]) hipEventDestroy (e_down[b]); for (int k = 0; k < 2; k++) if (e_mot[b][k]) hipEventDestroy (e_mot[b][k]); }
     if (s_run) hipStreamDestroy (s_run);
     if (s_down) hipStreamDestroy (s_down);
   }
   size_t device_bytes() const {
-    size_t n = pics.bytes + d_out[0].cap + d_out[1].cap;
+    size_t n = pics.bytes + d_out[0].cap + d_out[1].cap + d_mjobs.cap + d_mot[0].cap + d_mot[1].cap + d_mbi[0].cap + d_mbi[1].cap;
     for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef, &d_std, &d_place}) n += b->cap;
     return n;
   }
   size_t pinned_bytes() const {
     size_t n = h_pbytes.cap + h_ptasks.cap + h_pres.cap;
-    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap + h_std[b].cap + h_place[b].cap;
+    for (int b = 0; b < 2; b++) n += h_mbs[b].cap + h_sparse[b].cap + h_sl[b].cap + h_jobs[b].cap + h_first[b].cap + h_pack[b].cap + h_out[b].cap + h_sjobs[b].cap + h_dig[b].cap + h_std[b].cap + h_place[b].cap + h_mjobs[b].cap + h_mot[b].cap + h_mbi[b].cap;
     return n;
   }
 };
@@ -1021,10 +1151,12 @@ struct DStream {
   long seen = 0;                                     // the pictures the parser has handed over so far (opts->pick: selected or not)
   long delivered = 0;                                // ... those of them that are handed out (a frozen picture is reconstructed only)
   uint64_t out_off = 0;                              // ... and their packed bytes
+  uint64_t mot_off = 0, mbi_off = 0;                 // ... and with fields their motion blocks' and macroblock blocks' bytes
   size_t pic_mbs = 0;                                // macroblocks of the stream's last picture (0: none seen yet)
   Geo geo;
   const uint8_t* grey = nullptr;                     // the arena's 128 picture of this geometry
   std::vector<Slot> pool;
+  std::map<int, long> held;                          // fields: id -> index of the pictures the pool holds (kept where no pool is used)
   // set by select(): the stream ends behind the pictures selected
   bool ending = false; int end_code = LH264_OK; std::string end_text;
   bool sha_started = false;                          // the stream's digest record on the device holds its message so far
@@ -1046,8 +1178,10 @@ struct RoundChain {
   std::vector<uint8_t> colour;                      // lh264_decode_batch_ex with colour: per delivered picture its standard byte
   size_t at = 0, bytes = 0;                          // in the round's output buffer
   size_t n_out = 0, dig0 = 0;                        // pictures the chain delivers; the first one's place among the round's digests
+  std::vector<lh264_decoded_motion_t> motion_geo;    // fields: per delivered picture; the chain's blocks in the round's two buffers
+  size_t mot_at = 0, mot_bytes = 0, mbi_at = 0, mbi_bytes = 0, mjob0 = 0;
 };
-struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0, dig_states_at = 0; bool live = false; };
+struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0, dig_states_at = 0, mot_bytes = 0, mbi_bytes = 0; bool live = false, timed = false; };
 
 // opts->pick: is the picture one of those the call decodes?  (slice_type: 0 P, 2 I)
 bool picture_selected (const FrameOut& f, uint32_t pick) {
@@ -1111,6 +1245,7 @@ void view_of (int w, int h, const lh264_rect_t& crop, uint32_t fit, int s, int o
 
 lh264host::PerDevice<Arena> g_arena;     // one decode call at a time per device
 double g_timing[6] = {0, 0, 0, 0, 0, 0};
+double g_motion_ms = 0; unsigned long long g_motion_bytes = 0;      // lh264_decode_last_motion
 long long g_chains[3] = {0, 0, 0};      // rounds, chains and jobs of the last call's lh264_recon_chains launches
 double g_parse_timing[2] = {0, 0};      // of g_timing[1]: the device parse stage (tasks, upload, slice_parse_kernel, results), and its slices
 
@@ -1318,6 +1453,39 @@ int lh264_debug_view_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t
   return ok ? LH264_OK : LH264_E_HIP;
 }
 
+int lh264_debug_motion_cpu (const lh264_motion_job_t* jobs, int n) {
+  if (!jobs || n < 0) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) if (!lh264pack::motion_job_ok (jobs[k])) return LH264_E_ARG;
+  for (int k = 0; k < n; k++) {
+    const lh264_motion_job_t& j = jobs[k];
+    for (int row = 0; row < j.mb_h; row++) for (int c0 = 0; c0 < j.mb_w; c0 += lh264pack::kMotionChunkMbs) {
+      const lh264_mb_t* base = j.mbs + (size_t)row * j.mb_w + c0;
+      uint32_t w[32];
+      lh264pack::motion_chunk (j, j.back, row, c0, std::min (lh264pack::kMotionChunkMbs, j.mb_w - c0), [&] (int m) { memcpy (w, base + m, sizeof (w)); return (const uint32_t*)w; }, 0, 1);
+    }
+  }
+  return LH264_OK;
+}
+
+int lh264_debug_motion_dev (const lh264_motion_job_t* jobs, int n) {
+  if (!jobs || n < 0) return LH264_E_ARG;
+  int units = 0;
+  for (int k = 0; k < n; k++) {
+    if (!lh264pack::motion_job_ok (jobs[k]) || ((uintptr_t)jobs[k].mbs & 15u)) return LH264_E_ARG;
+    units = std::max (units, jobs[k].mb_h * lh264pack::motion_chunks (jobs[k].mb_w));
+  }
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  if (!n) return LH264_OK;
+  lh264_motion_job_t* d_jobs = nullptr;
+  bool ok = hipMalloc ((void**)&d_jobs, (size_t)n * sizeof (lh264_motion_job_t)) == hipSuccess && hipMemcpy (d_jobs, jobs, (size_t)n * sizeof (lh264_motion_job_t), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL (decode_pack_motion_kernel, dim3 ((unsigned)n, (unsigned)units), dim3 (256), 0, 0, d_jobs);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize (nullptr) == hipSuccess;
+  }
+  hipFree (d_jobs);
+  return ok ? LH264_OK : LH264_E_HIP;
+}
+
 int lh264_debug_sha1 (const uint8_t* bytes, const uint64_t* spans, int n_spans, int n_messages, int on_device, uint8_t* out) {
   if (!out || n_spans < 0 || n_messages < 0 || (n_spans && (!spans || !bytes))) return LH264_E_ARG;
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> of ((size_t)n_messages);
@@ -1381,7 +1549,14 @@ int lh264_decode_batch_ex2 (const uint8_t* const* data, const size_t* len, int n
 }
 
 int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex4 (data, len, n, threads, opts, ext, sample, view, nullptr, out);
+}
+
+int lh264_decode_batch_ex4 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
+  if (motion && (motion->struct_bytes != sizeof (lh264_decode_motion_t) || motion->fields > LH264_MOTION_FIELDS || motion->reserved0 != 0 || motion->reserved1 != 0)) return LH264_E_ARG;
+  // 0: the call is lh264_decode_batch_ex3; else decode_pack_motion_kernel gathers the round's records in front of the reconstruct launch
+  const uint32_t fields = motion ? motion->fields : 0;
   if (view && (view->struct_bytes != sizeof (lh264_decode_view_t) || view->fit > LH264_FIT_CONTAIN || view->reserved0 != 0 || view->reserved1 != 0 ||
                (view->fill && (view->fit != LH264_FIT_CONTAIN || view->fill >> 24)) || (view->n_crops != 0 && view->n_crops != 1 && view->n_crops != (uint32_t)n) ||
                (view->n_crops != 0 && !view->crops))) return LH264_E_ARG;
@@ -1407,7 +1582,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
   if (opts && ((opts->struct_bytes != sizeof (lh264_decode_opts_t) && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V5 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V4 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V3 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V2 && opts->struct_bytes != LH264_DECODE_OPTS_BYTES_V1) || opts->format > LH264_FMT_NV12 ||
                (opts->flags & ~ (LH264_DECODE_DEVICE_OUT | LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES)) ||
                (opts->sink && (opts->flags & LH264_DECODE_DEVICE_OUT)) ||
-               ((opts->flags & LH264_DECODE_NO_PICTURES) && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT) || opts->sink)))) return LH264_E_ARG;
+               ((opts->flags & LH264_DECODE_NO_PICTURES) && ((!fields && (!(opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM)) || (opts->flags & LH264_DECODE_DEVICE_OUT))) || opts->sink)))) return LH264_E_ARG;
   const int conceal = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V2 ? (int)opts->conceal : 0;
   const uint32_t parse = opts && opts->struct_bytes >= LH264_DECODE_OPTS_BYTES_V3 ? opts->parse : LH264_PARSE_HOST;
   if (parse != LH264_PARSE_HOST && parse != LH264_PARSE_DEVICE) return LH264_E_ARG;
@@ -1433,6 +1608,9 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
   const bool no_pictures = opts && (opts->flags & LH264_DECODE_NO_PICTURES);          // digests only: nothing is downloaded or kept
   const bool sha_pics = opts && (opts->flags & LH264_DECODE_SHA1_PICTURES), sha_stream = opts && (opts->flags & LH264_DECODE_SHA1_STREAM);
   const bool sha = sha_pics || sha_stream;
+  const bool motion_only = fields && no_pictures && !sha;      // no picture pool, no reconstruct, pack or digest kernel
+  const bool down = !device_out && (!no_pictures || fields);   // the round has bytes to bring down on the second stream
+  double motion_ms = 0; unsigned long long motion_bytes = 0;   // lh264_decode_last_motion
   const lh264_decode_sink_fn sink = opts ? opts->sink : nullptr;
   void* const sink_user = opts ? opts->user : nullptr;
   const size_t R = opts && opts->round_pictures ? opts->round_pictures : kDefaultRoundPictures;
@@ -1441,7 +1619,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
   if (threads < 1) threads = 1;
   int device = 0;
   if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
-  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sample_type = stype; out[i]->sha = opts ? opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM) : 0; }
+  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sample_type = stype; out[i]->fields = fields; out[i]->sha = opts ? opts->flags & (LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM) : 0; }
   auto arena_lock = g_arena.lock (device);
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
@@ -1545,7 +1723,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     if (!rd.live) return;
     rd.live = false;
     const double t0 = now_s();
-    if (!device_failed && hipEventSynchronize (device_out || no_pictures ? A.e_run[b] : A.e_down[b]) != hipSuccess) fail_device ("the device stage failed");
+    if (!device_failed && hipEventSynchronize (down ? A.e_down[b] : A.e_run[b]) != hipSuccess) fail_device ("the device stage failed");
     const double t1 = now_s();
     t_wait += t1 - t0;
     if (device_failed) {
@@ -1553,6 +1731,15 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
       return;
     }
     const uint8_t* hb = A.h_out[b].as<uint8_t>();
+    if (rd.timed) { float ms = 0; if (hipEventElapsedTime (&ms, A.e_mot[b][0], A.e_mot[b][1]) == hipSuccess) motion_ms += ms; motion_bytes += rd.mot_bytes + rd.mbi_bytes; }
+    // the round's fields: geometry per picture, and in host mode the chain's blocks behind what the handle holds
+    auto take_fields = [&] (RoundChain& c, lh264_decoded_t& r) {
+      r.motion_geo.insert (r.motion_geo.end(), c.motion_geo.begin(), c.motion_geo.end());
+      if (device_out) return;
+      const uint8_t* hm = A.h_mot[b].as<uint8_t>(); const uint8_t* hi = A.h_mbi[b].as<uint8_t>();
+      r.mot.insert (r.mot.end(), hm + c.mot_at, hm + c.mot_at + c.mot_bytes);
+      r.mbi.insert (r.mbi.end(), hi + c.mbi_at, hi + c.mbi_at + c.mbi_bytes);
+    };
     // the round's digests came down on the run stream, in front of the event: the pictures' 20 bytes, and the stream's record as this
     // round leaves it (a stream's digest covers the rounds that were delivered, whatever is on the device behind them)
     const uint8_t* hd = A.h_dig[b].as<uint8_t>();
@@ -1577,6 +1764,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, (int)k);
+        if (fields) take_fields (c, r);
       }
     } else {
       run_parallel ((int)rd.chains.size(), threads, [&] (int k) {
@@ -1591,6 +1779,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
         r.index.insert (r.index.end(), c.index.begin(), c.index.end());
         r.colour.insert (r.colour.end(), c.colour.begin(), c.colour.end());
         if (sha) take_digests (c, r, k);
+        if (fields) take_fields (c, r);
       });
     }
     t_deliver += now_s() - t1;
@@ -1771,7 +1960,8 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     // ---- the round: which streams fit, where their records and bytes go, which picture slots they take
     // (the buffers `rb` were last used by the round before the one that is on the device now: it has been delivered)
     Round& rd = rounds[rb];
-    rd.chains.clear(); rd.out_bytes = 0;
+    rd.chains.clear(); rd.out_bytes = 0; rd.mot_bytes = 0; rd.mbi_bytes = 0; rd.timed = false;
+    size_t n_mjobs = 0; int max_units = 1;      // fields: the round's motion jobs (its delivered pictures), the most chunks of one of them
     struct Place { size_t mb0, sl0, sp0, job0; };
     std::vector<Place> place;
     size_t n_mbs = 0, n_hmbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0;      // n_hmbs: the macroblocks whose records the host stages (not those in the parse arena)
@@ -1792,6 +1982,13 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
       RoundChain c;
       c.s = &s; c.first_picture = (int)s.delivered; c.at = rd.out_bytes; c.bytes = bytes; c.n_out = shown; c.dig0 = n_out;
       n_out += shown;
+      if (fields) {
+        size_t shown_mbs = 0;
+        for (auto& f : s.sel) if (!f->frozen) { shown_mbs += (size_t)f->mb_w * f->mb_h; max_units = std::max (max_units, f->mb_h * lh264pack::motion_chunks (f->mb_w)); }
+        c.mjob0 = n_mjobs; n_mjobs += shown;
+        c.mot_at = rd.mot_bytes; c.mot_bytes = shown_mbs * 96; rd.mot_bytes += (c.mot_bytes + 15) & ~ (size_t)15;
+        c.mbi_at = rd.mbi_bytes; c.mbi_bytes = shown_mbs * 8; rd.mbi_bytes += (c.mbi_bytes + 15) & ~ (size_t)15;
+      }
       place.push_back ({n_hmbs, n_sl, n_sp, n_jobs});
       n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       // a float type: every picture, and so every row, begins at a multiple of 4 bytes - the chain at one of 16, a picture 3*ow*oh*es
@@ -1811,13 +2008,16 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     // it references nothing, so the stream spreads over as many workgroups as it has pictures in the round.  (Delivery and the
     // stream's digest follow rd.chains, the streams, in both cases)
     const int n_launch = picking ? (int)n_jobs : n_chains;
-    alloc_ok = A.d_mbs.alloc (n_hmbs * sizeof (lh264_mb_t)) && A.d_coef.alloc (n_hmbs * 768) && A.d_sparse.alloc (n_sp * 8) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
+    alloc_ok = A.d_mbs.alloc (n_hmbs * sizeof (lh264_mb_t)) && (motion_only || (A.d_coef.alloc (n_hmbs * 768) && A.d_sparse.alloc (n_sp * 8))) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_launch + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
-               A.d_out[rb].alloc (rd.out_bytes) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
+               (motion_only || A.d_out[rb].alloc (rd.out_bytes)) && (device_out || no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
                A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                (!colour || (A.d_std.alloc (n_jobs) && A.h_std[rb].alloc (n_jobs))) &&
                (!placed || (A.d_place.alloc (n_jobs * sizeof (lh264_pack_place_t)) && A.h_place[rb].alloc (n_jobs * sizeof (lh264_pack_place_t))));
+    if (fields) alloc_ok = alloc_ok && A.d_mjobs.alloc (n_mjobs * sizeof (lh264_motion_job_t)) && A.h_mjobs[rb].alloc (n_mjobs * sizeof (lh264_motion_job_t)) &&
+                             A.d_mot[rb].alloc (rd.mot_bytes) && A.d_mbi[rb].alloc (rd.mbi_bytes) && (device_out || (A.h_mot[rb].alloc (rd.mot_bytes) && A.h_mbi[rb].alloc (rd.mbi_bytes)));
+    for (int k = 0; k < 2 && fields && alloc_ok; k++) if (!A.e_mot[rb][k]) alloc_ok = hipEventCreate (&A.e_mot[rb][k]) == hipSuccess;
     const size_t n_sjobs = (sha_pics ? n_out : 0) + (sha_stream ? (size_t)n_chains : 0);
     rd.dig_states_at = (n_out * 20 + 15) & ~ (size_t)15;
     const size_t dig_bytes = rd.dig_states_at + (size_t)n_chains * sizeof (lh264_sha1_state_t);
@@ -1826,7 +2026,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     // picture slots (serial: the cache is shared).  A picture takes a slot that was free when the round began; a slot becomes free
     // behind the round when its picture is in no DPB any more - the round's pictures are all packed by then
     std::vector<std::vector<int>> slot_of (n_chains);
-    for (int c = 0; c < n_chains && alloc_ok && offsets_ok; c++) {
+    for (int c = 0; c < n_chains && alloc_ok && offsets_ok && !motion_only; c++) {
       DStream& s = *rd.chains[c].s;
       s.grey = A.pics.grey (s.geo.bytes, A.s_run);
       if (!s.grey) { alloc_ok = false; break; }
@@ -1850,6 +2050,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     uint8_t* h_std = colour ? A.h_std[rb].as<uint8_t>() : nullptr;
     lh264_pack_place_t* h_place = placed ? A.h_place[rb].as<lh264_pack_place_t>() : nullptr;
     uint8_t* const d_out = A.d_out[rb].as<uint8_t>();
+    lh264_motion_job_t* h_mjobs = fields ? A.h_mjobs[rb].as<lh264_motion_job_t>() : nullptr;
     run_parallel (n_chains, threads, [&] (int c) {
       RoundChain& rc = rd.chains[c];
       DStream& s = *rc.s;
@@ -1863,15 +2064,26 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
         const bool on_dev = dev_it != s.dev_at.end();
         if (!on_dev) memcpy (&h_mbs[mo], f.mbs.data(), nm * sizeof (lh264_mb_t));
         memcpy (&h_sl[so], f.slices.data(), f.slices.size() * sizeof (lh264_slice_t));
-        { const uint64_t add = (uint64_t) (mo * 384) << 16; const size_t ns = f.sparse_coeffs.size(); for (size_t e = 0; e < ns; e++) h_sparse[po + e] = f.sparse_coeffs[e] + add; po += ns; }
-        const Slot& me = s.pool[slot_of[c][q]];
+        if (!motion_only) { const uint64_t add = (uint64_t) (mo * 384) << 16; const size_t ns = f.sparse_coeffs.size(); for (size_t e = 0; e < ns; e++) h_sparse[po + e] = f.sparse_coeffs[e] + add; po += ns; }
+        const Slot me = motion_only ? Slot {nullptr, -1} : s.pool[slot_of[c][q]];
         auto pic_at = [&] (const uint8_t* base) { lh264_pic_t p; p.y_dev = (uint8_t*)base + s.geo.off[0]; p.u_dev = (uint8_t*)base + s.geo.off[1]; p.v_dev = (uint8_t*)base + s.geo.off[2]; return p; };
         lh264_frame_job_t& jb = h_jobs[j];
         memset (&jb, 0, sizeof (jb));
         jb.mbs_dev = on_dev ? A.d_pmbs.as<lh264_mb_t>() + dev_it->second.mb : A.d_mbs.as<lh264_mb_t>() + mo;
         jb.coeffs_dev = on_dev ? A.d_pcoef.as<int16_t>() + dev_it->second.mb * 384 : A.d_coef.as<int16_t>() + mo * 384; jb.slices_dev = A.d_sl.as<lh264_slice_t>() + so;
-        jb.dst = pic_at (me.base);
-        for (size_t k = 0; k < LH264_MAX_REFS; k++) {
+        if (!motion_only) jb.dst = pic_at (me.base);
+        // fields: back[slot], how many pictures back the picture behind job reference `slot` lies (-1: none, or one no longer held)
+        int16_t back[LH264_MAX_REFS];
+        if (fields) {
+          for (size_t k = 0; k < LH264_MAX_REFS; k++) {
+            back[k] = -1;
+            if (picking || k >= f.ref_ids.size() || f.ref_ids[k] == f.id) continue;
+            const auto it = s.held.find (f.ref_ids[k]);
+            if (it != s.held.end() && f.index - it->second <= 32767) back[k] = (int16_t) (f.index - it->second);
+          }
+          s.held[f.id] = f.index;
+        }
+        for (size_t k = 0; k < LH264_MAX_REFS && !motion_only; k++) {
           // A slot the picture does not fill, or whose picture is not held, points at the 128 picture.  recon_chain_kernel reads job slot
           // 0 for a partition whose slice has no reference list entry (a P picture whose references are lost); the oracle predicts nothing
           // there and leaves its fresh picture's 128: the same samples.  The picture itself in that slot (what the ISVC object does) would
@@ -1908,6 +2120,17 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
         rc.source_wh.push_back (f.crop_w); rc.source_wh.push_back (f.crop_h);
         rc.index.push_back ((int32_t)f.index);
         if (colour) rc.colour.push_back (std_byte);
+        if (fields) {
+          size_t mot_off = 0, mbi_off = 0;
+          for (const lh264_decoded_motion_t& g : rc.motion_geo) { mot_off += (size_t)g.mb_w * g.mb_h * 96; mbi_off += (size_t)g.mb_w * g.mb_h * 8; }
+          lh264_motion_job_t& mj = h_mjobs[rc.mjob0 + rc.motion_geo.size()];
+          memset (&mj, 0, sizeof (mj));
+          mj.mbs = jb.mbs_dev; mj.slices = jb.slices_dev;
+          mj.motion = (int16_t*) (A.d_mot[rb].as<uint8_t>() + rc.mot_at + mot_off); mj.info = A.d_mbi[rb].as<uint8_t>() + rc.mbi_at + mbi_off;
+          mj.mb_w = f.mb_w; mj.mb_h = f.mb_h; mj.n_slices = (int32_t)f.slices.size();
+          memcpy (mj.back, back, sizeof (back));
+          rc.motion_geo.push_back ({f.mb_w, f.mb_h, f.crop_x, f.crop_y, s.mot_off + mot_off, s.mbi_off + mbi_off});
+        }
         at += bytes; off += bytes;
         if (!on_dev) mo += nm;
         so += f.slices.size(); j++;
@@ -1943,6 +2166,9 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
       s.next_picture += (long)s.sel.size();
       s.delivered += (long)rd.chains[c].pics.size();
       s.out_off += rd.chains[c].bytes;
+      s.mot_off += rd.chains[c].mot_bytes; s.mbi_off += rd.chains[c].mbi_bytes;
+      // (fields: the pictures whose slots are free now are no reference any more)
+      if (fields) for (auto it = s.held.begin(); it != s.held.end(); ) { if (picking || std::find (dpb.begin(), dpb.end(), it->first) == dpb.end()) it = s.held.erase (it); else ++it; }
       s.sel.clear();                                  // the pictures' records are staged: their memory goes back
     }
     const double t_c = now_s();
@@ -1951,13 +2177,24 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
     {
       hipStream_t st = A.s_run;
       auto up = [&] (DevBuf& d, const void* s, size_t bytes) { return bytes == 0 || hipMemcpyAsync (d.p, s, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
-      bool ok = up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
+      // (motion only: the records and the slice tables are all the gather reads)
+      bool ok = motion_only ? up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) :
+                up (A.d_mbs, h_mbs, n_hmbs * sizeof (lh264_mb_t)) && up (A.d_sparse, h_sparse, n_sp * 8) && up (A.d_sl, h_sl, n_sl * sizeof (lh264_slice_t)) &&
                 up (A.d_jobs, h_jobs, n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, h_first, (size_t) (n_launch + 1) * 4) && up (A.d_pack, h_pack, n_jobs * sizeof (lh264_pack_job_t)) && (!colour || up (A.d_std, h_std, n_jobs)) && (!placed || up (A.d_place, h_place, n_jobs * sizeof (lh264_pack_place_t))) &&
                 (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess);
-      if (ok && n_sp) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
-      if (ok) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
-      if (ok) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
-      if (ok) {
+      // the fields need the records only: the gather goes in front of the reconstruct launch
+      if (ok && n_mjobs) {
+        ok = up (A.d_mjobs, h_mjobs, n_mjobs * sizeof (lh264_motion_job_t)) && hipEventRecord (A.e_mot[rb][0], st) == hipSuccess;
+        if (ok) {
+          hipLaunchKernelGGL (decode_pack_motion_kernel, dim3 ((unsigned)n_mjobs, (unsigned)max_units), dim3 (256), 0, st, A.d_mjobs.as<lh264_motion_job_t>());
+          ok = hipGetLastError() == hipSuccess && hipEventRecord (A.e_mot[rb][1], st) == hipSuccess;
+          rd.timed = ok;
+        }
+      }
+      if (ok && n_sp && !motion_only) { lh264host::expand_sparse (A.d_sparse.as<uint64_t>(), n_sp, A.d_coef.as<int16_t>(), st); ok = hipGetLastError() == hipSuccess; }
+      if (ok && !motion_only) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
+      if (ok && !motion_only) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
+      if (ok && !motion_only) {
         if (placed) {
           const lh264_pack_place_t* d_place = A.d_place.as<lh264_pack_place_t>();
           if (stype) hipLaunchKernelGGL (decode_pack_sample_placed_kernel, dim3 ((unsigned)n_jobs, (unsigned)max_bands), dim3 (256), 0, st, A.d_pack.as<lh264_pack_job_t>(), d_place, A.d_std.as<uint8_t>(), out_w, out_h, colour, sample_arg);
@@ -1976,26 +2213,39 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
         if (ok && n_sjobs) { hipLaunchKernelGGL (sha1_spans_kernel, dim3 ((unsigned) ((n_sjobs + 63) / 64)), dim3 (64), 0, st, A.d_sjobs.as<lh264_sha1_job_t>(), (int)n_sjobs); ok = hipGetLastError() == hipSuccess; }
         ok = ok && hipMemcpyAsync (A.h_dig[rb].p, A.d_dig.p, dig_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
       }
-      if (ok && device_out) {
-        // the pictures stay on the device: every stream's run goes behind what its handle holds (the buffer grows by doubling)
+      // bytes that stay on the device go behind what the handle holds (the buffer grows by doubling)
+      auto keep_dev = [&] (uint8_t*& dev, size_t& dev_len, size_t& dev_cap, const uint8_t* src, size_t bytes) {
+        if (dev_len + bytes > dev_cap) {
+          const size_t cap = std::max<size_t> (4 * (dev_len + bytes), (size_t)1 << 16);
+          uint8_t* p = nullptr;
+          if (hipMalloc ((void**)&p, cap) != hipSuccess) return false;
+          if (dev_len && hipMemcpyAsync (p, dev, dev_len, hipMemcpyDeviceToDevice, st) != hipSuccess) { hipFree (p); return false; }
+          if (dev) { hipStreamSynchronize (st); hipFree (dev); }
+          dev = p; dev_cap = cap;
+        }
+        if (hipMemcpyAsync (dev + dev_len, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+        dev_len += bytes;
+        return true;
+      };
+      if (ok && device_out && fields) for (RoundChain& c : rd.chains) {
+        lh264_decoded_t& r = *out[c.s->i];
+        if (!c.mot_bytes) continue;
+        if (!keep_dev (r.mot_dev, r.mot_len, r.mot_cap, A.d_mot[rb].as<uint8_t>() + c.mot_at, c.mot_bytes) ||
+            !keep_dev (r.mbi_dev, r.mbi_len, r.mbi_cap, A.d_mbi[rb].as<uint8_t>() + c.mbi_at, c.mbi_bytes)) { ok = false; break; }
+      }
+      if (ok && device_out && !no_pictures) {
+        // the pictures stay on the device: every stream's run goes behind what its handle holds
         for (RoundChain& c : rd.chains) {
           lh264_decoded_t& r = *out[c.s->i];
           if (!c.bytes) continue;                   // (every picture of the chain withheld)
-          if (r.dev_len + c.bytes > r.dev_cap) {
-            const size_t cap = std::max<size_t> (4 * (r.dev_len + c.bytes), (size_t)1 << 16);
-            uint8_t* p = nullptr;
-            if (hipMalloc ((void**)&p, cap) != hipSuccess) { ok = false; break; }
-            if (r.dev_len && hipMemcpyAsync (p, r.dev, r.dev_len, hipMemcpyDeviceToDevice, st) != hipSuccess) { hipFree (p); ok = false; break; }
-            if (r.dev) { hipStreamSynchronize (st); hipFree (r.dev); }
-            r.dev = p; r.dev_cap = cap;
-          }
-          if (hipMemcpyAsync (r.dev + r.dev_len, d_out + c.at, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) { ok = false; break; }
-          r.dev_len += c.bytes;
+          if (!keep_dev (r.dev, r.dev_len, r.dev_cap, d_out + c.at, c.bytes)) { ok = false; break; }
         }
       }
       ok = ok && hipEventRecord (A.e_run[rb], st) == hipSuccess;
-      if (ok && !device_out && !no_pictures) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
-                                  (!rd.out_bytes || hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess) &&
+      if (ok && down) ok = hipStreamWaitEvent (A.s_down, A.e_run[rb], 0) == hipSuccess &&
+                                  (no_pictures || !rd.out_bytes || hipMemcpyAsync (A.h_out[rb].p, d_out, rd.out_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess) &&
+                                  (!fields || !rd.mot_bytes || (hipMemcpyAsync (A.h_mot[rb].p, A.d_mot[rb].p, rd.mot_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess &&
+                                                                hipMemcpyAsync (A.h_mbi[rb].p, A.d_mbi[rb].p, rd.mbi_bytes, hipMemcpyDeviceToHost, A.s_down) == hipSuccess)) &&
                                   hipEventRecord (A.e_down[rb], A.s_down) == hipSuccess;
       if (!ok) { const char* le = lh264_last_error(); fail_device (std::string ("launching the device stage failed") + (le && *le ? std::string (": ") + le : std::string())); for (RoundChain& c : rd.chains) c.s->stopped = true; }
       else rd.live = true;
@@ -2016,6 +2266,7 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
   if (device_failed) for (int i = next_stream; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = device_error; }
   g_timing[0] = (now_s() - t_call) * 1e3; g_timing[1] = t_parse * 1e3; g_timing[2] = t_stage * 1e3; g_timing[3] = t_enqueue * 1e3; g_timing[4] = t_wait * 1e3; g_timing[5] = t_deliver * 1e3;
   g_parse_timing[0] = t_dev_parse * 1e3; g_parse_timing[1] = n_dev_slices;
+  g_motion_ms = motion_ms; g_motion_bytes = motion_bytes;
   g_chains[0] = n_rounds; g_chains[1] = n_launched; g_chains[2] = n_launched_jobs;
   if (trace_on()) fprintf (stderr, "[lh264 decode] %d streams: %.3f s (parse %.3f, staging %.3f, enqueue %.3f, waiting for the device %.3f, delivery %.3f); arena %.1f MB device, %.1f MB pinned\n",
                            n, g_timing[0] / 1e3, t_parse, t_stage, t_enqueue, t_wait, t_deliver, A.device_bytes() / 1e6, A.pinned_bytes() / 1e6);
@@ -2144,6 +2395,38 @@ int lh264_parser_window (const uint8_t* data, size_t len, int32_t* width, int32_
   if (!Parser::first_sps_window (data, len, &w, &h)) return LH264_E_UNSUPPORTED;
   if (width) *width = w;
   if (height) *height = h;
+  return LH264_OK;
+}
+int lh264_decoded_picture_motion (const lh264_decoded_t* d, int idx, lh264_decoded_motion_t* o) {
+  if (!d || !o || !d->fields || idx < 0 || (size_t)idx >= d->pics.size() || d->motion_geo.size() != d->pics.size()) return LH264_E_ARG;
+  *o = d->motion_geo[idx];
+  return LH264_OK;
+}
+int lh264_decoded_motion (const lh264_decoded_t* d, const int16_t** motion, size_t* motion_bytes, const uint8_t** info, size_t* info_bytes) {
+  if (!d || !d->fields) return LH264_E_ARG;
+  if (motion) *motion = d->mot.empty() ? nullptr : (const int16_t*)d->mot.data();
+  if (motion_bytes) *motion_bytes = d->mot.size();
+  if (info) *info = d->mbi.empty() ? nullptr : d->mbi.data();
+  if (info_bytes) *info_bytes = d->mbi.size();
+  return LH264_OK;
+}
+int lh264_decoded_motion_dev (const lh264_decoded_t* d, const int16_t** motion, size_t* motion_bytes, const uint8_t** info, size_t* info_bytes) {
+  if (!d || !d->fields) return LH264_E_ARG;
+  if (motion) *motion = (const int16_t*)d->mot_dev;
+  if (motion_bytes) *motion_bytes = d->mot_len;
+  if (info) *info = d->mbi_dev;
+  if (info_bytes) *info_bytes = d->mbi_len;
+  return LH264_OK;
+}
+int lh264_decoded_motion_copy_dev (const lh264_decoded_t* d, void* motion_dst_dev, size_t motion_cap, void* info_dst_dev, size_t info_cap) {
+  if (!d || !d->fields || (motion_dst_dev && motion_cap < d->mot_len) || (info_dst_dev && info_cap < d->mbi_len)) return LH264_E_ARG;
+  if (motion_dst_dev && d->mot_len && hipMemcpy (motion_dst_dev, d->mot_dev, d->mot_len, hipMemcpyDeviceToDevice) != hipSuccess) return LH264_E_HIP;
+  if (info_dst_dev && d->mbi_len && hipMemcpy (info_dst_dev, d->mbi_dev, d->mbi_len, hipMemcpyDeviceToDevice) != hipSuccess) return LH264_E_HIP;
+  return LH264_OK;
+}
+int lh264_decode_last_motion (double* ms, unsigned long long* bytes) {
+  if (ms) *ms = g_motion_ms;
+  if (bytes) *bytes = g_motion_bytes;
   return LH264_OK;
 }
 int lh264_decoded_concealed (const lh264_decoded_t* d, int idx) {

@@ -22,8 +22,9 @@ class _DevSpan:
 class DecodedBatch:
     """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
 
-    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None, dtype="uint8", affine=None):
+    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None, dtype="uint8", affine=None, motion=False):
         self._lib, self._h, self.device_out, self._keep, self.size, self.colour = lib, handles, device_out, sink_keepalive, size, colour
+        self.has_motion = bool(motion)
         # dtype: the dtype= of the call; affine: the six binary32 values it passed, ((mul R, G, B), (add R, G, B)), None with "uint8"
         self.dtype, self.affine = dtype, affine
 
@@ -169,6 +170,96 @@ class DecodedBatch:
             return t.view(t.numel() // (w * h * 3), 3, h, w)
         return t.view(t.numel() // (w * h * 3 // 2), h * 3 // 2, w)      # (a stream that delivered nothing: 0 pictures)
 
+    def motion_geometry(self, i):
+        """motion=True: [(mb_w, mb_h, crop_x, crop_y, motion_offset, info_offset)] per delivered picture of stream i: the coded picture in
+        macroblocks, where the delivered window begins in it (luma sample (x, y) of the window lies in cell ((crop_x + x) >> 2,
+        (crop_y + y) >> 2)), and the byte offsets of the picture's two blocks in the stream's two buffers"""
+        if not self.has_motion:
+            raise RuntimeError("decode_batch was not called with motion=True")
+        out = []
+        g = L.DecodedMotion()
+        for k in range(self._lib.lh264_decoded_pictures(self._h[i])):
+            L.check(self._lib.lh264_decoded_picture_motion(self._h[i], k, C.byref(g)))
+            out.append((g.mb_w, g.mb_h, g.crop_x, g.crop_y, int(g.motion_offset), int(g.info_offset)))
+        return out
+
+    def _field_buffers(self, i):
+        """stream i's two field buffers: numpy int16 / uint8 arrays (copies) on the host, torch views of the handle's device memory
+        (copies where torch refuses the interface) under device_out=True"""
+        if not self.has_motion:
+            raise RuntimeError("decode_batch was not called with motion=True")
+        mp, ip, mn, inn = C.c_void_p(0), C.c_void_p(0), C.c_size_t(0), C.c_size_t(0)
+        if not self.device_out:
+            L.check(self._lib.lh264_decoded_motion(self._h[i], C.byref(mp), C.byref(mn), C.byref(ip), C.byref(inn)))
+            mot = np.frombuffer(C.string_at(mp.value, mn.value), dtype="<i2") if mp.value and mn.value else np.zeros(0, "<i2")
+            mbi = np.frombuffer(C.string_at(ip.value, inn.value), dtype=np.uint8) if ip.value and inn.value else np.zeros(0, np.uint8)
+            return mot, mbi
+        import torch
+        L.check(self._lib.lh264_decoded_motion_dev(self._h[i], C.byref(mp), C.byref(mn), C.byref(ip), C.byref(inn)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if not mp.value or not mn.value:
+            return torch.empty(0, dtype=torch.int16, device=dev), torch.empty(0, dtype=torch.uint8, device=dev)
+        try:
+            mot = torch.as_tensor(_DevSpan(mp.value, mn.value, self), device=dev)
+            mbi = torch.as_tensor(_DevSpan(ip.value, inn.value, self), device=dev)
+        except (TypeError, RuntimeError, ValueError):
+            mot, mbi = self.motion_copy(i)
+        return mot.view(torch.int16), mbi
+
+    def motion_copy(self, i):
+        """motion=True with device_out=True: stream i's two field buffers copied device-to-device into fresh torch.uint8 tensors
+        (lh264_decoded_motion_copy_dev) -> (motion bytes, macroblock bytes)"""
+        import torch
+        if not self.has_motion or not self.device_out:
+            raise RuntimeError("motion_copy() needs decode_batch (motion=True, device_out=True)")
+        mn, inn = C.c_size_t(0), C.c_size_t(0)
+        L.check(self._lib.lh264_decoded_motion_dev(self._h[i], None, C.byref(mn), None, C.byref(inn)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        mot, mbi = torch.empty(mn.value, dtype=torch.uint8, device=dev), torch.empty(inn.value, dtype=torch.uint8, device=dev)
+        L.check(self._lib.lh264_decoded_motion_copy_dev(self._h[i], mot.data_ptr() if mn.value else None, mn.value, mbi.data_ptr() if inn.value else None, inn.value))
+        return mot, mbi
+
+    def _field_list(self, i, which):
+        mot, mbi = self._field_buffers(i)
+        out = []
+        for (mb_w, mb_h, _cx, _cy, mo, io) in self.motion_geometry(i):
+            if which == 0:
+                out.append(mot[mo // 2:mo // 2 + 48 * mb_w * mb_h].reshape(3, 4 * mb_h, 4 * mb_w))
+            else:
+                out.append(mbi[io:io + 8 * mb_w * mb_h].reshape(8, mb_h, mb_w))
+        return out
+
+    def motion(self, i):
+        """motion=True: per delivered picture of stream i a (3, 4 * mb_h, 4 * mb_w) int16 array over the CODED picture's 4x4 blocks -
+        [0] dx, [1] dy in quarter-pel (the final vectors, for P_Skip the inferred one), [2] how many pictures back in decode order the
+        block predicts from (-1: no decoded picture); all three 0 in intra and uncovered macroblocks.  numpy on the host, torch views of
+        the handle's device memory (valid until free()) under device_out=True.  The definition: include/lh264.h at lh264_decode_batch_ex4"""
+        return self._field_list(i, 0)
+
+    def mb_info(self, i):
+        """motion=True: per delivered picture of stream i an (8, mb_h, mb_w) uint8 array - [0] kind (0 not covered, 1 I4x4, 2 I8x8,
+        3 I16x16, 4 I_PCM, 5 P_Skip, 6 P16x16, 7 P16x8, 8 P8x16, 9 P8x8, 10 P8x8ref0), [1] qp_y, [2] cbp, [3] flags (bit 0 the 8x8
+        transform, bit 1 concealed), [4..7] the sub-macroblock types of kinds 9 and 10"""
+        return self._field_list(i, 1)
+
+    def _field_frames(self, i, which):
+        geo = self.motion_geometry(i)
+        if len({(g[0], g[1]) for g in geo}) > 1:
+            raise ValueError("stream %d changes its size: use motion(i) / mb_info(i)" % i)
+        mot, mbi = self._field_buffers(i)
+        mb_w, mb_h = (geo[0][0], geo[0][1]) if geo else (0, 0)
+        if which == 0:
+            return mot.reshape(len(geo), 3, 4 * mb_h, 4 * mb_w)
+        return mbi.reshape(len(geo), 8, mb_h, mb_w)
+
+    def motion_frames(self, i):
+        """motion=True: motion(i) as one (pictures, 3, 4 * mb_h, 4 * mb_w) array or device view; ValueError where the stream changes size"""
+        return self._field_frames(i, 0)
+
+    def mb_info_frames(self, i):
+        """motion=True: mb_info(i) as one (pictures, 8, mb_h, mb_w) array or device view; ValueError where the stream changes size"""
+        return self._field_frames(i, 1)
+
     def free(self):
         for h in self._h:
             self._lib.lh264_decoded_free(h)
@@ -181,7 +272,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=False):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -246,7 +337,13 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     rectangle of the size, every sample outside it fill = (y, cb, cr), default (16, 128, 128); with colour= a bar pixel is the conversion
     of the fill, with a float dtype its fma.  The rectangles are even and keep the aspect to the nearest even sample, not exactly:
     view_rects (w, h, crop, fit, size) is the rule (include/lh264.h at lh264_decode_batch_ex3), DecodedBatch.views(i) what was applied.
-    source_sizes keeps giving the windows; frames(i) keeps its shapes."""
+    source_sizes keeps giving the windows; frames(i) keeps its shapes.
+    motion: False | True: beside the pictures, which are delivered exactly as without it, every delivered picture's motion field and
+    macroblock data, gathered on the device from the records the parse left there (decode_pack_motion_kernel through
+    lh264_decode_batch_ex4): DecodedBatch.motion(i), mb_info(i), motion_frames(i), mb_info_frames(i), motion_geometry(i).  They cover
+    the coded picture, whatever scale, size, crop, fit, colour and dtype are.  With a sink the fields stay on the handles.
+    pictures=False with motion=True and no sha1 is the motion-only call: nothing is reconstructed, no picture pool is used; the
+    picture records are those of the digests-only call."""
     lib = L.lib()
     if not isinstance(dtype, str) or dtype not in L.SAMPLE:
         raise ValueError("dtype must be 'uint8', 'float32', 'float16' or 'bfloat16'")
@@ -299,8 +396,10 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise ValueError("sha1 must be None, 'pictures', 'stream' or 'both'")
     if parse not in L.PARSE_MODES:
         raise ValueError("parse must be 'host', 'device' or 'device+cabac'")
-    if not pictures and (sha1 is None or device_out or sink is not None):
-        raise ValueError("pictures=False needs sha1= and neither device_out nor a sink")
+    if not pictures and sink is not None:
+        raise ValueError("pictures=False excludes a sink")
+    if not pictures and not motion and (sha1 is None or device_out):
+        raise ValueError("pictures=False needs sha1= or motion=True, and device_out only with motion=True")
     n = len(datas)
     keep = [bytes(d) for d in datas]
     ptrs = (C.c_char_p * n)(*keep)
@@ -331,13 +430,15 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         cb = L.DECODE_SINK_FN(_cb)
         opts.sink = cb
     outs = (C.c_void_p * n)()
-    if fit != "stretch" or crops is not None:
-        # a view: every struct the call takes, the colour and sample ones where they are asked for
-        view = L.DecodeView()
-        view.struct_bytes, view.fit, view.fill = C.sizeof(L.DecodeView), L.FIT[fit], fill_word
-        if crops is not None:
-            rects = (L.Rect * len(crops))(*[L.Rect(*c) for c in crops])
-            view.n_crops, view.crops = len(crops), rects
+    if fit != "stretch" or crops is not None or motion:
+        # a view or the fields: every struct the call takes, the colour and sample ones where they are asked for
+        view = None
+        if fit != "stretch" or crops is not None:
+            view = L.DecodeView()
+            view.struct_bytes, view.fit, view.fill = C.sizeof(L.DecodeView), L.FIT[fit], fill_word
+            if crops is not None:
+                rects = (L.Rect * len(crops))(*[L.Rect(*c) for c in crops])
+                view.n_crops, view.crops = len(crops), rects
         ext = sm = None
         if colour is not None:
             ext = L.DecodeExt()
@@ -347,7 +448,13 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
             sm.struct_bytes, sm.type = C.sizeof(L.DecodeSample), L.SAMPLE[dtype]
             for k in range(3):
                 sm.mul[k], sm.add[k] = affine[0][k], affine[1][k]
-        rc = lib.lh264_decode_batch_ex3(ptrs, lens, n, threads, C.byref(opts), C.byref(ext) if ext is not None else None, C.byref(sm) if sm is not None else None, C.byref(view), outs)
+        ref = lambda st: C.byref(st) if st is not None else None
+        if motion:
+            mo = L.DecodeMotion()
+            mo.struct_bytes, mo.fields = C.sizeof(L.DecodeMotion), L.MOTION_FIELDS
+            rc = lib.lh264_decode_batch_ex4(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), C.byref(mo), outs)
+        else:
+            rc = lib.lh264_decode_batch_ex3(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), C.byref(view), outs)
     elif colour is None:
         rc = lib.lh264_decode_batch(ptrs, lens, n, threads, C.byref(opts), outs)
     else:
@@ -365,7 +472,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
-    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine, motion)
 
 
 def _rect(c):
@@ -451,11 +558,19 @@ def decode_arena_bytes():
 _SUFFIX = {"uint8": ".rgb", "float32": ".f32", "float16": ".f16", "bfloat16": ".bf16"}
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=0):
     """out_dir/<basename>.yuv - with colour= <basename>.rgb, with a float dtype= <basename>.f32 | .f16 | .bf16 - for every input, through one decode_batch with a sink that appends to the
-    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch"""
+    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch.
+    motion: 1: beside them <basename>.mv and <basename>.mbi, every stream's motion blocks and macroblock blocks as the handle holds them
+    (decode_batch (motion=True)); 2: those two and no picture file, through the motion-only call (path and bytes are then the .mv file's
+    and both files')"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
+    if motion == 2:
+        b = decode_batch(datas, fmt=fmt, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=True, pictures=False)
+        res = [_write_fields(b, i, os.path.join(out_dir, os.path.basename(p))) for i, p in enumerate(paths)]
+        b.free()
+        return res
     names = [os.path.join(out_dir, os.path.basename(p) + (".yuv" if colour is None else _SUFFIX.get(dtype, ".rgb"))) for p in paths]
     files = [open(q, "wb") for q in names]
     total = [0] * len(paths)
@@ -465,13 +580,26 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=bool(motion))
     finally:
         for f in files:
             f.close()
+    if motion:
+        for i, p in enumerate(paths):
+            _write_fields(b, i, os.path.join(out_dir, os.path.basename(p)))
     res = [(names[i], b.status(i), b.error(i), len(b.pictures(i)), total[i]) for i in range(len(paths))]
     b.free()
     return res
+
+
+def _write_fields(b, i, stem):
+    """stem.mv and stem.mbi: stream i's two field buffers -> (stem.mv, status, error, pictures, bytes of both)"""
+    mot, mbi = b._field_buffers(i)
+    with open(stem + ".mv", "wb") as f:
+        f.write(mot.tobytes())
+    with open(stem + ".mbi", "wb") as f:
+        f.write(mbi.tobytes())
+    return stem + ".mv", b.status(i), b.error(i), len(b.pictures(i)), mot.nbytes + mbi.nbytes
 
 
 def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):

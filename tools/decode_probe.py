@@ -3,7 +3,7 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h] [--motion]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
@@ -13,6 +13,9 @@ lh264_parse_batch_discard - the host front end alone - on the same batch in the 
 normalise of the ImageNet means and deviations) and adds "dtype" to the rows;
 --fit cover|contain asks for a fitted view (decode_batch (fit=...), with --size only; contain fills with 16, 128, 128) and --crop x,y,w,h
 for a rectangle of every picture's window (decode_batch (crop=...)); they add "fit" and "crop" to the rows;
+--motion asks for the motion fields beside the pictures (decode_batch (motion=True)) and adds "motion", the field bytes and the
+milliseconds of decode_pack_motion_kernel (lh264_decode_last_motion) to the rows; the mode motion_only (--modes ...,motion_only) is the
+call with pictures=False: nothing is reconstructed;
 --pick intra|idr decodes the selected pictures only (decode_batch (pick=...)) and adds "pick" to the rows; every row carries
 parsed_slices (the slices whose data was parsed, all streams) and the launch shape of the call (rounds, chains, jobs);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
@@ -69,6 +72,7 @@ def main(argv):
         text = argv[argv.index("--crop") + 1]
         scale = dict(scale, crop=tuple(int(v) for v in text.split(",")))
         args.remove(text)
+    motion = "--motion" in argv
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
     data = open(path, "rb").read()
@@ -80,10 +84,12 @@ def main(argv):
         for r in range(runs):
             t0 = time.perf_counter()
             factors = dict(mul=mul, add=add) if "dtype" in scale else {}
-            if mode == "digests":
+            if mode == "motion_only":
+                b = lh.decode_batch(datas, fmt=fmt, motion=True, pictures=False, parse=parse, **scale, **factors)
+            elif mode == "digests":
                 b = lh.decode_batch(datas, fmt=fmt, sha1="both", pictures=False, parse=parse, **scale, **factors)
             else:
-                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse, **scale, **factors)
+                b = lh.decode_batch(datas, fmt=fmt, device_out=mode == "device", parse=parse, motion=motion, **scale, **factors)
             dt = time.perf_counter() - t0
             ms = (C.c_double * 6)()
             lib.lh264_decode_last_timing(ms)
@@ -96,7 +102,11 @@ def main(argv):
             pics = sum(len(b.pictures(i)) for i in (0, streams - 1)) // 2 * streams
             bad = [i for i in range(streams) if b.status(i) != 0]
             extra = {"stream_sha1": b.stream_sha1(0).hex(), "same_digests": len(set(b.stream_sha1(i) for i in range(streams))) == 1} if mode == "digests" else {}
-            out_bytes = sum(p[5] for p in b.pictures(0)) * streams
+            if motion or mode == "motion_only":
+                mms, mbytes = C.c_double(0), C.c_ulonglong(0)
+                lib.lh264_decode_last_motion(C.byref(mms), C.byref(mbytes))
+                extra = dict(extra, motion=True, field_MB=round(mbytes.value / 1e6, 1), motion_kernel_ms=round(mms.value, 3))
+            out_bytes = 0 if mode == "motion_only" else sum(p[5] for p in b.pictures(0)) * streams
             b.free()
             dev, pin = lh.decode_arena_bytes()
             print(json.dumps(dict(base, what="decode_batch", out=mode, run=r, seconds=round(dt, 4), MBps=round(mb / dt, 1), pictures_per_s=round(pics / dt),
