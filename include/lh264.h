@@ -996,6 +996,70 @@ int lh264_decoded_motion_copy_dev (const lh264_decoded_t* d, void* motion_dst_de
 /* the last call's decode_pack_motion_kernel launches in this process: *ms their milliseconds on the device (between events around each
  * launch), *bytes the field bytes they wrote (104 a macroblock).  Either may be NULL; 0, 0 after a call without fields */
 int lh264_decode_last_motion (double* ms, unsigned long long* bytes);
+/* ---- the pictures asked for by number, with their reference chains: lh264_decode_batch_ex5 ----------------------------------------------
+ * The five structs above are frozen; the selection travels in a sixth.  select == NULL or n_selects == 0 is lh264_decode_batch_ex4,
+ * byte for byte and launch for launch (lh264_decode_batch_ex4 is this call with NULL).
+ * THE RULE (normative).  Pictures are numbered in decode order from 0, as lh264_decoded_picture_index numbers them (withheld and
+ * unselected pictures count).  For one stream with the set Q of requested numbers:
+ *   ENTRY pictures are picture 0 and every IDR picture.  A non-IDR picture whose slices are all I slices is NOT an entry: a later P
+ *     picture may reference across it.  entry (r) is the largest entry picture <= r.
+ *   NEEDED pictures are the union over r in Q of entry (r) .. r.  A RUN is a stretch of needed pictures that starts at an entry and
+ *     ends in front of the next needed entry.
+ *   needed and requested: decoded and DELIVERED.
+ *   needed and not requested: decoded and RECONSTRUCTED ONLY - a pool slot and a reconstruct job, no pack job, no record, no bytes, no
+ *     digest, no fields.
+ *   not needed, at or before the last requested picture: walked by its headers only (NAL split, parameter sets, slice headers,
+ *     reference marking, picture boundaries).  Its slice data is never looked at: no records, no slot, no job, exactly like an
+ *     unselected picture under opts->pick.
+ *   BEHIND THE LAST REQUESTED PICTURE THE STREAM ENDS: nothing more of it is read.  The end of that picture is found as always, so the
+ *     header of the next access unit may be seen.  If every requested picture that exists was delivered the status is LH264_OK.
+ *   A requested number at or beyond the stream's picture count delivers nothing and is no error: lh264_decoded_picture_index tells
+ *     what arrived.
+ * EVERY DELIVERED PICTURE IS BYTE FOR BYTE THAT PICTURE OF THE LH264_PICK_ALL CALL with the same format, scale, size, view, colour and
+ * sample type.  Offsets, the handles, the sink (first_picture counts delivered pictures), DEVICE_OUT, NO_PICTURES and both kinds of
+ * digest work on the delivered pictures only.  The fields of a delivered picture (lh264_decode_batch_ex4) are those of the full call,
+ * `back` included: it counts pictures of the stream, not delivered ones.
+ * FAILURES.  A failure of the header walk in front of the last requested picture stops the stream there, as ever, with the same
+ * `picture N: text`.  A needed picture the full call would refuse (uncovered macroblocks, an incomplete slice, a slice that does not
+ * parse, a crop that does not fit, a matrix without a conversion) stops the stream at that picture with the full call's code and text:
+ * the refusals are checked on every picture of a run, as the full call checks them on every picture.  The requested pictures in front
+ * of a stop are delivered.  DAMAGE INSIDE THE SLICE DATA OF A PICTURE THAT IS NOT NEEDED, OR ANYWHERE BEHIND THE LAST REQUESTED PICTURE,
+ * IS NEITHER SEEN NOR REPORTED: a stream that the full call stops at such a place is decoded to its last requested picture here.
+ * The slice data of the needed pictures is parsed by the host threads, or under LH264_PARSE_DEVICE by the kernels, on the paths and
+ * with the fallback rules of opts->pick.  Within a round every run that begins at an IDR picture is a chain of its own in the
+ * lh264_recon_chains launch (lh264_decode_last_chains): its first picture references nothing and its slots were free when the round
+ * began, so two runs of one stream in one round are independent; a run that spans rounds goes on as the stream's chain in the next.
+ * ONE ENTRY (lh264_select_t): list != NULL - the n_list numbers of the list, strictly increasing, none negative (n_list 0: nothing);
+ * list == NULL - the range first + k * step for k < count, count 0 meaning "to the stream's end", step >= 1: {NULL, 0, 0, 0, 1} is
+ * every picture of the stream.  n_selects is 1 (the entry holds for every stream) or n (one entry per stream).
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of the calls above: a struct_bytes other than 24,
+ * n_selects other than 0, 1 or n, selects NULL with n_selects > 0, a list that is not strictly increasing or holds a negative number,
+ * list NULL with n_list > 0, step 0 in a range, a reserved word that is not 0, a selection together with opts->pick other than
+ * LH264_PICK_ALL, a selection together with conceal (for pick's reason, and because deferred records are not concealed). */
+typedef struct lh264_select {
+  const int32_t* list;                  /* NULL: the range below                                                */
+  uint32_t n_list;
+  uint32_t first, count, step;          /* list == NULL: first + k * step, k < count (0: to the end), step >= 1  */
+} lh264_select_t;
+typedef struct lh264_decode_select {
+  uint32_t struct_bytes;                /* 24                                                                   */
+  uint32_t n_selects;                   /* 0: none (the call is lh264_decode_batch_ex4); 1; or n                */
+  const lh264_select_t* selects;
+  uint64_t reserved;                    /* 0                                                                    */
+} lh264_decode_select_t;
+int lh264_decode_batch_ex5 (const uint8_t* const* data, const size_t* len, int n, int threads,
+                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
+                            const lh264_decode_sample_t* sample /* NULL = uint8 */, const lh264_decode_view_t* view /* NULL = none */,
+                            const lh264_decode_motion_t* motion /* NULL = no fields */, const lh264_decode_select_t* select /* NULL = every picture */,
+                            lh264_decoded_t** out);
+/* the pictures of the stream that were reconstructed, delivered or not (0 in the motion-only call, which reconstructs nothing) */
+long long lh264_decoded_chain_pictures (const lh264_decoded_t* d);
+/* the rule above for one Annex-B file and one entry, headers only, no device: the needed pictures and the delivered ones, ascending.
+ * The first min (cap_needed, *n_needed) needed numbers go to needed (may be NULL with cap 0), *n_needed is their number whatever the
+ * cap is; the same for delivered.  The walk goes no further than the last requested picture and stops where a failure of the header
+ * walk stops the call.  LH264_E_ARG: sel NULL or an entry the call above refuses, a count pointer NULL, a cap < 0 */
+int lh264_parser_plan (const uint8_t* data, size_t len, const lh264_select_t* sel, int32_t* needed, int cap_needed, int* n_needed,
+                       int32_t* delivered, int cap_delivered, int* n_delivered);
 /* one delivered picture's fields to gather (decode_pack_motion_kernel): its mb_w * mb_h records in raster order, its slice table, where
  * the two blocks begin, and back[slot] for every job reference slot (-1: no picture).  The blocks begin at multiples of 8 bytes.
  * lh264_debug_motion_cpu steps the kernel's code over HOST memory with t = 0, nt = 1; lh264_debug_motion_dev uploads the table (its
@@ -1037,7 +1101,8 @@ long long lh264_decoded_device_slices (const lh264_decoded_t* d);
 /* ... and how many of those were CABAC slices, parsed by slice_parse_cabac_kernel (0 without LH264_PARSE_FLAG_CABAC) */
 long long lh264_decoded_device_cabac_slices (const lh264_decoded_t* d);
 /* the distinct slices of the stream whose slice data was parsed, by the host front end or by a kernel (a slice that waited for another
- * round, or that the host parsed again behind a fallback, counts once): with opts->pick the slices of the selected pictures only */
+ * round, or that the host parsed again behind a fallback, counts once): with opts->pick the slices of the selected pictures only,
+ * with a selection (lh264_decode_batch_ex5) those of the needed pictures */
 long long lh264_decoded_parsed_slices (const lh264_decoded_t* d);
 /* the number of delivered picture idx among all pictures the front end found in the stream, in decode order from 0 (withheld and
  * unselected pictures count).  With LH264_PICK_ALL and nothing withheld it equals idx.  LH264_E_ARG: a bad index */
@@ -1070,7 +1135,7 @@ int lh264_decode_last_timing (double* ms);
 int lh264_decode_last_parse_timing (double* out);
 /* the launch shape of the last lh264_decode_batch call in this process: v[0] its rounds (lh264_recon_chains launches), v[1] the chains
  * and v[2] the jobs (pictures) of all of them.  With LH264_PICK_ALL a chain is a stream's pictures of a round; with opts->pick every
- * picture is a chain */
+ * picture is a chain; with a selection (lh264_decode_batch_ex5) every run of a stream that begins at an IDR picture in the round */
 int lh264_decode_last_chains (long long v[3]);
 /* the decode-order indices lh264_decode_batch would select from one Annex-B file under `pick` (LH264_PICK_*; LH264_PICK_ALL: every
  * index), up to the first failure of the header walk: the first min (cap, *n) of them go to idx (may be NULL with cap 0), *n is

@@ -31,6 +31,10 @@
                                                             line `stream hex`, the SHA-1 of all pictures in order (computed on the device)
     python -m losslessh264_amd --decode [--sha1] --scale N ...   N = 1 | 2 | 3: reduced-size pictures, the means of 2x2 / 4x4 / 8x8
                                                             blocks computed on the device (decode_batch (scale=N)); 0 = full size
+    python -m losslessh264_amd --decode [--sha1] --at SPEC ...   only the pictures with the given numbers (decode order from 0) are
+                                                            delivered: SPEC is a,b,c or start:stop:step (decode_batch (select=...));
+                                                            of the stream only what they need is decoded, nothing behind the last
+                                                            of them is read.  One SPEC for all files.  Not with --pick or --conceal
     python -m losslessh264_amd --decode [--sha1] --pick intra|idr ...   only the pictures whose slices are all I slices / the IDR pictures
                                                             are decoded and written (decode_batch (pick=...)); the index column of a
                                                             .sha1 file is the picture's number in the stream.  Not with --conceal
@@ -219,14 +223,32 @@ def parse_size(text):
     return (w, h) if all(2 <= v <= 4096 and v % 2 == 0 for v in (w, h)) else None
 
 
+AT_USAGE = "--at: a,b,c (strictly increasing picture numbers) | start:stop:step (stop, step optional); not with --pick or --conceal"
+
+
+def parse_at(text):
+    """--at SPEC -> a list of numbers or a slice, as decode_batch (select=) takes them; None: not a spec"""
+    import re
+    if ":" in text:
+        m = re.fullmatch(r"(\d{1,9})?:(\d{1,9})?(?::(\d{1,9})?)?", text)
+        if not m or (m.group(3) is not None and int(m.group(3)) < 1):
+            return None
+        return slice(int(m.group(1) or 0), None if m.group(2) is None else int(m.group(2)), int(m.group(3) or 1))
+    if not re.fullmatch(r"\d{1,9}(,\d{1,9})*", text):
+        return None
+    nums = [int(v) for v in text.split(",")]
+    return nums if all(b > a for a, b in zip(nums, nums[1:])) else None
+
+
 def decode(argv):
     import losslessh264_amd as lh
+    at = None
     nv12, conceal, sha1, parse, scale, pick, size = False, None, False, "host", 0, "all", None
     colour, matrix, crange = None, None, None
     dtype, mul, add = None, None, None
     fit, fill, crop = None, None, None
     motion = 0      # 1: --motion, 2: --motion-only
-    while argv and argv[0] in ("--motion", "--motion-only", "--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+    while argv and argv[0] in ("--motion", "--motion-only", "--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--at", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
         if argv[0] in ("--fit", "--fill", "--crop"):
             value = None
             if len(argv) >= 2:
@@ -277,6 +299,13 @@ def decode(argv):
                 return 2
             argv = argv[2:]
             continue
+        if argv[0] == "--at":
+            at = parse_at(argv[1]) if len(argv) >= 2 else None
+            if at is None:
+                print(AT_USAGE)
+                return 2
+            argv = argv[2:]
+            continue
         if argv[0] == "--pick":
             if len(argv) < 2 or argv[1] not in ("intra", "idr"):
                 print("--pick: intra | idr")
@@ -319,7 +348,10 @@ def decode(argv):
     if motion and sha1:
         print("--motion, --motion-only: not with --sha1")
         return 2
-    vkw = dict(fit=fit or "stretch", fill=fill, crop=crop)
+    if at is not None and (pick != "all" or conceal not in (None, "off")):
+        print(AT_USAGE)
+        return 2
+    vkw = dict(fit=fit or "stretch", fill=fill, crop=crop, select=at)
     ckw = dict(vkw, colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)

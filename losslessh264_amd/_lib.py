@@ -198,6 +198,11 @@ class MotionJob(C.Structure):       # lh264_motion_job_t: one picture's records 
                 ("mb_w", C.c_int32), ("mb_h", C.c_int32), ("n_slices", C.c_int32), ("reserved", C.c_int32), ("back", C.c_int16 * 16)]
 assert C.sizeof(DecodeMotion) == 16 and C.sizeof(DecodedMotion) == 32 and C.sizeof(MotionJob) == 80
 MOTION_FIELDS = 1                   # LH264_MOTION_FIELDS
+class Select(C.Structure):          # lh264_select_t: one stream's requested pictures, a list or a range
+    _fields_ = [("list", C.POINTER(C.c_int32)), ("n_list", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("step", C.c_uint32)]
+class DecodeSelect(C.Structure):    # lh264_decode_select_t: what lh264_decode_batch_ex5 takes beside the five frozen structs
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_selects", C.c_uint32), ("selects", C.POINTER(Select)), ("reserved", C.c_uint64)]
+assert C.sizeof(Select) == 24 and C.sizeof(DecodeSelect) == 24
 MOTION_CHUNK_MBS = 64               # LH264_MOTION_CHUNK_MBS: the macroblocks of a row one workgroup of decode_pack_motion_kernel handles
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
@@ -211,6 +216,9 @@ _SIGS.update({
     "lh264_decode_batch_ex3": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decoded_picture_view": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_decode_batch_ex4": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decode_batch_ex5": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_chain_pictures": (C.c_longlong, [C.c_void_p]),
+    "lh264_parser_plan": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     "lh264_decoded_picture_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lh264_decoded_motion": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "lh264_decoded_motion_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

@@ -19,6 +19,10 @@
 //                                       frame_num idr hex` per picture and a last line `stream hex`, the SHA-1 of all of them in order
 //   lh264dec --decode [--sha1] --scale N ...   N = 1 | 2 | 3: reduced-size pictures, the means of 2x2 / 4x4 / 8x8 blocks computed on the
 //                                       device (lh264.h: scale_log2); 0 = full size
+//   lh264dec --decode [--sha1] --at SPEC ...   only the pictures with the given numbers (decode order from 0) are delivered: SPEC is a,b,c
+//                                       or start:stop:step (lh264.h: lh264_decode_batch_ex5); of the stream only what they need is
+//                                       decoded, and nothing behind the last of them is read.  One SPEC for all files.  Not together
+//                                       with --pick or --conceal
 //   lh264dec --decode [--sha1] --pick intra|idr ...   only the pictures whose slices are all I slices / the IDR pictures are decoded and
 //                                       written (lh264.h: pick); the index column of a .sha1 file is the picture's number in the stream.
 //   lh264dec --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096), resampled on the
@@ -263,6 +267,51 @@ static bool parse_size (const char* text, int* w, int* h) {
 // --motion | --motion-only: what lh264_decode_batch_ex4 takes beside the four (0: NULL, the call as ever); 2: the fields and no picture
 static int g_motion = 0;
 static const char* const kMotionUsage = "--motion, --motion-only: not with --sha1";
+// --at SPEC: the selection lh264_decode_batch_ex5 takes beside the five (NULL without it), one entry for every file.  SPEC is a,b,c
+// (strictly increasing numbers) or start:stop:step with start, stop and step optional (stop: exclusive, none: to the stream's end)
+static std::vector<int32_t> g_at_list;
+static lh264_select_t g_at = {nullptr, 0, 0, 0, 1};
+static lh264_decode_select_t g_select = {sizeof (lh264_decode_select_t), 0, &g_at, 0};
+static const char* const kAtUsage = "--at: a,b,c (strictly increasing picture numbers) | start:stop:step (stop, step optional); not with --pick or --conceal";
+static const lh264_decode_select_t* select_arg() { return g_select.n_selects ? &g_select : nullptr; }
+static bool parse_at (const char* v) {
+  auto number = [] (const char*& p, long long* out) {      // digits, at most nine of them
+    const char* b = p; long long x = 0;
+    while (*p >= '0' && *p <= '9' && p - b < 10) x = x * 10 + (*p++ - '0');
+    *out = x;
+    return p != b && p - b < 10;
+  };
+  g_at_list.clear();
+  g_at = {nullptr, 0, 0, 0, 1};
+  if (strchr (v, ':')) {
+    long long part[3] = {0, -1, 1};
+    const char* p = v;
+    for (int k = 0; k < 3; k++) {
+      if (*p != ':' && *p != 0 && !number (p, &part[k])) return false;
+      if (*p == 0) break;
+      if (*p != ':' || k == 2) return false;
+      p++;
+    }
+    if (part[2] < 1) return false;
+    g_at.first = (uint32_t)part[0]; g_at.step = (uint32_t)part[2];
+    if (part[1] >= 0) {
+      g_at.count = part[1] > part[0] ? (uint32_t) ((part[1] - part[0] + part[2] - 1) / part[2]) : 0;
+      if (!g_at.count) { g_at_list.reserve (1); g_at.list = g_at_list.data(); }      // (an empty range: the empty list)
+    }
+  } else {
+    const char* p = v;
+    for (;;) {
+      long long x;
+      if (!number (p, &x) || (!g_at_list.empty() && x <= g_at_list.back())) return false;
+      g_at_list.push_back ((int32_t)x);
+      if (*p == 0) break;
+      if (*p++ != ',') return false;
+    }
+    g_at.list = g_at_list.data(); g_at.n_list = (uint32_t)g_at_list.size();
+  }
+  g_select.n_selects = 1;
+  return true;
+}
 static int decode_files (const std::string& out_dir, const std::vector<std::string>& srcs, bool nv12, int conceal, int device_parse /* 0 host, 1 device, 2 device with CABAC */, int scale, uint32_t pick, int out_w, int out_h) {
   const int n = (int)srcs.size();
   std::vector<Bytes> in (n);
@@ -280,7 +329,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   if (g_motion == 2) { o.sink = nullptr; o.user = nullptr; o.flags = LH264_DECODE_NO_PICTURES; }
   const lh264_decode_motion_t motion = {sizeof (lh264_decode_motion_t), LH264_MOTION_FIELDS, 0, 0};
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex4 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), g_motion ? &motion : nullptr, h.data());
+  const int rc = lh264_decode_batch_ex5 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), g_motion ? &motion : nullptr, select_arg(), h.data());
   for (FILE* f : files.f) if (f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
@@ -311,7 +360,7 @@ static int decode_sha1_files (const std::string& out_dir, const std::vector<std:
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex3 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), h.data());
+  const int rc = lh264_decode_batch_ex5 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), nullptr, select_arg(), h.data());
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
@@ -384,6 +433,9 @@ int main (int argc, char** argv) {
         else if (!strcmp (argv[first + 1], "idr")) pick = LH264_PICK_IDR;
         else { fprintf (stderr, "--pick: intra | idr\n"); return 2; }
         first += 2;
+      } else if (first < argc && !strcmp (argv[first], "--at")) {
+        if (first + 1 >= argc || !parse_at (argv[first + 1])) { fprintf (stderr, "%s\n", kAtUsage); return 2; }
+        first += 2;
       } else if (first + 1 < argc && !strcmp (argv[first], "--size")) {
         if (!parse_size (argv[first + 1], &out_w, &out_h)) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
         first += 2;
@@ -431,14 +483,15 @@ int main (int argc, char** argv) {
     if (g_motion && sha1) { fprintf (stderr, "%s\n", kMotionUsage); return 2; }
     if ((g_view.fit != LH264_FIT_STRETCH && !out_w) || (fill_named && g_view.fit != LH264_FIT_CONTAIN)) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
     if (g_view.fit == LH264_FIT_CONTAIN && !fill_named) g_view.fill = 16u | 128u << 8 | 128u << 16;
+    if (select_arg() && (pick != LH264_PICK_ALL || conceal != 0)) { fprintf (stderr, "%s\n", kAtUsage); return 2; }
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

@@ -145,6 +145,7 @@ struct lh264_decoded {
   long device_cabac_slices = 0;                 // ... of them CABAC slices (slice_parse_cabac_kernel)
   long device_slices = 0;                       // slices of the stream that slice_parse_kernel parsed and the host kept
   long parsed_slices = 0;                       // distinct slices whose slice data was parsed, on either route
+  long chain_pictures = 0;                      // pictures of the stream that were reconstructed, delivered or not
   std::vector<int32_t> index;                   // per delivered picture: its number among the stream's pictures in decode order
   std::vector<uint8_t> colour;                  // lh264_decode_batch_ex with colour: per delivered picture the standard byte that was applied
   int sample_type = (int)LH264_SAMPLE_U8;       // lh264_decode_batch_ex2: the LH264_SAMPLE_* of the call
@@ -284,6 +285,10 @@ struct DStream {
   bool sha_started = false;                          // the stream's digest record on the device holds its message so far
   bool stopped = false;                              // the sink refused, or the device stage failed: nothing more is delivered
   std::vector<std::unique_ptr<FrameOut>> sel;        // the pictures of the round in preparation
+  // lh264_decode_batch_ex5: the walked pictures of the current run that no requested picture has made needed yet (their slices deferred);
+  // the walk is over (the last requested picture, or a failure of the header walk, is behind it)
+  std::vector<std::unique_ptr<FrameOut>> run_held;
+  bool walk_over = false;
   // parse = LH264_PARSE_DEVICE: the stream's CAVLC slices go to slice_parse_kernel (until a CABAC picture or a fallback ends that), and
   // where in the parse arena the records / the slice table of the pictures parsed there in this round lie
   bool dev_route = false;
@@ -307,6 +312,26 @@ struct RoundChain {
   std::vector<PicPlan> plan;                         // per picture of the round, withheld ones included (plan_round: staging reads it)
 };
 struct Round { std::vector<RoundChain> chains; size_t out_bytes = 0, dig_states_at = 0, mot_bytes = 0, mbi_bytes = 0; bool live = false, timed = false; };
+
+// lh264_decode_batch_ex5: one stream's entry (the rule: include/lh264.h at that call)
+struct Selection {
+  const int32_t* list = nullptr; uint32_t n_list = 0, first = 0, count = 0, step = 1;
+  explicit Selection (const lh264_select_t& e) : list (e.list), n_list (e.n_list), first (e.first), count (e.count), step (e.step) {}
+  bool requested (long k) const {
+    if (list) return k <= 0x7fffffffl && std::binary_search (list, list + n_list, (int32_t)k);
+    return k >= (long)first && (k - (long)first) % (long)step == 0 && (count == 0 || (k - (long)first) / (long)step < (long)count);
+  }
+  // the last requested number: -1 for none, the largest long for "to the stream's end"
+  long last() const {
+    if (list) return n_list ? (long)list[n_list - 1] : -1;
+    return count ? (long)first + (long) (count - 1) * (long)step : 0x7fffffffffffffffl;
+  }
+};
+bool select_entry_ok (const lh264_select_t& e) {
+  if (!e.list) return e.n_list == 0 && e.step >= 1;
+  for (uint32_t k = 0; k < e.n_list; k++) if (e.list[k] < 0 || (k && e.list[k] <= e.list[k - 1])) return false;
+  return true;
+}
 
 // opts->pick: is the picture one of those the call decodes?  (slice_type: 0 P, 2 I)
 bool picture_selected (const FrameOut& f, uint32_t pick) {
@@ -442,6 +467,8 @@ struct DecodeConfig {
   uint32_t parse; bool parse_dev, parse_cabac;      // slice data goes to slice_parse_kernel (not with concealment, which builds records on the host); CABAC slices too
   int scale;                                        // 0: decode_pack_kernel; 1..3: decode_pack_scaled_kernel
   uint32_t pick; bool picking;                      // unselected pictures are walked by their headers only, every selected one is a chain
+  std::vector<Selection> selects; bool selecting;   // lh264_decode_batch_ex5: every stream's entry; only needed pictures are decoded, a run is a chain
+  bool sparse;                                      // picking or selecting: every slice is deferred, pictures leave the stream unparsed
   int out_w, out_h;                                 // 0, 0: the window (or its scale); else decode_pack_resized_kernel
   uint32_t fit, fill; std::vector<lh264_rect_t> crops;      // the view: the fit, the bars' fill, and every stream's crop (w = 0: none)
   bool placed;                                      // LH264_FIT_CONTAIN: the placed kernels and a place per pack job
@@ -465,8 +492,14 @@ struct DecodeConfig {
 };
 
 // LH264_OK, or LH264_E_ARG for arguments the call does not take
-int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, int n, DecodeConfig* cfg) {
+int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, int n, DecodeConfig* cfg) {
   DecodeConfig& c = *cfg;
+  if (select && (select->struct_bytes != sizeof (lh264_decode_select_t) || select->reserved != 0 || (select->n_selects != 0 && select->n_selects != 1 && select->n_selects != (uint32_t)n) ||
+                 (select->n_selects != 0 && !select->selects))) return LH264_E_ARG;
+  if (select) for (uint32_t k = 0; k < select->n_selects; k++) if (!select_entry_ok (select->selects[k])) return LH264_E_ARG;
+  c.selecting = select && select->n_selects;
+  c.selects.clear();
+  if (c.selecting) for (int i = 0; i < n; i++) c.selects.push_back (Selection (select->selects[select->n_selects == 1 ? 0 : i]));
   if (motion && (motion->struct_bytes != sizeof (lh264_decode_motion_t) || motion->fields > LH264_MOTION_FIELDS || motion->reserved0 != 0 || motion->reserved1 != 0)) return LH264_E_ARG;
   c.fields = motion ? motion->fields : 0;
   if (view && (view->struct_bytes != sizeof (lh264_decode_view_t) || view->fit > LH264_FIT_CONTAIN || view->reserved0 != 0 || view->reserved1 != 0 ||
@@ -506,6 +539,8 @@ int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ex
   if (v5 && (opts->pick > LH264_PICK_IDR || opts->reserved3 != 0 || (opts->pick != LH264_PICK_ALL && c.conceal != 0))) return LH264_E_ARG;
   c.pick = v5 ? opts->pick : LH264_PICK_ALL;
   c.picking = c.pick != LH264_PICK_ALL;
+  if (c.selecting && (c.picking || c.conceal != 0)) return LH264_E_ARG;
+  c.sparse = c.picking || c.selecting;
   const bool sized = v6 && (opts->out_width || opts->out_height);
   if (v6 && (opts->reserved4 != 0 || opts->reserved5 != 0 || (sized && (!lh264pack::size_ok (opts->out_width, opts->out_height) || c.scale != 0)))) return LH264_E_ARG;
   c.out_w = sized ? (int)opts->out_width : 0; c.out_h = sized ? (int)opts->out_height : 0;
@@ -554,6 +589,7 @@ struct DecodeCall {
   std::vector<std::vector<int>> slot_of;
   size_t n_hmbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0, n_mjobs = 0, n_sjobs = 0, dig_bytes = 0;
   int n_launch = 0, max_units = 1, max_w = 1, max_h = 1, max_bands = 1;
+  std::vector<int32_t> chain_first;                // the round's jobs that begin a chain of the lh264_recon_chains launch
 
   void release_pool (DStream& s) {
     for (Slot& sl : s.pool) A.pics.put (s.geo.bytes, sl.base);
@@ -593,10 +629,11 @@ struct DecodeCall {
       std::unique_ptr<DStream> s (new DStream());
       s->i = next_stream++;
       s->dev_route = cfg.parse_dev;
+      s->walk_over = cfg.selecting && cfg.selects[s->i].last() < 0;      // (an empty list: nothing of the stream is read)
       Parser& P = * (s->parser = std::make_unique<Parser>());
       P.set_sparse_coeffs (true); P.set_sparse_levels (true);       // (the parser has no mode without levels: their list is the cheapest form)
       P.set_conceal (cfg.conceal);
-      P.set_defer_slice_data (cfg.parse_dev || cfg.picking); P.set_defer_cabac (cfg.parse_cabac || cfg.picking);
+      P.set_defer_slice_data (cfg.parse_dev || cfg.sparse); P.set_defer_cabac (cfg.parse_cabac || cfg.sparse);
       P.begin_file (data[s->i], data[s->i] ? len[s->i] : 0);
       active.push_back (std::move (s));
       used += avg * cfg.R; admitted++;
@@ -604,12 +641,30 @@ struct DecodeCall {
     return !active.empty();
   }
 
+  // lh264_decode_batch_ex5, a walked picture: an entry (an IDR picture; picture 0 has nothing in front of it) drops what is held, a
+  // requested picture makes everything held needed - the others of them reconstructed only - and behind the last requested picture,
+  // or at a failure of the header walk, the walk is over
+  void hold_or_promote (DStream& s, std::unique_ptr<FrameOut> f) {
+    const Selection& q = cfg.selects[s.i];
+    const Parser& P = *s.parser;
+    if (s.walk_over) return;
+    if (!P.error().empty() && f->index >= P.error_pictures()) { s.walk_over = true; s.run_held.clear(); return; }
+    if (f->idr) s.run_held.clear();
+    const long k = f->index;
+    s.run_held.push_back (std::move (f));
+    if (q.requested (k)) {
+      for (auto& h : s.run_held) { h->frozen = h->index != k; s.pending.push_back (std::move (h)); }
+      s.run_held.clear();
+    }
+    if (k >= q.last()) { s.walk_over = true; s.run_held.clear(); }
+  }
+
   // host threads: parse until the stream has a round's pictures (or ends), then pick the round's pictures
   // tentative (a stream on the device route): the round's candidates, before their slice data is parsed - nothing is refused yet
   void fill_and_select (DStream& s, bool fill, bool tentative) {
     Parser& P = *s.parser;
     const size_t R = cfg.R;
-    while (fill && s.pending.size() < R && !P.file_finished()) {
+    while (fill && s.pending.size() < R && !P.file_finished() && !s.walk_over) {
       const size_t want = s.pic_mbs ? (R - s.pending.size()) * s.pic_mbs - 1 : 0;
       P.feed_file_some (want);
       for (auto& f : P.frames()) {
@@ -619,19 +674,22 @@ struct DecodeCall {
         out[s.i]->parsed_slices += (long) (f->slices.size() - f->deferred.size());
         // opts->pick: an unselected picture leaves here, its slice data unseen
         if (cfg.picking && !picture_selected (*f, cfg.pick)) continue;
+        if (cfg.selecting) { hold_or_promote (s, std::move (f)); continue; }
         s.pending.push_back (std::move (f));
       }
       P.frames().clear();
+      if (cfg.selecting && !P.error().empty()) { s.walk_over = true; s.run_held.clear(); }      // (what the failure means is decided below)
     }
     s.ending = false; s.end_code = LH264_OK; s.end_text.clear();
-    const bool has_err = !tentative && !P.error().empty();
+    // (lh264_decode_batch_ex5: a failure behind the last requested picture is not the call's)
+    const bool has_err = !tentative && !P.error().empty() && (!cfg.selecting || P.error_pictures() <= cfg.selects[s.i].last());
     const long limit = has_err ? P.error_pictures() : 0x7fffffffffffffffl;
     while (s.sel.size() < R) {
       // the picture's number in the stream: with opts->pick the next selected picture's own, or where the pictures seen so far end
-      const long idx = !cfg.picking ? s.next_picture + (long)s.sel.size() : !s.pending.empty() ? s.pending.front()->index : s.seen;
-      if (idx >= limit) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (cfg.picking ? limit : idx) + ": " + P.error(); break; }
+      const long idx = !cfg.sparse ? s.next_picture + (long)s.sel.size() : !s.pending.empty() ? s.pending.front()->index : has_err ? limit : s.seen;
+      if (idx >= limit) { s.ending = true; s.end_code = LH264_E_UNSUPPORTED; s.end_text = "picture " + std::to_string (cfg.sparse ? limit : idx) + ": " + P.error(); break; }
       if (s.pending.empty()) {
-        if (P.file_finished()) { s.ending = true; if (has_err) { s.end_code = LH264_E_UNSUPPORTED; s.end_text = P.error(); } }
+        if (P.file_finished() || s.walk_over) { s.ending = true; if (has_err) { s.end_code = LH264_E_UNSUPPORTED; s.end_text = P.error(); } }
         break;
       }
       FrameOut& f = *s.pending.front();
@@ -672,7 +730,7 @@ struct DecodeCall {
           continue;
         }
         // (opts->pick defers every slice, whoever parses it: without LH264_PARSE_FLAG_CABAC a CABAC picture is the host's all the same)
-        if (cfg.picking && !cfg.parse_cabac && f.deferred[0].cabac) { s.dev_route = false; continue; }
+        if (cfg.sparse && !cfg.parse_cabac && f.deferred[0].cabac) { s.dev_route = false; continue; }
         if (!s.dev_route) continue;
         s.dev_at[&f] = {pm};
         pm += (size_t)f.mb_w * f.mb_h;
@@ -765,7 +823,7 @@ struct DecodeCall {
     for (size_t j = 0; j < nt; j++) if (res[j].status != lh264slice::SLICE_OK && refs[j].s->dev_route) {
       DStream& s = *refs[j].s;
       s.dev_route = false; s.dev_at.clear();
-      if (!cfg.picking) s.parser->set_defer_slice_data (false);
+      if (!cfg.sparse) s.parser->set_defer_slice_data (false);
       out[s.i]->parse_path = LH264_PARSE_PATH_FALLBACK;
     }
     for (size_t j = 0; j < nt; j++) {
@@ -798,7 +856,7 @@ struct DecodeCall {
   bool plan_round() {
     Round& rd = rounds[rb];
     rd.chains.clear(); rd.out_bytes = 0; rd.mot_bytes = 0; rd.mbi_bytes = 0; rd.timed = false;
-    place.clear();
+    place.clear(); chain_first.clear();
     size_t n_mbs = 0;
     n_hmbs = n_sl = n_sp = n_jobs = n_out = n_mjobs = 0;
     max_units = max_w = max_h = max_bands = 1;
@@ -830,6 +888,10 @@ struct DecodeCall {
         c.mot_at = rd.mot_bytes; c.mot_bytes = shown_mbs * 96; rd.mot_bytes += (c.mot_bytes + 15) & ~ (size_t)15;
         c.mbi_at = rd.mbi_bytes; c.mbi_bytes = shown_mbs * 8; rd.mbi_bytes += (c.mbi_bytes + 15) & ~ (size_t)15;
       }
+      // the chains of the launch: a stream's pictures of the round one behind the other - or, with opts->pick, every picture on its own:
+      // it references nothing, so the stream spreads over as many workgroups as it has pictures in the round; with a selection every run
+      // that begins at an IDR picture.  (Delivery and the stream's digest follow rd.chains, the streams, in every case)
+      for (size_t q = 0; q < s.sel.size(); q++) if (q == 0 || cfg.picking || (cfg.selecting && s.sel[q]->idr)) chain_first.push_back ((int32_t) (n_jobs + q));
       place.push_back ({n_hmbs, n_sl, n_sp, n_jobs});
       n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       for (size_t q = 0; q < plan.size(); q++) {
@@ -845,10 +907,7 @@ struct DecodeCall {
     }
     if (rd.chains.empty()) return false;            // nothing to reconstruct (streams that ended without a picture)
     const int n_chains = (int)rd.chains.size();
-    // the chains of the launch: a stream's pictures of the round one behind the other - or, with opts->pick, every picture on its own:
-    // it references nothing, so the stream spreads over as many workgroups as it has pictures in the round.  (Delivery and the
-    // stream's digest follow rd.chains, the streams, in both cases)
-    n_launch = cfg.picking ? (int)n_jobs : n_chains;
+    n_launch = (int)chain_first.size();
     alloc_ok = A.d_mbs.alloc (n_hmbs * sizeof (lh264_mb_t)) && (cfg.motion_only || (A.d_coef.alloc (n_hmbs * 768) && A.d_sparse.alloc (n_sp * 8))) && A.d_sl.alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.d_jobs.alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.d_first.alloc ((size_t) (n_launch + 1) * 4) && A.d_pack.alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                (cfg.motion_only || A.d_out[rb].alloc (rd.out_bytes)) && (cfg.device_out || cfg.no_pictures || A.h_out[rb].alloc (rd.out_bytes)) &&
@@ -896,7 +955,7 @@ struct DecodeCall {
     const int n_chains = (int)rd.chains.size();
     run_parallel (n_chains, threads, [&] (int c) { stage_chain (c); });
     int32_t* h_first = A.h_first[rb].as<int32_t>();
-    if (cfg.picking) for (size_t j = 0; j < n_jobs; j++) h_first[j] = (int32_t)j;
+    std::copy (chain_first.begin(), chain_first.end(), h_first);
     h_first[n_launch] = (int32_t)n_jobs;
     if (cfg.sha) {
       // the span jobs: a picture is a message of its own (its record is scratch), a chain's bytes are the next span of its stream's
@@ -924,6 +983,7 @@ struct DecodeCall {
       const std::vector<int>& dpb = s.sel.back()->dpb_ids;
       for (Slot& sl : s.pool) if (sl.pic_id >= 0 && (cfg.picking || std::find (dpb.begin(), dpb.end(), sl.pic_id) == dpb.end())) sl.pic_id = -1;      // (opts->pick: a slot is needed for its round only)
       s.next_picture += (long)s.sel.size();
+      if (!cfg.motion_only) out[s.i]->chain_pictures += (long)s.sel.size();
       s.delivered += (long)rd.chains[c].pics.size();
       s.out_off += rd.chains[c].bytes;
       s.mot_off += rd.chains[c].mot_bytes; s.mbi_off += rd.chains[c].mbi_bytes;
@@ -943,7 +1003,6 @@ struct DecodeCall {
     RoundChain& rc = rounds[rb].chains[c];
     DStream& s = *rc.s;
     size_t mo = place[c].mb0, so = place[c].sl0, po = place[c].sp0, j = place[c].job0, at = rc.at;
-    if (!picking) A.h_first[rb].as<int32_t>()[c] = (int32_t)j;
     uint64_t off = s.out_off;
     for (size_t q = 0; q < s.sel.size(); q++) {
       FrameOut& f = *s.sel[q];
@@ -1128,7 +1187,7 @@ struct DecodeCall {
   }
 
   void run() {
-    const bool deferring = cfg.parse_dev || cfg.picking;
+    const bool deferring = cfg.parse_dev || cfg.sparse;
     while (admit()) {
       const double t_a = now_s();
       run_parallel ((int)active.size(), threads, [&] (int k) { fill_and_select (*active[k], true, deferring); });
@@ -1398,9 +1457,13 @@ int lh264_decode_batch_ex3 (const uint8_t* const* data, const size_t* len, int n
 }
 
 int lh264_decode_batch_ex4 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex5 (data, len, n, threads, opts, ext, sample, view, motion, nullptr, out);
+}
+
+int lh264_decode_batch_ex5 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
   DecodeConfig cfg;
-  if (decode_config (opts, ext, sample, view, motion, n, &cfg) != LH264_OK) return LH264_E_ARG;      // (every refusal of an argument comes before the device is asked for)
+  if (decode_config (opts, ext, sample, view, motion, select, n, &cfg) != LH264_OK) return LH264_E_ARG;      // (every refusal of an argument comes before the device is asked for)
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   if (threads < 1) threads = 1;
@@ -1448,6 +1511,37 @@ int lh264_parser_pick (const uint8_t* data, size_t len, uint32_t pick, int32_t* 
   *n = count;
   return LH264_OK;
 }
+// the header walk of lh264_decode_batch_ex5 with a selection, and its rule: every slice deferred, none resolved
+int lh264_parser_plan (const uint8_t* data, size_t len, const lh264_select_t* sel, int32_t* needed, int cap_needed, int* n_needed, int32_t* delivered, int cap_delivered, int* n_delivered) {
+  if (!sel || !select_entry_ok (*sel) || !n_needed || !n_delivered || cap_needed < 0 || cap_delivered < 0 || (cap_needed && !needed) || (cap_delivered && !delivered) || (!data && len)) return LH264_E_ARG;
+  const Selection q (*sel);
+  Parser P;
+  P.set_sparse_coeffs (true); P.set_sparse_levels (true);
+  P.set_defer_slice_data (true); P.set_defer_cabac (true);
+  P.begin_file (data, data ? len : 0);
+  int nn = 0, nd = 0;
+  long run_from = 0;                                   // the first picture of the current run that is not needed yet
+  bool over = q.last() < 0;
+  while (!over && !P.file_finished()) {
+    P.feed_file_some (0);
+    const long limit = P.error().empty() ? 0x7fffffffffffffffl : P.error_pictures();
+    for (auto& f : P.frames()) {
+      const long k = f->index;
+      if (over || k >= limit) { over = true; break; }
+      if (f->idr) run_from = k;
+      if (q.requested (k)) {
+        for (long j = run_from; j <= k; j++) { if (nn < cap_needed) needed[nn] = (int32_t)j; nn++; }
+        if (nd < cap_delivered) delivered[nd] = (int32_t)k;
+        nd++; run_from = k + 1;
+      }
+      over = k >= q.last();
+    }
+    P.frames().clear();
+    over = over || !P.error().empty();
+  }
+  *n_needed = nn; *n_delivered = nd;
+  return LH264_OK;
+}
 int lh264_parser_colour (const uint8_t* data, size_t len, int32_t* matrix_coefficients, int32_t* full_range, int32_t* present) {
   if (!data) return LH264_E_ARG;
   int mc = 2, fr = 0, pr = 0;
@@ -1465,6 +1559,7 @@ int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* m
 }
 int lh264_decoded_sample_type (const lh264_decoded_t* d) { return d ? d->sample_type : LH264_E_ARG; }
 long long lh264_decoded_parsed_slices (const lh264_decoded_t* d) { return d ? (long long)d->parsed_slices : 0; }
+long long lh264_decoded_chain_pictures (const lh264_decoded_t* d) { return d ? (long long)d->chain_pictures : 0; }
 int lh264_decoded_picture_index (const lh264_decoded_t* d, int idx) {
   if (!d || idx < 0 || (size_t)idx >= d->pics.size() || d->index.size() != d->pics.size()) return LH264_E_ARG;
   return d->index[idx];

@@ -52,6 +52,10 @@ class DecodedBatch:
         the selected pictures only (an unselected picture is walked by its headers)"""
         return int(self._lib.lh264_decoded_parsed_slices(self._h[i]))
 
+    def chain_pictures(self, i):
+        """the pictures of stream i that were reconstructed, delivered or not: with select= the needed pictures (0 in the motion-only call)"""
+        return int(self._lib.lh264_decoded_chain_pictures(self._h[i]))
+
     def picture_indices(self, i):
         """per delivered picture of stream i: its number among all pictures of the stream, in decode order from 0 (with pick="all" and
         nothing withheld: 0, 1, 2, ...)"""
@@ -272,7 +276,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=False):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=False, select=None):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -343,8 +347,21 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     lh264_decode_batch_ex4): DecodedBatch.motion(i), mb_info(i), motion_frames(i), mb_info_frames(i), motion_geometry(i).  They cover
     the coded picture, whatever scale, size, crop, fit, colour and dtype are.  With a sink the fields stay on the handles.
     pictures=False with motion=True and no sha1 is the motion-only call: nothing is reconstructed, no picture pool is used; the
-    picture records are those of the digests-only call."""
+    picture records are those of the digests-only call.
+    select: None (every picture) | a slice (start, stop >= 0, step >= 1; stop None: to the stream's end) | a sequence of strictly
+    increasing ints >= 0, for every stream | a list with one entry per stream, each one of those or None (every picture of that stream):
+    THE PICTURES ASKED FOR BY NUMBER (decode order from 0, as picture_indices counts) are delivered, each byte for byte that picture of
+    the call without select.  Of the stream only the runs from the last IDR picture (or picture 0) at or before a requested picture up
+    to it are parsed and reconstructed - the pictures of a run that were not requested are reconstructed only - the others in front of
+    the last requested picture are walked by their headers, and behind it the stream is not read: damage in what is not needed is
+    neither seen nor reported.  A number the stream does not have delivers nothing and is no error.  The rule: include/lh264.h at
+    lh264_decode_batch_ex5; plan (data, select) computes it without a device; chain_pictures(i) counts what was reconstructed.  Not
+    together with pick or conceal.  With device_out=True, size= and a selection of equal length per stream, frames(i) is the (T, ...)
+    clip of stream i, and torch.stack over the batch gives (N, T, ...)."""
     lib = L.lib()
+    sel, sel_keep = _select_struct(select, len(datas))
+    if sel is not None and (pick != "all" or conceal not in (None, "off")):
+        raise ValueError("select excludes pick and conceal")
     if not isinstance(dtype, str) or dtype not in L.SAMPLE:
         raise ValueError("dtype must be 'uint8', 'float32', 'float16' or 'bfloat16'")
     if dtype == "uint8":
@@ -430,8 +447,8 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         cb = L.DECODE_SINK_FN(_cb)
         opts.sink = cb
     outs = (C.c_void_p * n)()
-    if fit != "stretch" or crops is not None or motion:
-        # a view or the fields: every struct the call takes, the colour and sample ones where they are asked for
+    if fit != "stretch" or crops is not None or motion or sel is not None:
+        # a view, the fields or a selection: every struct the call takes, the colour and sample ones where they are asked for
         view = None
         if fit != "stretch" or crops is not None:
             view = L.DecodeView()
@@ -449,9 +466,13 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
             for k in range(3):
                 sm.mul[k], sm.add[k] = affine[0][k], affine[1][k]
         ref = lambda st: C.byref(st) if st is not None else None
+        mo = None
         if motion:
             mo = L.DecodeMotion()
             mo.struct_bytes, mo.fields = C.sizeof(L.DecodeMotion), L.MOTION_FIELDS
+        if sel is not None:
+            rc = lib.lh264_decode_batch_ex5(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), ref(mo), C.byref(sel), outs)
+        elif motion:
             rc = lib.lh264_decode_batch_ex4(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), C.byref(mo), outs)
         else:
             rc = lib.lh264_decode_batch_ex3(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), C.byref(view), outs)
@@ -473,6 +494,63 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
     return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine, motion)
+
+
+def _select_entry(s):
+    """one stream's select= -> (numbers or None, first, count, step) of an lh264_select_t"""
+    if s is None:
+        return None, 0, 0, 1
+    if isinstance(s, slice):
+        start, stop, step = 0 if s.start is None else s.start, s.stop, 1 if s.step is None else s.step
+        if not all(v is None or (isinstance(v, int) and not isinstance(v, bool)) for v in (start, stop, step)) or start < 0 or step < 1 or (stop is not None and stop < 0) or start >= 2 ** 31 or step >= 2 ** 31:
+            raise ValueError("a select slice has start, stop >= 0 and step >= 1")
+        if stop is None:
+            return None, start, 0, step
+        count = len(range(start, min(stop, 2 ** 31), step))
+        return ([], 0, 0, 1) if count == 0 else (None, start, count, step)
+    if isinstance(s, (list, tuple, range, np.ndarray)) and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in s):
+        nums = [int(v) for v in s]
+        if any(v < 0 or v >= 2 ** 31 for v in nums) or any(b <= a for a, b in zip(nums, nums[1:])):
+            raise ValueError("a select sequence holds strictly increasing ints >= 0")
+        return nums, 0, 0, 1
+    raise ValueError("select must be None, a slice, a sequence of ints, or a list with one of those per stream")
+
+
+def _select_struct(select, n):
+    """select= of decode_batch -> (None, None) or the lh264_decode_select_t the call passes and what keeps its arrays alive"""
+    if select is None:
+        return None, None
+    per_stream = isinstance(select, list) and any(v is None or isinstance(v, (slice, list, tuple, range, np.ndarray)) for v in select)
+    if per_stream and len(select) != n:
+        raise ValueError("a list of selections has one entry per stream")
+    entries = [_select_entry(s) for s in select] if per_stream else [_select_entry(select)]
+    arr = (L.Select * max(1, len(entries)))()
+    keep = [arr]
+    for k, (nums, first, count, step) in enumerate(entries):
+        if nums is not None:
+            a = (C.c_int32 * max(1, len(nums)))(*nums)
+            keep.append(a)
+            arr[k].list, arr[k].n_list = a, len(nums)
+        arr[k].first, arr[k].count, arr[k].step = first, count, step
+    st = L.DecodeSelect()
+    st.struct_bytes, st.n_selects, st.selects = C.sizeof(L.DecodeSelect), len(entries), arr
+    if not entries:
+        return None, None
+    return st, keep
+
+
+def plan(data, select):
+    """(needed, delivered): the picture numbers decode_batch (select=select) reconstructs and delivers from one Annex-B stream, by the
+    rule of include/lh264.h at lh264_decode_batch_ex5 (lh264_parser_plan): headers only, no device, no further than the last requested
+    picture, up to the first failure of the header walk.  select: None | a slice | a sequence of ints, as one stream's select="""
+    st, keep = _select_struct([select], 1)
+    lib = L.lib()
+    data = bytes(data)
+    nn, nd = C.c_int(0), C.c_int(0)
+    L.check(lib.lh264_parser_plan(data, len(data), C.byref(st.selects[0]), None, 0, C.byref(nn), None, 0, C.byref(nd)))
+    a, b = (C.c_int32 * max(1, nn.value))(), (C.c_int32 * max(1, nd.value))()
+    L.check(lib.lh264_parser_plan(data, len(data), C.byref(st.selects[0]), a, nn.value, C.byref(nn), b, nd.value, C.byref(nd)))
+    return [int(a[k]) for k in range(nn.value)], [int(b[k]) for k in range(nd.value)]
 
 
 def _rect(c):
@@ -558,16 +636,16 @@ def decode_arena_bytes():
 _SUFFIX = {"uint8": ".rgb", "float32": ".f32", "float16": ".f16", "bfloat16": ".bf16"}
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=0):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=0, select=None):
     """out_dir/<basename>.yuv - with colour= <basename>.rgb, with a float dtype= <basename>.f32 | .f16 | .bf16 - for every input, through one decode_batch with a sink that appends to the
-    files -> [(path, status, error, pictures, bytes)]; scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch.
+    files -> [(path, status, error, pictures, bytes)]; select (one entry, for every file), scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch.
     motion: 1: beside them <basename>.mv and <basename>.mbi, every stream's motion blocks and macroblock blocks as the handle holds them
     (decode_batch (motion=True)); 2: those two and no picture file, through the motion-only call (path and bytes are then the .mv file's
     and both files')"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     if motion == 2:
-        b = decode_batch(datas, fmt=fmt, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=True, pictures=False)
+        b = decode_batch(datas, fmt=fmt, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=True, pictures=False, select=select)
         res = [_write_fields(b, i, os.path.join(out_dir, os.path.basename(p))) for i, p in enumerate(paths)]
         b.free()
         return res
@@ -580,7 +658,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=bool(motion))
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=bool(motion), select=select)
     finally:
         for f in files:
             f.close()
@@ -602,13 +680,13 @@ def _write_fields(b, i, stem):
     return stem + ".mv", b.status(i), b.error(i), len(b.pictures(i)), mot.nbytes + mbi.nbytes
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, select=None):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
-    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; scale, pick, size, fit, fill and crop as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
+    per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; select (one entry, for every file), scale, pick, size, fit, fill and crop as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, select=select)
     res = []
     try:
         for i, p in enumerate(paths):

@@ -3,7 +3,7 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h] [--motion]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h] [--motion] [--select SPEC]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
@@ -18,6 +18,8 @@ milliseconds of decode_pack_motion_kernel (lh264_decode_last_motion) to the rows
 call with pictures=False: nothing is reconstructed;
 --pick intra|idr decodes the selected pictures only (decode_batch (pick=...)) and adds "pick" to the rows; every row carries
 parsed_slices (the slices whose data was parsed, all streams) and the launch shape of the call (rounds, chains, jobs);
+--select SPEC (a,b,c or start:stop:step, as --at of the command lines) asks for the pictures with those numbers of every stream
+(decode_batch (select=...)) and adds "select" to the rows; every row carries chain_pictures too (the pictures reconstructed, all streams);
 --modes picks the measurements (default host,device,parse; with --sha1 host,device,digests,parse).
 
 One JSON line per measurement."""
@@ -72,6 +74,14 @@ def main(argv):
         text = argv[argv.index("--crop") + 1]
         scale = dict(scale, crop=tuple(int(v) for v in text.split(",")))
         args.remove(text)
+    select, select_row = {}, {}
+    if "--select" in argv:
+        from losslessh264_amd.__main__ import parse_at
+        text = argv[argv.index("--select") + 1]
+        select, select_row = {"select": parse_at(text)}, {"select": text}
+        if select["select"] is None:
+            raise SystemExit("--select: a,b,c | start:stop:step")
+        args.remove(text)
     motion = "--motion" in argv
     streams = int(args[0]) if args else 512
     path = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden", "streams", "BA_MW_D.264")
@@ -83,7 +93,7 @@ def main(argv):
     for mode in [m for m in modes if m != "parse"]:
         for r in range(runs):
             t0 = time.perf_counter()
-            factors = dict(mul=mul, add=add) if "dtype" in scale else {}
+            factors = dict(select, **(dict(mul=mul, add=add) if "dtype" in scale else {}))
             if mode == "motion_only":
                 b = lh.decode_batch(datas, fmt=fmt, motion=True, pictures=False, parse=parse, **scale, **factors)
             elif mode == "digests":
@@ -98,7 +108,7 @@ def main(argv):
             route = {} if parse == "host" else {"parse": parse, "routes": sorted(set(b.parse_path(i) for i in range(streams))), "device_parse_ms": round(pt[0], 1), "device_parse_slices": int(pt[1])}
             ch = (C.c_longlong * 3)()
             lib.lh264_decode_last_chains(ch)
-            shape = {"parsed_slices": sum(b.parsed_slices(i) for i in range(streams)), "rounds": int(ch[0]), "chains": int(ch[1]), "jobs": int(ch[2])}
+            shape = {"parsed_slices": sum(b.parsed_slices(i) for i in range(streams)), "chain_pictures": sum(b.chain_pictures(i) for i in range(streams)), "rounds": int(ch[0]), "chains": int(ch[1]), "jobs": int(ch[2])}
             pics = sum(len(b.pictures(i)) for i in (0, streams - 1)) // 2 * streams
             bad = [i for i in range(streams) if b.status(i) != 0]
             extra = {"stream_sha1": b.stream_sha1(0).hex(), "same_digests": len(set(b.stream_sha1(i) for i in range(streams))) == 1} if mode == "digests" else {}
@@ -113,7 +123,7 @@ def main(argv):
                                   output_MB=round(out_bytes / 1e6, 1), failed=len(bad),
                                   ms={"call": round(ms[0], 1), "parse": round(ms[1], 1), "staging": round(ms[2], 1), "enqueue": round(ms[3], 1),
                                       "wait_device": round(ms[4], 1), "delivery": round(ms[5], 1)},
-                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **shape, **extra, **route, **scale)), flush=True)
+                                  arena_device_MB=round(dev / 1e6, 1), arena_pinned_MB=round(pin / 1e6, 1), **shape, **extra, **route, **scale, **select_row)), flush=True)
     for r in range(runs if "parse" in modes else 0):
         dt, pics = lh.parse_batch_time(datas, threads=0, keep=False)
         print(json.dumps(dict(base, what="parse_batch_discard", run=r, seconds=round(dt, 4), MBps=round(mb / dt, 1), pictures_per_s=round(pics / dt))), flush=True)
