@@ -12,7 +12,7 @@ committed CABAC stream reaches (tests/test_slice_parse_cabac.py counts what the 
                    picture also from P_L0_16x16 macroblocks with the 8x8 transform); mb_type increments 0, 1 and 2 on I8x8 and on
                    I16x16 macroblocks (an I_NxN neighbour adds nothing); prev_intra8x8_pred_mode_flag both ways, with the predicted
                    mode coming from the left macroblock's right column and from the upper macroblock's bottom row.  Every I8x8
-                   macroblock carries a coefficient.
+                   macroblock carries a coefficient (those without: tests/golden/uncoded_t8/).
 
 main() writes the files and runs the unmodified reference (oracle/_ref/h264dec, built by oracle/Makefile) on each of them, once, on the
 CPU: `h264dec in.264 out.pip out.yuv`.  tests/golden/slice_parse_cabac_ref.json keeps its verdict: the exit status and the SHA-1 of

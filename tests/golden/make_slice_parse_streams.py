@@ -3,8 +3,9 @@
 
   i8_first.264   I_NxN with the 8x8 transform as the first macroblock of a slice - neither the left nor the upper neighbour is
                  available - beside I8x8 macroblocks that have the left or the upper neighbour.  Every I8x8 macroblock carries at
-                 least one coefficient: one with coded_block_pattern 0 reconstructs 1-2 off the reference around its inner 8x8
-                 edges, which is not this stream's subject
+                 least one coefficient: for one with coded_block_pattern 0 in a CAVLC I slice the reference's filter reads the QP that the
+                 picture before left at its address (its decode_slice.cpp:3328 refreshes the entry under IS_INTRA4x4 only; DESIGN.md
+                 section 6), which is the subject of tests/golden/uncoded_t8/ (make_uncoded_t8_streams.py), not of this stream
 
 main() writes the files and runs the unmodified reference (oracle/_ref/h264dec, built by oracle/Makefile) on each of them, once, on the
 CPU: `h264dec in.264 out.pip out.yuv`.  tests/golden/slice_parse_ref.json keeps its verdict: the exit status and the SHA-1 of the

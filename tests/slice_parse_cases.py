@@ -5,7 +5,7 @@ import random
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-DIRS = ("streams", "edge", "cabac_edge", "escape", "slice_parse")
+DIRS = ("streams", "edge", "cabac_edge", "escape", "slice_parse", "uncoded_t8")
 
 
 def committed():

@@ -116,6 +116,12 @@ def coverage():
                 seen.add("nref2" if nr == 2 else "nref>2" if nr > 2 else "nref1")
             if ((m["flags"] & 1) != 0).any():
                 seen.add("t8")
+                # under a PPS with transform_8x8_mode_flag 1 (a macroblock of the picture has the flag): an inter macroblock without
+                # luma coefficients, whose flag is not transmitted
+                if ((t & 0xf8) != 0)[((m["cbp"] & 15) == 0) & ((m["flags"] & 1) == 0) & cov].any():
+                    seen.add("inter_t8_absent")
+            if ((t == 4) & (m["cbp"] == 0) & cov).any():
+                seen.add(("I8", "cbp0"))                 # no mb_qp_delta: the QP is the one carried from the macroblock before
             if (f.slices["luma_dc_weight"] != 16).any():
                 seen.add("scaling")
             if len(f.slices) > 1:
@@ -132,7 +138,7 @@ def coverage():
 
 WANT = ([(k, l, t) for k in ("I4", "I16", "I8") for l in "L-" for t in "T-"] + [(k, "T", r) for k in ("I4", "I8") for r in ("TR", "noTR")] +
         [(k, m) for k in ("I4", "I8") for m in ("ddl_top", "vl_top")] + list(MB) + ["sub1", "sub2", "sub4", "sub8", "skip_inferred", "skip_zero",
-        "nref2", "nref>2", "t8", "scaling", "multi_slice", "mid_row", "qp_wrap"])
+        "nref2", "nref>2", "t8", "scaling", "multi_slice", "mid_row", "qp_wrap", ("I8", "cbp0"), "inter_t8_absent"])
 
 
 @pytest.mark.parametrize("what", WANT, ids=[str(w) for w in WANT])
