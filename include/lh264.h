@@ -1060,6 +1060,57 @@ long long lh264_decoded_chain_pictures (const lh264_decoded_t* d);
  * walk stops the call.  LH264_E_ARG: sel NULL or an entry the call above refuses, a count pointer NULL, a cap < 0 */
 int lh264_parser_plan (const uint8_t* data, size_t len, const lh264_select_t* sel, int32_t* needed, int cap_needed, int* n_needed,
                        int32_t* delivered, int cap_delivered, int* n_delivered);
+/* lh264_decode_batch_ex6: THE FILTER OF A CALL THAT NAMES A SIZE - LH264_FILTER_AREA (the exact area average defined at
+ * lh264_decode_batch, the default), LH264_FILTER_BILINEAR (a triangle) or LH264_FILTER_BICUBIC (Catmull-Rom), both widened when
+ * shrinking (antialiased), as the resize of an image library is.  The six structs above are frozen; the filter travels in a seventh.
+ * filter == NULL or LH264_FILTER_AREA is lh264_decode_batch_ex5, byte for byte and launch for launch (lh264_decode_batch_ex5 is this call
+ * with NULL).
+ * THE DEFINITION (normative).  One plane of w x h window samples p[y][x] is delivered as ow x oh; a view's source and destination
+ * rectangles take the window's and the output's places exactly as for the area average.  Each axis on its own, all arithmetic in
+ * integers, `/` is floor.
+ *   TAPS of delivered column X (source length w, delivered length ow): m = 2 * max (w, ow); n (x) = |2*ow*x + ow - (2*X + 1)*w|.
+ *     n / (2*ow) is the distance from x to the centre (X + 1/2) * w / ow - 1/2, n / m that distance in units of the kernel, which is
+ *     widened by w / ow when shrinking.
+ *   RAW WEIGHT r (x), for x in 0 .. w - 1 only - nothing outside the window, the crop or the cover rectangle enters; a kernel cut by an
+ *     edge is renormalised by what follows.  Bilinear: r = m - n where n < m, else 0.  Bicubic (a = -1/2, times 2 m^3):
+ *     n < m: r = 3n^3 - 5n^2 m + 2m^3;  m <= n < 2m: r = -n^3 + 5n^2 m - 8n m^2 + 4m^3;  else 0.
+ *   NORMALISED WEIGHT kx (X, x): R = the sum of r over x (> 0: the centre lies inside the window); k = floor ((2^15 * r + R) / (2R))
+ *     (for a negative r: toward minus infinity); e = 2^14 - sum k is added to the tap with the largest r, the lowest x among equals.
+ *     Every row of weights sums to exactly 2^14.  (r reaches 2^48: the library computes them on the host in 128 bits.)
+ *   DELIVERED SAMPLE: ky (Y, y) the same rule with h, oh; H (y, X) = sum_x kx (X, x) * p[y][x] (fits int32);
+ *     S = sum_y ky (Y, y) * H (y, X) (int64); sample = clip (0, 255, (S + 2^27) >> 28), the shift arithmetic.  One rounding, at the end.
+ *   CHROMA: the same rule on the chroma planes with their own lengths; siting is not modelled, as everywhere in this call.
+ * ow == w and oh == h gives the window itself; enlarging, bilinear has two taps a column and one at an edge (edge replication).  The
+ * sum of the absolute weights of a row stays far below 2^31 / 255 and every weight fits int16; the table builder checks both and fails
+ * the call (LH264_E_HIP on every stream) should either ever be false.  Against a float64 antialiased bilinear / bicubic resize,
+ * rounded half up and clipped, the samples differ by at most 1 (informative; the integers above are the definition).
+ * The filter applies to stretch, cover, contain and a caller's crop, in I420, NV12, RGB24, planar RGB and the three float types, in
+ * every output mode, with digests, pick, select, concealment and both parse routes.  Colour and the float types keep acting on the
+ * delivered planes: RGB bytes are the integer function of the I420 bytes the same call delivers without colour, float elements their fma.
+ * LH264_E_ARG, checked before the device with out untouched, beside every case of the calls above: a struct_bytes other than 16, a
+ * filter above 2, a reserved word that is not 0, a filter other than LH264_FILTER_AREA without out_width / out_height (scale_log2
+ * included: it is exclusive with a size). */
+#define LH264_FILTER_AREA     0u
+#define LH264_FILTER_BILINEAR 1u
+#define LH264_FILTER_BICUBIC  2u
+typedef struct lh264_decode_filter {
+  uint32_t struct_bytes;                /* 16                                                                   */
+  uint32_t filter;                      /* LH264_FILTER_*                                                       */
+  uint32_t reserved0, reserved1;        /* 0                                                                    */
+} lh264_decode_filter_t;
+int lh264_decode_batch_ex6 (const uint8_t* const* data, const size_t* len, int n, int threads,
+                            const lh264_decode_opts_t* opts /* NULL = defaults */, const lh264_decode_ext_t* ext /* NULL = no colour */,
+                            const lh264_decode_sample_t* sample /* NULL = uint8 */, const lh264_decode_view_t* view /* NULL = none */,
+                            const lh264_decode_motion_t* motion /* NULL = no fields */, const lh264_decode_select_t* select /* NULL = every picture */,
+                            const lh264_decode_filter_t* filter /* NULL = the area average */, lh264_decoded_t** out);
+/* the LH264_FILTER_* the call used (LH264_E_ARG: d NULL) */
+int lh264_decoded_filter (const lh264_decoded_t* d);
+/* the normalised weights of delivered coordinate X of an axis of src_len samples delivered as dst_len, by the definition above, without
+ * a device: *first is the first tap's index (the lowest x whose weight is not 0), the first min (cap, *n) weights go to k (may be NULL
+ * with cap 0), *n is their number (up to the highest x whose weight is not 0) whatever the cap is.  LH264_E_ARG: LH264_FILTER_AREA
+ * (the area average has no such table) or a filter above 2, src_len outside 1..16384, dst_len outside 1..4096, X outside 0..dst_len - 1,
+ * first or n NULL, cap < 0, k NULL with cap > 0 */
+int lh264_filter_taps (uint32_t filter, int src_len, int dst_len, int X, int32_t* first, int16_t* k, int cap, int* n);
 /* one delivered picture's fields to gather (decode_pack_motion_kernel): its mb_w * mb_h records in raster order, its slice table, where
  * the two blocks begin, and back[slot] for every job reference slot (-1: no picture).  The blocks begin at multiples of 8 bytes.
  * lh264_debug_motion_cpu steps the kernel's code over HOST memory with t = 0, nt = 1; lh264_debug_motion_dev uploads the table (its
@@ -1197,6 +1248,15 @@ typedef struct lh264_pack_place { int32_t x, y, w, h; uint32_t fill, reserved; }
  * without a device: LH264_E_NODEVICE */
 int lh264_debug_view_cpu (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
 int lh264_debug_view_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
+/* the same table delivered as out_w x out_h pictures resampled by `filter` (LH264_FILTER_BILINEAR or _BICUBIC, lh264_decode_batch_ex6):
+ * places NULL - every window to the whole picture - or job k placed by places[k]; colour, std_per_job and sample as above
+ * (decode_pack_filtered_kernel, decode_pack_rgb_filtered_kernel, decode_pack_sample_filtered_kernel).  The weight tables of the jobs'
+ * geometries are built by the call.  lh264_debug_filter_cpu steps the kernels' code over HOST memory with t = 0, nt = 1,
+ * lh264_debug_filter_dev uploads the tables (the jobs' pointers are device pointers), launches the production kernel and returns when
+ * it is through.  LH264_E_ARG: everything lh264_debug_view_cpu refuses (but places may be NULL), a filter that is not 1 or 2;
+ * lh264_debug_filter_dev without a device: LH264_E_NODEVICE */
+int lh264_debug_filter_cpu (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, uint32_t filter, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
+int lh264_debug_filter_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, uint32_t filter, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample);
 /* SHA-1 of n_messages messages given as spans of `bytes`: n_spans triples {message, offset, length}, in order.  The k-th span of
  * every message is fed in step k - on the device (on_device != 0) one launch of sha1_spans_kernel per step, the state carried from
  * step to step as a stream's is from round to round; on_device = 0 steps the same code on the host and needs no device.  A message

@@ -41,6 +41,9 @@
     python -m losslessh264_amd --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096),
                                                             resampled on the device by an exact area average (decode_batch
                                                             (size=(W, H))); the aspect ratio is not kept.  Not with a non-zero --scale
+    python -m losslessh264_amd --decode [--sha1] --size WxH --filter area|bilinear|bicubic ...   the filter of the resampling
+                                                            (decode_batch (filter=...)): area (the default), or an antialiased
+                                                            triangle / Catmull-Rom kernel.  bilinear and bicubic need --size
     python -m losslessh264_amd --decode [--sha1] --rgb rgb24|rgbp [--matrix auto|bt601|bt709] [--range auto|limited|full] ...   RGB pictures,
                                                             colour-converted on the device (decode_batch (colour=...)): out_dir/<name>.rgb
                                                             holds R, G, B per pixel (rgb24) or three planes per picture (rgbp); the
@@ -185,6 +188,7 @@ def restore(src, dst):
 
 
 SIZE_USAGE = "--size: WxH, both even, 2..4096; not with a non-zero --scale"
+FILTER_USAGE = "--filter: area | bilinear | bicubic; bilinear and bicubic with --size only"
 RGB_USAGE = "--rgb: rgb24 | rgbp, not with --nv12; --matrix: auto | bt601 | bt709 and --range: auto | limited | full, with --rgb only"
 SAMPLE_USAGE = "--sample: f32 | f16 | bf16, with --rgb only; --mul and --add: three finite numbers a,b,c (R, G, B), with --sample only"
 VIEW_USAGE = "--fit: cover | contain, with --size only; --fill: y,cb,cr in 0..255, with --fit contain only; --crop: x,y,w,h, four even numbers, x, y >= 0, w, h >= 2"
@@ -248,7 +252,8 @@ def decode(argv):
     dtype, mul, add = None, None, None
     fit, fill, crop = None, None, None
     motion = 0      # 1: --motion, 2: --motion-only
-    while argv and argv[0] in ("--motion", "--motion-only", "--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--at", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
+    filt = "area"
+    while argv and argv[0] in ("--filter", "--motion", "--motion-only", "--fit", "--fill", "--crop", "--nv12", "--conceal", "--sha1", "--device-parse", "--device-parse-cabac", "--scale", "--pick", "--at", "--size", "--rgb", "--matrix", "--range", "--sample", "--mul", "--add"):
         if argv[0] in ("--fit", "--fill", "--crop"):
             value = None
             if len(argv) >= 2:
@@ -299,6 +304,12 @@ def decode(argv):
                 return 2
             argv = argv[2:]
             continue
+        if argv[0] == "--filter":
+            if len(argv) < 2 or argv[1] not in lh._lib.FILTER:
+                print(FILTER_USAGE)
+                return 2
+            filt, argv = argv[1], argv[2:]
+            continue
         if argv[0] == "--at":
             at = parse_at(argv[1]) if len(argv) >= 2 else None
             if at is None:
@@ -345,13 +356,16 @@ def decode(argv):
     if (fit is not None and size is None) or (fill is not None and fit != "contain"):
         print(VIEW_USAGE)
         return 2
+    if filt != "area" and size is None:
+        print(FILTER_USAGE)
+        return 2
     if motion and sha1:
         print("--motion, --motion-only: not with --sha1")
         return 2
     if at is not None and (pick != "all" or conceal not in (None, "off")):
         print(AT_USAGE)
         return 2
-    vkw = dict(fit=fit or "stretch", fill=fill, crop=crop, select=at)
+    vkw = dict(fit=fit or "stretch", fill=fill, crop=crop, select=at, filter=filt)
     ckw = dict(vkw, colour=colour, matrix=matrix or "auto", colour_range=crange or "auto", dtype=dtype or "uint8", mul=mul, add=add)
     if len(argv) < 2 or (pick != "all" and conceal not in (None, "off")):      # (--pick with --conceal: nothing to copy from)
         print(__doc__)

@@ -203,6 +203,10 @@ class Select(C.Structure):          # lh264_select_t: one stream's requested pic
 class DecodeSelect(C.Structure):    # lh264_decode_select_t: what lh264_decode_batch_ex5 takes beside the five frozen structs
     _fields_ = [("struct_bytes", C.c_uint32), ("n_selects", C.c_uint32), ("selects", C.POINTER(Select)), ("reserved", C.c_uint64)]
 assert C.sizeof(Select) == 24 and C.sizeof(DecodeSelect) == 24
+class DecodeFilter(C.Structure):    # lh264_decode_filter_t: what lh264_decode_batch_ex6 takes beside the six frozen structs
+    _fields_ = [("struct_bytes", C.c_uint32), ("filter", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+assert C.sizeof(DecodeFilter) == 16
+FILTER = {"area": 0, "bilinear": 1, "bicubic": 2}         # LH264_FILTER_*
 MOTION_CHUNK_MBS = 64               # LH264_MOTION_CHUNK_MBS: the macroblocks of a row one workgroup of decode_pack_motion_kernel handles
 RESTORE_CABAC_DEVICE = 1
 class RestoreOpts(C.Structure):
@@ -217,6 +221,11 @@ _SIGS.update({
     "lh264_decoded_picture_view": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_decode_batch_ex4": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "lh264_decode_batch_ex5": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decode_batch_ex6": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lh264_decoded_filter": (C.c_int, [C.c_void_p]),
+    "lh264_filter_taps": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "lh264_debug_filter_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "lh264_debug_filter_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
     "lh264_decoded_chain_pictures": (C.c_longlong, [C.c_void_p]),
     "lh264_parser_plan": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     "lh264_decoded_picture_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -28,6 +28,9 @@
 //   lh264dec --decode [--sha1] --size WxH ...   every picture of every stream is written W x H (both even, 2..4096), resampled on the
 //                                       device by an exact area average (lh264.h: out_width, out_height).  Not with a non-zero --scale
 //                                       Not together with --conceal
+//   lh264dec --decode [--sha1] --size WxH --filter area|bilinear|bicubic ...   the filter of that resampling (lh264.h:
+//                                       lh264_decode_batch_ex6): the area average (the default), or an antialiased triangle / Catmull-Rom
+//                                       kernel.  bilinear and bicubic need --size
 //   lh264dec --decode [--sha1] [--crop x,y,w,h] [--size WxH --fit cover|contain [--fill y,cb,cr]] ...   fitted views (lh264.h:
 //                                       lh264_decode_batch_ex3): a rectangle of every picture's window in the window's place; the largest
 //                                       centred part of it with the size's aspect (cover), or the whole of it inside the size, the rest
@@ -247,6 +250,10 @@ static bool parse_ints (const char* text, int n, int top, int* v) {      // "a,b
   return true;
 }
 static const lh264_decode_view_t* view_arg() { return g_view_named ? &g_view : nullptr; }
+// --filter area|bilinear|bicubic: what lh264_decode_batch_ex6 takes beside the six (area: NULL, the call as ever)
+static lh264_decode_filter_t g_filter = {sizeof (lh264_decode_filter_t), LH264_FILTER_AREA, 0, 0};
+static const char* const kFilterUsage = "--filter: area | bilinear | bicubic; bilinear and bicubic with --size only";
+static const lh264_decode_filter_t* filter_arg() { return g_filter.filter != LH264_FILTER_AREA ? &g_filter : nullptr; }
 static const char* out_suffix() {
   return !g_ext.colour ? ".yuv" : g_sample.type == LH264_SAMPLE_F32 ? ".f32" : g_sample.type == LH264_SAMPLE_F16 ? ".f16" : g_sample.type == LH264_SAMPLE_BF16 ? ".bf16" : ".rgb";
 }
@@ -329,7 +336,7 @@ static int decode_files (const std::string& out_dir, const std::vector<std::stri
   if (g_motion == 2) { o.sink = nullptr; o.user = nullptr; o.flags = LH264_DECODE_NO_PICTURES; }
   const lh264_decode_motion_t motion = {sizeof (lh264_decode_motion_t), LH264_MOTION_FIELDS, 0, 0};
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex5 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), g_motion ? &motion : nullptr, select_arg(), h.data());
+  const int rc = lh264_decode_batch_ex6 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), g_motion ? &motion : nullptr, select_arg(), filter_arg(), h.data());
   for (FILE* f : files.f) if (f) fclose (f);
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
@@ -360,7 +367,7 @@ static int decode_sha1_files (const std::string& out_dir, const std::vector<std:
   o.struct_bytes = sizeof (o); o.format = nv12 ? LH264_FMT_NV12 : LH264_FMT_I420; o.conceal = (uint32_t)conceal; o.parse = device_parse ? LH264_PARSE_DEVICE : LH264_PARSE_HOST; o.parse_flags = device_parse == 2 ? LH264_PARSE_FLAG_CABAC : 0; o.scale_log2 = (uint32_t)scale; o.pick = pick; o.out_width = (uint32_t)out_w; o.out_height = (uint32_t)out_h;
   o.flags = LH264_DECODE_SHA1_PICTURES | LH264_DECODE_SHA1_STREAM | LH264_DECODE_NO_PICTURES;
   std::vector<lh264_decoded_t*> h (n, nullptr);
-  const int rc = lh264_decode_batch_ex5 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), nullptr, select_arg(), h.data());
+  const int rc = lh264_decode_batch_ex6 (d.data(), l.data(), n, 0, &o, g_ext.colour ? &g_ext : nullptr, g_sample.type ? &g_sample : nullptr, view_arg(), nullptr, select_arg(), filter_arg(), h.data());
   if (rc != LH264_OK) { fprintf (stderr, "lh264_decode_batch failed: %d%s\n", rc, rc == LH264_E_NODEVICE ? " (no HIP device visible)" : ""); return 1; }
   int ret = 0;
   for (int i = 0; i < n; i++) {
@@ -439,6 +446,11 @@ int main (int argc, char** argv) {
       } else if (first + 1 < argc && !strcmp (argv[first], "--size")) {
         if (!parse_size (argv[first + 1], &out_w, &out_h)) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
         first += 2;
+      } else if (first < argc && !strcmp (argv[first], "--filter")) {
+        const int k = one_of (first + 1 < argc ? argv[first + 1] : "", "area", "bilinear", "bicubic");
+        if (k < 0) { fprintf (stderr, "%s\n", kFilterUsage); return 2; }
+        g_filter.filter = (uint32_t)k;
+        first += 2;
       } else if (first < argc && (!strcmp (argv[first], "--rgb") || !strcmp (argv[first], "--matrix") || !strcmp (argv[first], "--range"))) {
         const char* v = first + 1 < argc ? argv[first + 1] : "";
         const bool rgb = !strcmp (argv[first], "--rgb"), matrix = !strcmp (argv[first], "--matrix");
@@ -480,18 +492,19 @@ int main (int argc, char** argv) {
     if ((g_sample.type && !g_ext.colour) || (!g_sample.type && (add_named || mul_named))) { fprintf (stderr, "%s\n", kSampleUsage); return 2; }
     if (g_sample.type && !mul_named) g_sample.mul[0] = g_sample.mul[1] = g_sample.mul[2] = 1.0f;
     if (out_w && scale) { fprintf (stderr, "%s\n", kSizeUsage); return 2; }
+    if (filter_arg() && !out_w) { fprintf (stderr, "%s\n", kFilterUsage); return 2; }
     if (g_motion && sha1) { fprintf (stderr, "%s\n", kMotionUsage); return 2; }
     if ((g_view.fit != LH264_FIT_STRETCH && !out_w) || (fill_named && g_view.fit != LH264_FIT_CONTAIN)) { fprintf (stderr, "%s\n", kViewUsage); return 2; }
     if (g_view.fit == LH264_FIT_CONTAIN && !fill_named) g_view.fill = 16u | 128u << 8 | 128u << 16;
     if (select_arg() && (pick != LH264_PICK_ALL || conceal != 0)) { fprintf (stderr, "%s\n", kAtUsage); return 2; }
     // (--pick with --conceal: concealment copies from the picture decoded before, which is not decoded)
-    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
+    if (argc < first + 2 || (pick != LH264_PICK_ALL && conceal != 0)) { fprintf (stderr, "usage: %s --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--filter area|bilinear|bicubic] [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]); return 2; }
     std::vector<std::string> srcs;
     for (int i = first + 1; i < argc; i++) srcs.push_back (argv[i]);
     return sha1 ? decode_sha1_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h) : decode_files (argv[first], srcs, nv12, conceal, device_parse, scale, pick, out_w, out_h);
   }
   if (argc < 3) {
-    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
+    fprintf (stderr, "usage: %s [--segment-mbs N] [--escapes] [--tolerant] in.264 out.pip [out.yuv] | in.pip out.264 | in.264 out.lhp | in.lhp out.264 | --batch out_dir in.264... | --decode [--device-parse | --device-parse-cabac] [--sha1 | --motion | --motion-only] [--nv12] [--conceal METHOD | --pick intra|idr | --at SPEC] [--crop x,y,w,h] [--scale N | --size WxH [--filter area|bilinear|bicubic] [--fit cover|contain [--fill y,cb,cr]]] [--rgb rgb24|rgbp [--matrix M] [--range R] [--sample f32|f16|bf16 [--mul a,b,c] [--add a,b,c]]] out_dir in.264...\n", argv[0]);
     return 2;
   }
   const std::string a = argv[1], b = argv[2];

@@ -107,6 +107,30 @@ __global__ void __launch_bounds__ (256) decode_pack_sample_placed_kernel (const 
   lh264pack::pack_band_sample_placed (j, pl, out_w, out_h, layout, (int)std[blockIdx.x], sample, (int)blockIdx.y, (int)threadIdx.x, 256);
 }
 
+// lh264_decode_batch_ex6 with a bilinear or bicubic filter: the planes, RGB and float RGB resampled by the tables filt[job] names.
+// places may be null: every window then goes to the whole out_w x out_h picture.  Kernels of their own: every launch above stays as it was
+__device__ inline lh264_pack_place_t place_of (const lh264_pack_place_t* places, int out_w, int out_h) {
+  return places ? places[blockIdx.x] : lh264_pack_place_t {0, 0, out_w, out_h, 0u, 0u};
+}
+__global__ void __launch_bounds__ (256) decode_pack_filtered_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, const lh264pack::FilterJob* __restrict__ filt, int out_w, int out_h) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.crop_w <= 0 || j.crop_h <= 0 || (int)blockIdx.y * lh264pack::kBandRows >= out_h) return;
+  const lh264pack::FilterJob fj = filt[blockIdx.x];
+  lh264pack::pack_band_filtered (j, fj, place_of (places, out_w, out_h), out_w, out_h, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+__global__ void __launch_bounds__ (256) decode_pack_rgb_filtered_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, const lh264pack::FilterJob* __restrict__ filt, const uint8_t* __restrict__ std, int out_w, int out_h, int layout) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.crop_w <= 0 || j.crop_h <= 0 || (int)blockIdx.y * lh264pack::kBandRows >= out_h) return;
+  const lh264pack::FilterJob fj = filt[blockIdx.x];
+  lh264pack::pack_band_rgb_filtered (j, fj, place_of (places, out_w, out_h), out_w, out_h, layout, (int)std[blockIdx.x], (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+__global__ void __launch_bounds__ (256) decode_pack_sample_filtered_kernel (const lh264_pack_job_t* __restrict__ jobs, const lh264_pack_place_t* __restrict__ places, const lh264pack::FilterJob* __restrict__ filt, const uint8_t* __restrict__ std, int out_w, int out_h, int layout, lh264_decode_sample_t sample) {
+  const lh264_pack_job_t j = jobs[blockIdx.x];
+  if (j.crop_w <= 0 || j.crop_h <= 0 || (int)blockIdx.y * lh264pack::kBandRows >= out_h) return;
+  const lh264pack::FilterJob fj = filt[blockIdx.x];
+  lh264pack::pack_band_sample_filtered (j, fj, place_of (places, out_w, out_h), out_w, out_h, layout, (int)std[blockIdx.x], sample, (int)blockIdx.y, (int)threadIdx.x, 256);
+}
+
 // ---- the digests: SHA-1 of packed pictures where they lie ---------------------------------------------------------------------------
 // One lane per span job, 64 jobs per wave (a message is serial; the width comes from the batch).  The host orders a launch's jobs by
 // descending length, so the lanes of a wave end near one another.  No LDS, no wave waits for another; every bound is the job's.
@@ -149,7 +173,8 @@ struct lh264_decoded {
   std::vector<int32_t> index;                   // per delivered picture: its number among the stream's pictures in decode order
   std::vector<uint8_t> colour;                  // lh264_decode_batch_ex with colour: per delivered picture the standard byte that was applied
   int sample_type = (int)LH264_SAMPLE_U8;       // lh264_decode_batch_ex2: the LH264_SAMPLE_* of the call
-  std::vector<uint8_t> bytes;                   // host mode
+  int filter = (int)LH264_FILTER_AREA;          // lh264_decode_batch_ex6: the LH264_FILTER_* of the call
+  std::vector<uint8_t> bytes;                  // host mode
   DevGrow dev; int device = 0;                  // LH264_DECODE_DEVICE_OUT
   uint32_t sha = 0;                             // the LH264_DECODE_SHA1_* bits of the call
   std::vector<uint8_t> pic_sha;                 // 20 bytes per delivered picture
@@ -221,6 +246,7 @@ struct Arena {
   PinBuf h_mbs[2], h_sparse[2], h_sl[2], h_jobs[2], h_first[2], h_pack[2], h_out[2];
   DevBuf d_std; PinBuf h_std[2];      // lh264_decode_batch_ex with colour: the standard byte of every pack job, beside d_pack
   DevBuf d_place; PinBuf h_place[2];  // lh264_decode_batch_ex3 with LH264_FIT_CONTAIN: the place of every pack job, beside d_pack
+  DevBuf d_filter; PinBuf h_filter[2];  // lh264_decode_batch_ex6 with a filter: a FilterJob per pack job, behind them the weight tables they name
   // lh264_decode_batch_ex4 with fields: the round's motion jobs, its motion blocks and macroblock blocks (downloaded like d_out)
   DevBuf d_mjobs, d_mot[2], d_mbi[2]; PinBuf h_mjobs[2], h_mot[2], h_mbi[2];
   hipEvent_t e_mot[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // around the round's decode_pack_motion_kernel launch (created on first use)
@@ -250,9 +276,9 @@ struct Arena {
   }
   // every buffer of the arena, once: dev (a DevBuf), pin (a PinBuf).  A buffer that is declared above is named here, and nowhere else
   template <typename FD, typename FP> void each_buffer (FD dev, FP pin) const {
-    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_out[0], &d_out[1], &d_std, &d_place, &d_mjobs, &d_mot[0], &d_mot[1], &d_mbi[0], &d_mbi[1],
+    for (const DevBuf* b : {&d_mbs, &d_coef, &d_sparse, &d_sl, &d_jobs, &d_first, &d_pack, &d_out[0], &d_out[1], &d_std, &d_place, &d_filter, &d_mjobs, &d_mot[0], &d_mot[1], &d_mbi[0], &d_mbi[1],
                             &d_sjobs, &d_dig, &d_rec, &d_state, &d_pbytes, &d_ptasks, &d_pres, &d_pmbs, &d_pcoef}) dev (*b);
-    for (const PinBuf* two : {h_mbs, h_sparse, h_sl, h_jobs, h_first, h_pack, h_out, h_std, h_place, h_mjobs, h_mot, h_mbi, h_sjobs, h_dig}) { pin (two[0]); pin (two[1]); }
+    for (const PinBuf* two : {h_mbs, h_sparse, h_sl, h_jobs, h_first, h_pack, h_out, h_std, h_place, h_filter, h_mjobs, h_mot, h_mbi, h_sjobs, h_dig}) { pin (two[0]); pin (two[1]); }
     for (const PinBuf* b : {&h_pbytes, &h_ptasks, &h_pres}) pin (*b);
   }
   size_t device_bytes() const { size_t n = pics.bytes; each_buffer ([&] (const DevBuf& b) { n += b.cap; }, [] (const PinBuf&) {}); return n; }
@@ -402,7 +428,7 @@ double g_parse_timing[2] = {0, 0};      // of g_timing[1]: the device parse stag
 const uint32_t kDefaultRoundPictures = 8;
 const uint64_t kDefaultGroupMbs = 1000000;
 
-// ---- the pack launch: one descriptor, one ladder over the eight kernels ------------------------------------------------------------
+// ---- the pack launch: one descriptor, one ladder over the eleven kernels -----------------------------------------------------------
 // what every entry point asks of a pack job: planes and a destination, an even window of up to max_side a side at an even place, I420
 // or NV12, reserved (the job's scale) in 0..max_reserved.  A caller's stricter conditions stand beside its call
 struct PackLimits { int max_side, max_reserved; };
@@ -419,10 +445,14 @@ struct PackLaunch {
   const lh264_pack_job_t* jobs; const lh264_pack_place_t* places; const uint8_t* std;
   int n, max_bands, out_w, out_h, colour, scale;
   const lh264_decode_sample_t* sample;
+  const lh264pack::FilterJob* filt;     // lh264_decode_batch_ex6 with a bilinear or bicubic filter: the jobs' tables; else null
 };
 bool launch_pack (const PackLaunch& p, hipStream_t st) {
   const dim3 grid ((unsigned)p.n, (unsigned)p.max_bands), wg (256);
-  if (p.places && p.sample) hipLaunchKernelGGL (decode_pack_sample_placed_kernel, grid, wg, 0, st, p.jobs, p.places, p.std, p.out_w, p.out_h, p.colour, *p.sample);
+  if (p.filt && p.sample) hipLaunchKernelGGL (decode_pack_sample_filtered_kernel, grid, wg, 0, st, p.jobs, p.places, p.filt, p.std, p.out_w, p.out_h, p.colour, *p.sample);
+  else if (p.filt && p.colour) hipLaunchKernelGGL (decode_pack_rgb_filtered_kernel, grid, wg, 0, st, p.jobs, p.places, p.filt, p.std, p.out_w, p.out_h, p.colour);
+  else if (p.filt) hipLaunchKernelGGL (decode_pack_filtered_kernel, grid, wg, 0, st, p.jobs, p.places, p.filt, p.out_w, p.out_h);
+  else if (p.places && p.sample) hipLaunchKernelGGL (decode_pack_sample_placed_kernel, grid, wg, 0, st, p.jobs, p.places, p.std, p.out_w, p.out_h, p.colour, *p.sample);
   else if (p.places && p.colour) hipLaunchKernelGGL (decode_pack_rgb_placed_kernel, grid, wg, 0, st, p.jobs, p.places, p.std, p.out_w, p.out_h, p.colour);
   else if (p.places) hipLaunchKernelGGL (decode_pack_placed_kernel, grid, wg, 0, st, p.jobs, p.places, p.out_w, p.out_h);
   else if (p.sample) hipLaunchKernelGGL (decode_pack_sample_kernel, grid, wg, 0, st, p.jobs, p.std, p.out_w, p.out_h, p.colour, *p.sample);
@@ -437,13 +467,101 @@ bool launch_motion (const lh264_motion_job_t* jobs, int n, int units, hipStream_
   hipLaunchKernelGGL (decode_pack_motion_kernel, dim3 ((unsigned)n, (unsigned)units), dim3 (256), 0, st, jobs);
   return hipGetLastError() == hipSuccess;
 }
+// ---- the filter tables: lh264_decode_batch_ex6 (the definition: include/lh264.h at that call) -----------------------------------------
+// One axis: src_len source samples delivered as dst_len, every delivered coordinate's taps by the definition.  The raw weights reach
+// 2^48 and their scaled quotients need more than 64 bits: 128-bit integers, here and nowhere on the device.  ent gets {first, count,
+// offset into k} per coordinate, k the weights, zero weights at a row's ends trimmed.  false: a property the kernels rely on does not
+// hold (a weight outside int16, a row whose absolute weights times 255 leave int32) - no shape in range is known to do that
+bool filter_axis (uint32_t filter, int src_len, int dst_len, std::vector<int32_t>* ent, std::vector<int16_t>* k) {
+  typedef __int128 wide;
+  const int64_t w = src_len, ow = dst_len, m = 2 * std::max (w, ow), support = filter == LH264_FILTER_BILINEAR ? m : 2 * m;
+  auto floor_div = [] (int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && (a < 0)) ? q - 1 : q; };      // (b > 0)
+  std::vector<int64_t> r;
+  std::vector<int32_t> kk;
+  for (int64_t X = 0; X < ow; X++) {
+    const int64_t c = (2 * X + 1) * w - ow;                                   // n (x) = |2*ow*x - c|
+    const int64_t x0 = std::max<int64_t> (0, floor_div (c - support, 2 * ow) + 1), x1 = std::min<int64_t> (w - 1, floor_div (c + support - 1, 2 * ow));
+    if (x1 < x0) return false;
+    r.clear();
+    wide R = 0;
+    size_t best = 0;
+    for (int64_t x = x0; x <= x1; x++) {
+      const int64_t d = 2 * ow * x - c, n = d < 0 ? -d : d;
+      int64_t v;
+      if (filter == LH264_FILTER_BILINEAR) v = n < m ? m - n : 0;
+      else v = n < m ? 3 * n * n * n - 5 * n * n * m + 2 * m * m * m : n < 2 * m ? -n * n * n + 5 * n * n * m - 8 * n * m * m + 4 * m * m * m : 0;
+      if (!r.empty() && v > r[best]) best = r.size();                         // (the largest, the lowest x among equals)
+      r.push_back (v);
+      R += v;
+    }
+    if (R <= 0) return false;
+    kk.assign (r.size(), 0);
+    int64_t sum = 0;
+    for (size_t i = 0; i < r.size(); i++) {
+      const wide num = ((wide)r[i] << 15) + R, den = 2 * R;
+      wide q = num / den;
+      if (num % den != 0 && num < 0) q--;                                     // floor, toward minus infinity
+      kk[i] = (int32_t)q;
+      sum += kk[i];
+    }
+    kk[best] += (int32_t) (16384 - sum);
+    size_t a = 0, b = kk.size();
+    while (a < b && kk[a] == 0) a++;
+    while (b > a && kk[b - 1] == 0) b--;
+    int64_t mag = 0;
+    for (size_t i = a; i < b; i++) { if (kk[i] < -32768 || kk[i] > 32767) return false; mag += kk[i] < 0 ? -kk[i] : kk[i]; }
+    if (a == b || mag * 255 > 0x7fffffff) return false;
+    ent->push_back ((int32_t) (x0 + (int64_t)a)); ent->push_back ((int32_t) (b - a)); ent->push_back ((int32_t)k->size());
+    for (size_t i = a; i < b; i++) k->push_back ((int16_t)kk[i]);
+  }
+  return true;
+}
+// the tables of one call: one per distinct (src_len, dst_len), laid out one behind the other as the device reads them - 3 * dst_len
+// int32 entries, then the int16 weights, padded to 4 bytes
+struct FilterPlan {
+  uint32_t filter = LH264_FILTER_AREA;
+  std::map<std::pair<int, int>, size_t> at;     // where the table of a geometry begins in blob
+  std::vector<uint8_t> blob;
+  bool add (int src_len, int dst_len) {
+    if (at.count ({src_len, dst_len})) return true;
+    std::vector<int32_t> ent; std::vector<int16_t> k;
+    if (!filter_axis (filter, src_len, dst_len, &ent, &k)) return false;
+    if (k.size() & 1) k.push_back (0);
+    const size_t off = blob.size();
+    blob.resize (off + ent.size() * 4 + k.size() * 2);
+    memcpy (&blob[off], ent.data(), ent.size() * 4);
+    memcpy (&blob[off + ent.size() * 4], k.data(), k.size() * 2);
+    at[{src_len, dst_len}] = off;
+    return true;
+  }
+  // the four tables of a job whose w x h window is resampled to pw x ph (all even)
+  bool add_job (int w, int h, int pw, int ph) { return add (w, pw) && add (h, ph) && add (w >> 1, pw >> 1) && add (h >> 1, ph >> 1); }
+  lh264pack::FilterAxis axis (const uint8_t* base, int src_len, int dst_len) const {
+    const uint8_t* t = base + at.at ({src_len, dst_len});
+    return {(const int32_t*)t, (const int16_t*) (t + (size_t)dst_len * 12)};
+  }
+  // ... as the job's record, the blob lying (or going to lie) at base
+  lh264pack::FilterJob job (const uint8_t* base, int w, int h, int pw, int ph) const {
+    return {axis (base, w, pw), axis (base, h, ph), axis (base, w >> 1, pw >> 1), axis (base, h >> 1, ph >> 1)};
+  }
+};
+
 // the lh264_debug_*_dev entry points: the host tables p names go up, one launch on the null stream is waited for, the tables go
+// (fp: the filter tables of a filtered launch, whose job records p.filt were written for a blob at address 0)
 bool upload (DevBuf& d, const void* src, size_t bytes) { return d.alloc (bytes) && hipMemcpy (d.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
-int debug_launch (PackLaunch p) {
+int debug_launch (PackLaunch p, const FilterPlan* fp = nullptr) {
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   if (!p.n) return LH264_OK;
-  DevBuf d_jobs, d_places, d_std;
+  DevBuf d_jobs, d_places, d_std, d_blob, d_filt;
   bool ok = upload (d_jobs, p.jobs, (size_t)p.n * sizeof (lh264_pack_job_t)) && (!p.places || upload (d_places, p.places, (size_t)p.n * sizeof (lh264_pack_place_t))) && (!p.std || upload (d_std, p.std, (size_t)p.n));
+  if (ok && fp) {
+    ok = upload (d_blob, fp->blob.data(), fp->blob.size());
+    std::vector<lh264pack::FilterJob> rec (p.filt, p.filt + p.n);
+    const uintptr_t base = (uintptr_t)d_blob.p;
+    for (lh264pack::FilterJob& f : rec) for (lh264pack::FilterAxis* a : {&f.lx, &f.ly, &f.cx, &f.cy}) { a->ent = (const int32_t*) ((uintptr_t)a->ent + base); a->k = (const int16_t*) ((uintptr_t)a->k + base); }
+    ok = ok && upload (d_filt, rec.data(), rec.size() * sizeof (lh264pack::FilterJob));
+    p.filt = d_filt.as<lh264pack::FilterJob>();
+  }
   p.jobs = d_jobs.as<lh264_pack_job_t>(); p.places = d_places.as<lh264_pack_place_t>(); p.std = d_std.as<uint8_t>();      // (null where none went up)
   ok = ok && launch_pack (p, nullptr) && hipStreamSynchronize (nullptr) == hipSuccess;
   return ok ? LH264_OK : LH264_E_HIP;
@@ -472,6 +590,7 @@ struct DecodeConfig {
   int out_w, out_h;                                 // 0, 0: the window (or its scale); else decode_pack_resized_kernel
   uint32_t fit, fill; std::vector<lh264_rect_t> crops;      // the view: the fit, the bars' fill, and every stream's crop (w = 0: none)
   bool placed;                                      // LH264_FIT_CONTAIN: the placed kernels and a place per pack job
+  uint32_t filter;                                  // LH264_FILTER_AREA: the kernels above; else the filtered kernels and a FilterJob per pack job
   int colour; uint32_t matrix, range;               // 0: the planes; else decode_pack_rgb_kernel, 3 bytes per delivered luma sample
   int stype; size_t es; lh264_decode_sample_t sample;       // 0: bytes; else decode_pack_sample_kernel in decode_pack_rgb_kernel's place, es bytes per element
   uint32_t fields, sha_bits;                        // fields 0: the call is lh264_decode_batch_ex3; else decode_pack_motion_kernel gathers the round's records
@@ -492,8 +611,10 @@ struct DecodeConfig {
 };
 
 // LH264_OK, or LH264_E_ARG for arguments the call does not take
-int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, int n, DecodeConfig* cfg) {
+int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, const lh264_decode_filter_t* filter, int n, DecodeConfig* cfg) {
   DecodeConfig& c = *cfg;
+  if (filter && (filter->struct_bytes != sizeof (lh264_decode_filter_t) || filter->filter > LH264_FILTER_BICUBIC || filter->reserved0 != 0 || filter->reserved1 != 0)) return LH264_E_ARG;
+  c.filter = filter ? filter->filter : LH264_FILTER_AREA;
   if (select && (select->struct_bytes != sizeof (lh264_decode_select_t) || select->reserved != 0 || (select->n_selects != 0 && select->n_selects != 1 && select->n_selects != (uint32_t)n) ||
                  (select->n_selects != 0 && !select->selects))) return LH264_E_ARG;
   if (select) for (uint32_t k = 0; k < select->n_selects; k++) if (!select_entry_ok (select->selects[k])) return LH264_E_ARG;
@@ -545,6 +666,7 @@ int decode_config (const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ex
   if (v6 && (opts->reserved4 != 0 || opts->reserved5 != 0 || (sized && (!lh264pack::size_ok (opts->out_width, opts->out_height) || c.scale != 0)))) return LH264_E_ARG;
   c.out_w = sized ? (int)opts->out_width : 0; c.out_h = sized ? (int)opts->out_height : 0;
   if (c.fit != LH264_FIT_STRETCH && !c.out_w) return LH264_E_ARG;
+  if (c.filter != LH264_FILTER_AREA && !c.out_w) return LH264_E_ARG;
   c.placed = c.fit == LH264_FIT_CONTAIN;
   if (!Parser::conceal_method_ok (c.conceal)) return LH264_E_ARG;           // a method that is not provided (FRAME_COPY), or no method at all
   c.format = opts ? (int)opts->format : LH264_FMT_I420;
@@ -587,6 +709,7 @@ struct DecodeCall {
   struct Place { size_t mb0, sl0, sp0, job0; };
   std::vector<Place> place;
   std::vector<std::vector<int>> slot_of;
+  FilterPlan filters {cfg.filter, {}, {}};                            // a filter: the tables of every geometry the call has met so far
   size_t n_hmbs = 0, n_sl = 0, n_sp = 0, n_jobs = 0, n_out = 0, n_mjobs = 0, n_sjobs = 0, dig_bytes = 0;
   int n_launch = 0, max_units = 1, max_w = 1, max_h = 1, max_bands = 1;
   std::vector<int32_t> chain_first;                // the round's jobs that begin a chain of the lh264_recon_chains launch
@@ -860,7 +983,7 @@ struct DecodeCall {
     size_t n_mbs = 0;
     n_hmbs = n_sl = n_sp = n_jobs = n_out = n_mjobs = 0;
     max_units = max_w = max_h = max_bands = 1;
-    bool alloc_ok = true, offsets_ok = true;
+    bool alloc_ok = true, offsets_ok = true, tables_ok = true;
     for (auto& sp : active) {
       DStream& s = *sp;
       if (s.sel.empty()) continue;
@@ -896,6 +1019,7 @@ struct DecodeCall {
       n_mbs += m; n_hmbs += mh; n_sl += sl; n_sp += ents; n_jobs += s.sel.size();
       for (size_t q = 0; q < plan.size(); q++) {
         max_bands = std::max (max_bands, bands_of (plan[q].oh));
+        if (cfg.filter && !s.sel[q]->frozen && !filters.add_job (plan[q].src.w, plan[q].src.h, plan[q].dst.w, plan[q].dst.h)) tables_ok = false;
         // a float type: every picture, and so every row, begins at a multiple of 4 bytes - the chain at one of 16, a picture 3*ow*oh*es
         // bytes behind the one before (decode_pack_sample_kernel stores nothing narrower)
         if (cfg.stype && !s.sel[q]->frozen && ((plan[q].bytes | rd.out_bytes) & 3)) offsets_ok = false;
@@ -914,7 +1038,8 @@ struct DecodeCall {
                A.h_mbs[rb].alloc (n_hmbs * sizeof (lh264_mb_t)) && A.h_sparse[rb].alloc (n_sp * 8) && A.h_sl[rb].alloc (n_sl * sizeof (lh264_slice_t)) &&
                A.h_jobs[rb].alloc (n_jobs * sizeof (lh264_frame_job_t)) && A.h_first[rb].alloc ((size_t) (n_launch + 1) * 4) && A.h_pack[rb].alloc (n_jobs * sizeof (lh264_pack_job_t)) &&
                (!cfg.colour || (A.d_std.alloc (n_jobs) && A.h_std[rb].alloc (n_jobs))) &&
-               (!cfg.placed || (A.d_place.alloc (n_jobs * sizeof (lh264_pack_place_t)) && A.h_place[rb].alloc (n_jobs * sizeof (lh264_pack_place_t))));
+               (!cfg.placed || (A.d_place.alloc (n_jobs * sizeof (lh264_pack_place_t)) && A.h_place[rb].alloc (n_jobs * sizeof (lh264_pack_place_t)))) &&
+               (!cfg.filter || (A.d_filter.alloc (filter_bytes()) && A.h_filter[rb].alloc (filter_bytes())));
     if (cfg.fields) alloc_ok = alloc_ok && A.d_mjobs.alloc (n_mjobs * sizeof (lh264_motion_job_t)) && A.h_mjobs[rb].alloc (n_mjobs * sizeof (lh264_motion_job_t)) &&
                                A.d_mot[rb].alloc (rd.mot_bytes) && A.d_mbi[rb].alloc (rd.mbi_bytes) && (cfg.device_out || (A.h_mot[rb].alloc (rd.mot_bytes) && A.h_mbi[rb].alloc (rd.mbi_bytes)));
     for (int k = 0; k < 2 && cfg.fields && alloc_ok; k++) if (!A.e_mot[rb][k]) alloc_ok = hipEventCreate (&A.e_mot[rb][k]) == hipSuccess;
@@ -943,17 +1068,21 @@ struct DecodeCall {
         slot_of[c].push_back (at);
       }
     }
-    if (alloc_ok && offsets_ok) return true;
-    fail_device (offsets_ok ? "device allocation failed" : "a float picture would not begin at a multiple of 4 bytes");
+    if (alloc_ok && offsets_ok && tables_ok) return true;
+    fail_device (!tables_ok ? "a filter table leaves the range the kernels take" : offsets_ok ? "device allocation failed" : "a float picture would not begin at a multiple of 4 bytes");
     for (auto& s : active) s->sel.clear();
     return false;
   }
+
+  // a filter: the round's FilterJob records, behind them every table the call has built so far
+  size_t filter_bytes() const { return n_jobs * sizeof (lh264pack::FilterJob) + filters.blob.size(); }
 
   // ---- staging (host threads): records to the page-locked buffers, the job tables; then what the round leaves with its streams
   void stage_round() {
     Round& rd = rounds[rb];
     const int n_chains = (int)rd.chains.size();
     run_parallel (n_chains, threads, [&] (int c) { stage_chain (c); });
+    if (cfg.filter) memcpy (A.h_filter[rb].as<uint8_t>() + n_jobs * sizeof (lh264pack::FilterJob), filters.blob.data(), filters.blob.size());
     int32_t* h_first = A.h_first[rb].as<int32_t>();
     std::copy (chain_first.begin(), chain_first.end(), h_first);
     h_first[n_launch] = (int32_t)n_jobs;
@@ -999,6 +1128,8 @@ struct DecodeCall {
     uint8_t* h_std = cfg.colour ? A.h_std[rb].as<uint8_t>() : nullptr;
     lh264_pack_place_t* h_place = cfg.placed ? A.h_place[rb].as<lh264_pack_place_t>() : nullptr;
     lh264_motion_job_t* h_mjobs = cfg.fields ? A.h_mjobs[rb].as<lh264_motion_job_t>() : nullptr;
+    lh264pack::FilterJob* h_filt = cfg.filter ? A.h_filter[rb].as<lh264pack::FilterJob>() : nullptr;
+    const uint8_t* d_tables = A.d_filter.as<uint8_t>() + n_jobs * sizeof (lh264pack::FilterJob);      // (where the tables will lie on the device)
     const bool picking = cfg.picking, motion_only = cfg.motion_only;
     RoundChain& rc = rounds[rb].chains[c];
     DStream& s = *rc.s;
@@ -1045,6 +1176,7 @@ struct DecodeCall {
       lh264_pack_job_t& pj = h_pack[j];
       memset (&pj, 0, sizeof (pj));
       if (h_place) memset (&h_place[j], 0, sizeof (lh264_pack_place_t));
+      if (h_filt) memset (&h_filt[j], 0, sizeof (lh264pack::FilterJob));
       pj.reserved = cfg.scale;
       const uint8_t std_byte = cfg.standard (f);      // (a picture select let through: its standard is defined)
       if (h_std) h_std[j] = std_byte & 3;
@@ -1055,6 +1187,7 @@ struct DecodeCall {
       // the picture's view: the source rectangle takes the window's place in the job, the destination goes to the job's place
       const PicPlan& v = rc.plan[q];
       pj.crop_x = f.crop_x + v.src.x; pj.crop_y = f.crop_y + v.src.y; pj.crop_w = v.src.w; pj.crop_h = v.src.h; pj.format = cfg.format;
+      if (h_filt) h_filt[j] = filters.job (d_tables, v.src.w, v.src.h, v.dst.w, v.dst.h);
       if (h_place) { h_place[j].x = v.dst.x; h_place[j].y = v.dst.y; h_place[j].w = v.dst.w; h_place[j].h = v.dst.h; h_place[j].fill = cfg.fill; }
       for (const lh264_rect_t* r : {&v.src, &v.dst}) { rc.view.push_back (r->x); rc.view.push_back (r->y); rc.view.push_back (r->w); rc.view.push_back (r->h); }
       lh264_decoded_pic_t dp;
@@ -1091,7 +1224,7 @@ struct DecodeCall {
     // (motion only: the records and the slice tables are all the gather reads)
     bool ok = up (A.d_mbs, A.h_mbs[rb], n_hmbs * sizeof (lh264_mb_t)) && (motion_only || up (A.d_sparse, A.h_sparse[rb], n_sp * 8)) && up (A.d_sl, A.h_sl[rb], n_sl * sizeof (lh264_slice_t)) &&
               (motion_only || (up (A.d_jobs, A.h_jobs[rb], n_jobs * sizeof (lh264_frame_job_t)) && up (A.d_first, A.h_first[rb], (size_t) (n_launch + 1) * 4) && up (A.d_pack, A.h_pack[rb], n_jobs * sizeof (lh264_pack_job_t)) &&
-                               (!cfg.colour || up (A.d_std, A.h_std[rb], n_jobs)) && (!cfg.placed || up (A.d_place, A.h_place[rb], n_jobs * sizeof (lh264_pack_place_t))) &&
+                               (!cfg.colour || up (A.d_std, A.h_std[rb], n_jobs)) && (!cfg.placed || up (A.d_place, A.h_place[rb], n_jobs * sizeof (lh264_pack_place_t))) && (!cfg.filter || up (A.d_filter, A.h_filter[rb], filter_bytes())) &&
                                (n_hmbs == 0 || hipMemsetAsync (A.d_coef.p, 0, n_hmbs * 768, st) == hipSuccess)));
     // the fields need the records only: the gather goes in front of the reconstruct launch
     if (ok && n_mjobs) {
@@ -1103,7 +1236,7 @@ struct DecodeCall {
     if (ok && !motion_only) ok = lh264_recon_chains (A.d_jobs.as<lh264_frame_job_t>(), A.d_first.as<int32_t>(), n_launch, max_w, max_h, st) == LH264_OK;
     if (ok && !motion_only) { n_rounds++; n_launched += n_launch; n_launched_jobs += (long long)n_jobs; }
     if (ok && !motion_only) ok = launch_pack ({A.d_pack.as<lh264_pack_job_t>(), cfg.placed ? A.d_place.as<lh264_pack_place_t>() : nullptr, A.d_std.as<uint8_t>(), (int)n_jobs, max_bands,
-                                               cfg.out_w, cfg.out_h, cfg.colour, cfg.scale, cfg.stype ? &cfg.sample : nullptr}, st);
+                                               cfg.out_w, cfg.out_h, cfg.colour, cfg.scale, cfg.stype ? &cfg.sample : nullptr, cfg.filter ? A.d_filter.as<lh264pack::FilterJob>() : nullptr}, st);
     if (ok && cfg.sha) {
       ok = up (A.d_sjobs, A.h_sjobs[rb], n_sjobs * sizeof (lh264_sha1_job_t));
       if (ok && n_sjobs) { hipLaunchKernelGGL (sha1_spans_kernel, dim3 ((unsigned) ((n_sjobs + 63) / 64)), dim3 (64), 0, st, A.d_sjobs.as<lh264_sha1_job_t>(), (int)n_sjobs); ok = hipGetLastError() == hipSuccess; }
@@ -1362,6 +1495,63 @@ int lh264_debug_view_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t
   return debug_launch ({jobs, places, colour ? std_per_job : nullptr, n, max_bands, out_w, out_h, colour, 0, typed ? sample : nullptr});
 }
 
+int lh264_filter_taps (uint32_t filter, int src_len, int dst_len, int X, int32_t* first, int16_t* k, int cap, int* n) {
+  if ((filter != LH264_FILTER_BILINEAR && filter != LH264_FILTER_BICUBIC) || src_len < 1 || src_len > kFrontEndSide || dst_len < 1 || dst_len > 4096 || X < 0 || X >= dst_len ||
+      !first || !n || cap < 0 || (cap && !k)) return LH264_E_ARG;
+  std::vector<int32_t> ent; std::vector<int16_t> w;
+  if (!filter_axis (filter, src_len, dst_len, &ent, &w)) return LH264_E_UNSUPPORTED;
+  *first = ent[3 * (size_t)X]; *n = ent[3 * (size_t)X + 1];
+  for (int i = 0; i < *n && i < cap; i++) k[i] = w[(size_t)ent[3 * (size_t)X + 2] + i];
+  return LH264_OK;
+}
+
+// a table the filtered entry points take: what lh264_debug_view_* take, but places may be NULL, and a filter that has tables
+static bool filter_jobs_ok (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, uint32_t filter, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample, int* max_bands) {
+  if ((filter != LH264_FILTER_BILINEAR && filter != LH264_FILTER_BICUBIC) || !lh264pack::size_ok (out_w, out_h)) return false;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  if (sample && !sample_ok (sample)) return false;
+  if (typed ? !sample_jobs_ok (jobs, n, out_w, out_h, colour, std_per_job, sample, max_bands) :
+      colour ? !rgb_jobs_ok (jobs, n, out_w, out_h, colour, std_per_job, max_bands) : !resize_jobs_ok (jobs, n, out_w, out_h)) return false;
+  *max_bands = bands_of (out_h);
+  for (int k = 0; k < n && places; k++) if (!lh264pack::place_ok (places[k], out_w, out_h)) return false;
+  return true;
+}
+// fp gets the tables of every job's geometry, rec the jobs' records: for the blob where it lies in host memory, or (at_zero) for a blob
+// at address 0, which debug_launch moves to where it went on the device
+static bool filter_tables (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, FilterPlan* fp, std::vector<lh264pack::FilterJob>* rec, bool at_zero) {
+  for (int k = 0; k < n; k++) if (!fp->add_job (jobs[k].crop_w, jobs[k].crop_h, places ? places[k].w : out_w, places ? places[k].h : out_h)) return false;
+  const uint8_t* base = at_zero ? nullptr : fp->blob.data();
+  for (int k = 0; k < n; k++) rec->push_back (fp->job (base, jobs[k].crop_w, jobs[k].crop_h, places ? places[k].w : out_w, places ? places[k].h : out_h));
+  return true;
+}
+
+int lh264_debug_filter_cpu (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, uint32_t filter, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!filter_jobs_ok (jobs, places, n, out_w, out_h, filter, colour, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  FilterPlan fp {filter, {}, {}};
+  std::vector<lh264pack::FilterJob> rec;
+  if (!filter_tables (jobs, places, n, out_w, out_h, &fp, &rec, false)) return LH264_E_UNSUPPORTED;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  for (int k = 0; k < n; k++) for (int band = 0; band < max_bands; band++) {
+    const lh264_pack_place_t pl = places ? places[k] : lh264_pack_place_t {0, 0, out_w, out_h, 0u, 0u};
+    if (typed) lh264pack::pack_band_sample_filtered (jobs[k], rec[k], pl, out_w, out_h, colour, std_per_job[k], *sample, band, 0, 1);
+    else if (colour) lh264pack::pack_band_rgb_filtered (jobs[k], rec[k], pl, out_w, out_h, colour, std_per_job[k], band, 0, 1);
+    else lh264pack::pack_band_filtered (jobs[k], rec[k], pl, out_w, out_h, band, 0, 1);
+  }
+  return LH264_OK;
+}
+
+int lh264_debug_filter_dev (const lh264_pack_job_t* jobs, const lh264_pack_place_t* places, int n, int out_w, int out_h, uint32_t filter, int colour, const uint8_t* std_per_job, const lh264_decode_sample_t* sample) {
+  int max_bands = 0;
+  if (!filter_jobs_ok (jobs, places, n, out_w, out_h, filter, colour, std_per_job, sample, &max_bands)) return LH264_E_ARG;
+  if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
+  FilterPlan fp {filter, {}, {}};
+  std::vector<lh264pack::FilterJob> rec;
+  if (!filter_tables (jobs, places, n, out_w, out_h, &fp, &rec, true)) return LH264_E_UNSUPPORTED;
+  const bool typed = sample && sample->type != LH264_SAMPLE_U8;
+  return debug_launch ({jobs, places, colour ? std_per_job : nullptr, n, max_bands, out_w, out_h, colour, 0, typed ? sample : nullptr, rec.data()}, &fp);
+}
+
 int lh264_debug_motion_cpu (const lh264_motion_job_t* jobs, int n) {
   if (!jobs || n < 0) return LH264_E_ARG;
   for (int k = 0; k < n; k++) if (!lh264pack::motion_job_ok (jobs[k])) return LH264_E_ARG;
@@ -1461,15 +1651,19 @@ int lh264_decode_batch_ex4 (const uint8_t* const* data, const size_t* len, int n
 }
 
 int lh264_decode_batch_ex5 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, lh264_decoded_t** out) {
+  return lh264_decode_batch_ex6 (data, len, n, threads, opts, ext, sample, view, motion, select, nullptr, out);
+}
+
+int lh264_decode_batch_ex6 (const uint8_t* const* data, const size_t* len, int n, int threads, const lh264_decode_opts_t* opts, const lh264_decode_ext_t* ext, const lh264_decode_sample_t* sample, const lh264_decode_view_t* view, const lh264_decode_motion_t* motion, const lh264_decode_select_t* select, const lh264_decode_filter_t* filter, lh264_decoded_t** out) {
   if (!data || !len || !out || n < 0) return LH264_E_ARG;
   DecodeConfig cfg;
-  if (decode_config (opts, ext, sample, view, motion, select, n, &cfg) != LH264_OK) return LH264_E_ARG;      // (every refusal of an argument comes before the device is asked for)
+  if (decode_config (opts, ext, sample, view, motion, select, filter, n, &cfg) != LH264_OK) return LH264_E_ARG;      // (every refusal of an argument comes before the device is asked for)
   if (lh264_device_count() <= 0) return LH264_E_NODEVICE;
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   if (threads < 1) threads = 1;
   int device = 0;
   if (hipGetDevice (&device) != hipSuccess || device < 0 || device >= lh264host::kMaxDevices) return LH264_E_ARG;
-  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sample_type = cfg.stype; out[i]->fields = cfg.fields; out[i]->sha = cfg.sha_bits; }
+  for (int i = 0; i < n; i++) { out[i] = new lh264_decoded(); out[i]->device = device; out[i]->sample_type = cfg.stype; out[i]->filter = (int)cfg.filter; out[i]->fields = cfg.fields; out[i]->sha = cfg.sha_bits; }
   auto arena_lock = g_arena.lock (device);
   Arena& A = arena_lock.get();
   if (!A.init()) { for (int i = 0; i < n; i++) { out[i]->status = LH264_E_HIP; out[i]->error = "creating the HIP streams failed"; } return LH264_OK; }
@@ -1558,6 +1752,7 @@ int lh264_decoded_picture_colour (const lh264_decoded_t* d, int idx, uint32_t* m
   return LH264_OK;
 }
 int lh264_decoded_sample_type (const lh264_decoded_t* d) { return d ? d->sample_type : LH264_E_ARG; }
+int lh264_decoded_filter (const lh264_decoded_t* d) { return d ? d->filter : LH264_E_ARG; }
 long long lh264_decoded_parsed_slices (const lh264_decoded_t* d) { return d ? (long long)d->parsed_slices : 0; }
 long long lh264_decoded_chain_pictures (const lh264_decoded_t* d) { return d ? (long long)d->chain_pictures : 0; }
 int lh264_decoded_picture_index (const lh264_decoded_t* d, int idx) {

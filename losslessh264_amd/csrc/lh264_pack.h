@@ -265,8 +265,15 @@ __host__ __device__ inline uint8_t rounded_mean (uint64_t S, uint64_t D) {
   while (r >= (int64_t)den) { q++; r -= (int64_t)den; }
   return (uint8_t)q;
 }
-// one plane as the resize step sees it: the window's first sample, its size, the delivered size
-struct ResizePlane { const uint8_t* p; int stride; uint32_t w, h, ow, oh; };
+// one axis of a filter table (lh264_decode_batch_ex6: bilinear, bicubic), built on the host and only read here: ent[3 * X] .. [3 * X + 2]
+// are the first tap of delivered coordinate X, the number of its taps and where their weights begin in k.  The weights of one X sum to
+// 2^14; every tap lies inside the window
+struct FilterAxis { const int32_t* ent; const int16_t* k; };
+// the four tables of one pack job: luma columns, luma rows, chroma columns, chroma rows
+struct FilterJob { FilterAxis lx, ly, cx, cy; };
+// one plane as the resize step sees it: the window's first sample, its size, the delivered size (fx, fy: the filtered step's tables)
+struct ResizePlane { const uint8_t* p; int stride; uint32_t w, h, ow, oh; FilterAxis fx = {nullptr, nullptr}, fy = {nullptr, nullptr}; };
+__host__ __device__ inline uint32_t filtered_sample (const ResizePlane& pl, int X, int Y);      // (behind clip8, below)
 // delivered sample X of the delivered row whose source rows are sy
 __host__ __device__ inline uint8_t resized_sample (const ResizePlane& pl, const Span& sy, int X) {
   const Span sx = span_of ((uint32_t)X, pl.w, pl.ow);
@@ -339,7 +346,9 @@ inline bool size_ok (int64_t out_w, int64_t out_h) {
 // are the luma's halved.  No byte outside the window is read, none outside the picture's bytes written.  No LDS.
 
 // piece p of delivered row Y (n bytes at d): bytes b0 .. b1 - 1 of rows y0 .. y0 + a.oh - 1 are the picture's, byte k of them sample
-// k - b0 of plane a (interleaved: sample (k - b0) / 2 of a or b, b0 even); every other byte is fa (k even) or fb (k odd)
+// k - b0 of plane a (interleaved: sample (k - b0) / 2 of a or b, b0 even); every other byte is fa (k even) or fb (k odd).
+// M = 4: the area means; M = 6: the planes' filter tables (filtered_sample)
+template <int M = 4>
 __host__ __device__ inline void piece_placed (uint8_t* d, int n, int Y, int p, const ResizePlane& a, const ResizePlane& b, bool interleaved,
                                               int b0, int b1, int y0, uint32_t fa, uint32_t fb) {
   int k0 = p * 4 - (int) ((uintptr_t)d & 3u), k1 = k0 + 4;
@@ -352,42 +361,45 @@ __host__ __device__ inline void piece_placed (uint8_t* d, int n, int Y, int p, c
     else for (int k = k0; k < k1; k++) d[k] = (uint8_t) ((k & 1) ? fb : fa);
     return;
   }
-  const Span sy = span_of ((uint32_t) (Y - y0), a.h, a.oh);
+  const Span sy = M == 4 ? span_of ((uint32_t) (Y - y0), a.h, a.oh) : Span();
   uint32_t o = 0;
   for (int k = k0; k < k1; k++) {
     uint8_t v;
     if (k < b0 || k >= b1) v = (uint8_t) ((k & 1) ? fb : fa);
-    else { const int x = k - b0; v = interleaved ? resized_sample ((x & 1) ? b : a, sy, x >> 1) : resized_sample (a, sy, x); }
+    else if constexpr (M == 4) { const int x = k - b0; v = interleaved ? resized_sample ((x & 1) ? b : a, sy, x >> 1) : resized_sample (a, sy, x); }
+    else { const int x = k - b0; v = (uint8_t) (interleaved ? filtered_sample ((x & 1) ? b : a, x >> 1, Y - y0) : filtered_sample (a, x, Y - y0)); }
     if (whole) o |= (uint32_t)v << (8 * (k - k0));
     else d[k] = v;
   }
   if (whole) * (uint32_t*) (d + k0) = o;
 }
 // band `band` (16 delivered luma rows, 8 chroma rows) of one job delivered as ow x oh with its window placed by pl, worked on by item
-// t of nt (the host steps it with t = 0, nt = 1)
-__host__ __device__ inline void pack_band_placed (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int ow, int oh, int band, int t, int nt) {
+// t of nt (the host steps it with t = 0, nt = 1).  M = 6: resampled by the job's filter tables fj
+template <int M = 4>
+__host__ __device__ inline void pack_band_placed (const lh264_pack_job_t& j, const lh264_pack_place_t& pl, int ow, int oh, int band, int t, int nt, const FilterJob* fj = nullptr) {
+  const FilterAxis none = {nullptr, nullptr};
   const int w = j.crop_w, h = j.crop_h, ocw = ow >> 1, och = oh >> 1;
   const uint32_t fy = pl.fill & 0xffu, fcb = pl.fill >> 8 & 0xffu, fcr = pl.fill >> 16 & 0xffu;
   const int r0 = band * kBandRows, r1 = r0 + kBandRows < oh ? r0 + kBandRows : oh;
   if (r1 > r0) {
-    const ResizePlane y = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pl.w, (uint32_t)pl.h};
+    const ResizePlane y = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pl.w, (uint32_t)pl.h, M == 6 ? fj->lx : none, M == 6 ? fj->ly : none};
     const int pieces = (ow + 6) >> 2, items = (r1 - r0) * pieces;
     for (int it = t; it < items; it += nt) {
       const int r = r0 + it / pieces, p = it % pieces;
-      piece_placed (j.dst + (size_t)r * ow, ow, r, p, y, y, false, pl.x, pl.x + pl.w, pl.y, fy, fy);
+      piece_placed<M> (j.dst + (size_t)r * ow, ow, r, p, y, y, false, pl.x, pl.x + pl.w, pl.y, fy, fy);
     }
   }
   const int c0 = band * (kBandRows / 2), c1 = c0 + kBandRows / 2 < och ? c0 + kBandRows / 2 : och;
   if (c1 <= c0) return;
   const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
-  const ResizePlane u = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1)};
-  const ResizePlane v = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1)};
+  const ResizePlane u = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1), M == 6 ? fj->cx : none, M == 6 ? fj->cy : none};
+  const ResizePlane v = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pl.w >> 1), (uint32_t) (pl.h >> 1), M == 6 ? fj->cx : none, M == 6 ? fj->cy : none};
   uint8_t* dc = j.dst + (size_t)ow * oh;
   if (j.format == LH264_FMT_NV12) {
     const int pieces = (ow + 6) >> 2, items = (c1 - c0) * pieces;
     for (int it = t; it < items; it += nt) {
       const int r = c0 + it / pieces, p = it % pieces;
-      piece_placed (dc + (size_t)r * ow, ow, r, p, u, v, true, pl.x, pl.x + pl.w, pl.y >> 1, fcb, fcr);
+      piece_placed<M> (dc + (size_t)r * ow, ow, r, p, u, v, true, pl.x, pl.x + pl.w, pl.y >> 1, fcb, fcr);
     }
   } else {
     const int pieces = (ocw + 6) >> 2, per_plane = (c1 - c0) * pieces;
@@ -395,7 +407,7 @@ __host__ __device__ inline void pack_band_placed (const lh264_pack_job_t& j, con
       const int plane = it >= per_plane, q = it - plane * per_plane;
       const int r = c0 + q / pieces, p = q % pieces;
       const uint32_t f = plane ? fcr : fcb;
-      piece_placed (dc + (size_t)plane * ocw * och + (size_t)r * ocw, ocw, r, p, plane ? v : u, u, false, pl.x >> 1, (pl.x + pl.w) >> 1, pl.y >> 1, f, f);
+      piece_placed<M> (dc + (size_t)plane * ocw * och + (size_t)r * ocw, ocw, r, p, plane ? v : u, u, false, pl.x >> 1, (pl.x + pl.w) >> 1, pl.y >> 1, f, f);
     }
   }
 }
@@ -432,11 +444,32 @@ __host__ __device__ inline uint32_t clip8 (int32_t v) {
 #endif
 }
 
-// delivered sample (X, Y) of one plane under sizing M: 0 the window, 1..3 the means of scale_log2, 4 the given size (sy: the rows of Y)
+// delivered sample (X, Y) of a plane resampled by its filter tables (the definition: include/lh264.h at lh264_decode_batch_ex6): the row
+// sums H by the column weights in 32 bits, their sum by the row weights in 64, one rounding and the clamp at the end.  Every tap lies
+// inside the window: no byte outside it is read
+__host__ __device__ inline uint32_t filtered_sample (const ResizePlane& pl, int X, int Y) {
+  const int32_t* ex = pl.fx.ent + 3 * X;
+  const int32_t* ey = pl.fy.ent + 3 * Y;
+  const int16_t* kx = pl.fx.k + ex[2];
+  const int16_t* ky = pl.fy.k + ey[2];
+  const int nx = ex[1], ny = ey[1];
+  const uint8_t* row = pl.p + (size_t)ey[0] * pl.stride + ex[0];
+  int64_t S = 0;
+  for (int y = 0; y < ny; y++, row += pl.stride) {
+    int32_t H = 0;
+    for (int x = 0; x < nx; x++) H += (int32_t)kx[x] * (int32_t)row[x];
+    S += (int64_t)ky[y] * H;
+  }
+  return clip8 ((int32_t) ((S + ((int64_t)1 << 27)) >> 28));
+}
+
+// delivered sample (X, Y) of one plane under sizing M: 0 the window, 1..3 the means of scale_log2, 4 the given size (sy: the rows of Y),
+// 6 the given size by the plane's filter tables
 template <int M>
 __host__ __device__ inline int plane_sample (const ResizePlane& pl, const Span& sy, int X, int Y) {
   if constexpr (M == 0) return pl.p[(size_t)Y * pl.stride + X];
   else if constexpr (M <= 3) return mean_clamped<M> (pl.p, pl.stride, (int)pl.w, (int)pl.h, X, Y);
+  else if constexpr (M == 6) return (int)filtered_sample (pl, X, Y);
   else return resized_sample (pl, sy, X);
 }
 // delivered luma samples (X, Y) and (X + 1, Y), X even: the second in bits 8..15
@@ -471,7 +504,10 @@ __host__ __device__ inline void quad_rgb (const ResizePlane& py, const ResizePla
 // sizing M = 5, "placed" (LH264_FIT_CONTAIN): the planes' ow x oh is the rectangle the window is resampled to, which lies at (x, y) of
 // the delivered picture; every pixel outside it is the conversion of the fill.  x, y and the rectangle are even, so a quad is wholly
 // picture - quad_rgb<4> with the coordinates shifted - or wholly bar
+// Sizing M = 7 is M = 5 with the rectangle's samples from quad_rgb<6>: the planes' filter tables in the area means' place
 struct Placed { int x, y; uint32_t fill; };
+constexpr bool placed_sizing (int M) { return M == 5 || M == 7; }
+constexpr int placed_inner (int M) { return M == 5 ? 4 : 6; }
 // the bar's pixel: quad_rgb's arithmetic on (fill_y, fill_cb, fill_cr), once per item
 __host__ __device__ inline void bar_rgb (uint32_t fill, const int32_t* f, int y0, uint32_t o[3]) {
   const int D = (int) (fill >> 8 & 0xffu) - 128, E = (int) (fill >> 16 & 0xffu) - 128;
@@ -500,10 +536,10 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
   // M = 5: the bar's pixel, and whether the pair's rows cross the rectangle at all (then their spans, counted from its first row)
   uint32_t bar[3] = {0, 0, 0};
   bool rows_in = false;
-  if constexpr (M == 5) {
+  if constexpr (placed_sizing (M)) {
     bar_rgb (pc.fill, f, y0, bar);
     rows_in = 2 * R >= pc.y && 2 * R < pc.y + (int)py.oh;
-    if (rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
+    if (M == 5 && rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
   }
   // the 12 pixels of both rows as byte streams: RGB24 one stream of 36 bytes, RGBP three of 12
   uint32_t W[2][NP][NW + 1];
@@ -513,8 +549,8 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
     const int X = x0 + 2 * q;
     if (X < 0 || X >= ow) continue;
     uint32_t px[2][2][3];
-    if constexpr (M == 5) {
-      if (rows_in && X >= pc.x && X < pc.x + (int)py.ow) quad_rgb<4> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
+    if constexpr (placed_sizing (M)) {
+      if (rows_in && X >= pc.x && X < pc.x + (int)py.ow) quad_rgb<placed_inner (M)> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
       else for (int rr = 0; rr < 2; rr++) for (int i = 0; i < 2; i++) for (int c = 0; c < 3; c++) px[rr][i][c] = bar[c];
     } else quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X, R, px);
     _Pragma ("unroll")
@@ -556,16 +592,17 @@ __host__ __device__ inline void piece_rgb (uint8_t* dst, const ResizePlane& py, 
 // band `band` (16 delivered luma rows) of one job delivered as ow x oh RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
 // (pl: the job's place, read under M = 5 only - the planes are then resampled to pl->w x pl->h)
 template <int M, int L>
-__host__ __device__ inline void pack_band_rgb_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr) {
+__host__ __device__ inline void pack_band_rgb_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr, const FilterJob* fj = nullptr) {
   const int w = j.crop_w, h = j.crop_h;
   const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
   if (R1 <= R0) return;
   const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
-  const int pw = M == 5 ? pl->w : ow, ph = M == 5 ? pl->h : oh;
-  const Placed pc = M == 5 ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
-  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph};
-  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
-  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
+  const int pw = placed_sizing (M) ? pl->w : ow, ph = placed_sizing (M) ? pl->h : oh;
+  const Placed pc = placed_sizing (M) ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
+  const FilterAxis none = {nullptr, nullptr};
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph, M == 7 ? fj->lx : none, M == 7 ? fj->ly : none};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1), M == 7 ? fj->cx : none, M == 7 ? fj->cy : none};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1), M == 7 ? fj->cx : none, M == 7 ? fj->cy : none};
   int32_t f[5];
   for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
   const int y0 = (std_byte & 2) ? 0 : 16;
@@ -679,12 +716,12 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
   // M = 5: the bar's three elements, once per item, and whether the pair's rows cross the rectangle (piece_rgb has the same lines)
   float barv[3] = {0.0f, 0.0f, 0.0f};
   bool rows_in = false;
-  if constexpr (M == 5) {
+  if constexpr (placed_sizing (M)) {
     uint32_t bar[3];
     bar_rgb (pc.fill, f, y0, bar);
     for (int c = 0; c < 3; c++) barv[c] = __builtin_fmaf ((float)bar[c], mul[c], add[c]);
     rows_in = 2 * R >= pc.y && 2 * R < pc.y + (int)py.oh;
-    if (rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
+    if (M == 5 && rows_in) { sy[0] = span_of ((uint32_t) (2 * R - pc.y), py.h, py.oh); sy[1] = span_of ((uint32_t) (2 * R + 1 - pc.y), py.h, py.oh); sc = span_of ((uint32_t) (R - (pc.y >> 1)), pu.h, pu.oh); }
   }
   uint32_t W[2][NP][NW];                                                             // the item's words, per row and plane
   for (int rr = 0; rr < 2; rr++) for (int c = 0; c < NP; c++) for (int k = 0; k < NW; k++) W[rr][c][k] = 0;
@@ -693,10 +730,10 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
     if (q >= nq) continue;
     uint32_t px[2][2][3];
     bool in_bar = false;
-    if constexpr (M == 5) {
+    if constexpr (placed_sizing (M)) {
       const int X = X0 + 2 * q;
       in_bar = !(rows_in && X >= pc.x && X < pc.x + (int)py.ow);
-      if (!in_bar) quad_rgb<4> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
+      if (!in_bar) quad_rgb<placed_inner (M)> (py, pu, pv, sy, sc, f, y0, X - pc.x, R - (pc.y >> 1), px);
       else for (int rr = 0; rr < 2; rr++) for (int i = 0; i < 2; i++) for (int c = 0; c < 3; c++) px[rr][i][c] = 0;
     } else quad_rgb<M> (py, pu, pv, sy, sc, f, y0, X0 + 2 * q, R, px);
     _Pragma ("unroll")
@@ -705,7 +742,7 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
       _Pragma ("unroll")
       for (int i = 0; i < 2; i++) {
         _Pragma ("unroll")
-        for (int c = 0; c < 3; c++) v[i][c] = (M == 5 && in_bar) ? barv[c] : __builtin_fmaf ((float)px[rr][i][c], mul[c], add[c]);      // one fused multiply-add: the definition's
+        for (int c = 0; c < 3; c++) v[i][c] = (placed_sizing (M) && in_bar) ? barv[c] : __builtin_fmaf ((float)px[rr][i][c], mul[c], add[c]);      // one fused multiply-add: the definition's
       }
       // the quad's elements of this row in memory order: R G B R G B in one plane, or the pixel pair in each of three
       if constexpr (kPacked) {
@@ -745,16 +782,17 @@ __host__ __device__ LH264_SAMPLE_INLINE void piece_sample (uint8_t* dst, const R
 
 // band `band` (16 delivered luma rows) of one job delivered as ow x oh float RGB, worked on by item t of nt (the host steps it with t = 0, nt = 1)
 template <int M, int L, int T>
-__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, const float* mul, const float* add, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr) {
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_as (const lh264_pack_job_t& j, int ow, int oh, int std_byte, const float* mul, const float* add, int band, int t, int nt, const lh264_pack_place_t* pl = nullptr, const FilterJob* fj = nullptr) {
   const int w = j.crop_w, h = j.crop_h;
   const int R0 = band * (kBandRows / 2), R1 = R0 + kBandRows / 2 < (oh >> 1) ? R0 + kBandRows / 2 : (oh >> 1);
   if (R1 <= R0) return;
   const size_t co = (size_t) (j.crop_y >> 1) * j.stride_c + (j.crop_x >> 1);
-  const int pw = M == 5 ? pl->w : ow, ph = M == 5 ? pl->h : oh;      // (pl: the job's place, read under M = 5 only)
-  const Placed pc = M == 5 ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
-  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph};
-  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
-  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1)};
+  const int pw = placed_sizing (M) ? pl->w : ow, ph = placed_sizing (M) ? pl->h : oh;      // (pl: the job's place, read under M = 5 and 7 only)
+  const Placed pc = placed_sizing (M) ? Placed {pl->x, pl->y, pl->fill} : Placed {0, 0, 0u};
+  const FilterAxis none = {nullptr, nullptr};
+  const ResizePlane py = {j.y + (size_t)j.crop_y * j.stride_y + j.crop_x, j.stride_y, (uint32_t)w, (uint32_t)h, (uint32_t)pw, (uint32_t)ph, M == 7 ? fj->lx : none, M == 7 ? fj->ly : none};
+  const ResizePlane pu = {j.u + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1), M == 7 ? fj->cx : none, M == 7 ? fj->cy : none};
+  const ResizePlane pv = {j.v + co, j.stride_c, (uint32_t) (w >> 1), (uint32_t) (h >> 1), (uint32_t) (pw >> 1), (uint32_t) (ph >> 1), M == 7 ? fj->cx : none, M == 7 ? fj->cy : none};
   int32_t f[5];
   for (int k = 0; k < 5; k++) f[k] = kColourFactors[std_byte & 3][k];
   const int y0 = (std_byte & 2) ? 0 : 16;
@@ -796,6 +834,31 @@ __host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_placed (const lh26
   if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved || ((uintptr_t)j.dst & 3u)) return;
   if (layout == (int)LH264_COLOUR_RGB24) pack_band_sample_placed_in<(int)LH264_COLOUR_RGB24> (j, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
   else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_placed_in<(int)LH264_COLOUR_RGBP> (j, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+}
+
+// ---- the filtered pack step: lh264_decode_batch_ex6 with LH264_FILTER_BILINEAR / _BICUBIC (the definition: include/lh264.h there) ------
+// The placed steps above with filtered_sample in resized_sample's place: the window is resampled to pl.w x pl.h by the job's four
+// tables and lies at (pl.x, pl.y) of the out_w x out_h picture (a job that is not placed: the whole picture, no bar).  Bands, pieces,
+// stores and bars are the placed steps'; a sample costs taps_y * taps_x multiply-adds, each tap read from the window once per sample.
+__host__ __device__ inline void pack_band_filtered (const lh264_pack_job_t& j, const FilterJob& fj, const lh264_pack_place_t& pl, int out_w, int out_h, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved) return;
+  pack_band_placed<6> (j, pl, out_w, out_h, band, t, nt, &fj);
+}
+__host__ __device__ inline void pack_band_rgb_filtered (const lh264_pack_job_t& j, const FilterJob& fj, const lh264_pack_place_t& pl, int out_w, int out_h, int layout, int std_byte, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved) return;
+  if (layout == (int)LH264_COLOUR_RGB24) pack_band_rgb_as<7, (int)LH264_COLOUR_RGB24> (j, out_w, out_h, std_byte, band, t, nt, &pl, &fj);
+  else if (layout == (int)LH264_COLOUR_RGBP) pack_band_rgb_as<7, (int)LH264_COLOUR_RGBP> (j, out_w, out_h, std_byte, band, t, nt, &pl, &fj);
+}
+template <int L>
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_filtered_in (const lh264_pack_job_t& j, const FilterJob& fj, const lh264_pack_place_t& pl, int ow, int oh, int type, int std_byte, const float* mul, const float* add, int band, int t, int nt) {
+  if (type == (int)LH264_SAMPLE_F32) pack_band_sample_as<7, L, (int)LH264_SAMPLE_F32> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl, &fj);
+  else if (type == (int)LH264_SAMPLE_F16) pack_band_sample_as<7, L, (int)LH264_SAMPLE_F16> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl, &fj);
+  else if (type == (int)LH264_SAMPLE_BF16) pack_band_sample_as<7, L, (int)LH264_SAMPLE_BF16> (j, ow, oh, std_byte, mul, add, band, t, nt, &pl, &fj);
+}
+__host__ __device__ LH264_SAMPLE_INLINE void pack_band_sample_filtered (const lh264_pack_job_t& j, const FilterJob& fj, const lh264_pack_place_t& pl, int out_w, int out_h, int layout, int std_byte, const lh264_decode_sample_t& sm, int band, int t, int nt) {
+  if (j.crop_w <= 0 || j.crop_h <= 0 || j.reserved || ((uintptr_t)j.dst & 3u)) return;
+  if (layout == (int)LH264_COLOUR_RGB24) pack_band_sample_filtered_in<(int)LH264_COLOUR_RGB24> (j, fj, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
+  else if (layout == (int)LH264_COLOUR_RGBP) pack_band_sample_filtered_in<(int)LH264_COLOUR_RGBP> (j, fj, pl, out_w, out_h, (int)sm.type, std_byte, sm.mul, sm.add, band, t, nt);
 }
 
 // ---- the motion fields: lh264_decode_batch_ex4 (the definition: include/lh264.h at that call) ---------------------------------------

@@ -22,8 +22,9 @@ class _DevSpan:
 class DecodedBatch:
     """the handles of one decode_batch call; free() gives them back (device tensors made by tensor() are copies or views, see there)"""
 
-    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None, dtype="uint8", affine=None, motion=False):
+    def __init__(self, lib, handles, device_out, sink_keepalive=None, size=None, colour=None, dtype="uint8", affine=None, motion=False, filter="area"):
         self._lib, self._h, self.device_out, self._keep, self.size, self.colour = lib, handles, device_out, sink_keepalive, size, colour
+        self.filter = filter                   # the filter= of the call: "area" | "bilinear" | "bicubic"
         self.has_motion = bool(motion)
         # dtype: the dtype= of the call; affine: the six binary32 values it passed, ((mul R, G, B), (add R, G, B)), None with "uint8"
         self.dtype, self.affine = dtype, affine
@@ -276,7 +277,7 @@ class DecodedBatch:
             pass
 
 
-def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=False, select=None):
+def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=None, group_mbs=None, sink=None, conceal=None, sha1=None, pictures=True, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=False, select=None, filter="area"):
     """decode a batch of Annex-B streams on the current device -> DecodedBatch.
     fmt: "i420" | "nv12".  device_out=True: the pictures stay in device memory (tensor(i)).  sink: a callable
     (stream, first_picture, pictures, data) -> falsy to go on, called with runs of consecutive pictures of one stream (pictures as in
@@ -357,8 +358,18 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
     neither seen nor reported.  A number the stream does not have delivers nothing and is no error.  The rule: include/lh264.h at
     lh264_decode_batch_ex5; plan (data, select) computes it without a device; chain_pictures(i) counts what was reconstructed.  Not
     together with pick or conceal.  With device_out=True, size= and a selection of equal length per stream, frames(i) is the (T, ...)
-    clip of stream i, and torch.stack over the batch gives (N, T, ...)."""
+    clip of stream i, and torch.stack over the batch gives (N, T, ...).
+    filter: "area" (the default: the area average of size=) | "bilinear" | "bicubic", the latter two with size= only: the window - after
+    crop= and fit=, exactly as for the area average - is resampled by a triangle or a Catmull-Rom kernel, widened when shrinking
+    (antialiased), as torchvision's and PIL's resize do; integer weights that sum to 2^14 per axis, built on the host, applied on the
+    device by decode_pack_filtered_kernel and its RGB and float siblings through lh264_decode_batch_ex6, one rounding at the end.  The
+    definition: include/lh264.h at that call; filter_taps (filter, src_len, dst_len) gives the weights without a device.  Colour and a
+    float dtype act on the filtered planes; DecodedBatch.filter is the filter of the call."""
     lib = L.lib()
+    if not isinstance(filter, str) or filter not in L.FILTER:
+        raise ValueError("filter must be 'area', 'bilinear' or 'bicubic'")
+    if filter != "area" and size is None:
+        raise ValueError("a filter other than 'area' needs size=")
     sel, sel_keep = _select_struct(select, len(datas))
     if sel is not None and (pick != "all" or conceal not in (None, "off")):
         raise ValueError("select excludes pick and conceal")
@@ -447,7 +458,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         cb = L.DECODE_SINK_FN(_cb)
         opts.sink = cb
     outs = (C.c_void_p * n)()
-    if fit != "stretch" or crops is not None or motion or sel is not None:
+    if fit != "stretch" or crops is not None or motion or sel is not None or filter != "area":
         # a view, the fields or a selection: every struct the call takes, the colour and sample ones where they are asked for
         view = None
         if fit != "stretch" or crops is not None:
@@ -470,7 +481,11 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         if motion:
             mo = L.DecodeMotion()
             mo.struct_bytes, mo.fields = C.sizeof(L.DecodeMotion), L.MOTION_FIELDS
-        if sel is not None:
+        if filter != "area":
+            fl = L.DecodeFilter()
+            fl.struct_bytes, fl.filter = C.sizeof(L.DecodeFilter), L.FILTER[filter]
+            rc = lib.lh264_decode_batch_ex6(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), ref(mo), ref(sel), C.byref(fl), outs)
+        elif sel is not None:
             rc = lib.lh264_decode_batch_ex5(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), ref(mo), C.byref(sel), outs)
         elif motion:
             rc = lib.lh264_decode_batch_ex4(ptrs, lens, n, threads, C.byref(opts), ref(ext), ref(sm), ref(view), C.byref(mo), outs)
@@ -493,7 +508,7 @@ def decode_batch(datas, fmt="i420", threads=0, device_out=False, round_pictures=
         raise RuntimeError("losslessh264_amd: no GPU visible (there is no CPU fallback)")
     if rc != 0:
         raise RuntimeError("lh264_decode_batch: error %d" % rc)
-    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine, motion)
+    return DecodedBatch(lib, [outs[i] for i in range(n)], device_out, cb, tuple(size) if size is not None else None, colour, dtype, affine, motion, filter)
 
 
 def _select_entry(s):
@@ -551,6 +566,28 @@ def plan(data, select):
     a, b = (C.c_int32 * max(1, nn.value))(), (C.c_int32 * max(1, nd.value))()
     L.check(lib.lh264_parser_plan(data, len(data), C.byref(st.selects[0]), a, nn.value, C.byref(nn), b, nd.value, C.byref(nd)))
     return [int(a[k]) for k in range(nn.value)], [int(b[k]) for k in range(nd.value)]
+
+
+def filter_taps(filter, src_len, dst_len):
+    """the weights of filter= "bilinear" | "bicubic" for an axis of src_len samples delivered as dst_len -> [(first, weights)] per
+    delivered coordinate: the index of the first source sample with a weight and the int weights from there, which sum to 16384.  The
+    rule of include/lh264.h at lh264_decode_batch_ex6, computed by the library without a device (lh264_filter_taps); ValueError for
+    "area", which has no such table, and for lengths outside 1..16384 and 1..4096"""
+    if not isinstance(filter, str) or filter not in L.FILTER:
+        raise ValueError("filter must be 'bilinear' or 'bicubic'")
+    lib = L.lib()
+    out = []
+    first, n = C.c_int32(0), C.c_int(0)
+    buf = (C.c_int16 * 64)()
+    for X in range(max(1, int(dst_len))):
+        rc = lib.lh264_filter_taps(L.FILTER[filter], int(src_len), int(dst_len), X, C.byref(first), buf, len(buf), C.byref(n))
+        if rc == 0 and n.value > len(buf):
+            buf = (C.c_int16 * n.value)()
+            rc = lib.lh264_filter_taps(L.FILTER[filter], int(src_len), int(dst_len), X, C.byref(first), buf, len(buf), C.byref(n))
+        if rc != 0:
+            raise ValueError("filter_taps: a filter without a table, or a length or coordinate that is not defined")
+        out.append((first.value, [int(buf[k]) for k in range(n.value)]))
+    return out
 
 
 def _rect(c):
@@ -636,16 +673,16 @@ def decode_arena_bytes():
 _SUFFIX = {"uint8": ".rgb", "float32": ".f32", "float16": ".f16", "bfloat16": ".bf16"}
 
 
-def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=0, select=None):
+def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, motion=0, select=None, filter="area"):
     """out_dir/<basename>.yuv - with colour= <basename>.rgb, with a float dtype= <basename>.f32 | .f16 | .bf16 - for every input, through one decode_batch with a sink that appends to the
-    files -> [(path, status, error, pictures, bytes)]; select (one entry, for every file), scale, pick, size, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch.
+    files -> [(path, status, error, pictures, bytes)]; select (one entry, for every file), scale, pick, size, filter, colour, matrix, colour_range, dtype, mul, add, fit, fill and crop as in decode_batch.
     motion: 1: beside them <basename>.mv and <basename>.mbi, every stream's motion blocks and macroblock blocks as the handle holds them
     (decode_batch (motion=True)); 2: those two and no picture file, through the motion-only call (path and bytes are then the .mv file's
     and both files')"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
     if motion == 2:
-        b = decode_batch(datas, fmt=fmt, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=True, pictures=False, select=select)
+        b = decode_batch(datas, fmt=fmt, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=True, pictures=False, select=select, filter=filter)
         res = [_write_fields(b, i, os.path.join(out_dir, os.path.basename(p))) for i, p in enumerate(paths)]
         b.free()
         return res
@@ -658,7 +695,7 @@ def decode_to_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scal
         total[stream] += len(data)
         return 0
     try:
-        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=bool(motion), select=select)
+        b = decode_batch(datas, fmt=fmt, sink=sink, conceal=conceal, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, motion=bool(motion), select=select, filter=filter)
     finally:
         for f in files:
             f.close()
@@ -680,13 +717,13 @@ def _write_fields(b, i, stem):
     return stem + ".mv", b.status(i), b.error(i), len(b.pictures(i)), mot.nbytes + mbi.nbytes
 
 
-def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, select=None):
+def decode_to_sha1_files(paths, out_dir, fmt="i420", conceal=None, parse="host", scale=0, pick="all", size=None, colour=None, matrix="auto", colour_range="auto", dtype="uint8", mul=None, add=None, fit="stretch", fill=None, crop=None, select=None, filter="area"):
     """out_dir/<basename>.sha1 for every input, through one digests-only decode_batch: a line `index width height frame_num idr hex`
     per picture, then `stream hex` -> [(path, status, error, pictures, stream digest as hex)]; select (one entry, for every file), scale, pick, size, fit, fill and crop as in decode_batch (the digests are of the delivered bytes; index is the picture's number in the stream in decode
     order, which with pick="all" and nothing withheld counts the lines)"""
     datas = [open(p, "rb").read() for p in paths]
     os.makedirs(out_dir, exist_ok=True)
-    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, select=select)
+    b = decode_batch(datas, fmt=fmt, conceal=conceal, sha1="both", pictures=False, parse=parse, scale=scale, pick=pick, size=size, colour=colour, matrix=matrix, colour_range=colour_range, dtype=dtype, mul=mul, add=add, fit=fit, fill=fill, crop=crop, select=select, filter=filter)
     res = []
     try:
         for i, p in enumerate(paths):

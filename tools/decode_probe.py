@@ -3,11 +3,13 @@
 (arenas warm after the first): MB/s of .264, pictures/s, the split per stage (lh264_decode_last_timing), the arena's size, and
 lh264_parse_batch_discard - the host front end alone - on the same batch in the same process.
 
-    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h] [--motion] [--select SPEC]
+    tools/decode_probe.py [streams] [stream file] [--runs N] [--nv12] [--sha1] [--modes host,device,digests,parse] [--parse device|device+cabac] [--scale N] [--pick all|intra|idr] [--size WxH] [--filter area|bilinear|bicubic] [--colour rgb24|rgbp] [--dtype float32|float16|bfloat16] [--fit cover|contain] [--crop x,y,w,h] [--motion] [--select SPEC]
 
 --sha1 adds the digests-only call (sha1="both", pictures=False: SHA-1 per picture and per stream on the device, nothing downloaded);
 --scale N (1..3) asks for reduced-size pictures (decode_batch (scale=N)) and adds "scale" to the rows;
 --size WxH asks for pictures of that size (decode_batch (size=(W, H)), both even, 2..4096, not with --scale) and adds "size" to the rows;
+--filter area|bilinear|bicubic names the filter of that resampling (decode_batch (filter=...), the latter two with --size only); every
+row carries "filter", "area" where none was named;
 --colour rgb24|rgbp asks for RGB pictures (decode_batch (colour=...), not with --nv12) and adds "colour" to the rows;
 --dtype float32|float16|bfloat16 asks for float RGB pictures (decode_batch (dtype=...), with --colour only; the factors are
 normalise of the ImageNet means and deviations) and adds "dtype" to the rows;
@@ -60,6 +62,11 @@ def main(argv):
         text = argv[argv.index("--size") + 1]
         scale = dict(scale, size=tuple(int(v) for v in text.split("x")))
         args.remove(text)
+    filt = "area"
+    if "--filter" in argv:
+        filt = argv[argv.index("--filter") + 1]
+        args.remove(filt)
+    scale = dict(scale, filter=filt)
     if "--colour" in argv:
         scale = dict(scale, colour=argv[argv.index("--colour") + 1])
         args.remove(argv[argv.index("--colour") + 1])
